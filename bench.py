@@ -2,6 +2,14 @@
 """Headline benchmark: speech-probability throughput of the Silero-VAD hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|8k|stream|stream_host|stream_8k|stream_host_8k|corpus|plumbing|plumbing_8k]
+                    [--full] [--dump-outputs DIR]
+
+A plain run measures the headline figure only: it sets up, warms up, times K steps of the main leg and prints the line (`value`,
+`ms_per_step` = milliseconds per timed step).  `--full` adds everything else this file measures or checks: the CPU baseline, every
+leg's parity check against the CPU oracle, the other configs and arithmetic, and the live rocprofv3 --pmc traffic pass.
+`--dump-outputs DIR` (c2 / 8k) writes what the last timed step handed back -- probs [B, T], the final (h, c) state [2, B, 128] and
+the context [B, n / 8] -- as DIR/<name>.npy in float32; the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 `--gpus N` (N > 1) works both ways the driver may start it: under `python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N` (RANK/LOCAL_RANK/WORLD_SIZE in the environment), and as a plain
@@ -14,11 +22,11 @@ vad_forward_audio call through the C ABI (zeroed context/state, like the referen
 are sharded across ranks with no data-path collective (weak scaling: every rank owns 4096 streams); the only
 communication is the barrier + MAX-reduce of the elapsed time that the measurement contract asks for.
 
-Every leg CERTIFIES ITSELF: after its timed region the CPU oracle recomputes streams of the leg's own PCM (c2 / 8k: streams 0..15
+With --full every leg CERTIFIES ITSELF: after its timed region the CPU oracle recomputes streams of the leg's own PCM (c2 / 8k: streams 0..15
 and the last 16, all 256 chunks, probabilities and final (h, c); stream legs: 24 ticks of streams 0..15 through the leg's own graph;
 corpus: every 10 000th recording + its segments) and the leg fails above 1e-4 (`parity`, `parity_max_abs_dp`).
 
-The same JSON line also carries, for the record (none of them is the headline `value`):
+With --full the same JSON line also carries, for the record (none of them is the headline `value`):
   other_configs    8k           configs[2]: 8 kHz, 256-sample chunks, 4096 streams x 256 chunks (the 8 kHz net)            [N = 1]
                    stream       configs[4], KERNEL ONLY: 8192 live streams per GPU (65 536 per 8-GPU node), persistent state in
                                 HBM, one hipGraph-captured vad_step per 32 ms tick from a device-side audio ring           [any N]
@@ -387,6 +395,26 @@ def base_line(args, world, metric_sr, value, elapsed, steps):
             "dtype": "f32", "data": "synthetic"}
 
 
+DUMP_CAP = 64 << 20      # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` {name: (tensor, stream axis)} as DIR/<name>.npy, float32.  Past DUMP_CAP in all, every array keeps the
+    same fixed, seeded sample of streams (sorted), so that two runs stay comparable row for row."""
+    import numpy as np
+    out = {k: (np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32), ax) for k, (t, ax) in arrays.items()}
+    total = sum(a.nbytes for a, _ in out.values())
+    if total > DUMP_CAP:
+        a0, ax0 = next(iter(out.values()))
+        B = a0.shape[ax0]
+        keep = np.sort(np.random.default_rng(0).choice(B, max(1, B * DUMP_CAP // total), replace=False))
+        out = {k: (np.take(a, keep, axis=ax), ax) for k, (a, ax) in out.items()}
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, (a, _) in out.items():
+        np.save(d / f"{k}.npy", a)
+
+
 # ---- c2 / 8k: HBM-resident batch ------------------------------------------------------------------------
 def time_batch(eng, step, probs, world, dist, dev, steps, warmup):
     """Clock ramp, warm-up, `steps` timed calls with the engine's hipEvents on."""
@@ -406,7 +434,7 @@ def time_batch(eng, step, probs, world, dist, dev, steps, warmup):
     return elapsed, front_ms / c, rec_ms / c, ok
 
 
-def run_batch(args, sr, rank, world, local, dist, steps, with_other=False):
+def run_batch(args, sr, rank, world, local, dist, steps, with_other=False, dump=None):
     import torch
     from silero_vad_amd import Engine
     dev = torch.device("cuda", local)
@@ -428,8 +456,10 @@ def run_batch(args, sr, rank, world, local, dist, steps, with_other=False):
         eng.forward_audio(pcm, sr, ctx, state, probs)
 
     elapsed, front_ms, rec_ms, ok = time_batch(eng, step, probs, world, dist, dev, steps, args.warmup)
+    if dump and rank == 0:                                      # (rank 0's shard; before anything else runs on these buffers)
+        dump_outputs(dump, {"probs": (probs, 0), "state": (state, 1), "context": (ctx, 0)})
     parity = None
-    if not args.no_parity:
+    if args.check:
         # self-certification: streams 0..15 and the last 16 (speech), all T chunks, of the PCM that was just timed
         idx = torch.tensor(sel, device=dev)
         parity = certify(pcm[idx].cpu().numpy(), probs[idx].cpu().numpy(), state[:, idx].cpu().numpy(), sr,
@@ -559,7 +589,7 @@ def run_stream(args, rank, world, local, dist, steps, sr=16000):
     eng.set_option("profile", "0")
     ok = bool(torch.isfinite(pool.prob).all().item())
     parity = None
-    if not args.no_parity:
+    if args.check:
         def feed(j):
             pool.pcm.copy_(src[j % ring])
             pool.tick_staged()
@@ -720,7 +750,7 @@ def run_stream_host(args, rank, world, local, dist, ticks, sr=16000, gaps=0.0):
                      "what": "the same ticks with every stream's row crossing the link (vad_pump_play_gaps)"}
     link = h2d_rate_GBps(dev)
     parity = None
-    if not args.no_parity:
+    if args.check:
         # streams 0..15 restart from zero state, 24 ticks of the leg's own audio go through the pump; the oracle recomputes them
         nt = 24
         for b in range(16):
@@ -970,7 +1000,7 @@ def run_corpus(args, rank, world, local, dist, passes, sr=16000, main_only=False
         legs["pre_refill"], _ = run_leg(base_i, "refill", "gather", min(len(lens), 18 * R), False)
     legs["main"], res = run_leg(base_i, "buckets", main_mode, len(lens), True)
     parity = None
-    if not args.no_parity:
+    if args.check:
         parity = corpus_parity_sample(model, gids, lens, offs, base_i, res["counts"], res["segs"], sr)
     if not (args.corpus_main_only or main_only):                # the other ingest routes on 6 passes' worth, for comparison
         for other in (() if os.environ.get("VAD_BENCH_ONLY_REFILL") else ("window", "gather", "dma")):
@@ -1350,7 +1380,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extras", action="store_true", help="skip other_configs")
     ap.add_argument("--dry", action="store_true", help="no GPU: exercise launch/shard/gather/barrier/reduce/print only (gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the parity checks, the other configs and arithmetic and the live PMC pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; configs c2 and 8k)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry or args.config not in ("c2", "8k")):
+        ap.error("--dump-outputs: the batch configs c2 and 8k only, without --dry")
+    args.check = args.full and not args.no_parity       # the legs' parity checks (the checked streams carry speech either way)
     default_steps = {"c2": 200, "8k": 200, "stream": 2000, "stream_8k": 2000, "stream_host": 2000, "stream_host_8k": 2000, "stream_gaps": 2000,
                      "corpus": 1, "plumbing": 1, "plumbing_8k": 1}   # corpus: one step = the whole shard
     if args.steps is None:
@@ -1361,7 +1398,7 @@ def main():
 
     # the CPU baseline runs first, in its own CPU-only process, before this process touches the GPU
     # (at N > 1 too, on rank 0: the other ranks wait for it in the rendezvous -- the multi-rank line carries its own baseline)
-    want_cpu = int(os.environ.get("RANK", 0)) == 0 and not args.no_cpu_baseline and not args.dry
+    want_cpu = args.full and int(os.environ.get("RANK", 0)) == 0 and not args.no_cpu_baseline and not args.dry
     cpu = cpu_baseline(16000 if args.config != "8k" else 8000) if want_cpu else None
 
     import torch
@@ -1375,10 +1412,10 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.set_device(torch.device("cuda", local))
-        extras = not args.no_extras
+        extras = args.full and not args.no_extras
         if args.config in ("c2", "8k"):
             sr = 16000 if args.config == "c2" else 8000
-            out = run_batch(args, sr, rank, world, local, dist, args.steps, with_other=extras and args.config == "c2")
+            out = run_batch(args, sr, rank, world, local, dist, args.steps, with_other=extras and args.config == "c2", dump=args.dump_outputs)
         elif args.config in ("stream", "stream_8k"):
             out = run_stream(args, rank, world, local, dist, args.steps, 16000 if args.config == "stream" else 8000)
         elif args.config in ("stream_host", "stream_host_8k", "stream_gaps"):

@@ -1632,7 +1632,7 @@ def test_bench_multi_rank_legs_run_on_shared_gpu(built):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["VAD_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--config", "corpus", "--corpus-passes", "2",
-                        "--recordings", "1024", "--corpus-main-only", "--no-cpu-baseline"],
+                        "--recordings", "1024", "--corpus-main-only", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -1649,6 +1649,36 @@ def test_bench_multi_rank_legs_run_on_shared_gpu(built):
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
     assert d["n_gpus"] == 2 and d["outputs_finite"] and d["value"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_its_outputs(built, oracle, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (no --full): the headline line only, `steps` = K timed steps, and the last
+    timed step's outputs in DIR -- probs [B, T], final (h, c) [2, B, 128], context [B, 64], float32.  The dumped probabilities of the
+    streams that carry speech (0..15 and the last 16: bench.speech_rows) are the oracle's on the same PCM."""
+    import json
+    import subprocess
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+    assert not {"cpu_baseline", "parity", "other_arithmetic"} & set(d) and set(d["legs"]) == {"c2"}
+    B, T, n = 4096, 256, 512
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("probs", "state", "context")}
+    assert {k: (v.shape, v.dtype) for k, v in got.items()} == {"probs": ((B, T), np.float32), "state": ((2, B, 128), np.float32),
+                                                             "context": ((B, n // 8), np.float32)}
+    assert np.isfinite(got["probs"]).all() and got["probs"].min() >= 0.0 and got["probs"].max() <= 1.0
+    sys.path.insert(0, str(root))
+    import bench
+    sel = list(range(16)) + list(range(B - 16, B))
+    pcm = bench.speech_rows(16000, len(sel), T * n, torch.device("cpu")).numpy()
+    want, _, wst = oracle.forward_audio(pcm, 16000)
+    assert np.abs(got["probs"][sel] - want).max() < TOL
+    assert state_err(got["state"][:, sel], wst) < TOL
+    assert want.max() > 0.5                                      # (speech: the checked probabilities leave 0)
 
 
 def test_rccl_process_group_carries_the_bench_barrier_reduce_and_gather():

@@ -1,44 +1,49 @@
 """The reference's OWN, unmodified callers over the drop-in model object:
 
-    /root/reference/src/silero_vad/utils_vad.py:314,328   get_speech_timestamps -> model.reset_states(), model(chunk, sr).item()
-    /root/reference/src/silero_vad/utils_vad.py:501,528   VADIterator           -> model.reset_states(), model(x, sr).item()
+    src/silero_vad/utils_vad.py:314,328   get_speech_timestamps -> model.reset_states(), model(chunk, sr).item()
+    src/silero_vad/utils_vad.py:501,528   VADIterator           -> model.reset_states(), model(x, sr).item()
 
-are imported from the reference checkout and run with a `HipSileroVAD` whose engine is the CPU replay engine
-(tests/replay_engine.py: the oracle behind the engine's Python surface), i.e. everything of the drop-in except the
-kernels: protocol, validation, state ownership, shapes and dtypes the reference code relies on.  Outputs must equal
-what the reference produced with its own model (tests/golden/golden_segments.json).  The reference checkout only
-exists in the authoring container; on the GPU box this module is skipped (the GPU suite runs the same protocol
-through silero_vad_amd's own callers, tests/test_gpu_parity.py)."""
-import sys
-import types
+were run from the reference checkout with a `HipSileroVAD` whose engine is the CPU replay engine (tests/replay_engine.py: the
+oracle behind the engine's Python surface), i.e. everything of the drop-in except the kernels.  What they did is stored in
+tests/golden/golden_callers.json (tests/golden/make_caller_golden.py): every call they made on the model object -- reset_states(),
+model(x, sr) with the fixture samples x held -- what the model returned, and what the caller returned.  These tests replay those call
+transcripts on a fresh model object (protocol, validation, state ownership, shapes and dtypes the reference code relies on), require
+the same probabilities, and hold the callers' results against what the reference produced with its own model
+(tests/golden/golden_segments.json) and against silero_vad_amd's own callers and native scanner on the same probabilities."""
+import json
 import warnings
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import SRS
+from conftest import GOLD, SRS
 
-REF_SRC = Path("/root/reference/src")
-pytestmark = pytest.mark.skipif(not (REF_SRC / "silero_vad" / "utils_vad.py").exists(),
-                                reason="reference checkout not present (GPU box)")
+PROB_TOL = 1e-6          # the replay engine is the CPU oracle both times: the same probabilities up to the oracle's own round-off
 
 
 @pytest.fixture(scope="module")
-def ref():
-    """`silero_vad.utils_vad` exactly as shipped; only torchaudio (file I/O helpers, not on the path) is stubbed."""
-    if "torchaudio" not in sys.modules:
-        stub = types.ModuleType("torchaudio")
-        stub.__version__ = "2.8.0"
-        sys.modules["torchaudio"] = stub
-    sys.path.insert(0, str(REF_SRC))
-    try:
-        import silero_vad.utils_vad as uv
-    finally:
-        sys.path.remove(str(REF_SRC))
-    assert Path(uv.__file__).resolve().is_relative_to(REF_SRC)
-    return uv
+def callers():
+    return json.loads((GOLD / "golden_callers.json").read_text())
+
+
+def replay(model, wav, rec):
+    """Make exactly the calls a reference caller made on its model object (rec["calls"]) on `model`; the model must answer
+    each one the way the caller uses it (a [1, 1] float32 tensor, `.item()` a float) with the recorded probability."""
+    got = []
+    for c in rec["calls"]:
+        if c[0] == "reset":
+            model.reset_states()
+            continue
+        _, start, n, sr = c
+        out = model(wav[start:start + n], sr)
+        assert out.shape == (1, 1) and out.dtype == torch.float32
+        p = out.item()
+        assert isinstance(p, float)
+        got.append(p)
+    got = np.asarray(got, dtype=np.float32)
+    assert len(got) == len(rec["probs"]) and np.abs(got - np.asarray(rec["probs"], dtype=np.float32)).max() <= PROB_TOL
+    return got
 
 
 @pytest.fixture()
@@ -49,49 +54,62 @@ def model(oracle):
 
 
 @pytest.mark.parametrize("tag", ["16k", "8k"])
-def test_reference_get_speech_timestamps_accepts_the_model(ref, model, golden, tag):
-    sr, info = SRS[tag], golden["segments"][tag]
+def test_reference_get_speech_timestamps_accepts_the_model(callers, model, golden, tag):
+    from silero_vad_amd import get_speech_timestamps
+    from silero_vad_amd.timestamps import segment_probs
+    sr, info, rec = SRS[tag], golden["segments"][tag], callers["get_speech_timestamps"][tag]
     n_use = 400 * (512 if sr == 16000 else 256)               # 400 chunks: the per-chunk Python loop is slow
-    wav = torch.from_numpy(golden[tag]["wav"][:n_use])
-    got = ref.get_speech_timestamps(wav, model, sampling_rate=sr)
+    assert rec["n_use"] == n_use
+    wav = torch.from_numpy(golden[tag]["wav"])
+    probs = replay(model, wav, rec["default"])
+    assert rec["default"]["calls"][0] == ["reset"] and len(probs) == 400
     assert model.engine.calls["step"] == 400 and model.engine.calls["forward_audio"] == 0   # the per-chunk protocol
     # the same call through the reference's own model produced info["timestamps"]["default"] for the WHOLE file;
     # every segment that closes well inside the prefix must be identical
+    got = rec["default"]["out"]
     want = [s for s in info["timestamps"]["default"]["out"] if s["end"] < n_use - 16000]
     assert len(want) >= 1 and got[:len(want)] == want
+    # the reference's scan over these probabilities is the native scanner's
+    assert segment_probs(probs, n_use, sr) == got
     # seconds / other kwargs take the same code path in the caller; one more variant for the argument plumbing
-    got = ref.get_speech_timestamps(wav, model, sampling_rate=sr, threshold=0.3, return_seconds=True, time_resolution=3)
-    assert all(isinstance(s["start"], float) for s in got) and len(got) >= 1
+    v = rec["variant"]
+    replay(model, wav, v)
+    assert all(isinstance(s["start"], float) for s in v["out"]) and len(v["out"]) >= 1
+    assert get_speech_timestamps(wav[:n_use], model, sampling_rate=sr, **v["kwargs"]) == v["out"]
 
 
 @pytest.mark.parametrize("tag", ["16k", "8k"])
-def test_reference_vad_iterator_accepts_the_model(ref, model, golden, tag):
-    sr, info = SRS[tag], golden["segments"][tag]
+def test_reference_vad_iterator_accepts_the_model(callers, model, golden, tag):
+    from silero_vad_amd import VADIterator
+    sr, info, rec = SRS[tag], golden["segments"][tag], callers["vad_iterator"][tag]
     n = 512 if sr == 16000 else 256
-    it = ref.VADIterator(model, sampling_rate=sr)
     wav = torch.from_numpy(golden[tag]["wav"])
-    events = []
-    for s in range(0, 500 * n, n):
-        ev = it(wav[s:s + n])
-        if ev:
-            events.append(ev)
+    assert [c[1] for c in rec["calls"] if c[0] == "call"] == list(range(0, 500 * n, n))
+    replay(model, wav, rec)
+    assert rec["calls"][-1] == ["reset"] and len(model._state) == 0      # the iterator's reset_states() reached the model object
+    events = [ev for _, ev in rec["events"]]
     want = info["iterator"]["default"]["events"]
     assert len(events) >= 4 and events == want[:len(events)]
-    it.reset_states()
-    assert len(model._state) == 0                                # reset reached the model object
+    # silero_vad_amd's own iterator emits the same events at the same chunks
+    it = VADIterator(model, sampling_rate=sr)
+    ours = []
+    for i, s in enumerate(range(0, 500 * n, n)):
+        ev = it(wav[s:s + n])
+        if ev:
+            ours.append([i, ev])
+    assert ours == rec["events"]
 
 
-def test_reference_caller_and_own_caller_agree(ref, model, golden):
+def test_reference_caller_and_own_caller_agree(callers, model, golden):
     """silero_vad_amd.get_speech_timestamps (one audio_forward + native scan) == the reference's caller
     (per-chunk loop + Python scan) on the same model object."""
     from silero_vad_amd import get_speech_timestamps
-    sr = 16000
-    wav = torch.from_numpy(golden["16k"]["wav"][:300 * 512])
+    rec = callers["caller_agree"]
+    wav = torch.from_numpy(golden["16k"]["wav"][:rec["n_use"]])
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        a = ref.get_speech_timestamps(wav, model, sampling_rate=sr, min_silence_duration_ms=300, speech_pad_ms=100)
-        b = get_speech_timestamps(wav, model, sampling_rate=sr, min_silence_duration_ms=300, speech_pad_ms=100)
-    assert a == b and model.engine.calls["forward_audio"] == 1
+        b = get_speech_timestamps(wav, model, sampling_rate=rec["sr"], **rec["kwargs"])
+    assert len(rec["out"]) >= 1 and b == rec["out"] and model.engine.calls["forward_audio"] == 1
 
 
 def test_model_protocol_details_the_reference_relies_on(model):
@@ -105,28 +123,9 @@ def test_model_protocol_details_the_reference_relies_on(model):
     assert p.shape == (2, 2) and p.device.type == "cpu"
 
 
-class _Replay:
-    """Model object that replays given probabilities (protocol: utils_vad.py:57-92)."""
-
-    def __init__(self, probs):
-        self.probs, self.i = [float(p) for p in probs], 0
-
-    def reset_states(self):
-        self.i = 0
-
-    def __call__(self, x, sr):
-        p = self.probs[self.i]
-        self.i += 1
-        return torch.tensor([[p]], dtype=torch.float32)
-
-
-def test_native_scanner_equals_reference_scan_fuzz(ref, built):
-    """The native segmenter (csrc/scanner.hpp: O(1) state instead of the reference's `possible_ends` list) against the
-    reference's own Python scan (utils_vad.py:338-450) on random-walk probabilities and random argument sets, with the
-    emphasis on the max_speech_duration_s branches that the speech fixtures barely reach."""
-    from silero_vad_amd.timestamps import segment_probs
+def fuzz_cases():
+    """Random-walk probabilities and random argument sets (seeded): (sr, probs, audio length, kwargs) per case."""
     rng = np.random.default_rng(2024)
-    checked = with_cut = 0
     for case in range(160):
         sr = 16000 if case % 2 == 0 else 8000
         n = 512 if sr == 16000 else 256
@@ -145,12 +144,20 @@ def test_native_scanner_equals_reference_scan_fuzz(ref, built):
                   use_max_poss_sil_at_max_speech=bool(rng.integers(0, 2)))
         if rng.random() < 0.3:
             kw["neg_threshold"] = float(rng.choice([0.05, 0.2, 0.45, 0.8]))
-        audio = torch.zeros(audio_len)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            want = ref.get_speech_timestamps(audio, _Replay(probs), sampling_rate=sr, **kw)
+        yield sr, probs, audio_len, kw
+
+
+def test_native_scanner_equals_reference_scan_fuzz(callers, built):
+    """The native segmenter (csrc/scanner.hpp: O(1) state instead of the reference's `possible_ends` list) against the
+    reference's own Python scan (utils_vad.py:338-450, its results on these cases stored in golden_callers.json) on random-walk
+    probabilities and random argument sets, with the emphasis on the max_speech_duration_s branches that the speech fixtures barely reach."""
+    from silero_vad_amd.timestamps import segment_probs
+    wants = callers["scanner_fuzz"]
+    checked = with_cut = 0
+    for case, (sr, probs, audio_len, kw) in enumerate(fuzz_cases()):
+        want = wants[case]
         got = segment_probs(probs, audio_len, sr, **kw)
         assert got == want, (case, sr, kw, want[:3], got[:3])
         checked += 1
         with_cut += int(np.isfinite(kw["max_speech_duration_s"]) and len(want) > 1)
-    assert checked == 160 and with_cut > 30
+    assert checked == len(wants) == 160 and with_cut > 30

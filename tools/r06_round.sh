@@ -11,7 +11,7 @@ echo "pytest rc=$?" >> $out/pytest_gpu.log
 tail -n ${PYTEST_TAIL:-30} $out/pytest_gpu.log | cut -c1-400
 fi
 if [ -z "${SKIP_BENCH:-}" ]; then
-( time timeout 900 python bench.py "$@" ) > $out/bench.log 2> $out/bench.err; echo "bench rc=$?"
+( time timeout 900 python bench.py --full "$@" ) > $out/bench.log 2> $out/bench.err; echo "bench rc=$?"
 grep -v '^bench detail: ' $out/bench.err | tail -n 8
 grep '"metric"' $out/bench.log > $out/bench_line.json
 cp gpurun_out/bench_detail.json $out/bench_detail.json 2>/dev/null
