@@ -347,6 +347,22 @@ int  vad_pump_submit_compact(vad_pump *p, int r, const uint8_t *present);
  * VAD_ERR_ARG and nothing is queued.  n_rows == 0: a tick in which nobody delivers.  Results as vad_pump_submit_present with the same
  * set of streams, bit for bit.                                                                                                   */
 int  vad_pump_submit_rows(vad_pump *p, int r, const int32_t *stream_of_row, long n_rows);
+/* A PACKET tick -- what RTP / WebRTC / SIP receive paths deliver (10 / 20 / 30 ms frames, odd lengths after a loss): row i of slot r's
+ * sample area (vad_pump_slot(p, r) seen as one flat int16 array of streams * N samples) holds len_of_row[i] samples of stream
+ * stream_of_row[i], starting at sample offset off_of_row[i] -- a multiple of 8 samples, so that packets start on 16-byte boundaries
+ * (receive threads append with one atomic sample counter rounded up to 8).  1 <= len <= N.  A stream's packets are appended to what
+ * it has pending; a stream whose pending samples reach N this tick is stepped once on the first N of them and the rest stay pending;
+ * every other stream is absent (vad_pump_submit_present semantics).  Probabilities, events, (h, c) and context are bit for bit those of
+ * the same pump fed the concatenation of each stream's packets cut into N-sample chunks through vad_pump_submit_rows, each chunk at the
+ * tick its last sample arrived (the reference's VADIterator on the concatenated audio, utils_vad.py:507-549).  A packet longer than N
+ * (e.g. a 60 ms Opus frame at 16 kHz) is refused, not split: submit it over two ticks.  Invalid input is VAD_ERR_ARG and nothing is
+ * queued: a stream out of range or listed twice, a length out of range, an offset that is misaligned or runs past the slot.  The chunk
+ * routes (vad_pump_submit / _present / _compact / _rows) refuse (VAD_ERR_ARG, nothing queued) a chunk for a stream with samples
+ * pending; vad_pump_open / vad_pump_close drop a stream's pending samples.  One copy per tick: row table, flags, packet samples.       */
+int  vad_pump_submit_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *off_of_row, const int32_t *len_of_row,
+                             long n_rows);
+/* Samples of `stream` submitted in packets and not yet stepped (0 ... N - 1; host bookkeeping, no synchronisation); < 0: bad argument. */
+long vad_pump_pending(const vad_pump *p, int stream);
 /* Retire the OLDEST submitted tick: wait for it (block != 0) or return VAD_PUMP_BUSY, run the iterator logic of every open
  * stream over its probabilities and write the tick's events (stream order; at most `cap`, the return value is how many there
  * were, <= streams).  *slot = the ring slot that is free again.  The probabilities stay readable in vad_pump_probs(p, slot)

@@ -118,6 +118,11 @@ hipError_t launch_carry_absent(const uint8_t *present, const float *ctx_in, floa
 // A compact tick of the pump (vad_pump_submit_compact): row pos[b] of `src` (the delivering streams' chunks back to back, row_bytes each,
 // a multiple of 16) -> row b of `dst` for every b with present[b] != 0; rows of absent streams are not touched.  HBM to HBM.
 hipError_t launch_expand_rows(const uint8_t *present, const int32_t *pos, const uint8_t *src, void *dst, long row_bytes, int B, hipStream_t s);
+// A packet tick of the pump (vad_pump_submit_packets): table[i] = {stream b, sample offset into `pkt` (a multiple of 8), len (1 ... N),
+// pending c (0 ... N - 1)}, at most one row per stream.  carry [streams][N] int16 holds each stream's pending samples (in place).  c + len
+// >= N: row b of `batch` <- carry[b][0:c] ++ pkt[off:off + N - c], carry[b] <- the rest of the packet; otherwise carry[b][c:c + len] <-
+// the packet and row b of `batch` is not touched.  N <= 512.  HBM to HBM.
+hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int16_t *pkt, int16_t *carry, int16_t *batch, int N, hipStream_t s);
 // The same recurrence, bit for bit, for at most kRecSmallMaxB streams (1, 2 or 4 per workgroup): W_hh * h as matrix-vector products on the VALU (kernel_rec_small.hip);
 // `whh` points at the row image (layout.hpp "whh_rows").
 constexpr int kRecSmallMaxB = 1024;

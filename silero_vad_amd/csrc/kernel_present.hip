@@ -15,6 +15,13 @@
 //
 // expand_rows (compact ticks of the pump, pump.hip): the delivering streams' chunks crossed the link back to back; this pass copies row
 // pos[b] of that block to row b of the batch buffer the step kernels read -- HBM-bound byte work, 2 x B x N x 2 bytes at most.
+//
+// assemble_packets (packet ticks of the pump, pump.hip): receive paths deliver 10 / 20 / 30 ms frames, not 32 ms chunks.  The packets of
+// a tick crossed the link back to back (each starting on a 16-byte boundary); a device carry buffer [streams][N] holds what every stream
+// has pending.  A stream whose pending samples plus its packet reach N gets its batch row spliced together here (carry ++ packet head)
+// and keeps the packet's tail as its new carry; any other stream appends its packet to its carry.  The reference's VADIterator takes
+// one chunk per call (utils_vad.py:507-549): a packet stream is the concatenation of its packets, cut into chunks.  HBM-bound byte work:
+// 16-byte global loads and stores only, the splice at the unaligned pending length done in LDS.
 #include <hip/hip_runtime.h>
 
 #include "device_api.hpp"
@@ -47,7 +54,47 @@ __global__ void __launch_bounds__(256) expand_rows_kernel(const uint8_t *__restr
     dst[(size_t)b * vec_per_row + v] = __builtin_nontemporal_load(src + (size_t)pos[b] * vec_per_row + v);
 }
 
+// one wave per packet row, four rows per workgroup.  Each lane moves one 16-byte vector of the carry, of the packet and of the output
+// (N / 8 <= 64 vectors each).  The carry is updated in place: the wave's reads of its row finish before the first barrier, its writes
+// come after the second, and no other wave touches that row (one packet per stream and tick).
+using i16x8 = short __attribute__((ext_vector_type(8)));
+constexpr int kPacketRowsPerBlock = 4;
+
+__global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_packets_kernel(const int4 *__restrict__ table, long n_rows,
+                                                                                     const int16_t *__restrict__ pkt, int16_t *carry,
+                                                                                     i16x8 *__restrict__ batch, int N) {
+    __shared__ __attribute__((aligned(16))) short joined[kPacketRowsPerBlock][2 * 512];      // carry[0:c] ++ packet, < 2N samples
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * kPacketRowsPerBlock + w;
+    const bool live = i < n_rows;                // (no early return: the barriers are the workgroup's)
+    const int4 e = live ? table[i] : make_int4(0, 0, 0, 0);
+    const int b = e.x, off = e.y, len = e.z, c = e.w, at = lane * 8;
+    short *row = joined[w];
+    i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
+    i16x8 v = {};
+    if (at < len) v = __builtin_nontemporal_load(reinterpret_cast<const i16x8 *>(pkt + off) + lane);
+    if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
+    __syncthreads();
+    // the packet behind the pending samples, at the unaligned offset c
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (at + j < len) row[c + at + j] = v[j];
+    __syncthreads();
+    const int base = c + len >= N ? N : 0, rest = c + len - base;     // base N: a chunk is complete, the rest is the new carry
+    if (base && at < N) batch[(size_t)b * (N / 8) + lane] = *reinterpret_cast<const i16x8 *>(row + at);
+    if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
+}
+
 }  // namespace
+
+hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int16_t *pkt, int16_t *carry, int16_t *batch, int N, hipStream_t s) {
+    if (n_rows <= 0) return hipSuccess;
+    if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
+    const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
+    hipLaunchKernelGGL(assemble_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
+                       reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
+    return hipGetLastError();
+}
 
 hipError_t launch_expand_rows(const uint8_t *present, const int32_t *pos, const uint8_t *src, void *dst, long row_bytes, int B, hipStream_t s) {
     if (B <= 0) return hipSuccess;

@@ -38,6 +38,14 @@
 // stream (kernel_present.hip expand_rows: HBM to HBM, ~8 MB at most, a few us) puts every row where the step kernels read it.  The
 // link cost of a tick then falls with the delivery rate; everything behind the expansion is the masked tick, bit for bit.
 //
+// PACKET ticks (vad_pump_submit_packets): receive paths deliver 10 / 20 / 30 ms frames of any length up to N, not chunks.  Row i of the
+// slot's sample area is a packet of stream_of_row[i] at a 16-byte aligned offset; the host knows every length at submit time, so it
+// keeps each stream's pending count, writes a row table {stream, offset, length, pending before} in front of the flags and sets the flag
+// of every stream whose pending samples reach N.  ONE copy carries [row table | flags | packet samples] into the compact buffers, and
+// kernel_present.hip assemble_packets splices each completing stream's batch row from its device carry and the packet head (and keeps
+// the tail as the new carry) in place of expand_rows; everything behind it is the masked tick, bit for bit.  The chunk routes refuse a
+// stream with pending samples; while no stream has any, they run exactly as before.
+//
 // Waits block.  A source thread of a real server sleeps in its socket; the source threads of vad_pump_play, and its server loop, spin
 // for at most 20 us on the counter they wait for and then sleep on it (futex), whatever the CPU budget: one of eight ranks under a
 // 16-CPU quota has two CPUs for a server loop, a source thread and the HIP runtime's own threads, and a spinning (or yielding) thread
@@ -72,17 +80,19 @@ struct vad_pump {
     std::vector<int> lo, hi;                     // part k = streams [lo[k], hi[k])
     double threshold = 0.5, min_silence = 1600, pad = 480;
 
-    // a ring slot / a device batch buffer: [hpos bytes: int32 pos[streams], padded][hdr bytes: present[streams], padded][streams][N] int16
-    // (the position table is written and copied by compact ticks only: it lies in FRONT of the flags so that a masked tick's one copy
-    //  starts at the flags and a compact tick's one copy at the table)
-    size_t hpos = 0, hdr = 0, slot_bytes = 0;
+    // a ring slot / a device batch buffer: [htab bytes][hpos bytes: int32 pos[streams], padded][hdr bytes: present[streams], padded]
+    // [streams][N] int16 (the position table is written and copied by compact ticks only: it lies in FRONT of the flags so that a masked
+    // tick's one copy starts at the flags and a compact tick's one copy at the table; a packet tick's row table, 16 bytes per row, ends
+    // where the flags start and may reach back over the position table into htab)
+    size_t htab = 0, hpos = 0, hdr = 0, slot_bytes = 0;
     uint8_t *h_ring = nullptr;                   // [R] slots, page-locked ingest ring
     float *h_prob = nullptr;                     // [R][streams]      page-locked, mapped: the kernels store here
     float *d_prob = nullptr;                     // device alias of h_prob
     static constexpr int NB = 3;                 // device batch buffers
     int nb = NB;                                 // ... in use (A/B knob SILERO_VAD_AMD_PUMP_BUFFERS=2: profiles/r06_pump_three_buffers.md)
     uint8_t *d_batch = nullptr;                  // [NB] device batch buffers (same layout as a ring slot)
-    uint8_t *d_compact = nullptr;                // [NB] the same again: where a compact tick's copy lands
+    uint8_t *d_compact = nullptr;                // [NB] the same again: where a compact / packet tick's copy lands
+    int16_t *d_carry = nullptr;                  // [streams][N] the pending samples of every stream (packet ticks; in place)
     float *d_ctx[2] = {nullptr, nullptr};        // [streams][C]      ping-pong
     std::vector<float *> d_state;                // per part: [2][hi - lo][128]
     hipStream_t copy[2] = {nullptr, nullptr}, compute = nullptr;    // copy[t & 1]: the copies of tick t
@@ -104,12 +114,19 @@ struct vad_pump {
     struct Op { long at_tick; int stream; bool open; };
     std::deque<Op> pending;
     std::vector<long> src_pos;                   // vad_pump_play with a presence pattern: chunks stream b has delivered so far
+    std::vector<int32_t> held;                   // [streams] samples submitted in packets and not yet stepped (host bookkeeping)
+    long n_held = 0;                             // streams with held[b] > 0: the chunk routes check for them only while this is not 0
+    std::vector<uint8_t> seen;                   // [streams] scratch of the packet-row validation (all zero between calls)
     bool poisoned = false;                       // a tick failed half-way: the carried state is no longer what any caller expects
     std::string err;
 
-    int32_t *slot_pos(int r) const { return reinterpret_cast<int32_t *>(h_ring + (size_t)r * slot_bytes); }
-    uint8_t *slot_present(int r) const { return h_ring + (size_t)r * slot_bytes + hpos; }
-    int16_t *slot_pcm(int r) const { return reinterpret_cast<int16_t *>(h_ring + (size_t)r * slot_bytes + hpos + hdr); }
+    int32_t *slot_pos(int r) const { return reinterpret_cast<int32_t *>(h_ring + (size_t)r * slot_bytes + htab); }
+    uint8_t *slot_present(int r) const { return h_ring + (size_t)r * slot_bytes + htab + hpos; }
+    int16_t *slot_pcm(int r) const { return reinterpret_cast<int16_t *>(h_ring + (size_t)r * slot_bytes + htab + hpos + hdr); }
+    void drop_held(int b) {
+        n_held -= held[b] > 0;
+        held[b] = 0;
+    }
 };
 
 namespace {
@@ -268,6 +285,7 @@ void vad_pump_destroy(vad_pump *p) {
     for (float *s : p->d_state) (void)hipFree(s);
     if (p->d_batch) (void)hipFree(p->d_batch);
     if (p->d_compact) (void)hipFree(p->d_compact);
+    if (p->d_carry) (void)hipFree(p->d_carry);
     if (p->h_ring) (void)hipHostFree(p->h_ring);
     if (p->h_prob) (void)hipHostFree(p->h_prob);
     for (hipStream_t cs : p->copy)
@@ -318,7 +336,8 @@ int vad_pump_create(vad_engine *e, const vad_pump_params *prm, vad_pump **out) {
     const size_t S = (size_t)p->streams;
     p->hdr = (S + 4095) / 4096 * 4096;
     p->hpos = (S * sizeof(int32_t) + 4095) / 4096 * 4096;
-    p->slot_bytes = p->hpos + p->hdr + S * N * sizeof(int16_t);
+    p->htab = (S * 4 * sizeof(int32_t) + 4095) / 4096 * 4096 - p->hpos;
+    p->slot_bytes = p->htab + p->hpos + p->hdr + S * N * sizeof(int16_t);
     if (hipHostMalloc((void **)&p->h_ring, (size_t)p->R * p->slot_bytes, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&p->h_prob, (size_t)p->R * S * sizeof(float), hipHostMallocMapped) != hipSuccess)
         return bail(VAD_ERR_ALLOC);
@@ -329,7 +348,8 @@ int vad_pump_create(vad_engine *e, const vad_pump_params *prm, vad_pump **out) {
     if (hipHostGetDevicePointer(&dv, p->h_prob, 0) != hipSuccess || !dv) return bail(VAD_ERR_HIP);
     p->d_prob = static_cast<float *>(dv);
     if (hipMalloc((void **)&p->d_batch, vad_pump::NB * p->slot_bytes) != hipSuccess ||
-        hipMalloc((void **)&p->d_compact, vad_pump::NB * p->slot_bytes) != hipSuccess)
+        hipMalloc((void **)&p->d_compact, vad_pump::NB * p->slot_bytes) != hipSuccess ||
+        hipMalloc((void **)&p->d_carry, S * N * sizeof(int16_t)) != hipSuccess)
         return bail(VAD_ERR_ALLOC);
     // (compact ticks fill only the delivering streams' rows; rows no tick has filled yet are computed too: let them be silence)
     if (hipMemset(p->d_batch, 0, vad_pump::NB * p->slot_bytes) != hipSuccess) return bail(VAD_ERR_HIP);
@@ -372,6 +392,8 @@ int vad_pump_create(vad_engine *e, const vad_pump_params *prm, vad_pump **out) {
     p->temp_end.assign(S, 0);
     p->current.assign(S, 0);
     p->src_pos.assign(S, 0);
+    p->held.assign(S, 0);
+    p->seen.assign(S, 0);
     *out = p;
     return VAD_OK;
 }
@@ -397,9 +419,49 @@ const float *vad_pump_probs(const vad_pump *p, int r) {
 
 namespace {
 
+// a packet tick's rows (vad_pump_submit_packets)
+struct Packets {
+    const int32_t *stream, *off, *len;
+};
+
+// Validate a packet tick's rows and write its row table (ending where slot r's flags start) and its flags (the streams that complete
+// a chunk).  -> the samples of the slot's sample area the copy has to carry, or < 0 (VAD_ERR_ARG, p->err says why; nothing queued).
+long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows) {
+    const long S = p->streams, N = p->N;
+    if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
+        return pfail(p, VAD_ERR_ARG, "vad_pump_submit_packets: bad row list"), -1;
+    uint8_t *fl = p->slot_present(r);
+    int32_t *tab = reinterpret_cast<int32_t *>(fl) - 4 * n_rows;
+    std::memset(fl, 0, (size_t)S);
+    long end = 0, i = 0;
+    const char *why = nullptr;
+    for (; i < n_rows && !why; ++i) {
+        const int32_t b = pk.stream[i], off = pk.off[i], len = pk.len[i];
+        if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
+        else if (len < 1 || len > N) why = "a packet length out of 1 ... N (a longer packet goes in over two ticks)";
+        else if (off < 0 || off % 8 || (long)off + len > S * N) why = "a packet offset that is not a multiple of 8 samples, or runs past the slot";
+        else {
+            p->seen[b] = 1;
+            const int32_t c = p->held[b];
+            tab[4 * i] = b, tab[4 * i + 1] = off, tab[4 * i + 2] = len, tab[4 * i + 3] = c;
+            fl[b] = c + len >= N;
+            end = std::max(end, ((long)off + len + 7) / 8 * 8);
+        }
+    }
+    for (long k = 0; k < i; ++k)                 // (only valid streams were marked)
+        if (pk.stream[k] >= 0 && pk.stream[k] < S) p->seen[pk.stream[k]] = 0;
+    if (why) {
+        std::memset(fl, 0, (size_t)S);
+        return pfail(p, VAD_ERR_ARG, std::string("vad_pump_submit_packets: ") + why), -1;
+    }
+    return end;
+}
+
 // rows != nullptr: a compact tick whose rows lie in ARRIVAL order -- row i of the slot is the chunk of stream rows[i] (n_rows of them);
 // flags and positions are built here.  rows == nullptr && compact: row i is the i-th stream (ascending) whose flag is set.
-int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const int32_t *rows = nullptr, long n_rows = 0) {
+// pk != nullptr: a packet tick of n_rows rows (compact: its copy lands in the compact buffers, and masked).
+int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const int32_t *rows = nullptr, long n_rows = 0,
+                const Packets *pk = nullptr) {
     if (!p) return VAD_ERR_ARG;
     if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
     if (r < 0 || r >= p->R) return pfail(p, VAD_ERR_ARG, "vad_pump_submit: no such ring slot");
@@ -407,7 +469,11 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     PUMP_TRY(p, hipSetDevice(p->device));
     const int buf = (int)(p->ticks % p->nb), pp = (int)(p->ticks & 1);
     const size_t S = (size_t)p->streams, N = (size_t)p->N, C = (size_t)p->C;
-    if (rows != nullptr || n_rows != 0) {
+    long pk_samples = 0;                         // a packet tick: the samples of the slot's sample area its copy carries
+    if (pk) {
+        if ((pk_samples = build_packets(p, r, *pk, n_rows)) < 0) return VAD_ERR_ARG;
+        present = p->slot_present(r);
+    } else if (rows != nullptr || n_rows != 0) {
         if (!rows || n_rows < 0 || n_rows > (long)S) return pfail(p, VAD_ERR_ARG, "vad_pump_submit_rows: bad row list");
         uint8_t *fl = p->slot_present(r);
         int32_t *pos = p->slot_pos(r);
@@ -425,19 +491,27 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     }
     const bool masked = present != nullptr;
     if (compact && !masked) return pfail(p, VAD_ERR_ARG, "vad_pump_submit_compact: a compact tick needs its flags");
+    if (!pk && p->n_held > 0) {                  // a chunk may not overtake samples a stream has pending from its packets
+        for (size_t b = 0; b < S; ++b)
+            if (p->held[b] > 0 && (!masked || present[b]))
+                return pfail(p, VAD_ERR_ARG, "vad_pump_submit: stream " + std::to_string(b) +
+                                                 " has samples pending from packets; its next chunk must arrive as packets");
+    }
     if (masked && present != p->slot_present(r)) std::memcpy(p->slot_present(r), present, S);
-    uint8_t *dbuf = p->d_batch + (size_t)buf * p->slot_bytes;
+    uint8_t *dbuf = p->d_batch + (size_t)buf * p->slot_bytes + p->htab;
     int16_t *batch = reinterpret_cast<int16_t *>(dbuf + p->hpos + p->hdr);
     const uint8_t *d_present = masked ? dbuf + p->hpos : nullptr;
     uint8_t *cbuf = nullptr;                     // compact tick: where its one copy lands
     size_t n_present = 0;
     if (compact) {
-        cbuf = p->d_compact + (size_t)buf * p->slot_bytes;
+        cbuf = p->d_compact + (size_t)buf * p->slot_bytes + p->htab;
         d_present = cbuf + p->hpos;
         // the position table: row of the slot that holds stream b's chunk (the i-th delivering stream's chunk is row i)
         const uint8_t *fl = p->slot_present(r);
         int32_t *pos = p->slot_pos(r);
-        if (rows != nullptr) {
+        if (pk) {
+            // (no position table: the row table written with the flags lies over it)
+        } else if (rows != nullptr) {
             n_present = (size_t)n_rows;                  // (positions were written with the flags)
         } else {
             for (size_t b = 0; b < S; ++b) {
@@ -463,7 +537,17 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     } while (0)
     // the copies may not overwrite the batch buffer before the kernels of two ticks ago have read it
     if (p->batch_used[buf]) TICK_TRY(hipStreamWaitEvent(copy, p->batch_free[buf], 0));
-    if (compact) {
+    if (pk) {
+        // ONE copy: row table + flags + the packets; the assembly pass on the compute stream splices the completing streams' rows out
+        // of their carries and their packets (the carry's previous users and the batch buffer's previous readers are earlier there)
+        const size_t tab_bytes = (size_t)n_rows * 4 * sizeof(int32_t);
+        TICK_TRY(hipMemcpyAsync(cbuf + p->hpos - tab_bytes, p->slot_present(r) - tab_bytes, tab_bytes + p->hdr + pk_samples * sizeof(int16_t),
+                                hipMemcpyHostToDevice, copy));
+        TICK_TRY(hipEventRecord(p->h2d_done[buf][0], copy));
+        TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));
+        TICK_TRY(vad::launch_assemble_packets(reinterpret_cast<const int32_t *>(cbuf + p->hpos - tab_bytes), n_rows,
+                                              reinterpret_cast<const int16_t *>(cbuf + p->hpos + p->hdr), p->d_carry, batch, p->N, p->compute));
+    } else if (compact) {
         // ONE copy whatever `parts` says: table + flags + the delivering streams' rows; the expansion pass on the compute stream puts
         // every row where the kernels read it (the batch buffer's previous readers are earlier on that stream)
         TICK_TRY(hipMemcpyAsync(cbuf, p->slot_pos(r), p->hpos + p->hdr + n_present * N * sizeof(int16_t), hipMemcpyHostToDevice, copy));
@@ -492,6 +576,13 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     TICK_TRY(hipEventRecord(p->batch_free[buf], p->compute));
     TICK_TRY(hipEventRecord(p->tick_done[r], p->compute));
 #undef TICK_TRY
+    if (pk)                                      // the pending counts after this tick (the table holds each row's count before it)
+        for (long i = 0; i < n_rows; ++i) {
+            const int32_t b = pk->stream[i], c = p->held[b] + pk->len[i];
+            const int32_t now = c >= p->N ? c - p->N : c;
+            p->n_held += (now > 0) - (p->held[b] > 0);
+            p->held[b] = now;
+        }
     p->batch_used[buf] = true;
     p->slot_busy[r] = 1;
     p->inflight.push_back(vad_pump::Flight{r, masked});
@@ -515,6 +606,17 @@ int vad_pump_submit_rows(vad_pump *p, int r, const int32_t *stream_of_row, long 
 }
 
 int vad_pump_submit(vad_pump *p, int r) { return submit_tick(p, r, nullptr, false); }
+
+int vad_pump_submit_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *off_of_row, const int32_t *len_of_row,
+                            long n_rows) {
+    const Packets pk{stream_of_row, off_of_row, len_of_row};
+    return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+long vad_pump_pending(const vad_pump *p, int stream) {
+    if (!p || stream < 0 || stream >= p->streams) return -1;
+    return p->held[stream];
+}
 
 long vad_pump_poll(vad_pump *p, int block, vad_iter_event *out, long cap, int *slot) {
     if (!p || cap < 0 || (cap > 0 && !out)) return VAD_PUMP_ERROR;
@@ -565,6 +667,7 @@ int vad_pump_open(vad_pump *p, int stream) {
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + row * 128, 0, 128 * sizeof(float), p->compute));
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + (n + row) * 128, 0, 128 * sizeof(float), p->compute));
     PUMP_TRY(p, hipMemsetAsync(p->d_ctx[p->ticks & 1] + (size_t)stream * p->C, 0, (size_t)p->C * sizeof(float), p->compute));
+    p->drop_held(stream);                        // (the device carry needs nothing: the next packet tick's table says 0 samples pending)
     // ... and the host side (iterator state, active flag) when those ticks have been retired: their probabilities belong to the slot's
     // previous occupant and must neither advance the new stream's sample counter nor open a segment for it
     p->pending.push_back(vad_pump::Op{p->ticks, stream, true});
@@ -579,7 +682,8 @@ int vad_pump_close(vad_pump *p, int stream) {
     if (!p) return VAD_ERR_ARG;
     if (stream < 0 || stream >= p->streams) return pfail(p, VAD_ERR_ARG, "vad_pump_close: no such stream");
     // the slot is still computed (lock-step batch) but emits no events -- from the next tick submitted on: the ticks in flight carry
-    // chunks the stream did deliver, their events are still its own
+    // chunks the stream did deliver, their events are still its own; samples it has pending are dropped
+    p->drop_held(stream);
     p->pending.push_back(vad_pump::Op{p->ticks, stream, false});
     if (p->inflight.empty()) {
         p->retired = p->ticks;

@@ -1833,6 +1833,10 @@ class StreamPump:
         events, r = pump.poll()                                  # retire the oldest tick: [(stream, {'start' | 'end': sample}), ...]
         pump.probs(r)                                            # its probabilities, [streams] float32 (page-locked)
 
+    Streams that arrive in 10 / 20 / 30 ms packets: `pump.write_packets(r, [(stream, int16 packet), ...])` (or the packets written
+    into `packet_area(r)` + `submit_packets(r, streams, lengths, offsets)`); the device cuts each stream's concatenated packets into
+    chunks, and `pending(stream)` says how many samples wait for the next one.
+
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
     def __init__(self, engine, sampling_rate: int = 16000, streams: int = 8192, parts: int = 0, ring_slots: int = 0,
@@ -1907,6 +1911,60 @@ class StreamPump:
         other stream is absent this tick.  A stream listed twice, or out of range, raises and queues nothing."""
         rows = np.ascontiguousarray(stream_of_row, dtype=np.int32).reshape(-1)
         self._check(self._L.vad_pump_submit_rows(self._h, int(r), rows.ctypes.data if len(rows) else None, len(rows)))
+
+    def packet_area(self, r: int) -> np.ndarray:
+        """Slot r's sample area as one flat int16 array of streams * N samples (page-locked): where a packet tick's packets go."""
+        return self._slots[r].reshape(-1)
+
+    def submit_packets(self, r: int, streams, lengths, offsets=None):
+        """A PACKET tick (vad_pump_submit_packets): row i of `packet_area(r)` holds lengths[i] samples (1 ... N) of stream streams[i]
+        at sample offset offsets[i] (a multiple of 8; None = the rows back to back, each rounded up to 8 samples).  Each stream's
+        packets are appended to what it has pending; a stream whose pending samples reach N is stepped on the first N of them, every
+        other stream is absent this tick.  A stream listed twice or out of range, a bad length or offset raises and queues nothing."""
+        def table(x, name):
+            a = np.asarray(x)
+            if a.ndim != 1 or (a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < -2**31 or a.max() >= 2**31)):
+                raise ValueError(f"{name} must be a 1-D sequence of int32 values, got {a.dtype} of shape {a.shape}")
+            return np.ascontiguousarray(a, dtype=np.int32)
+
+        st, ln = table(streams, "streams"), table(lengths, "lengths")
+        off = None if offsets is None else table(offsets, "offsets")
+        if len(ln) != len(st) or (off is not None and len(off) != len(st)):
+            raise ValueError(f"streams, lengths and offsets must have one entry per packet, got {len(st)}, {len(ln)}, "
+                             f"{len(st) if off is None else len(off)}")
+        if off is None:
+            off = np.zeros(len(st), np.int32)
+            if len(st):
+                off[1:] = np.cumsum((ln[:-1].astype(np.int64) + 7) // 8 * 8)
+        n = len(st)
+        self._check(self._L.vad_pump_submit_packets(self._h, int(r), *(x.ctypes.data if n else None for x in (st, off, ln)), n))
+
+    def write_packets(self, r: int, packets):
+        """Pack [(stream, int16 samples), ...] back to back (each rounded up to 8 samples) into `packet_area(r)` and submit the packet
+        tick -- the convenience form for tests and small servers."""
+        area = self.packet_area(r)
+        streams, lengths, offsets, at = [], [], [], 0
+        for s, x in packets:
+            x = np.asarray(x)
+            if x.dtype != np.int16 or x.ndim != 1:
+                raise ValueError("a packet must be a 1-D int16 array")
+            if not 1 <= len(x) <= self.n:
+                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {len(x)} (submit a longer one over two ticks)")
+            if at + len(x) > len(area):
+                raise ValueError("the packets do not fit into the slot")
+            area[at:at + len(x)] = x
+            streams.append(s)
+            lengths.append(len(x))
+            offsets.append(at)
+            at += (len(x) + 7) // 8 * 8
+        self.submit_packets(r, streams, lengths, offsets)
+
+    def pending(self, stream: int) -> int:
+        """Samples of `stream` submitted in packets and not yet stepped (0 ... N - 1)."""
+        v = self._L.vad_pump_pending(self._h, int(stream))
+        if v < 0:
+            raise ValueError(f"no such stream: {stream}")
+        return int(v)
 
     def poll(self, block: bool = True):
         """-> (events, ring slot) of the oldest submitted tick; (None, None) if nothing is in flight or (block=False) it has not finished."""
