@@ -361,6 +361,23 @@ int  vad_pump_submit_rows(vad_pump *p, int r, const int32_t *stream_of_row, long
  * pending; vad_pump_open / vad_pump_close drop a stream's pending samples.  One copy per tick: row table, flags, packet samples.       */
 int  vad_pump_submit_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *off_of_row, const int32_t *len_of_row,
                              long n_rows);
+/* Sample formats of a packet row: 16-bit linear PCM, ITU-T G.711 mu-law (PCMU) or A-law (PCMA), 1 byte per sample (SIP trunks,
+ * telephony media streams: 8 kHz).                                                                                              */
+enum { VAD_PCM_S16 = 0, VAD_PCM_ULAW = 1, VAD_PCM_ALAW = 2 };
+/* A packet tick whose rows may be G.711: row i of slot r's sample area (seen as streams * N * 2 BYTES) holds len_of_row[i] samples
+ * (1 ... N) of stream stream_of_row[i] in format codec_of_row[i] (VAD_PCM_*; NULL = every row VAD_PCM_S16), starting at BYTE offset
+ * byte_off_of_row[i], a multiple of 16; the row takes len bytes (G.711) or 2 * len bytes (S16).  The device expands G.711 to int16
+ * (the values of vad_g711_expand) on its way into the stream's chunk, so results are bit for bit those of vad_pump_submit_packets fed
+ * the expanded int16 packets, and a stream may change its format from one packet to the next.  The payload of an RTP packet goes into
+ * the slot as it came off the wire: half the host and link bytes of int16.  Invalid input is VAD_ERR_ARG and nothing is queued: a
+ * bad codec, a stream out of range or listed twice, a length out of 1 ... N, a byte offset that is not a multiple of 16 or a row that
+ * runs past the slot.  Pending samples, open / close and the chunk routes' refusal behave as for vad_pump_submit_packets.           */
+int  vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
+                                   const int32_t *len_of_row, const uint8_t *codec_of_row, long n_rows);
+/* n samples in format `codec` at `in` (n bytes for G.711, n int16 for VAD_PCM_S16: copied) -> out[0 .. n) int16 on the host: ITU-T
+ * G.711 expansion, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2), from the same definition the device uses.  VAD_OK, or
+ * VAD_ERR_ARG for a bad codec, n < 0 or a NULL buffer with n > 0.                                                               */
+int  vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out);
 /* Samples of `stream` submitted in packets and not yet stepped (0 ... N - 1; host bookkeeping, no synchronisation); < 0: bad argument. */
 long vad_pump_pending(const vad_pump *p, int stream);
 /* Retire the OLDEST submitted tick: wait for it (block != 0) or return VAD_PUMP_BUSY, run the iterator logic of every open

@@ -123,6 +123,30 @@ hipError_t launch_expand_rows(const uint8_t *present, const int32_t *pos, const 
 // >= N: row b of `batch` <- carry[b][0:c] ++ pkt[off:off + N - c], carry[b] <- the rest of the packet; otherwise carry[b][c:c + len] <-
 // the packet and row b of `batch` is not touched.  N <= 512.  HBM to HBM.
 hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int16_t *pkt, int16_t *carry, int16_t *batch, int N, hipStream_t s);
+// The same for a tick with G.711 rows (vad_pump_submit_coded_packets): table[i] = {stream b, BYTE offset into `pkt` (a multiple of 16),
+// len | codec << kCodecShift (codec VAD_PCM_S16 / _ULAW / _ALAW), pending c}; a G.711 row is expanded to int16 (g711_to_s16) on its way
+// into the carry / the batch row.  Only ticks with at least one G.711 row take this kernel.
+constexpr int kCodecShift = 16;
+hipError_t launch_assemble_coded_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
+                                         hipStream_t s);
+
+// ITU-T G.711 code -> 16-bit linear PCM, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2).  The one definition the pump's
+// assembly kernel (kernel_present.hip) and the host export vad_g711_expand (pump.hip) share.
+__host__ __device__ inline int16_t ulaw_to_s16(uint8_t code) {
+    const unsigned u = ~code & 0xffu;                                        // sign, 3-bit exponent, 4-bit mantissa, sent inverted
+    const int t = (int)((((u & 0x0fu) << 3) + 0x84u) << ((u & 0x70u) >> 4));
+    return (int16_t)((u & 0x80u) ? 0x84 - t : t - 0x84);
+}
+__host__ __device__ inline int16_t alaw_to_s16(uint8_t code) {
+    const unsigned a = code ^ 0x55u;                                         // sign, 3-bit segment, 4-bit mantissa, even bits inverted
+    const unsigned seg = (a & 0x70u) >> 4;
+    const int m = (int)((a & 0x0fu) << 4);
+    const int t = seg == 0 ? m + 8 : (m + 0x108) << (seg - 1);
+    return (int16_t)((a & 0x80u) ? t : -t);
+}
+__host__ __device__ inline int16_t g711_to_s16(int codec, uint8_t code) {
+    return codec == VAD_PCM_ULAW ? ulaw_to_s16(code) : alaw_to_s16(code);
+}
 // The same recurrence, bit for bit, for at most kRecSmallMaxB streams (1, 2 or 4 per workgroup): W_hh * h as matrix-vector products on the VALU (kernel_rec_small.hip);
 // `whh` points at the row image (layout.hpp "whh_rows").
 constexpr int kRecSmallMaxB = 1024;

@@ -22,6 +22,10 @@
 // and keeps the packet's tail as its new carry; any other stream appends its packet to its carry.  The reference's VADIterator takes
 // one chunk per call (utils_vad.py:507-549): a packet stream is the concatenation of its packets, cut into chunks.  HBM-bound byte work:
 // 16-byte global loads and stores only, the splice at the unaligned pending length done in LDS.
+//
+// assemble_coded_packets (packet ticks with G.711 rows, vad_pump_submit_coded_packets): the same splice, with mu-law / A-law rows
+// crossing the link at 1 byte a sample and expanded to int16 in registers between their 16-byte load and the LDS row.  Ticks with
+// only int16 rows keep taking assemble_packets.
 #include <hip/hip_runtime.h>
 
 #include "device_api.hpp"
@@ -85,6 +89,44 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_packets_ker
     if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
 }
 
+// assemble_packets for a tick with G.711 rows: the row table's offsets are in bytes and len carries the row's codec in its high bits
+// (uniform across the wave).  An S16 row moves as above; a G.711 row's lane loads 16 codes (16 bytes, N / 16 <= 32 lanes cover a row),
+// expands them in registers and writes them into the LDS row at c + 16 * lane.  The carry and batch stores are those of
+// assemble_packets: the carry holds expanded int16, whatever format the packets arrived in.
+using u32x4 = unsigned __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_coded_packets_kernel(const int4 *__restrict__ table, long n_rows,
+                                                                                           const uint8_t *__restrict__ pkt, int16_t *carry,
+                                                                                           i16x8 *__restrict__ batch, int N) {
+    __shared__ __attribute__((aligned(16))) short joined[kPacketRowsPerBlock][2 * 512];      // carry[0:c] ++ packet, < 2N samples
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * kPacketRowsPerBlock + w;
+    const bool live = i < n_rows;                // (no early return: the barriers are the workgroup's)
+    const int4 e = live ? table[i] : make_int4(0, 0, 0, 0);
+    const int b = e.x, off = e.y, len = e.z & ((1 << kCodecShift) - 1), codec = e.z >> kCodecShift, c = e.w, at = lane * 8;
+    short *row = joined[w];
+    i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
+    const int from = codec == VAD_PCM_S16 ? at : lane * 16;         // the lane's first sample of the packet: 16 bytes hold 8 or 16
+    u32x4 v = {};
+    if (from < len) v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(pkt + off) + lane);
+    if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
+    __syncthreads();
+    // the packet behind the pending samples, at the unaligned offset c
+    if (codec == VAD_PCM_S16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (from + j < len) row[c + from + j] = (short)(v[j >> 1] >> (16 * (j & 1)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (from + j < len) row[c + from + j] = g711_to_s16(codec, (uint8_t)(v[j >> 2] >> (8 * (j & 3))));
+    }
+    __syncthreads();
+    const int base = c + len >= N ? N : 0, rest = c + len - base;     // base N: a chunk is complete, the rest is the new carry
+    if (base && at < N) batch[(size_t)b * (N / 8) + lane] = *reinterpret_cast<const i16x8 *>(row + at);
+    if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
+}
+
 }  // namespace
 
 hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int16_t *pkt, int16_t *carry, int16_t *batch, int N, hipStream_t s) {
@@ -92,6 +134,16 @@ hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int1
     if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
     const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
     hipLaunchKernelGGL(assemble_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
+                       reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_coded_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
+                                         hipStream_t s) {
+    if (n_rows <= 0) return hipSuccess;
+    if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
+    const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
+    hipLaunchKernelGGL(assemble_coded_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
                        reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
     return hipGetLastError();
 }

@@ -44,7 +44,9 @@
 // of every stream whose pending samples reach N.  ONE copy carries [row table | flags | packet samples] into the compact buffers, and
 // kernel_present.hip assemble_packets splices each completing stream's batch row from its device carry and the packet head (and keeps
 // the tail as the new carry) in place of expand_rows; everything behind it is the masked tick, bit for bit.  The chunk routes refuse a
-// stream with pending samples; while no stream has any, they run exactly as before.
+// stream with pending samples; while no stream has any, they run exactly as before.  vad_pump_submit_coded_packets: the same tick with
+// rows that may be G.711 mu-law / A-law (1 byte a sample, byte offsets); a tick with such a row takes assemble_coded_packets, which
+// expands them to int16 on the device, and the carry holds int16 whatever the packets were.
 //
 // Waits block.  A source thread of a real server sleeps in its socket; the source threads of vad_pump_play, and its server loop, spin
 // for at most 20 us on the counter they wait for and then sleep on it (futex), whatever the CPU budget: one of eight ranks under a
@@ -419,17 +421,29 @@ const float *vad_pump_probs(const vad_pump *p, int r) {
 
 namespace {
 
-// a packet tick's rows (vad_pump_submit_packets)
+// a packet tick's rows (vad_pump_submit_packets; vad_pump_submit_coded_packets: `coded`, offsets in bytes, codec per row or null)
 struct Packets {
     const int32_t *stream, *off, *len;
+    bool coded = false;
+    const uint8_t *codec = nullptr;
 };
 
 // Validate a packet tick's rows and write its row table (ending where slot r's flags start) and its flags (the streams that complete
-// a chunk).  -> the samples of the slot's sample area the copy has to carry, or < 0 (VAD_ERR_ARG, p->err says why; nothing queued).
-long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows) {
+// a chunk).  -> the bytes of the slot's sample area the copy has to carry, or < 0 (VAD_ERR_ARG, p->err says why; nothing queued).
+// *g711: a row is mu-law or A-law -- the table then holds byte offsets and each row's codec in the high bits of its length, for
+// assemble_coded_packets; otherwise it holds sample offsets, for assemble_packets, whichever entry point was called.
+long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g711) {
     const long S = p->streams, N = p->N;
+    const char *fn = pk.coded ? "vad_pump_submit_coded_packets: " : "vad_pump_submit_packets: ";
     if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
-        return pfail(p, VAD_ERR_ARG, "vad_pump_submit_packets: bad row list"), -1;
+        return pfail(p, VAD_ERR_ARG, std::string(fn) + "bad row list"), -1;
+    *g711 = false;
+    for (long i = 0; pk.codec && i < n_rows; ++i) {
+        if (pk.codec[i] > VAD_PCM_ALAW)
+            return pfail(p, VAD_ERR_ARG, std::string(fn) + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) +
+                                             " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW"), -1;
+        *g711 |= pk.codec[i] != VAD_PCM_S16;
+    }
     uint8_t *fl = p->slot_present(r);
     int32_t *tab = reinterpret_cast<int32_t *>(fl) - 4 * n_rows;
     std::memset(fl, 0, (size_t)S);
@@ -437,22 +451,26 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows) {
     const char *why = nullptr;
     for (; i < n_rows && !why; ++i) {
         const int32_t b = pk.stream[i], off = pk.off[i], len = pk.len[i];
+        const int codec = pk.codec ? pk.codec[i] : VAD_PCM_S16;
+        const long at = pk.coded ? off : 2L * off, bytes = codec == VAD_PCM_S16 ? 2L * len : len;      // the row, in bytes
         if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
         else if (len < 1 || len > N) why = "a packet length out of 1 ... N (a longer packet goes in over two ticks)";
-        else if (off < 0 || off % 8 || (long)off + len > S * N) why = "a packet offset that is not a multiple of 8 samples, or runs past the slot";
+        else if (at < 0 || at % 16 || at + bytes > S * N * 2)
+            why = pk.coded ? "a packet byte offset that is not a multiple of 16, or a row that runs past the slot"
+                           : "a packet offset that is not a multiple of 8 samples, or runs past the slot";
         else {
             p->seen[b] = 1;
             const int32_t c = p->held[b];
-            tab[4 * i] = b, tab[4 * i + 1] = off, tab[4 * i + 2] = len, tab[4 * i + 3] = c;
+            tab[4 * i] = b, tab[4 * i + 1] = (int32_t)(*g711 ? at : at / 2), tab[4 * i + 2] = len | codec << vad::kCodecShift, tab[4 * i + 3] = c;
             fl[b] = c + len >= N;
-            end = std::max(end, ((long)off + len + 7) / 8 * 8);
+            end = std::max(end, (at + bytes + 15) / 16 * 16);
         }
     }
     for (long k = 0; k < i; ++k)                 // (only valid streams were marked)
         if (pk.stream[k] >= 0 && pk.stream[k] < S) p->seen[pk.stream[k]] = 0;
     if (why) {
         std::memset(fl, 0, (size_t)S);
-        return pfail(p, VAD_ERR_ARG, std::string("vad_pump_submit_packets: ") + why), -1;
+        return pfail(p, VAD_ERR_ARG, std::string(fn) + why), -1;
     }
     return end;
 }
@@ -469,9 +487,10 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     PUMP_TRY(p, hipSetDevice(p->device));
     const int buf = (int)(p->ticks % p->nb), pp = (int)(p->ticks & 1);
     const size_t S = (size_t)p->streams, N = (size_t)p->N, C = (size_t)p->C;
-    long pk_samples = 0;                         // a packet tick: the samples of the slot's sample area its copy carries
+    long pk_bytes = 0;                           // a packet tick: the bytes of the slot's sample area its copy carries
+    bool g711 = false;                           // ... and it has a mu-law / A-law row
     if (pk) {
-        if ((pk_samples = build_packets(p, r, *pk, n_rows)) < 0) return VAD_ERR_ARG;
+        if ((pk_bytes = build_packets(p, r, *pk, n_rows, &g711)) < 0) return VAD_ERR_ARG;
         present = p->slot_present(r);
     } else if (rows != nullptr || n_rows != 0) {
         if (!rows || n_rows < 0 || n_rows > (long)S) return pfail(p, VAD_ERR_ARG, "vad_pump_submit_rows: bad row list");
@@ -541,12 +560,16 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         // ONE copy: row table + flags + the packets; the assembly pass on the compute stream splices the completing streams' rows out
         // of their carries and their packets (the carry's previous users and the batch buffer's previous readers are earlier there)
         const size_t tab_bytes = (size_t)n_rows * 4 * sizeof(int32_t);
-        TICK_TRY(hipMemcpyAsync(cbuf + p->hpos - tab_bytes, p->slot_present(r) - tab_bytes, tab_bytes + p->hdr + pk_samples * sizeof(int16_t),
+        TICK_TRY(hipMemcpyAsync(cbuf + p->hpos - tab_bytes, p->slot_present(r) - tab_bytes, tab_bytes + p->hdr + pk_bytes,
                                 hipMemcpyHostToDevice, copy));
         TICK_TRY(hipEventRecord(p->h2d_done[buf][0], copy));
         TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));
-        TICK_TRY(vad::launch_assemble_packets(reinterpret_cast<const int32_t *>(cbuf + p->hpos - tab_bytes), n_rows,
-                                              reinterpret_cast<const int16_t *>(cbuf + p->hpos + p->hdr), p->d_carry, batch, p->N, p->compute));
+        const int32_t *table = reinterpret_cast<const int32_t *>(cbuf + p->hpos - tab_bytes);
+        if (g711)                                // (G.711 rows are expanded on the way; an all-int16 tick takes the int16 kernel)
+            TICK_TRY(vad::launch_assemble_coded_packets(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->N, p->compute));
+        else
+            TICK_TRY(vad::launch_assemble_packets(table, n_rows, reinterpret_cast<const int16_t *>(cbuf + p->hpos + p->hdr), p->d_carry, batch,
+                                                  p->N, p->compute));
     } else if (compact) {
         // ONE copy whatever `parts` says: table + flags + the delivering streams' rows; the expansion pass on the compute stream puts
         // every row where the kernels read it (the batch buffer's previous readers are earlier on that stream)
@@ -611,6 +634,22 @@ int vad_pump_submit_packets(vad_pump *p, int r, const int32_t *stream_of_row, co
                             long n_rows) {
     const Packets pk{stream_of_row, off_of_row, len_of_row};
     return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
+                                  const int32_t *len_of_row, const uint8_t *codec_of_row, long n_rows) {
+    const Packets pk{stream_of_row, byte_off_of_row, len_of_row, true, codec_of_row};
+    return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out) {
+    if (codec < VAD_PCM_S16 || codec > VAD_PCM_ALAW || n < 0 || (n > 0 && (!in || !out))) return VAD_ERR_ARG;
+    if (codec == VAD_PCM_S16) {
+        if (n > 0) std::memmove(out, in, (size_t)n * sizeof(int16_t));
+        return VAD_OK;
+    }
+    for (long i = 0; i < n; ++i) out[i] = vad::g711_to_s16(codec, in[i]);
+    return VAD_OK;
 }
 
 long vad_pump_pending(const vad_pump *p, int stream) {

@@ -1822,6 +1822,55 @@ class BatchVADIterator:
         return [(ev[i].slot, {"end" if ev[i].kind else "start": ev[i].sample}) for i in range(m)]
 
 
+# sample formats of a packet row (include/silero_vad_hip.h VAD_PCM_*): int16, G.711 mu-law (PCMU), G.711 A-law (PCMA)
+_PCM = {"s16": 0, "ulaw": 1, "alaw": 2}
+
+
+def _codec_id(codec) -> int:
+    if isinstance(codec, str):
+        if codec not in _PCM:
+            raise ValueError(f"codec must be one of {sorted(_PCM)}, got {codec!r}")
+        return _PCM[codec]
+    if not isinstance(codec, (int, np.integer)) or int(codec) not in _PCM.values():
+        raise ValueError(f"codec must be one of {sorted(_PCM)} or {sorted(_PCM.values())}, got {codec!r}")
+    return int(codec)
+
+
+def _codec_rows(codecs) -> np.ndarray:
+    """Per-row codecs as uint8: names are mapped here, numbers go to the pump as they are (it refuses a bad one)."""
+    a = np.asarray(codecs)
+    if a.ndim != 1:
+        raise ValueError(f"codecs must be a 1-D sequence, got shape {a.shape}")
+    if a.dtype.kind in "US":
+        return np.array([_codec_id(str(c)) for c in a], np.uint8)
+    if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 255):
+        raise ValueError(f"codecs must be names or uint8 values, got {a.dtype}")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _int32_rows(x, name) -> np.ndarray:
+    a = np.asarray(x)
+    if a.ndim != 1 or (a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < -2**31 or a.max() >= 2**31)):
+        raise ValueError(f"{name} must be a 1-D sequence of int32 values, got {a.dtype} of shape {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def g711_expand(data, codec) -> np.ndarray:
+    """ITU-T G.711 codes -> int16 linear PCM (vad_g711_expand: the values of audioop.ulaw2lin / alaw2lin(x, 2), from the definition the
+    pump's device expansion uses).  codec "ulaw" / "alaw" takes uint8 codes, "s16" int16 samples (returned as a copy).  Same shape.
+    A G.711 stream for `model(chunk, 8000)` or `StreamPump.write_packets`: `g711_expand(payload, "ulaw")`."""
+    c = _codec_id(codec)
+    x = np.ascontiguousarray(data)
+    want = np.int16 if c == _PCM["s16"] else np.uint8
+    if x.dtype != want:
+        raise ValueError(f"{codec!r} data must be {np.dtype(want).name}, got {x.dtype}")
+    out = np.empty(x.shape, np.int16)
+    rc = lib().vad_g711_expand(c, x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None)
+    if rc:
+        raise _lib.VadError(rc, "vad_g711_expand")
+    return out
+
+
 class StreamPump:
     """BASELINE configs[4] through the native pump (include/silero_vad_hip.h "live streams: the pump", csrc/pump.hip): `streams`
     live streams on one GPU, host int16 chunks in, VADIterator events out, with no Python and no torch on the per-tick path
@@ -1835,7 +1884,9 @@ class StreamPump:
 
     Streams that arrive in 10 / 20 / 30 ms packets: `pump.write_packets(r, [(stream, int16 packet), ...])` (or the packets written
     into `packet_area(r)` + `submit_packets(r, streams, lengths, offsets)`); the device cuts each stream's concatenated packets into
-    chunks, and `pending(stream)` says how many samples wait for the next one.
+    chunks, and `pending(stream)` says how many samples wait for the next one.  G.711 (PCMU / PCMA) packets go in as they came off
+    the wire, 1 byte a sample: `pump.write_coded_packets(r, [(stream, packet, "ulaw" | "alaw" | "s16"), ...])` (or `packet_bytes(r)` +
+    `submit_coded_packets(...)`); the device expands them.
 
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
@@ -1958,6 +2009,54 @@ class StreamPump:
             offsets.append(at)
             at += (len(x) + 7) // 8 * 8
         self.submit_packets(r, streams, lengths, offsets)
+
+    def packet_bytes(self, r: int) -> np.ndarray:
+        """Slot r's sample area as one flat uint8 array of streams * N * 2 bytes (page-locked): where a coded packet tick's rows go."""
+        return self._slots[r].reshape(-1).view(np.uint8)
+
+    def submit_coded_packets(self, r: int, streams, lengths, codecs, byte_offsets=None):
+        """A packet tick whose rows may be G.711 (vad_pump_submit_coded_packets): row i of `packet_bytes(r)` holds lengths[i] samples
+        (1 ... N) of stream streams[i] in format codecs[i] -- "s16" (2 bytes a sample), "ulaw" or "alaw" (1 byte), or the VAD_PCM_*
+        numbers; None = every row "s16" -- at byte offset byte_offsets[i] (a multiple of 16; None = the rows back to back, each
+        rounded up to 16 bytes).  The device expands G.711 to int16: the same results, bit for bit, as `submit_packets` with the rows
+        expanded by `g711_expand`.  A bad codec, stream, length or offset raises and queues nothing."""
+        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
+        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
+        cd = None if codecs is None else _codec_rows(codecs)
+        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (cd is not None and len(cd) != len(st)):
+            raise ValueError(f"streams, lengths, codecs and byte_offsets must have one entry per packet, got {len(st)}, {len(ln)}, "
+                             f"{len(st) if cd is None else len(cd)}, {len(st) if off is None else len(off)}")
+        if off is None:
+            nbytes = ln.astype(np.int64) * (2 if cd is None else np.where(cd == _PCM["s16"], 2, 1))
+            off = np.zeros(len(st), np.int32)
+            if len(st):
+                off[1:] = np.cumsum((nbytes[:-1] + 15) // 16 * 16)
+        n = len(st)
+        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [cd.ctypes.data if n and cd is not None else None]
+        self._check(self._L.vad_pump_submit_coded_packets(self._h, int(r), *ptrs, n))
+
+    def write_coded_packets(self, r: int, packets):
+        """Pack [(stream, samples, codec), ...] back to back (each rounded up to 16 bytes) into `packet_bytes(r)` and submit the tick:
+        codec "s16" takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes (an RTP payload as it came off the wire)."""
+        area = self.packet_bytes(r)
+        streams, lengths, codecs, offsets, at = [], [], [], [], 0
+        for s, x, codec in packets:
+            c = _codec_id(codec)
+            x = np.asarray(x)
+            want = np.int16 if c == _PCM["s16"] else np.uint8
+            if x.dtype != want or x.ndim != 1:
+                raise ValueError(f"a {codec!r} packet must be a 1-D {np.dtype(want).name} array, got {x.dtype} of shape {x.shape}")
+            if not 1 <= len(x) <= self.n:
+                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {len(x)} (submit a longer one over two ticks)")
+            if at + x.nbytes > len(area):
+                raise ValueError("the packets do not fit into the slot")
+            area[at:at + x.nbytes] = x.view(np.uint8)
+            streams.append(s)
+            lengths.append(len(x))
+            codecs.append(c)
+            offsets.append(at)
+            at += (x.nbytes + 15) // 16 * 16
+        self.submit_coded_packets(r, streams, lengths, np.array(codecs, np.uint8), offsets)
 
     def pending(self, stream: int) -> int:
         """Samples of `stream` submitted in packets and not yet stepped (0 ... N - 1)."""

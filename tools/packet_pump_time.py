@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
-"""The pump's packet route (vad_pump_submit_packets) against its chunk route (vad_pump_submit_rows) at full capacity: 8 192 streams at
-16 kHz, every stream delivering a 20 ms packet (320 samples) per packet tick against a 32 ms chunk (512 samples) per chunk tick, rows
-in a shuffled arrival order, two ticks in flight.  The ring slots are written once before the timed window: this times the device
-side and the link, not a receive path's host writes.  Prints one JSON line: per-tick time, link bytes per tick, the share of a plain
-pinned -> HBM copy's rate that reaches, and the time per second of audio of both routes (equal audio throughput).
+"""The pump's packet route (vad_pump_submit_packets) against its chunk route (vad_pump_submit_rows) at full capacity: 8 192 streams,
+every stream delivering a 20 ms packet per packet tick against a chunk (32 ms) per chunk tick, rows in a shuffled arrival order, two
+ticks in flight.  The ring slots are written once before the timed window: this times the device side and the link, not a receive
+path's host writes.  Prints one JSON line: per-tick time, link bytes per tick, the share of a plain pinned -> HBM copy's rate that
+reaches, and the time per second of audio of every route (equal audio throughput).
 
-    python tools/packet_pump_time.py [ticks] [reps]
+    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs]
 
-assemble_packets_kernel's own time: run it under `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/packet_pump_time.py`
-(in a run of its own) and read the kernel's line of the stats file."""
+sr: 16000 (default) or 8000.  codecs: a comma-separated list of packet formats, timed alternately with the chunk route -- "s16" (the
+default: int16 packets through vad_pump_submit_packets), "ulaw" / "alaw" (G.711 packets, 1 byte a sample, through
+vad_pump_submit_coded_packets; the device expands them).  The telephony case: `python tools/packet_pump_time.py 2000 3 8000 s16,ulaw,alaw`.
+
+assemble_packets_kernel's / assemble_coded_packets_kernel's own time: run it under
+`rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/packet_pump_time.py ...` (in a run of its own) and read the
+kernels' lines of the stats file."""
 import json
 import sys
 import time
@@ -18,6 +23,20 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
+def g711_encode(pcm, law):
+    """int16 -> the G.711 code whose expansion is nearest (what an encoder on the far side of the trunk would have sent)."""
+    import numpy as np
+    from silero_vad_amd import g711_expand
+    codes = np.arange(256, dtype=np.uint8)
+    lin = g711_expand(codes, law).astype(np.int32)
+    order = np.argsort(lin, kind="stable")
+    v = lin[order]
+    x = pcm.astype(np.int32)
+    j = np.clip(np.searchsorted(v, x), 1, len(v) - 1)
+    j -= (x - v[j - 1]) <= (v[j] - x)
+    return codes[order[j]]
+
+
 def main():
     import numpy as np
     import torch
@@ -25,7 +44,12 @@ def main():
     from silero_vad_amd import Engine, StreamPump
     ticks = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-    S, sr, N, P, R = 8192, 16000, 512, 320, 4
+    sr = int(sys.argv[3]) if len(sys.argv) > 3 else 16000
+    codecs = sys.argv[4].split(",") if len(sys.argv) > 4 else ["s16"]
+    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw"}:
+        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw]")
+    S, R = 8192, 4
+    N, P = (512 if sr == 16000 else 256), sr // 50                     # a chunk, a 20 ms packet (samples)
     dev = torch.device("cuda", 0)
     eng = Engine(device=0)
     link = bench.h2d_rate_GBps(dev)
@@ -33,32 +57,43 @@ def main():
     rng = np.random.default_rng(0)
     order = rng.permutation(S).astype(np.int32)
     page = lambda b: (b + 4095) // 4096 * 4096                          # noqa: E731  (the slot's header areas, csrc/pump.hip)
-    routes = {
-        # row table (16 bytes a row) + flags + the packets
-        "packets": {"bytes": 16 * S + page(S) + S * P * 2, "ms_audio": 1000.0 * P / sr},
-        # position table + flags + the chunks
-        "chunks": {"bytes": page(4 * S) + page(S) + S * N * 2, "ms_audio": 1000.0 * N / sr},
-    }
+    # route -> packet format (None: the chunk route)
+    names = {"s16": "packets", "ulaw": "packets_ulaw", "alaw": "packets_alaw"}
+    fmt = {names[c]: c for c in codecs}
+    fmt["chunks"] = None
+    routes = {}
+    for name, c in fmt.items():
+        if c is None:                                                   # position table + flags + the chunks
+            routes[name] = {"bytes": page(4 * S) + page(S) + S * N * 2, "ms_audio": 1000.0 * N / sr}
+        else:                                                           # row table (16 bytes a row) + flags + the packets
+            row = P * (2 if c == "s16" else 1)
+            routes[name] = {"bytes": 16 * S + page(S) + S * ((row + 15) // 16 * 16), "ms_audio": 1000.0 * P / sr}
     pumps = {}
-    for name in routes:
+    for name, c in fmt.items():
         pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R)
         for r in range(R):
-            if name == "packets":
+            if c is None:
+                pump.slot(r)[:] = rows[order]
+            elif c == "s16":
                 pump.packet_area(r)[:S * P].reshape(S, P)[:] = rows[order, :P]
             else:
-                pump.slot(r)[:] = rows[order]
+                pump.packet_bytes(r)[:S * P].reshape(S, P)[:] = g711_encode(rows[order, :P], c)
         pumps[name] = pump
-    lengths, offsets = np.full(S, P, np.int32), (np.arange(S) * P).astype(np.int32)
+    lengths = np.full(S, P, np.int32)
+    offsets = (np.arange(S) * P).astype(np.int32)                       # samples (s16) or bytes (G.711): 16-byte aligned either way
+    codec_rows = {"ulaw": np.full(S, 1, np.uint8), "alaw": np.full(S, 2, np.uint8)}
 
     def run(name, n):
-        pump = pumps[name]
+        pump, c = pumps[name], fmt[name]
         inflight = 0
         t0 = time.perf_counter()
         for t in range(n):
-            if name == "packets":
+            if c is None:
+                pump.submit_rows(t % R, order)
+            elif c == "s16":
                 pump.submit_packets(t % R, order, lengths, offsets)
             else:
-                pump.submit_rows(t % R, order)
+                pump.submit_coded_packets(t % R, order, lengths, codec_rows[c], offsets)
             inflight += 1
             if inflight >= 2:
                 pump.poll()
@@ -80,7 +115,9 @@ def main():
         out[name] = {"tick_us": round(tick_s * 1e6, 1), "link_bytes_per_tick": info["bytes"],
                      "link_GBps": round(info["bytes"] / tick_s / 1e9, 2), "of_link": round(info["bytes"] / tick_s / 1e9 / link, 3),
                      "ms_per_s_audio": round(tick_s * 1e3 / (info["ms_audio"] / 1000.0), 2)}
-    out["packets_over_chunks_per_s_audio"] = round(out["packets"]["ms_per_s_audio"] / out["chunks"]["ms_per_s_audio"], 3)
+    for name in routes:
+        if name != "chunks":
+            out[f"{name}_over_chunks_per_s_audio"] = round(out[name]["ms_per_s_audio"] / out["chunks"]["ms_per_s_audio"], 3)
     for pump in pumps.values():
         pump.close()
     print(json.dumps(out))
