@@ -374,6 +374,36 @@ enum { VAD_PCM_S16 = 0, VAD_PCM_ULAW = 1, VAD_PCM_ALAW = 2 };
  * runs past the slot.  Pending samples, open / close and the chunk routes' refusal behave as for vad_pump_submit_packets.           */
 int  vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
                                    const int32_t *len_of_row, const uint8_t *codec_of_row, long n_rows);
+/* BURST ticks -- a 60 ms Opus frame is longer than a chunk, a jitter buffer that waited out a stall releases several packets of one
+ * stream at once, a stream that fell behind must catch up: in a burst tick a stream may be listed in any number of rows, a row may be
+ * longer than N, and a stream that thereby completes several chunks is stepped that many times, in order, inside the one tick.
+ * vad_pump_set_burst(p, max_chunks) enables them: 1 ... VAD_PUMP_MAX_BURST chunks per stream and tick (8 chunks are 256 ms: deeper than
+ * the jitter buffers this is meant for); only while no tick is in flight (VAD_ERR_ARG otherwise).  It allocates what sub-steps
+ * 1 ... max_chunks - 1 need, linear in max_chunks: one device buffer [max_chunks - 1][streams][N] int16 (59 MB at 8 192 streams, 16 kHz,
+ * 8 chunks), their flag rows, and page-locked probabilities [ring_slots][max_chunks - 1][streams].  A pump on which it was never called
+ * allocates none of that and runs every other route through the code it always ran.
+ * vad_pump_submit_burst: rows as in vad_pump_submit_coded_packets (byte offsets, multiples of 16; codec per row or NULL = all S16),
+ * except that a stream may be listed more than once and len may exceed N.  Per stream, the samples of its rows are appended, in row
+ * order, behind what it has pending; with c pending before and L new samples it completes k = (c + L) / N chunks and keeps
+ * (c + L) % N pending.  The tick runs steps = max(1, largest k) sub-steps; sub-step j is a masked step (vad_step_present) of the
+ * streams with k > j on their chunk j.  Probabilities, (h, c), context, pending samples and events are bit for bit those of the same
+ * pump fed the same concatenated audio, cut into chunks, through vad_pump_submit_rows, one chunk per stream and tick; a burst tick in
+ * which no stream is listed twice and no row is longer than N gives exactly what vad_pump_submit_coded_packets gives.  Refused with
+ * VAD_ERR_ARG, nothing queued, the pending counts untouched: bursts not enabled; a stream that would complete more than max_chunks
+ * chunks; n_rows above `streams` (the row table stays 16 bytes x streams); a bad codec, a stream out of range, len < 1, a misaligned
+ * offset, a row that runs past the slot's sample area.  That area stays streams * N * 2 bytes, so not every stream can burst fully in
+ * the same tick: the rows of one tick hold at most `streams` chunks of int16 (twice that of G.711).  One H2D copy per tick, as before.
+ * vad_pump_poll returns such a tick's events sub-step by sub-step (sub-step 0's in stream order, then sub-step 1's, ...): up to
+ * steps x streams of them, and one stream may have a start and an end in the same poll.  vad_pump_burst_steps: the sub-steps slot r's
+ * last tick ran (1 for every tick of another route; < 0: bad argument).  vad_pump_burst_probs(p, r, j): [streams] of sub-step j
+ * (j = 0: vad_pump_probs(p, r)), VAD_PROB_ABSENT where k <= j; NULL on a bad argument (j beyond max_chunks - 1 included).
+ * vad_pump_pending, vad_pump_open / _close and the chunk routes' refusal behave as for packet ticks.                                */
+#define VAD_PUMP_MAX_BURST 8
+int  vad_pump_set_burst(vad_pump *p, int max_chunks);
+int  vad_pump_submit_burst(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
+                           const uint8_t *codec_of_row, long n_rows);
+int  vad_pump_burst_steps(const vad_pump *p, int r);
+const float *vad_pump_burst_probs(const vad_pump *p, int r, int j);
 /* n samples in format `codec` at `in` (n bytes for G.711, n int16 for VAD_PCM_S16: copied) -> out[0 .. n) int16 on the host: ITU-T
  * G.711 expansion, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2), from the same definition the device uses.  VAD_OK, or
  * VAD_ERR_ARG for a bad codec, n < 0 or a NULL buffer with n > 0.                                                               */
@@ -382,7 +412,7 @@ int  vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out);
 long vad_pump_pending(const vad_pump *p, int stream);
 /* Retire the OLDEST submitted tick: wait for it (block != 0) or return VAD_PUMP_BUSY, run the iterator logic of every open
  * stream over its probabilities and write the tick's events (stream order; at most `cap`, the return value is how many there
- * were, <= streams).  *slot = the ring slot that is free again.  The probabilities stay readable in vad_pump_probs(p, slot)
+ * were, <= streams; a burst tick: <= its sub-steps x streams).  *slot = the ring slot that is free again.  The probabilities stay readable in vad_pump_probs(p, slot)
  * until that slot's next tick.                                                                                             */
 long vad_pump_poll(vad_pump *p, int block, vad_iter_event *out, long cap, int *slot);
 const float *vad_pump_probs(const vad_pump *p, int r);   /* [streams] */

@@ -129,6 +129,17 @@ hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int1
 constexpr int kCodecShift = 16;
 hipError_t launch_assemble_coded_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
                                          hipStream_t s);
+// A burst tick of the pump (vad_pump_submit_burst): a stream may have several rows and a row may be longer than N.  The table's rows are
+// GROUPED BY STREAM, a stream's rows in arrival order: table[i] = {stream b, BYTE offset into `pkt` (a multiple of 16), len | codec <<
+// kCodecShift, w}, w = pending c | k << kCodecShift on the first row of a stream (k = (c + the stream's lengths) / N chunks complete,
+// k <= max_chunks) and < 0 on its other rows.  The work unit is the stream: carry[b][0:c] ++ row ++ row ... is cut into chunks of N;
+// chunk 0 -> row b of `batch`, chunk j >= 1 -> row b of more[j - 1] (`more` = [max_chunks - 1][streams][N]), the remainder -> carry[b]
+// (in place).  N <= 512, a multiple of 16.
+hipError_t launch_assemble_burst(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int16_t *more,
+                                 int max_chunks, int streams, int N, hipStream_t s);
+// The flag rows of a burst tick's sub-steps 1 ... steps - 1: the tick's flag row holds k[b] (0 for a stream that completes no chunk),
+// flags[(j - 1) * ld + b] = k[b] > j.
+hipError_t launch_burst_flags(const uint8_t *k_of_stream, uint8_t *flags, long ld, int steps, int streams, hipStream_t s);
 
 // ITU-T G.711 code -> 16-bit linear PCM, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2).  The one definition the pump's
 // assembly kernel (kernel_present.hip) and the host export vad_g711_expand (pump.hip) share.

@@ -127,7 +127,91 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_coded_packe
     if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
 }
 
+// assemble_burst (burst ticks, vad_pump_submit_burst): several rows per stream, rows longer than N.  The two kernels above are one wave
+// per ROW and rely on nobody else touching the row's carry; with several rows of one stream in a tick the wave that writes the new carry
+// would race the wave that reads the old one.  Here the work unit is the STREAM.  The host grouped the table's rows by stream; the wave
+// whose row is the first of its stream walks that stream's rows in order, the waves of its other rows have nothing to do.  One wave is
+// one workgroup, so the walk (whose length differs from stream to stream) may use the workgroup barrier.  `joined` holds carry[0:c] ++
+// what has arrived since, always < 2N samples: a row goes in in pieces of at most N samples (16-byte loads: 8 samples of int16 or 16
+// G.711 codes a lane, expanded in registers, written at the unaligned fill), and whenever N samples are there they leave as one chunk
+// (16-byte stores) and the rest moves to the front.  What is left at the end (< N) is the new carry, stored in place.
+__global__ void __launch_bounds__(64) assemble_burst_kernel(const int4 *__restrict__ table, long n_rows, const uint8_t *__restrict__ pkt,
+                                                            int16_t *carry, i16x8 *__restrict__ batch, i16x8 *__restrict__ more,
+                                                            int max_chunks, long streams, int N) {
+    __shared__ __attribute__((aligned(16))) short joined[2 * 512];
+    const int lane = threadIdx.x, at = lane * 8;
+    const long i0 = blockIdx.x;
+    const int4 first = table[i0];
+    if (first.w < 0) return;                     // (uniform: not the first row of its stream)
+    const int b = first.x;
+    i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
+    int fill = first.w & ((1 << kCodecShift) - 1), chunk = 0;
+    if (at < fill) *reinterpret_cast<i16x8 *>(joined + at) = crow[lane];
+    __syncthreads();
+    for (long i = i0; i < n_rows; ++i) {
+        const int4 e = i == i0 ? first : table[i];
+        if (i != i0 && (e.x != b || e.w >= 0)) break;                           // the next stream's first row
+        const int len = e.z & ((1 << kCodecShift) - 1), codec = e.z >> kCodecShift;
+        const int per = codec == VAD_PCM_S16 ? 8 : 16;                         // samples in a lane's 16 bytes
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(pkt + e.y);
+        for (int s0 = 0; s0 < len; s0 += N) {                                   // a piece: samples [s0, s0 + n) of the row
+            const int n = min(N, len - s0), from = lane * per;
+            u32x4 v = {};
+            if (from < n) v = __builtin_nontemporal_load(src + s0 / per + lane);
+            short *dst = joined + fill + from;
+            if (codec == VAD_PCM_S16) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (from + j < n) dst[j] = (short)(v[j >> 1] >> (16 * (j & 1)));
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (from + j < n) dst[j] = g711_to_s16(codec, (uint8_t)(v[j >> 2] >> (8 * (j & 3))));
+            }
+            __syncthreads();
+            fill += n;
+            if (fill < N) continue;
+            // a chunk is complete: joined[0:N] leaves, joined[N:fill] moves to the front
+            const i16x8 out = *reinterpret_cast<const i16x8 *>(joined + at), rest = *reinterpret_cast<const i16x8 *>(joined + N + at);
+            if (at < N && chunk < max_chunks) {
+                i16x8 *row = chunk == 0 ? batch + (size_t)b * (N / 8) : more + ((size_t)(chunk - 1) * streams + b) * (N / 8);
+                row[lane] = out;
+            }
+            __syncthreads();
+            fill -= N;
+            ++chunk;
+            if (at < fill) *reinterpret_cast<i16x8 *>(joined + at) = rest;
+            __syncthreads();
+        }
+    }
+    if (at < fill) crow[lane] = *reinterpret_cast<const i16x8 *>(joined + at);
+}
+
+// one thread per (sub-step j >= 1, stream): flags[j - 1][b] = k[b] > j
+__global__ void __launch_bounds__(256) burst_flags_kernel(const uint8_t *__restrict__ k_of_stream, uint8_t *__restrict__ flags, long ld, int streams) {
+    const int b = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y + 1;
+    if (b < streams) flags[(size_t)(j - 1) * ld + b] = k_of_stream[b] > j;
+}
+
 }  // namespace
+
+hipError_t launch_assemble_burst(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int16_t *more,
+                                 int max_chunks, int streams, int N, hipStream_t s) {
+    if (n_rows <= 0) return hipSuccess;
+    if (!table || !pkt || !carry || !batch || (max_chunks > 1 && !more) || max_chunks < 1 || streams <= 0 || N <= 0 || N > 512 || N % 16)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(assemble_burst_kernel, dim3((unsigned)n_rows), dim3(64), 0, s, reinterpret_cast<const int4 *>(table), n_rows, pkt, carry,
+                       reinterpret_cast<i16x8 *>(batch), reinterpret_cast<i16x8 *>(more), max_chunks, (long)streams, N);
+    return hipGetLastError();
+}
+
+hipError_t launch_burst_flags(const uint8_t *k_of_stream, uint8_t *flags, long ld, int steps, int streams, hipStream_t s) {
+    if (steps <= 1 || streams <= 0) return hipSuccess;
+    if (!k_of_stream || !flags || ld < streams) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(burst_flags_kernel, dim3((unsigned)((streams + 255) / 256), (unsigned)(steps - 1)), dim3(256), 0, s, k_of_stream, flags, ld,
+                       streams);
+    return hipGetLastError();
+}
 
 hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int16_t *pkt, int16_t *carry, int16_t *batch, int N, hipStream_t s) {
     if (n_rows <= 0) return hipSuccess;

@@ -48,6 +48,14 @@
 // rows that may be G.711 mu-law / A-law (1 byte a sample, byte offsets); a tick with such a row takes assemble_coded_packets, which
 // expands them to int16 on the device, and the carry holds int16 whatever the packets were.
 //
+// BURST ticks (vad_pump_set_burst + vad_pump_submit_burst): a stream may have several rows in a tick and a row may be longer than N (a 60 ms
+// Opus frame; what a jitter buffer releases after a stall), so a stream may complete k <= max_chunks chunks.  The host groups the rows by
+// stream (a counting sort, arrival order kept) and writes k into the stream's flag byte -- every step kernel tests the flag as != 0, so
+// the count IS sub-step 0's flag; kernel_present.hip assemble_burst (one wave per stream) cuts carry ++ rows into chunks: chunk 0 into the
+// batch row, chunk j >= 1 into row b of d_more[j - 1], and burst_flags derives flags_j[b] = k[b] > j.  The tick then runs max(1, largest
+// k) masked steps back to back on the compute stream, sub-step j over d_more[j - 1] with its probabilities in h_prob_more.  d_more and its
+// flag rows are written and read on the compute stream only, in order: one buffer, not three.  Still ONE copy per tick.
+//
 // Waits block.  A source thread of a real server sleeps in its socket; the source threads of vad_pump_play, and its server loop, spin
 // for at most 20 us on the counter they wait for and then sleep on it (futex), whatever the CPU budget: one of eight ranks under a
 // 16-CPU quota has two CPUs for a server loop, a source thread and the HIP runtime's own threads, and a spinning (or yielding) thread
@@ -103,9 +111,10 @@ struct vad_pump {
     std::vector<hipEvent_t> tick_done;           // [R]
     bool batch_used[NB] = {false, false, false};
 
-    long ticks = 0;                              // ticks submitted so far (tick t: batch buffer t % NB, copy stream t & 1, context t & 1 -> (t + 1) & 1)
+    long ticks = 0;                              // ticks submitted so far (tick t: batch buffer t % NB, copy stream t & 1)
+    long flips = 0;                              // steps submitted so far (step s: context s & 1 -> (s + 1) & 1); == ticks until a burst tick runs several
     long retired = 0;                            // ticks retired so far (vad_pump_poll)
-    struct Flight { int r; bool masked; };
+    struct Flight { int r; bool masked; int steps = 1; };      // steps: the masked steps the tick ran (a burst tick: up to max_burst)
     std::deque<Flight> inflight;                 // the submitted, not yet retired ticks, oldest first
     std::vector<uint8_t> slot_busy;              // [R]
     // VADIterator state of every stream (utils_vad.py:500-503)
@@ -119,12 +128,26 @@ struct vad_pump {
     std::vector<int32_t> held;                   // [streams] samples submitted in packets and not yet stepped (host bookkeeping)
     long n_held = 0;                             // streams with held[b] > 0: the chunk routes check for them only while this is not 0
     std::vector<uint8_t> seen;                   // [streams] scratch of the packet-row validation (all zero between calls)
+    // burst ticks (vad_pump_set_burst; max_burst == 0: not enabled, none of this is allocated)
+    int max_burst = 0;                           // chunks a stream may complete in one tick
+    int16_t *d_more = nullptr;                   // [max_burst - 1][streams][N] the batch rows of sub-steps 1 ... (compute stream only)
+    uint8_t *d_more_flags = nullptr;             // [max_burst - 1][hdr]        their flag rows
+    float *h_prob_more = nullptr;                // [R][max_burst - 1][streams] page-locked, mapped: their probabilities
+    float *d_prob_more = nullptr;                // device alias of h_prob_more
+    std::vector<int> slot_steps;                 // [R] the steps the slot's last tick ran
+    std::vector<int32_t> b_len, b_cnt, b_pos;    // [streams] scratch of build_burst: new samples, rows, next table row (b_len, b_cnt: zero between calls)
+    std::vector<int32_t> b_touched;              // the streams a burst tick lists, by first appearance
+    struct Held { int32_t stream, now; };
+    std::vector<Held> b_new;                     // ... and what each has pending after the tick
     bool poisoned = false;                       // a tick failed half-way: the carried state is no longer what any caller expects
     std::string err;
 
     int32_t *slot_pos(int r) const { return reinterpret_cast<int32_t *>(h_ring + (size_t)r * slot_bytes + htab); }
     uint8_t *slot_present(int r) const { return h_ring + (size_t)r * slot_bytes + htab + hpos; }
     int16_t *slot_pcm(int r) const { return reinterpret_cast<int16_t *>(h_ring + (size_t)r * slot_bytes + htab + hpos + hdr); }
+    float *step_probs(int r, int j) const {      // host side; the device aliases have the same layout
+        return j == 0 ? h_prob + (size_t)r * streams : h_prob_more + ((size_t)r * (max_burst - 1) + (j - 1)) * streams;
+    }
     void drop_held(int b) {
         n_held -= held[b] > 0;
         held[b] = 0;
@@ -288,6 +311,9 @@ void vad_pump_destroy(vad_pump *p) {
     if (p->d_batch) (void)hipFree(p->d_batch);
     if (p->d_compact) (void)hipFree(p->d_compact);
     if (p->d_carry) (void)hipFree(p->d_carry);
+    if (p->d_more) (void)hipFree(p->d_more);
+    if (p->d_more_flags) (void)hipFree(p->d_more_flags);
+    if (p->h_prob_more) (void)hipHostFree(p->h_prob_more);
     if (p->h_ring) (void)hipHostFree(p->h_ring);
     if (p->h_prob) (void)hipHostFree(p->h_prob);
     for (hipStream_t cs : p->copy)
@@ -388,6 +414,7 @@ int vad_pump_create(vad_engine *e, const vad_pump_params *prm, vad_pump **out) {
     if (vad_reserve(p->eng, p->sr, maxB, 1) != VAD_OK) return bail(VAD_ERR_ALLOC);
     if (hipDeviceSynchronize() != hipSuccess) return bail(VAD_ERR_HIP);
     p->slot_busy.assign(p->R, 0);
+    p->slot_steps.assign(p->R, 1);
     p->active.assign(S, 1);
     p->feed_mask.assign(S, 1);
     p->triggered.assign(S, 0);
@@ -426,6 +453,7 @@ struct Packets {
     const int32_t *stream, *off, *len;
     bool coded = false;
     const uint8_t *codec = nullptr;
+    bool burst = false;                          // vad_pump_submit_burst: a stream may have several rows, a row may be longer than N
 };
 
 // Validate a packet tick's rows and write its row table (ending where slot r's flags start) and its flags (the streams that complete
@@ -475,6 +503,69 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
     return end;
 }
 
+// The same for a burst tick (vad_pump_submit_burst).  The row table is written GROUPED BY STREAM (a counting sort over the tick's rows:
+// streams by first appearance, a stream's rows in arrival order): {stream, byte offset, len | codec, w}, w = pending before | k <<
+// kCodecShift on a stream's first row, -1 on its others -- assemble_burst's work unit is the stream.  The flag byte of a listed stream
+// holds k, the chunks it completes (0 ... max_burst).  *steps = max(1, largest k).  The pending counts are NOT touched: p->b_new holds
+// them for the caller to apply once the tick is queued.
+long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps) {
+    const long S = p->streams, N = p->N, M = p->max_burst;
+    const std::string fn = "vad_pump_submit_burst: ";
+    if (M < 1) return pfail(p, VAD_ERR_ARG, fn + "bursts are not enabled on this pump (vad_pump_set_burst)"), -1;
+    if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
+        return pfail(p, VAD_ERR_ARG, fn + "bad row list (a tick holds at most `streams` rows)"), -1;
+    for (long i = 0; pk.codec && i < n_rows; ++i)
+        if (pk.codec[i] > VAD_PCM_ALAW)
+            return pfail(p, VAD_ERR_ARG, fn + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) +
+                                             " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW"), -1;
+    p->b_touched.clear();
+    p->b_new.clear();
+    long end = 0;
+    const char *why = nullptr;
+    for (long i = 0; i < n_rows && !why; ++i) {
+        const int32_t b = pk.stream[i];
+        const long at = pk.off[i], len = pk.len[i], bytes = (pk.codec ? pk.codec[i] : VAD_PCM_S16) == VAD_PCM_S16 ? 2 * len : len;
+        if (b < 0 || b >= S) why = "a stream out of range";
+        else if (len < 1) why = "a row length below 1";
+        else if (at < 0 || at % 16 || at + bytes > S * N * 2) why = "a row byte offset that is not a multiple of 16, or a row that runs past the slot";
+        else {
+            if (p->b_cnt[b]++ == 0) p->b_touched.push_back(b);
+            if (p->held[b] + p->b_len[b] + len >= (M + 1) * N) why = "a stream would complete more than max_chunks chunks in one tick";
+            else p->b_len[b] += (int32_t)len;
+            end = std::max(end, (at + bytes + 15) / 16 * 16);
+        }
+    }
+    if (why) {
+        for (const int32_t b : p->b_touched) p->b_cnt[b] = p->b_len[b] = 0;
+        return pfail(p, VAD_ERR_ARG, fn + why), -1;
+    }
+    int32_t row = 0, kmax = 0;
+    for (const int32_t b : p->b_touched) {
+        p->b_pos[b] = row;
+        row += p->b_cnt[b];
+    }
+    uint8_t *fl = p->slot_present(r);
+    int32_t *tab = reinterpret_cast<int32_t *>(fl) - 4 * n_rows;
+    std::memset(fl, 0, (size_t)S);
+    for (long i = 0; i < n_rows; ++i) {
+        const int32_t b = pk.stream[i], c = p->held[b], k = (int32_t)((c + p->b_len[b]) / N);
+        const bool first = p->b_cnt[b] != 0;                 // (the row count has done its work: positions are assigned)
+        p->b_cnt[b] = 0;
+        int32_t *e = tab + 4 * (size_t)p->b_pos[b]++;
+        e[0] = b, e[1] = pk.off[i], e[2] = pk.len[i] | (pk.codec ? pk.codec[i] : VAD_PCM_S16) << vad::kCodecShift;
+        e[3] = first ? c | k << vad::kCodecShift : -1;
+    }
+    for (const int32_t b : p->b_touched) {
+        const int32_t total = p->held[b] + p->b_len[b], k = (int32_t)(total / N);
+        fl[b] = (uint8_t)k;
+        kmax = std::max(kmax, k);
+        p->b_new.push_back(vad_pump::Held{b, (int32_t)(total - k * N)});
+        p->b_len[b] = 0;
+    }
+    *steps = std::max(1, kmax);
+    return end;
+}
+
 // rows != nullptr: a compact tick whose rows lie in ARRIVAL order -- row i of the slot is the chunk of stream rows[i] (n_rows of them);
 // flags and positions are built here.  rows == nullptr && compact: row i is the i-th stream (ascending) whose flag is set.
 // pk != nullptr: a packet tick of n_rows rows (compact: its copy lands in the compact buffers, and masked).
@@ -485,12 +576,13 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     if (r < 0 || r >= p->R) return pfail(p, VAD_ERR_ARG, "vad_pump_submit: no such ring slot");
     if (p->slot_busy[r]) return pfail(p, VAD_ERR_ARG, "vad_pump_submit: the slot's previous tick has not been retired (vad_pump_poll)");
     PUMP_TRY(p, hipSetDevice(p->device));
-    const int buf = (int)(p->ticks % p->nb), pp = (int)(p->ticks & 1);
+    const int buf = (int)(p->ticks % p->nb), pp = (int)(p->ticks & 1), cp = (int)(p->flips & 1);
     const size_t S = (size_t)p->streams, N = (size_t)p->N, C = (size_t)p->C;
     long pk_bytes = 0;                           // a packet tick: the bytes of the slot's sample area its copy carries
     bool g711 = false;                           // ... and it has a mu-law / A-law row
+    int steps = 1;                               // a burst tick: the masked steps it runs
     if (pk) {
-        if ((pk_bytes = build_packets(p, r, *pk, n_rows, &g711)) < 0) return VAD_ERR_ARG;
+        if ((pk_bytes = pk->burst ? build_burst(p, r, *pk, n_rows, &steps) : build_packets(p, r, *pk, n_rows, &g711)) < 0) return VAD_ERR_ARG;
         present = p->slot_present(r);
     } else if (rows != nullptr || n_rows != 0) {
         if (!rows || n_rows < 0 || n_rows > (long)S) return pfail(p, VAD_ERR_ARG, "vad_pump_submit_rows: bad row list");
@@ -540,8 +632,6 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         }
     }
     const int16_t *src = p->slot_pcm(r);
-    const float *ctx_in = p->d_ctx[pp];
-    float *ctx_out = p->d_ctx[pp ^ 1];
     hipStream_t copy = p->copy[pp];
     // from the first queued operation on, a failure leaves the tick half-done: (h, c) of some parts advanced, the context ping-pong out
     // of step.  There is no retry that is right; the pump says so from then on.
@@ -565,7 +655,11 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         TICK_TRY(hipEventRecord(p->h2d_done[buf][0], copy));
         TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));
         const int32_t *table = reinterpret_cast<const int32_t *>(cbuf + p->hpos - tab_bytes);
-        if (g711)                                // (G.711 rows are expanded on the way; an all-int16 tick takes the int16 kernel)
+        if (pk->burst) {                         // (chunk 0 of every stream into `batch`, chunks 1 ... into d_more; flags_j = k > j)
+            TICK_TRY(vad::launch_assemble_burst(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->d_more, p->max_burst, p->streams, p->N,
+                                                p->compute));
+            TICK_TRY(vad::launch_burst_flags(d_present, p->d_more_flags, (long)p->hdr, steps, p->streams, p->compute));
+        } else if (g711)                         // (G.711 rows are expanded on the way; an all-int16 tick takes the int16 kernel)
             TICK_TRY(vad::launch_assemble_coded_packets(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->N, p->compute));
         else
             TICK_TRY(vad::launch_assemble_packets(table, n_rows, reinterpret_cast<const int16_t *>(cbuf + p->hpos + p->hdr), p->d_carry, batch,
@@ -587,19 +681,31 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
             TICK_TRY(hipMemcpyAsync(batch + a * N, src + a * N, n * N * sizeof(int16_t), hipMemcpyHostToDevice, copy));
         TICK_TRY(hipEventRecord(p->h2d_done[buf][k], copy));
     }
-    for (int k = 0; k < p->parts; ++k) {
-        const size_t a = (size_t)p->lo[k];
-        const int n = p->hi[k] - p->lo[k];
-        if (!compact) TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][k], 0));
-        if (k > 0 && masked && !compact) TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));     // (the flags came with part 0)
-        const int rc = vad_step_present(p->eng, p->sr, n, batch + a * N, sizeof(int16_t), (long)N, ctx_in + a * C, ctx_out + a * C, p->d_state[k],
-                                        p->d_prob + (size_t)r * S + a, masked ? d_present + a : nullptr, p->compute);
-        if (rc != VAD_OK) return broken(rc, std::string("vad_step_present: ") + vad_last_error(p->eng));
+    for (int j = 0; j < steps; ++j) {            // (one step; a burst tick: sub-step j over the chunks j of the streams with k > j)
+        const int16_t *rows_j = j == 0 ? batch : p->d_more + (size_t)(j - 1) * S * N;
+        const uint8_t *flags_j = j == 0 ? d_present : p->d_more_flags + (size_t)(j - 1) * p->hdr;
+        float *probs_j = j == 0 ? p->d_prob + (size_t)r * S : p->d_prob_more + ((size_t)r * (p->max_burst - 1) + (j - 1)) * S;
+        const float *ctx_in = p->d_ctx[(cp + j) & 1];
+        float *ctx_out = p->d_ctx[(cp + j + 1) & 1];
+        for (int k = 0; k < p->parts; ++k) {
+            const size_t a = (size_t)p->lo[k];
+            const int n = p->hi[k] - p->lo[k];
+            if (!compact) TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][k], 0));
+            if (k > 0 && masked && !compact) TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));     // (the flags came with part 0)
+            const int rc = vad_step_present(p->eng, p->sr, n, rows_j + a * N, sizeof(int16_t), (long)N, ctx_in + a * C, ctx_out + a * C, p->d_state[k],
+                                            probs_j + a, masked ? flags_j + a : nullptr, p->compute);
+            if (rc != VAD_OK) return broken(rc, std::string("vad_step_present: ") + vad_last_error(p->eng));
+        }
     }
     TICK_TRY(hipEventRecord(p->batch_free[buf], p->compute));
     TICK_TRY(hipEventRecord(p->tick_done[r], p->compute));
 #undef TICK_TRY
-    if (pk)                                      // the pending counts after this tick (the table holds each row's count before it)
+    if (pk && pk->burst)                         // the pending counts after this tick
+        for (const vad_pump::Held &h : p->b_new) {
+            p->n_held += (h.now > 0) - (p->held[h.stream] > 0);
+            p->held[h.stream] = h.now;
+        }
+    else if (pk)                                 // (the table holds each row's count before it)
         for (long i = 0; i < n_rows; ++i) {
             const int32_t b = pk->stream[i], c = p->held[b] + pk->len[i];
             const int32_t now = c >= p->N ? c - p->N : c;
@@ -608,8 +714,10 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         }
     p->batch_used[buf] = true;
     p->slot_busy[r] = 1;
-    p->inflight.push_back(vad_pump::Flight{r, masked});
+    p->slot_steps[r] = steps;
+    p->inflight.push_back(vad_pump::Flight{r, masked, steps});
     ++p->ticks;
+    p->flips += steps;
     return VAD_OK;
 }
 
@@ -640,6 +748,64 @@ int vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_r
                                   const int32_t *len_of_row, const uint8_t *codec_of_row, long n_rows) {
     const Packets pk{stream_of_row, byte_off_of_row, len_of_row, true, codec_of_row};
     return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_pump_submit_burst(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
+                          const uint8_t *codec_of_row, long n_rows) {
+    Packets pk{stream_of_row, byte_off_of_row, len_of_row, true, codec_of_row};
+    pk.burst = true;
+    return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_pump_set_burst(vad_pump *p, int max_chunks) {
+    if (!p) return VAD_ERR_ARG;
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (max_chunks < 1 || max_chunks > VAD_PUMP_MAX_BURST) return pfail(p, VAD_ERR_ARG, "vad_pump_set_burst: max_chunks out of 1 ... VAD_PUMP_MAX_BURST");
+    if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, "vad_pump_set_burst: ticks in flight (retire them with vad_pump_poll first)");
+    if (max_chunks == p->max_burst) return VAD_OK;
+    PUMP_TRY(p, hipSetDevice(p->device));
+    PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    if (p->d_more) (void)hipFree(p->d_more);
+    if (p->d_more_flags) (void)hipFree(p->d_more_flags);
+    if (p->h_prob_more) (void)hipHostFree(p->h_prob_more);
+    p->d_more = nullptr, p->d_more_flags = nullptr, p->h_prob_more = p->d_prob_more = nullptr;
+    p->max_burst = 0;
+    const size_t S = (size_t)p->streams, more = (size_t)max_chunks - 1;
+    if (more > 0) {
+        // (a sub-step computes every row, also the rows of the streams that are absent from it.  Rows no burst has filled yet must hold
+        // samples, and NOT digital silence: behind a live stream's context a chunk of exact zeros is a chunk in which silence begins, and
+        // the frontend evaluates those in double precision, ~0.1 ms a row (kernel_exact.hip).  A small constant is an ordinary chunk.)
+        void *dv = nullptr;
+        const bool ok = hipMalloc((void **)&p->d_more, more * S * p->N * sizeof(int16_t)) == hipSuccess &&
+                        hipMalloc((void **)&p->d_more_flags, more * p->hdr) == hipSuccess &&
+                        hipHostMalloc((void **)&p->h_prob_more, (size_t)p->R * more * S * sizeof(float), hipHostMallocMapped) == hipSuccess &&
+                        hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(p->d_more), 256, more * S * p->N) == hipSuccess &&
+                        hipMemset(p->d_more_flags, 0, more * p->hdr) == hipSuccess &&
+                        hipHostGetDevicePointer(&dv, p->h_prob_more, 0) == hipSuccess && dv && hipDeviceSynchronize() == hipSuccess;
+        if (!ok) {
+            if (p->d_more) (void)hipFree(p->d_more);
+            if (p->d_more_flags) (void)hipFree(p->d_more_flags);
+            if (p->h_prob_more) (void)hipHostFree(p->h_prob_more);
+            p->d_more = nullptr, p->d_more_flags = nullptr, p->h_prob_more = nullptr;
+            return pfail(p, VAD_ERR_ALLOC, "vad_pump_set_burst: no memory for the sub-steps' buffers");
+        }
+        p->d_prob_more = static_cast<float *>(dv);
+        std::fill(p->h_prob_more, p->h_prob_more + (size_t)p->R * more * S, VAD_PROB_ABSENT);
+    }
+    p->b_len.assign(S, 0);
+    p->b_cnt.assign(S, 0);
+    p->b_pos.assign(S, 0);
+    p->b_touched.reserve(S);
+    p->b_new.reserve(S);
+    p->max_burst = max_chunks;
+    return VAD_OK;
+}
+
+int vad_pump_burst_steps(const vad_pump *p, int r) { return (p && r >= 0 && r < p->R) ? p->slot_steps[r] : -1; }
+
+const float *vad_pump_burst_probs(const vad_pump *p, int r, int j) {
+    if (!p || r < 0 || r >= p->R || j < 0 || j >= std::max(1, p->max_burst)) return nullptr;
+    return p->step_probs(r, j);
 }
 
 int vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out) {
@@ -679,14 +845,18 @@ long vad_pump_poll(vad_pump *p, int block, vad_iter_event *out, long cap, int *s
     p->slot_busy[r] = 0;
     if (slot) *slot = r;
     apply_ops(p);                                // opens / closes issued before this tick was submitted take effect with it
-    const uint8_t *mask = p->active.data();
-    if (f.masked) {                              // a stream without a chunk this tick: no model call, no iterator call (utils_vad.py:507-549)
-        const uint8_t *pr = p->slot_present(r);
-        for (int s = 0; s < p->streams; ++s) p->feed_mask[s] = p->active[s] & (pr[s] != 0);
-        mask = p->feed_mask.data();
+    long m = 0;
+    for (int j = 0; j < f.steps; ++j) {          // (one step; a burst tick: one iterator call per sub-step, its events behind the earlier ones)
+        const uint8_t *mask = p->active.data();
+        if (f.masked) {                          // a stream without a chunk this step: no model call, no iterator call (utils_vad.py:507-549)
+            const uint8_t *pr = p->slot_present(r);                              // (0 / 1; a burst tick: the chunks the stream completed)
+            for (int s = 0; s < p->streams; ++s) p->feed_mask[s] = p->active[s] & (pr[s] > j);
+            mask = p->feed_mask.data();
+        }
+        const long at = std::min(m, cap);
+        m += vad_iterator_feed(p->step_probs(r, j), mask, p->streams, p->N, p->threshold, p->min_silence, p->pad, p->triggered.data(),
+                               p->temp_end.data(), p->current.data(), out ? out + at : nullptr, cap - at);
     }
-    const long m = vad_iterator_feed(p->h_prob + (size_t)r * p->streams, mask, p->streams, p->N, p->threshold, p->min_silence, p->pad,
-                                     p->triggered.data(), p->temp_end.data(), p->current.data(), out, cap);
     ++p->retired;
     if (p->inflight.empty()) {                   // nothing in flight: later opens / closes have nothing to wait for
         p->retired = p->ticks;
@@ -705,7 +875,7 @@ int vad_pump_open(vad_pump *p, int stream) {
     const size_t n = (size_t)(p->hi[k] - p->lo[k]), row = (size_t)(stream - p->lo[k]);
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + row * 128, 0, 128 * sizeof(float), p->compute));
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + (n + row) * 128, 0, 128 * sizeof(float), p->compute));
-    PUMP_TRY(p, hipMemsetAsync(p->d_ctx[p->ticks & 1] + (size_t)stream * p->C, 0, (size_t)p->C * sizeof(float), p->compute));
+    PUMP_TRY(p, hipMemsetAsync(p->d_ctx[p->flips & 1] + (size_t)stream * p->C, 0, (size_t)p->C * sizeof(float), p->compute));
     p->drop_held(stream);                        // (the device carry needs nothing: the next packet tick's table says 0 samples pending)
     // ... and the host side (iterator state, active flag) when those ticks have been retired: their probabilities belong to the slot's
     // previous occupant and must neither advance the new stream's sample counter nor open a segment for it
@@ -741,7 +911,7 @@ int vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx) {
     const size_t n = (size_t)(p->hi[k] - p->lo[k]), row = (size_t)(stream - p->lo[k]);
     if (h) PUMP_TRY(p, hipMemcpy(h, p->d_state[k] + row * 128, 128 * sizeof(float), hipMemcpyDeviceToHost));
     if (c) PUMP_TRY(p, hipMemcpy(c, p->d_state[k] + (n + row) * 128, 128 * sizeof(float), hipMemcpyDeviceToHost));
-    if (ctx) PUMP_TRY(p, hipMemcpy(ctx, p->d_ctx[p->ticks & 1] + (size_t)stream * p->C, (size_t)p->C * sizeof(float), hipMemcpyDeviceToHost));
+    if (ctx) PUMP_TRY(p, hipMemcpy(ctx, p->d_ctx[p->flips & 1] + (size_t)stream * p->C, (size_t)p->C * sizeof(float), hipMemcpyDeviceToHost));
     return VAD_OK;
 }
 

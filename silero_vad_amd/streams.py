@@ -1886,14 +1886,19 @@ class StreamPump:
     into `packet_area(r)` + `submit_packets(r, streams, lengths, offsets)`); the device cuts each stream's concatenated packets into
     chunks, and `pending(stream)` says how many samples wait for the next one.  G.711 (PCMU / PCMA) packets go in as they came off
     the wire, 1 byte a sample: `pump.write_coded_packets(r, [(stream, packet, "ulaw" | "alaw" | "s16"), ...])` (or `packet_bytes(r)` +
-    `submit_coded_packets(...)`); the device expands them.
+    `submit_coded_packets(...)`); the device expands them.  With `max_burst=M` (2 ... 8) a tick may be a BURST:
+    `pump.write_burst(r, [(stream, packet[, codec]), ...])` takes any number of packets of one stream and packets longer than a chunk (a
+    60 ms Opus frame, what a jitter buffer releases after a stall); a stream that completes k <= M chunks is stepped k times inside the
+    tick, `burst_steps(r)` / `burst_probs(r)` give the sub-steps, and `poll` returns their events one sub-step after the other.
 
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
     def __init__(self, engine, sampling_rate: int = 16000, streams: int = 8192, parts: int = 0, ring_slots: int = 0,
-                 threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30):
+                 threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1):
         if sampling_rate not in (8000, 16000):
             raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
+        if not isinstance(max_burst, (int, np.integer)) or not 1 <= max_burst <= 8:
+            raise ValueError(f"max_burst must be 1 ... 8 (VAD_PUMP_MAX_BURST), got {max_burst!r}")
         self._L = engine._L
         prm = _lib.PumpParams()
         self._L.vad_pump_params_default(ctypes.byref(prm), int(sampling_rate), int(streams))
@@ -1908,17 +1913,29 @@ class StreamPump:
         self._L.vad_pump_geometry(h, *[ctypes.byref(x) for x in g])
         self.streams, self.n, self.ring_slots, self.parts = (x.value for x in g)
         self.sr = int(sampling_rate)
-        self._events = (_lib.IterEvent * self.streams)()
+        self.max_burst = int(max_burst)
+        if self.max_burst > 1:                                   # (1: burst ticks stay off, nothing is allocated for them)
+            rc = self._L.vad_pump_set_burst(h, self.max_burst)
+            if rc:
+                msg = self._L.vad_pump_last_error(h).decode()
+                self._L.vad_pump_destroy(h)
+                self._h = None
+                raise _lib.VadError(rc, msg)
+        self._events = (_lib.IterEvent * (self.streams * self.max_burst))()
         self._slots = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_slot(h, r), ctypes.POINTER(ctypes.c_int16)),
                                              shape=(self.streams, self.n)) for r in range(self.ring_slots)]
         self._probs = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_probs(h, r), ctypes.POINTER(ctypes.c_float)),
                                              shape=(self.streams,)) for r in range(self.ring_slots)]
         self._present = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_present(h, r), ctypes.POINTER(ctypes.c_uint8)),
                                                shape=(self.streams,)) for r in range(self.ring_slots)]
+        # sub-steps 1 ... max_burst - 1 of a burst tick: per ring slot [max_burst - 1, streams] (page-locked, one block per slot)
+        self._probs_more = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_burst_probs(h, r, 1), ctypes.POINTER(ctypes.c_float)),
+                                                  shape=(self.max_burst - 1, self.streams)) for r in range(self.ring_slots)] \
+            if self.max_burst > 1 else None
 
     def close(self):
         if getattr(self, "_h", None):
-            self._slots = self._probs = self._present = None
+            self._slots = self._probs = self._present = self._probs_more = None
             self._L.vad_pump_destroy(self._h)
             self._h = None
 
@@ -2058,6 +2075,63 @@ class StreamPump:
             at += (x.nbytes + 15) // 16 * 16
         self.submit_coded_packets(r, streams, lengths, np.array(codecs, np.uint8), offsets)
 
+    def submit_burst(self, r: int, streams, lengths, codecs=None, byte_offsets=None):
+        """A BURST tick (vad_pump_submit_burst; needs `max_burst` > 1): rows as in `submit_coded_packets`, except that a stream may be
+        listed any number of times and a row may be longer than N.  Each stream's rows are appended, in row order, to what it has
+        pending; a stream that completes k chunks (k <= max_burst) is stepped k times, in order, inside this tick.  The results are
+        those of the same audio fed chunk by chunk, bit for bit.  A stream that would complete more than max_burst chunks, more rows
+        than `streams`, a bad codec, stream, length or offset raises and queues nothing."""
+        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
+        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
+        cd = None if codecs is None else _codec_rows(codecs)
+        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (cd is not None and len(cd) != len(st)):
+            raise ValueError(f"streams, lengths, codecs and byte_offsets must have one entry per row, got {len(st)}, {len(ln)}, "
+                             f"{len(st) if cd is None else len(cd)}, {len(st) if off is None else len(off)}")
+        if off is None:
+            nbytes = ln.astype(np.int64) * (2 if cd is None else np.where(cd == _PCM["s16"], 2, 1))
+            off = np.zeros(len(st), np.int32)
+            if len(st):
+                off[1:] = np.cumsum((nbytes[:-1] + 15) // 16 * 16)
+        n = len(st)
+        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [cd.ctypes.data if n and cd is not None else None]
+        self._check(self._L.vad_pump_submit_burst(self._h, int(r), *ptrs, n))
+
+    def write_burst(self, r: int, packets):
+        """Pack [(stream, samples) | (stream, samples, codec), ...] back to back in arrival order (each rounded up to 16 bytes) into
+        `packet_bytes(r)` and submit the burst tick: packets of any length, streams repeated as often as they delivered.  codec "s16"
+        (the default) takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes."""
+        area = self.packet_bytes(r)
+        streams, lengths, codecs, offsets, at = [], [], [], [], 0
+        for pk in packets:
+            s, x, codec = pk if len(pk) == 3 else (pk[0], pk[1], "s16")
+            c = _codec_id(codec)
+            x = np.asarray(x)
+            want = np.int16 if c == _PCM["s16"] else np.uint8
+            if x.dtype != want or x.ndim != 1:
+                raise ValueError(f"a {codec!r} packet must be a 1-D {np.dtype(want).name} array, got {x.dtype} of shape {x.shape}")
+            if len(x) < 1:
+                raise ValueError("a packet holds at least 1 sample")
+            if at + x.nbytes > len(area):
+                raise ValueError("the packets do not fit into the slot")
+            area[at:at + x.nbytes] = x.view(np.uint8)
+            streams.append(s)
+            lengths.append(len(x))
+            codecs.append(c)
+            offsets.append(at)
+            at += (x.nbytes + 15) // 16 * 16
+        self.submit_burst(r, streams, lengths, np.array(codecs, np.uint8), offsets)
+
+    def burst_steps(self, r: int) -> int:
+        """The sub-steps slot r's last tick ran: max(1, the most chunks a stream completed) for a burst tick, 1 for any other."""
+        return int(self._L.vad_pump_burst_steps(self._h, int(r)))
+
+    def burst_probs(self, r: int) -> np.ndarray:
+        """[burst_steps(r), streams] float32 (a copy): row j = the probabilities of sub-step j of slot r's last tick, -1.0 where the
+        stream completed no more than j chunks.  Row 0 is `probs(r)`."""
+        k = self.burst_steps(r)
+        first = self._probs[r][None, :]
+        return first.copy() if k == 1 else np.concatenate([first, self._probs_more[r][:k - 1]])
+
     def pending(self, stream: int) -> int:
         """Samples of `stream` submitted in packets and not yet stepped (0 ... N - 1)."""
         v = self._L.vad_pump_pending(self._h, int(stream))
@@ -2068,7 +2142,7 @@ class StreamPump:
     def poll(self, block: bool = True):
         """-> (events, ring slot) of the oldest submitted tick; (None, None) if nothing is in flight or (block=False) it has not finished."""
         r = ctypes.c_int(-1)
-        m = self._L.vad_pump_poll(self._h, 1 if block else 0, self._events, self.streams, ctypes.byref(r))
+        m = self._L.vad_pump_poll(self._h, 1 if block else 0, self._events, len(self._events), ctypes.byref(r))
         if m in (-1, -2):
             return None, None
         if m < 0:

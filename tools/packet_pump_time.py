@@ -5,13 +5,20 @@ ticks in flight.  The ring slots are written once before the timed window: this 
 path's host writes.  Prints one JSON line: per-tick time, link bytes per tick, the share of a plain pinned -> HBM copy's rate that
 reaches, and the time per second of audio of every route (equal audio throughput).
 
-    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs]
+    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs] [burst_share d]
 
 sr: 16000 (default) or 8000.  codecs: a comma-separated list of packet formats, timed alternately with the chunk route -- "s16" (the
 default: int16 packets through vad_pump_submit_packets), "ulaw" / "alaw" (G.711 packets, 1 byte a sample, through
 vad_pump_submit_coded_packets; the device expands them).  The telephony case: `python tools/packet_pump_time.py 2000 3 8000 s16,ulaw,alaw`.
 
-assemble_packets_kernel's / assemble_coded_packets_kernel's own time: run it under
+burst_share d (e.g. `0.1 3`): burst mode -- adds the route "burst" (vad_pump_submit_burst on a pump with max_burst = 8).  That share of
+the streams is withheld for d ticks at a time (in d + 1 phases, so every tick sees the same load) and then delivers its d + 1 packets
+in one tick as one long row; everybody else delivers a packet a tick.  Every tick carries the same audio as a tick of "packets", which
+is what the same streams cost an integrator without bursts: the withheld packets trickled in one per tick, the stream's events lagging
+d ticks behind.  Share, d and the sub-steps per tick are in the output, and so is
+"packets_on_burst_pump": the ordinary packet ticks of a burst-enabled pump, which must cost what "packets" costs.
+
+assemble_packets_kernel's / assemble_coded_packets_kernel's / assemble_burst_kernel's own time: run it under
 `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/packet_pump_time.py ...` (in a run of its own) and read the
 kernels' lines of the stats file."""
 import json
@@ -46,8 +53,10 @@ def main():
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     sr = int(sys.argv[3]) if len(sys.argv) > 3 else 16000
     codecs = sys.argv[4].split(",") if len(sys.argv) > 4 else ["s16"]
-    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw"}:
-        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw]")
+    share = float(sys.argv[5]) if len(sys.argv) > 6 else 0.0
+    d = int(sys.argv[6]) if len(sys.argv) > 6 else 0
+    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw"} or not 0.0 <= share <= 1.0 or not 0 <= d <= 11:
+        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw] [burst_share d (0 ... 11)]")
     S, R = 8192, 4
     N, P = (512 if sr == 16000 else 256), sr // 50                     # a chunk, a 20 ms packet (samples)
     dev = torch.device("cuda", 0)
@@ -61,18 +70,25 @@ def main():
     names = {"s16": "packets", "ulaw": "packets_ulaw", "alaw": "packets_alaw"}
     fmt = {names[c]: c for c in codecs}
     fmt["chunks"] = None
+    if share > 0:
+        fmt["burst"] = "burst"
+        fmt["packets_on_burst_pump"] = "s16"                              # ordinary packet ticks of a pump that has bursts enabled
     routes = {}
     for name, c in fmt.items():
-        if c is None:                                                   # position table + flags + the chunks
+        if c == "burst":                                                # row table + flags + the same samples as a tick of int16 packets
+            routes[name] = {"bytes": 16 * S + page(S) + S * P * 2, "ms_audio": 1000.0 * P / sr}
+        elif c is None:                                                 # position table + flags + the chunks
             routes[name] = {"bytes": page(4 * S) + page(S) + S * N * 2, "ms_audio": 1000.0 * N / sr}
         else:                                                           # row table (16 bytes a row) + flags + the packets
             row = P * (2 if c == "s16" else 1)
             routes[name] = {"bytes": 16 * S + page(S) + S * ((row + 15) // 16 * 16), "ms_audio": 1000.0 * P / sr}
     pumps = {}
     for name, c in fmt.items():
-        pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R)
+        pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R, max_burst=8 if "burst" in name else 1)
         for r in range(R):
-            if c is None:
+            if c == "burst":
+                pump.packet_area(r)[:S * P].reshape(S, P)[:] = rows[order, :P]
+            elif c is None:
                 pump.slot(r)[:] = rows[order]
             elif c == "s16":
                 pump.packet_area(r)[:S * P].reshape(S, P)[:] = rows[order, :P]
@@ -83,12 +99,26 @@ def main():
     offsets = (np.arange(S) * P).astype(np.int32)                       # samples (s16) or bytes (G.711): 16-byte aligned either way
     codec_rows = {"ulaw": np.full(S, 1, np.uint8), "alaw": np.full(S, 2, np.uint8)}
 
+    # burst mode: the first `share` of the arrival order stalls, in d + 1 phases; phase f delivers (d + 1) packets as ONE row at ticks
+    # t = f (mod d + 1), the rest of the group is silent, everybody else delivers a packet (rows back to back: S * P samples a tick)
+    phases = []
+    if share > 0:
+        group = int(S * share) // (d + 1) * (d + 1)
+        for f in range(d + 1):
+            who = np.concatenate([order[f:group:d + 1], order[group:]])
+            ln = np.concatenate([np.full(group // (d + 1), (d + 1) * P), np.full(S - group, P)]).astype(np.int32)
+            off = np.zeros(len(ln), np.int64)
+            off[1:] = np.cumsum(ln[:-1]) * 2
+            phases.append((who.astype(np.int32), ln, off.astype(np.int32)))
+
     def run(name, n):
         pump, c = pumps[name], fmt[name]
         inflight = 0
         t0 = time.perf_counter()
         for t in range(n):
-            if c is None:
+            if c == "burst":
+                pump.submit_burst(t % R, phases[t % (d + 1)][0], phases[t % (d + 1)][1], None, phases[t % (d + 1)][2])
+            elif c is None:
                 pump.submit_rows(t % R, order)
             elif c == "s16":
                 pump.submit_packets(t % R, order, lengths, offsets)
@@ -110,6 +140,9 @@ def main():
         for name in routes:
             best[name] = min(best[name], run(name, ticks))
     out = {"streams": S, "sr": sr, "packet_samples": P, "ticks": ticks, "reps": reps, "h2d_GBps": round(link, 2)}
+    if share > 0:
+        out.update({"burst_share": round(group / S, 4), "withheld_ticks": d,
+                    "burst_steps_last_ticks": sorted({pumps["burst"].burst_steps(r) for r in range(R)})})
     for name, info in routes.items():
         tick_s = best[name] / ticks
         out[name] = {"tick_us": round(tick_s * 1e6, 1), "link_bytes_per_tick": info["bytes"],
