@@ -57,7 +57,14 @@ void vad_destroy(vad_engine *e);
 /* A second handle on the same GPU: shares the read-only weight images (no second copy) and starts with the same options,
  * owns its scratch.  An engine and its clones may have calls in flight on different streams at the same time (one engine
  * may not: its scratch is per call).  The reference gets concurrency by one model object per process
- * (examples/parallel_example.ipynb cell 5); inside one process on one GPU this is the equivalent.  Destroy every handle. */
+ * (examples/parallel_example.ipynb cell 5); inside one process on one GPU this is the equivalent.  Destroy every handle.
+ * The calls may come from different host threads, one thread per handle at a time, on any streams (non-blocking ones included),
+ * beside handles that are being created, grow their scratch or are destroyed: every handle returns the bits it returns alone
+ * (tests/test_concurrency.py).  What the engine does not arrange: a hipGraph capture is a process-wide state of the runtime --
+ * while one thread captures (global capture mode), allocating calls of other threads (vad_create / vad_clone / vad_pump_create, a
+ * scratch growth) fail; capture while the other threads make no such call.
+ * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed and vad_g711_expand are re-entrant (no shared state);
+ * vad_stage_rows and vad_segment_probs_batch serialise themselves on the process-wide helper pool (tests/test_host_concurrency.py). */
 int  vad_clone(const vad_engine *e, vad_engine **out);
 const char *vad_strerror(int status);
 const char *vad_last_error(const vad_engine *e);   /* detail text of the last failing call */
@@ -316,8 +323,10 @@ enum { VAD_PUMP_IDLE = -1,   /* vad_pump_poll: nothing submitted                
        VAD_PUMP_ERROR = -3 };/* see vad_pump_last_error                                                                      */
 
 void vad_pump_params_default(vad_pump_params *p, int sampling_rate, int streams);
-/* The pump works on a clone of `e` (vad_clone): the caller's engine stays free for other calls.  Every stream starts open, from
- * zero state (VADIterator.reset_states, utils_vad.py:500-505).                                                             */
+/* The pump works on a clone of `e` (vad_clone): the caller's engine stays free for other calls, from another host thread too, and
+ * several pumps may run beside each other, each driven by its own thread (tests/test_concurrency.py: two pumps, the engine they were
+ * cloned from and further clones in flight together).  Every stream starts open, from zero state (VADIterator.reset_states,
+ * utils_vad.py:500-505).                                                                                                    */
 int  vad_pump_create(vad_engine *e, const vad_pump_params *p, vad_pump **out);
 void vad_pump_destroy(vad_pump *p);
 const char *vad_pump_last_error(const vad_pump *p);

@@ -194,7 +194,11 @@ int ensure_scratch(vad_engine *e, int sr, int B, long T, hipStream_t stream) {
             e->exact_ints = 0;
             if (hipMalloc((void **)&e->d_exact, need_exact * sizeof(int)) != hipSuccess)
                 return fail(e, VAD_ERR_ALLOC, "cannot allocate the exact-chunk list");
-            HIP_TRY(e, hipMemset(e->d_exact, 0, 2 * sizeof(int)));      // (the fix-up pass leaves the counters at zero: kernel_exact.hip)
+            // (the fix-up pass leaves the counters at zero: kernel_exact.hip.)  hipMemset on device memory is queued on the NULL stream and
+            // returns before it has run; the call that made the scratch grow may be on a non-blocking stream, which the null stream does
+            // not order: the frontend would add its chunks to whatever the fresh allocation held -- an index far outside the list.  Wait.
+            HIP_TRY(e, hipMemset(e->d_exact, 0, 2 * sizeof(int)));
+            HIP_TRY(e, hipDeviceSynchronize());
             e->exact_ints = need_exact;
         }
         if (need_tail > e->tail_bytes) {
