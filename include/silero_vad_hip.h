@@ -458,12 +458,14 @@ long vad_pump_play_compact(vad_pump *p, const int16_t *rows, long ld, long perio
                            long n_ticks, int depth, int fill_threads, vad_iter_event *out, long cap, vad_pump_stats *st);
 
 /* ---- host-side ingest ---------------------------------------------------------------------------------
- * Pack n recordings of different lengths (lens[i] samples of elem_size 2 = int16 or 4 = float32 at
+ * Pack n recordings of different lengths (lens[i] samples of elem_size 2 = int16, 4 = float32 or 1 = G.711 codes, packed as bytes, at
  * rows[i]) into one zero-padded row-major [n][width] batch at dst (typically pinned host memory that
  * is then copied to the GPU and handed to vad_forward_audio[_i16]).  Zero padding on the right is what
  * the reference does to a recording's last chunk (src/silero_vad/utils_vad.py:326-327); the network
  * is causal, so padding further does not change the recording's own probabilities.  The copy is
- * split over `threads` persistent host threads (<= 0: vad_host_threads(), at most 32).              */
+ * split over `threads` persistent host threads (<= 0: vad_host_threads(), at most 32).  elem_size 1 is a plain
+ * byte packing: its zero BYTES are not audio (A-law has no code for 0) -- the staged block goes to the device as it is and
+ * vad_upload_rows_coded (how = 2) expands it with the true lengths.                                  */
 int  vad_stage_rows(const void *const *rows, const long *lens, long n, long width, size_t elem_size,
                     void *dst, int threads);
 
@@ -479,6 +481,18 @@ int  vad_stage_rows(const void *const *rows, const long *lens, long n, long widt
  * For pageable sources use vad_stage_rows + one copy instead.                                                          */
 int  vad_upload_rows(vad_engine *e, const void *const *rows, const long *lens, long n, long width, size_t elem_size,
                      void *dst, int how, void *stream);
+/* vad_upload_rows for recordings that are still G.711 (call-centre archives, SIP-trunk recordings: 1 byte a sample): the wire bytes
+ * stay as they are in page-locked memory (how = 1) or cross the link in one large DMA of their arena (how = 2), and the gather
+ * kernel expands them (the values of vad_g711_expand) on their way into the batch -- half the link bytes of an int16 corpus.
+ * lens and width are in SAMPLES; dst = DEVICE int16 [n][width] (16-byte aligned, width a multiple of 8), zero padded behind each
+ * row's last sample.  codec_of_row[i] = VAD_PCM_S16 (2 bytes a sample, at an even address), VAD_PCM_ULAW or VAD_PCM_ALAW (1 byte a
+ * sample, at ANY byte address: recordings packed back to back move as aligned 16-byte loads all the same); NULL = every row is
+ * S16, and so is a table without a G.711 row: the call is then vad_upload_rows(..., elem_size = 2, ...).  The result is, bit for
+ * bit, that of vad_upload_rows over the rows expanded by vad_g711_expand.
+ * VAD_ERR_ARG, with nothing queued: how = 0 with a G.711 row (a DMA cannot expand), a codec above VAD_PCM_ALAW, lens[i] > width, a
+ * null row with a length, a misaligned dst or pitch, an S16 row at an odd address.                                            */
+int  vad_upload_rows_coded(vad_engine *e, const void *const *rows, const long *lens, const uint8_t *codec_of_row, long n, long width,
+                           void *dst_i16, int how, void *stream);
 /* Page-lock / unlock a host range so that it can be a vad_upload_rows source (hipHostRegister; a decoder's output
  * buffers, a memory-mapped corpus shard).  Process-wide.                                                              */
 int  vad_host_register(void *p, size_t bytes);

@@ -177,6 +177,11 @@ struct RowDesc {
     long len;
 };
 hipError_t launch_gather_rows(const RowDesc *rows, long n, long width, int esz, void *dst, bool rows_on_device, hipStream_t s);
+// The same into an int16 batch from rows that may be G.711 (vad_upload_rows_coded): rows[i].len = samples | codec << kRowCodecShift,
+// codec VAD_PCM_S16 (2 bytes a sample at an even address) or VAD_PCM_ULAW / _ALAW (1 byte a sample at ANY address, expanded by
+// g711_to_s16 on the way); dst[i][0 .. width) int16, zero padded behind the row's last sample; width a multiple of 8.
+constexpr int kRowCodecShift = 56;
+hipError_t launch_gather_expand_rows(const RowDesc *rows, long n, long width, void *dst_i16, bool rows_on_device, hipStream_t s);
 
 // Segmenter on the device (kernel_scan.hip): lane i scans probs[i * ldp ...] (or probs[row_off[i] ...] if row_off is
 // not null), n_chunks[i] entries (or n_chunks_all if n_chunks is null), writes its segments to out[i * cap ...] and

@@ -1055,6 +1055,73 @@ const void *device_view(const void *p) {
     }
     return dev;
 }
+
+// The row table of a gather launch (vad_upload_rows / vad_upload_rows_coded, how = 1 or 2): the next pinned slot of the ring -- the kernel
+// reads it itself; a slot is reused once its kernel is done -- filled with every row's DEVICE address and len_tag(i); row i is
+// row_bytes(i) bytes long.  Returns a status; *slot_out is the slot (the caller launches, records tab_ev[slot] and sets tab_busy).
+extern "C++" template <typename Bytes, typename Tag>
+int fill_row_table(vad_engine *e, const void *const *rows, const long *lens, long n, int how, const char *who, Bytes row_bytes,
+                          Tag len_tag, int *slot_out) {
+    const int slot = e->tab_next;
+    e->tab_next = (slot + 1) % vad_engine::kTabSlots;
+    if (e->tab_busy[slot]) {
+        HIP_TRY(e, hipEventSynchronize(e->tab_ev[slot]));
+        e->tab_busy[slot] = false;
+    }
+    if (e->tab_cap[slot] < n) {
+        if (e->h_tab[slot]) (void)hipHostFree(e->h_tab[slot]);
+        e->h_tab[slot] = nullptr;
+        e->tab_cap[slot] = 0;
+        // (hipHostFree waits for the device: a table that grows by a few rows per bucket would drain the whole pipeline every
+        //  time -- capacities are powers of two from 4096 up, so a slot is reallocated a handful of times in a process' life)
+        long cap = 4096;
+        while (cap < n) cap *= 2;
+        if (hipHostMalloc((void **)&e->h_tab[slot], (size_t)cap * sizeof(vad::RowDesc), hipHostMallocDefault) != hipSuccess)
+            return fail(e, VAD_ERR_ALLOC, "cannot allocate the pinned row table");
+        e->tab_cap[slot] = cap;
+    }
+    if (!e->tab_ev[slot]) HIP_TRY(e, hipEventCreateWithFlags(&e->tab_ev[slot], hipEventDisableTiming));
+    if (how == 2) {                                    // rows[] are device addresses already
+        for (long i = 0; i < n; ++i) e->h_tab[slot][i] = vad::RowDesc{lens[i] ? rows[i] : nullptr, len_tag(i)};
+    } else {
+        // Resolving a host address costs a runtime call (~1 us): thousands of short rows per slab, 92 slabs per 100 h of audio, made the
+        // refill route's upload call 190 ms of its 245.  The rows of a corpus lie in a few page-locked allocations, and inside ONE
+        // allocation the device view is the host address plus a constant: the allocation a row was resolved in is remembered (its
+        // extent from hipMemGetAddressRange on the device view) and the rows that fall inside it are translated by arithmetic.
+        const uint8_t *c_host = nullptr, *c_dev = nullptr;       // [c_host, c_host + c_bytes) -> c_dev + offset
+        size_t c_bytes = 0;
+        for (long i = 0; i < n; ++i) {
+            const void *dv = nullptr;
+            if (lens[i]) {
+                const uint8_t *hp = static_cast<const uint8_t *>(rows[i]);
+                if (c_bytes && hp >= c_host && hp + row_bytes(i) <= c_host + c_bytes) {
+                    dv = c_dev + (hp - c_host);
+                } else {
+                    dv = device_view(rows[i]);
+                    if (!dv)
+                        return fail(e, VAD_ERR_ARG, std::string(who) + ": a row is not in page-locked memory the runtime knows "
+                                                                       "(hipHostMalloc / pin_memory / vad_host_register)");
+                    hipDeviceptr_t base = nullptr;
+                    size_t bytes = 0;
+                    c_bytes = 0;
+                    if (hipMemGetAddressRange(&base, &bytes, const_cast<void *>(dv)) == hipSuccess && base && bytes) {
+                        const uint8_t *b = static_cast<const uint8_t *>(base), *d = static_cast<const uint8_t *>(dv);
+                        if (d >= b && d < b + bytes) {
+                            c_dev = b;
+                            c_host = hp - (d - b);
+                            c_bytes = bytes;
+                        }
+                    } else {
+                        (void)hipGetLastError();
+                    }
+                }
+            }
+            e->h_tab[slot][i] = vad::RowDesc{dv, len_tag(i)};
+        }
+    }
+    *slot_out = slot;
+    return VAD_OK;
+}
 }  // namespace
 
 int vad_host_register(void *p, size_t bytes) {
@@ -1143,65 +1210,43 @@ int vad_upload_rows(vad_engine *e, const void *const *rows, const long *lens, lo
             }
         return VAD_OK;
     }
-    // gather kernel: the row table goes into a pinned slot the kernel reads itself; a slot is reused once its kernel is done
-    const int slot = e->tab_next;
-    e->tab_next = (slot + 1) % vad_engine::kTabSlots;
-    if (e->tab_busy[slot]) {
-        HIP_TRY(e, hipEventSynchronize(e->tab_ev[slot]));
-        e->tab_busy[slot] = false;
-    }
-    if (e->tab_cap[slot] < n) {
-        if (e->h_tab[slot]) (void)hipHostFree(e->h_tab[slot]);
-        e->h_tab[slot] = nullptr;
-        e->tab_cap[slot] = 0;
-        // (hipHostFree waits for the device: a table that grows by a few rows per bucket would drain the whole pipeline every
-        //  time -- capacities are powers of two from 4096 up, so a slot is reallocated a handful of times in a process' life)
-        long cap = 4096;
-        while (cap < n) cap *= 2;
-        if (hipHostMalloc((void **)&e->h_tab[slot], (size_t)cap * sizeof(vad::RowDesc), hipHostMallocDefault) != hipSuccess)
-            return fail(e, VAD_ERR_ALLOC, "cannot allocate the pinned row table");
-        e->tab_cap[slot] = cap;
-    }
-    if (!e->tab_ev[slot]) HIP_TRY(e, hipEventCreateWithFlags(&e->tab_ev[slot], hipEventDisableTiming));
-    if (how == 2) {                                    // rows[] are device addresses already
-        for (long i = 0; i < n; ++i) e->h_tab[slot][i] = vad::RowDesc{lens[i] ? rows[i] : nullptr, lens[i]};
-    } else {
-        // Resolving a host address costs a runtime call (~1 us): thousands of short rows per slab, 92 slabs per 100 h of audio, made the
-        // refill route's upload call 190 ms of its 245.  The rows of a corpus lie in a few page-locked allocations, and inside ONE
-        // allocation the device view is the host address plus a constant: the allocation a row was resolved in is remembered (its
-        // extent from hipMemGetAddressRange on the device view) and the rows that fall inside it are translated by arithmetic.
-        const uint8_t *c_host = nullptr, *c_dev = nullptr;       // [c_host, c_host + c_bytes) -> c_dev + offset
-        size_t c_bytes = 0;
-        for (long i = 0; i < n; ++i) {
-            const void *dv = nullptr;
-            if (lens[i]) {
-                const uint8_t *hp = static_cast<const uint8_t *>(rows[i]);
-                if (c_bytes && hp >= c_host && hp + (size_t)lens[i] * elem_size <= c_host + c_bytes) {
-                    dv = c_dev + (hp - c_host);
-                } else {
-                    dv = device_view(rows[i]);
-                    if (!dv)
-                        return fail(e, VAD_ERR_ARG, "vad_upload_rows: a row is not in page-locked memory the runtime knows "
-                                                    "(hipHostMalloc / pin_memory / vad_host_register)");
-                    hipDeviceptr_t base = nullptr;
-                    size_t bytes = 0;
-                    c_bytes = 0;
-                    if (hipMemGetAddressRange(&base, &bytes, const_cast<void *>(dv)) == hipSuccess && base && bytes) {
-                        const uint8_t *b = static_cast<const uint8_t *>(base), *d = static_cast<const uint8_t *>(dv);
-                        if (d >= b && d < b + bytes) {
-                            c_dev = b;
-                            c_host = hp - (d - b);
-                            c_bytes = bytes;
-                        }
-                    } else {
-                        (void)hipGetLastError();
-                    }
-                }
-            }
-            e->h_tab[slot][i] = vad::RowDesc{dv, lens[i]};
-        }
-    }
+    // gather kernel: the row table goes into a pinned slot the kernel reads itself (fill_row_table)
+    int slot = 0;
+    if (int rc = fill_row_table(e, rows, lens, n, how, "vad_upload_rows", [&](long i) { return (size_t)lens[i] * elem_size; },
+                                [&](long i) { return lens[i]; }, &slot))
+        return rc;
     HIP_TRY(e, vad::launch_gather_rows(e->h_tab[slot], n, width, (int)elem_size, dst, how == 2, stream));
+    HIP_TRY(e, hipEventRecord(e->tab_ev[slot], stream));
+    e->tab_busy[slot] = true;
+    return VAD_OK;
+}
+
+int vad_upload_rows_coded(vad_engine *e, const void *const *rows, const long *lens, const uint8_t *codec_of_row, long n, long width,
+                          void *dst, int how, void *stream_v) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (n < 0 || width < 0 || how < 0 || how > 2) return fail(e, VAD_ERR_ARG, "bad argument");
+    if (n == 0 || width == 0) return VAD_OK;
+    if (!rows || !lens || !dst) return fail(e, VAD_ERR_ARG, "null pointer");
+    if (((size_t)dst & 15) || (width * 2) % 16) return fail(e, VAD_ERR_ARG, "dst and its row pitch must be 16-byte aligned");
+    bool g711 = false;
+    for (long i = 0; i < n; ++i) {
+        const int c = codec_of_row ? codec_of_row[i] : VAD_PCM_S16;
+        if (c > VAD_PCM_ALAW) return fail(e, VAD_ERR_ARG, "vad_upload_rows_coded: unknown codec");
+        if (lens[i] < 0 || lens[i] > width || (lens[i] > 0 && !rows[i])) return fail(e, VAD_ERR_ARG, "bad row");
+        if (c == VAD_PCM_S16 && lens[i] > 0 && ((size_t)rows[i] & 1)) return fail(e, VAD_ERR_ARG, "an int16 row at an odd address");
+        g711 = g711 || c != VAD_PCM_S16;
+    }
+    if (!g711) return vad_upload_rows(e, rows, lens, n, width, 2, dst, how, stream_v);     // every row S16: the plain call
+    if (how == 0) return fail(e, VAD_ERR_ARG, "vad_upload_rows_coded: a G.711 row cannot take the copy engines (how = 0): a DMA does not expand");
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(e, hipSetDevice(e->device));
+    int slot = 0;
+    if (int rc = fill_row_table(e, rows, lens, n, how, "vad_upload_rows_coded",
+                                [&](long i) { return (size_t)lens[i] * (codec_of_row[i] == VAD_PCM_S16 ? 2 : 1); },
+                                [&](long i) { return lens[i] | (long)codec_of_row[i] << vad::kRowCodecShift; }, &slot))
+        return rc;
+    HIP_TRY(e, vad::launch_gather_expand_rows(e->h_tab[slot], n, width, dst, how == 2, stream));
     HIP_TRY(e, hipEventRecord(e->tab_ev[slot], stream));
     e->tab_busy[slot] = true;
     return VAD_OK;

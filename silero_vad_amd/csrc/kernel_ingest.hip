@@ -74,6 +74,161 @@ __global__ void __launch_bounds__(64) gather_rows_kernel(const RowDesc *rows, lo
     }
 }
 
+// ---- G.711 recordings: gather AND expand ------------------------------------------------------------------------------
+// The same gather for recordings that are still G.711 (vad_upload_rows_coded): a row is 1 byte a sample at ANY byte address --
+// recordings packed back to back in an arena, 15 of 16 of them misaligned -- and leaves as int16 (g711_to_s16, device_api.hpp),
+// so the link carries half the bytes of an int16 corpus.  rows[i].len = samples | codec << kRowCodecShift, codec wave-uniform per row;
+// an S16 row is copied (2 bytes a sample, any EVEN address) and gives what gather_rows_kernel gives.
+//
+//   * the unit is the aligned 16-byte granule of the SOURCE.  With s = the row's first byte, m = s & 15 and A = s - m, lane l of
+//     wave-load k reads granule A + lo + (64 k + l) 16: always an aligned vector, and only granules that hold a byte of the row
+//     (such a granule cannot leave the row's page).  The 16 bytes a lane needs, [s + p, s + p + 16), are the upper 16 - m bytes of
+//     its granule and the lower m of the NEXT one -- which the next lane holds: one ds_bpermute per dword (no LDS is allocated), a
+//     v_alignbyte funnel per output dword.  Lane 63 takes lane 0 of the next wave-load, and the segment's last wave-load one extra
+//     granule that lane 0 alone reads: 1 / 512 more bytes than an aligned row, no byte-wise loads anywhere.
+//   * a segment is 8 KiB of source as above (8 x 16 B per lane in flight, non-temporal): 8 192 samples = 16 KiB of batch for a G.711
+//     row, 4 096 samples for an S16 row; a vector of 16 codes leaves as two 16-byte stores;
+//   * the segment that holds the row's end (and the padding behind it) takes the same loads one wave-load at a time; samples past the
+//     row's length are zeroed AFTER the expansion -- padding is int16 zero, never an expanded pad byte (A-law has no code for 0).
+//   * footprint as above: kGatherWaves one-wave workgroups for host sources, the wide grid for device sources.
+constexpr long kRowLenMask = (1L << kRowCodecShift) - 1;
+using u32x4 = unsigned __attribute__((ext_vector_type(4)));
+
+// bytes [m, m + 16) of the 32 bytes c ++ n; m is wave-uniform
+__device__ __forceinline__ u32x4 shift_bytes(u32x4 c, u32x4 n, int m) {
+    const int dq = m >> 2;
+    unsigned w0, w1, w2, w3, w4;
+    if (dq == 0) {
+        w0 = c.x, w1 = c.y, w2 = c.z, w3 = c.w, w4 = n.x;
+    } else if (dq == 1) {
+        w0 = c.y, w1 = c.z, w2 = c.w, w3 = n.x, w4 = n.y;
+    } else if (dq == 2) {
+        w0 = c.z, w1 = c.w, w2 = n.x, w3 = n.y, w4 = n.z;
+    } else {
+        w0 = c.w, w1 = n.x, w2 = n.y, w3 = n.z, w4 = n.w;
+    }
+    const unsigned r = (unsigned)m & 3u;                       // v_alignbyte_b32: ({hi, lo} >> 8 r) & 0xffffffff
+    return u32x4{__builtin_amdgcn_alignbyte(w1, w0, r), __builtin_amdgcn_alignbyte(w2, w1, r), __builtin_amdgcn_alignbyte(w3, w2, r),
+                 __builtin_amdgcn_alignbyte(w4, w3, r)};
+}
+
+// lane l <- lane l + 1's v; lane 63 <- `wrap`.  Every lane of the wave executes this.
+__device__ __forceinline__ u32x4 next_lane(u32x4 v, u32x4 wrap, int lane) {
+    u32x4 r{__shfl_down(v.x, 1u), __shfl_down(v.y, 1u), __shfl_down(v.z, 1u), __shfl_down(v.w, 1u)};
+    return lane == 63 ? wrap : r;
+}
+
+__device__ __forceinline__ u32x4 lane0_of(u32x4 v) {
+    return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)v.x), (unsigned)__builtin_amdgcn_readfirstlane((int)v.y),
+                 (unsigned)__builtin_amdgcn_readfirstlane((int)v.z), (unsigned)__builtin_amdgcn_readfirstlane((int)v.w)};
+}
+
+// four codes (one dword) -> four int16 in two dwords
+template <int CODEC>
+__device__ __forceinline__ void expand4(unsigned w, unsigned &lo, unsigned &hi) {
+    auto one = [](unsigned code) -> unsigned {
+        return (unsigned)(unsigned short)(CODEC == VAD_PCM_ULAW ? ulaw_to_s16((uint8_t)code) : alaw_to_s16((uint8_t)code));
+    };
+    lo = one(w & 0xffu) | one((w >> 8) & 0xffu) << 16;
+    hi = one((w >> 16) & 0xffu) | one(w >> 24) << 16;
+}
+
+// The 16 source bytes x of one lane -> the batch row at source position p.  CODEC 0: a copy (16 bytes at d + p); else 16 codes -> 16
+// int16 (32 bytes at d + 2 p).  keep: source bytes of x that belong to the row (>= 16: all), the rest leave as zeros; room: source
+// bytes the row has left at p (16, or 8 at the end of a G.711 row whose width is 8 mod 16).  NT: non-temporal stores.
+template <int CODEC, bool NT>
+__device__ __forceinline__ void put_vector(u32x4 x, uint8_t *d, long p, long keep, long room) {
+    auto store = [](u32x4 v, uint8_t *at) {
+        if (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(at));
+        else *reinterpret_cast<u32x4 *>(at) = v;
+    };
+    if (CODEC == 0) {
+        if (keep < 16) {
+            unsigned w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const long k = keep - 4 * i;
+                w[i] = k >= 4 ? w[i] : k <= 0 ? 0u : w[i] & ((1u << (8 * (int)k)) - 1u);
+            }
+            x = u32x4{w[0], w[1], w[2], w[3]};
+        }
+        store(x, d + p);
+    } else {
+        unsigned o[8];
+        expand4<CODEC>(x.x, o[0], o[1]);
+        expand4<CODEC>(x.y, o[2], o[3]);
+        expand4<CODEC>(x.z, o[4], o[5]);
+        expand4<CODEC>(x.w, o[6], o[7]);
+        if (keep < 16) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const long k = keep - 2 * j;
+                o[j] = k >= 2 ? o[j] : k == 1 ? o[j] & 0xffffu : 0u;
+            }
+        }
+        store(u32x4{o[0], o[1], o[2], o[3]}, d + 2 * p);
+        if (room >= 16) store(u32x4{o[4], o[5], o[6], o[7]}, d + 2 * p + 16);
+    }
+}
+
+// One (row, segment) item.  A: the aligned granule that holds the row's first byte, m: the first byte's place in it, live: source bytes
+// of the row, wsb: source bytes of a full batch row (a multiple of 16 for a copy, of 8 for G.711), d: the batch row.
+template <int CODEC>
+__device__ __forceinline__ void move_segment(const uint8_t *A, int m, long live, long wsb, uint8_t *d, long lo, int lane) {
+    if (lo >= wsb) return;                                     // (a G.711 row has half the segments of an S16 row of its width)
+    const u32x4 zero{0u, 0u, 0u, 0u};
+    if (lo + kSegBytes <= live) {
+        // a whole segment inside the recording: 8 wave-loads in flight (+ the one granule behind them when the row is misaligned:
+        // m > 0 and lo + 8192 <= live, so it holds row bytes), then the stores
+        u32x4 v[8], extra = zero;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(A + lo + (k * 64 + lane) * 16L));
+        if (m) {
+            if (lane == 0) extra = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(A + lo + kSegBytes));
+            extra = lane0_of(extra);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = shift_bytes(v[k], next_lane(v[k], lane0_of(k < 7 ? v[k + 1] : extra), lane), m);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) put_vector<CODEC, true>(v[k], d, lo + (k * 64 + lane) * 16L, 16, 16);
+        return;
+    }
+    // the segment with the recording's end and / or the padding: one wave-load at a time.  Granule p is read iff it holds a byte of the
+    // row: p < m + live.  A lane may read the granule BEHIND the segment's last vector (p < hi + 16) for its neighbour and stores
+    // nothing there: a misaligned row's last vector ends in it.  That also holds where hi is 8 mod 16 (the end of a G.711 row whose width
+    // is): the last vector starts at hi - 8, its 8 bytes end m + 8 bytes into its granule, past it when m > 8 -- and `p < end` still
+    // admits the read only if that granule holds a byte of the row, which is the page guarantee.
+    const long hi = lo + kSegBytes < wsb ? lo + kSegBytes : wsb;
+    const long end = live > 0 ? m + live : 0;                  // granules at p >= end hold nothing of the row
+    for (long base = lo; base < hi; base += 64 * 16L) {        // (wave-uniform trip count: next_lane needs every lane)
+        const long p = base + lane * 16L;
+        u32x4 c = zero, n = zero;
+        if (p < end && p < hi + 16) c = *reinterpret_cast<const u32x4 *>(A + p);
+        if (m) {
+            if (lane == 63 && p < hi && p + 16 < end) n = *reinterpret_cast<const u32x4 *>(A + p + 16);
+            c = shift_bytes(c, next_lane(c, n, lane), m);
+        }
+        if (p < hi) put_vector<CODEC, false>(c, d, p, live - p, hi - p);
+    }
+}
+
+__global__ void __launch_bounds__(64) gather_expand_rows_kernel(const RowDesc *rows, long n, long width, uint8_t *dst, long segs_per_row) {
+    const long items = n * segs_per_row;
+    const int lane = threadIdx.x;
+    __builtin_amdgcn_s_setprio(3);          // as in gather_rows_kernel
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+        const long row = item / segs_per_row, lo = (item % segs_per_row) * kSegBytes;
+        const size_t s = (size_t)rows[row].ptr;
+        const long tag = rows[row].len, len = tag & kRowLenMask;
+        const int codec = (int)(tag >> kRowCodecShift), m = (int)(s & 15);
+        const uint8_t *A = reinterpret_cast<const uint8_t *>(s - m);
+        uint8_t *d = dst + row * width * 2;
+        if (codec == VAD_PCM_S16) move_segment<0>(A, m, len * 2, width * 2, d, lo, lane);
+        else if (codec == VAD_PCM_ULAW) move_segment<VAD_PCM_ULAW>(A, m, len, width, d, lo, lane);
+        else move_segment<VAD_PCM_ALAW>(A, m, len, width, d, lo, lane);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_gather_rows(const RowDesc *rows, long n, long width, int esz, void *dst, bool rows_on_device, hipStream_t s) {
@@ -86,6 +241,20 @@ hipError_t launch_gather_rows(const RowDesc *rows, long n, long width, int esz, 
     const long waves = rows_on_device ? 4096 : kGatherWaves;
     const unsigned grid = (unsigned)(items < waves ? items : waves);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(64), 0, s, rows, n, wb, esz, static_cast<uint8_t *>(dst), segs);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_expand_rows(const RowDesc *rows, long n, long width, void *dst_i16, bool rows_on_device, hipStream_t s) {
+    if (n <= 0 || width <= 0) return hipSuccess;
+    // The items are sized for an S16 row (2 source bytes a sample), whatever the table holds: a G.711 row uses the first half of its
+    // items and leaves the others at once (move_segment: lo >= wsb), at the price of reading its table entry once more -- 16 bytes
+    // over PCIe per 8 KiB segment for host sources, nothing that shows for device sources.
+    const long segs = (width * 2 + kSegBytes - 1) / kSegBytes;
+    const long items = n * segs;
+    if (items > 0x7fffffffL) return hipErrorInvalidValue;
+    const long waves = rows_on_device ? 4096 : kGatherWaves;      // (as launch_gather_rows)
+    const unsigned grid = (unsigned)(items < waves ? items : waves);
+    hipLaunchKernelGGL(gather_expand_rows_kernel, dim3(grid), dim3(64), 0, s, rows, n, width, static_cast<uint8_t *>(dst_i16), segs);
     return hipGetLastError();
 }
 

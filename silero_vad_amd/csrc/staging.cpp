@@ -14,7 +14,7 @@
 
 extern "C" int vad_stage_rows(const void *const *rows, const long *lens, long n, long width,
                               size_t elem_size, void *dst, int threads) {
-    if (n < 0 || width < 0 || (elem_size != 2 && elem_size != 4)) return VAD_ERR_ARG;
+    if (n < 0 || width < 0 || (elem_size != 1 && elem_size != 2 && elem_size != 4)) return VAD_ERR_ARG;      // (1: G.711 codes, packed as bytes)
     if (n == 0 || width == 0) return VAD_OK;
     if (!rows || !lens || !dst) return VAD_ERR_ARG;
     for (long i = 0; i < n; ++i)

@@ -194,6 +194,13 @@ class Engine:
         (vad_upload_rows; how 0: copy engines, 1: gather kernel).  rows / lens: ctypes arrays."""
         self._check(self._L.vad_upload_rows(self._h, rows, lens, n, width, elem_size, dst.data_ptr(), how, self._stream()))
 
+    def upload_rows_coded(self, rows, lens, codecs, n, width, dst, how=1):
+        """`upload_rows` for rows that may be G.711 (vad_upload_rows_coded): lens / width in samples, codecs a uint8 numpy array (0 int16,
+        1 mu-law, 2 A-law; None: every row int16), dst the int16 [n, width] device batch -- a G.711 row is 1 byte a sample at any
+        address and is expanded on the device.  how 1: pinned host rows, 2: device addresses (0: copy engines, int16 rows only)."""
+        cp = None if codecs is None else codecs.ctypes.data
+        self._check(self._L.vad_upload_rows_coded(self._h, rows, lens, cp, n, width, dst.data_ptr(), how, self._stream()))
+
     def streams_overlap(self, a, b) -> bool:
         """vad_streams_overlap: do kernels on torch streams a and b run beside each other (distinct hardware queues)?"""
         rc = self._L.vad_streams_overlap(self._h, a.cuda_stream, b.cuda_stream)

@@ -7,6 +7,7 @@ only communication is a host-side gather of the (tiny) results to rank 0.
 import os
 from typing import List, Sequence
 
+import numpy as np
 import torch
 
 
@@ -57,17 +58,19 @@ def gather_to_rank0(obj, group=None):
 
 def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate: int = 16000,
                             rank: int = 0, world_size: int = 1, balance: str = "duration",
-                            scheduler: str = "buckets", **kwargs) -> List[list]:
+                            scheduler: str = "buckets", codec=None, **kwargs) -> List[list]:
     """`get_speech_timestamps` over many recordings (the reference's pattern is one worker process
     per file, examples/parallel_example.ipynb cells 5, 7): this rank processes its shard --
     `balance="duration"` (default) deals recordings out by total audio length, `"count"` by contiguous
     index blocks; recordings of any lengths go through `scheduler="buckets"` (length-sorted lock-step
     batches, `streams.ragged_speech_segments`) or `"refill"` (persistent slots, continuous refill,
     `streams.refill_speech_segments`), both scanned on the GPU -- and rank 0 receives every result in
-    input order (other ranks get None).  kwargs are those of get_speech_timestamps."""
+    input order (other ranks get None).  kwargs are those of get_speech_timestamps.  `codec` ("ulaw" / "alaw", or one per
+    recording): the recordings are uint8 G.711 codes; they go to the scheduler as they are (one byte a sample over the link, expanded on
+    the device) and the result is that of the `g711_expand`ed recordings."""
     import warnings
 
-    from .streams import ragged_speech_segments, refill_speech_segments
+    from .streams import _codec_of, g711_expand, ragged_speech_segments, refill_speech_segments
     from .timestamps import get_speech_timestamps
 
     if balance not in ("duration", "count") or scheduler not in ("buckets", "refill"):
@@ -76,6 +79,7 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
         mine = shard_by_duration([int(a.shape[-1]) if hasattr(a, "shape") else len(a) for a in audios], world_size, rank)
     else:
         mine = list(shard_range(len(audios), world_size, rank))
+    cd = _codec_of(audios, codec)                          # (uint8 without a codec, uint8 among int16 / float: refused here)
     results = {}
     scan_kw = {k: kwargs[k] for k in kwargs if k not in ("return_seconds", "time_resolution",
                                                          "visualize_probs", "progress_tracking_callback",
@@ -83,7 +87,10 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
     fast = getattr(model, "audio_forward_device", None)
     if fast is None or kwargs.get("visualize_probs") or kwargs.get("progress_tracking_callback"):
         for i in mine:
-            results[i] = get_speech_timestamps(audios[i], model, sampling_rate=sampling_rate, **kwargs)
+            a = audios[i]                                  # (a list's entry, or a PackedRecordings' view of its arena)
+            if cd is not None:                             # G.711 codes: expanded here, the per-recording path has no device batch
+                a = torch.from_numpy(g711_expand(np.ascontiguousarray(a), int(cd[i])))
+            results[i] = get_speech_timestamps(a, model, sampling_rate=sampling_rate, **kwargs)
     elif mine:
         step, sr = 1, sampling_rate
         if sr > 16000 and sr % 16000 == 0:                 # utils_vad.py:301-307
@@ -100,7 +107,8 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
         # (streams._rates) -- the reference's x[::step] (utils_vad.py:301-307) without the copy.  Segments come back in samples of
         # the 16 kHz signal, like the reference's before its final `* step`.
         lens = [(int(a.shape[0]) + step - 1) // step for a in local]
-        segs = (ragged_speech_segments if scheduler == "buckets" else refill_speech_segments)(local, model, sampling_rate, **scan_kw)
+        segs = (ragged_speech_segments if scheduler == "buckets" else refill_speech_segments)(
+            local, model, sampling_rate, codec=None if cd is None else cd[mine], **scan_kw)
         seconds, res = kwargs.get("return_seconds", False), kwargs.get("time_resolution", 1)
         for r, i in enumerate(mine):
             out = segs[r]

@@ -220,13 +220,15 @@ def _compute_lanes(model, want):
 
 class PackedRecordings:
     """Many recordings inside ONE host tensor -- a decoder's output arena, a memory-mapped shard: recording i is
-    `base[offsets[i] : offsets[i] + lengths[i]]`.  Accepted wherever the corpus functions take a list of recordings; it
+    `base[offsets[i] : offsets[i] + lengths[i]]` (a uint8 base: G.711 codes, 1 byte a sample, packed at any byte offset -- pass
+    `codec=` to the corpus function).  Accepted wherever the corpus functions take a list of recordings; it
     spares the per-recording Python work (150 000 tensor views cost more host time than their audio costs GPU time) and,
     when `base` is pinned, the whole set is one page-locked source for `vad_upload_rows`."""
 
     def __init__(self, base: torch.Tensor, offsets, lengths):
-        if base.dim() != 1 or base.is_cuda or not base.is_contiguous() or base.dtype not in (torch.int16, torch.float32):
-            raise ValueError("base must be a contiguous 1-D CPU tensor of int16 or float32 samples")
+        if base.dim() != 1 or base.is_cuda or not base.is_contiguous() or base.dtype not in (torch.int16, torch.float32, torch.uint8):
+            raise ValueError("base must be a contiguous 1-D CPU tensor of int16 or float32 samples, or of uint8 G.711 codes "
+                             "(the corpus functions' `codec` says which law)")
         self.base = base
         self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         self.lengths = np.ascontiguousarray(lengths, dtype=np.int64)
@@ -301,13 +303,15 @@ class WindowedPlan:
     `density` = live bytes / copied bytes: a sparse set (recordings scattered over a large arena) is better served by the
     gather kernel (streams.ragged_buckets)."""
 
-    def __init__(self, rec: PackedRecordings, max_waste, max_bytes, itemsize, window_bytes, on_windows=None):
-        """on_windows(plan): called as soon as the windows, their spans and the density are known and BEFORE the buckets are planned --
+    def __init__(self, rec: PackedRecordings, max_waste, max_bytes, itemsize, window_bytes, on_windows=None, src_itemsize=None):
+        """itemsize: bytes per sample of the DEVICE batch (what the buckets are planned on); src_itemsize (default: the same): bytes per
+        sample in the arena, what a window's span is measured in -- 1 for G.711 recordings, whose batch is int16.
+        on_windows(plan): called as soon as the windows, their spans and the density are known and BEFORE the buckets are planned --
         the hook for starting the first windows' DMA while the rest of the planning runs."""
         self.lengths = rec.lengths.tolist()
         offs, lens = rec.offsets, rec.lengths
         self.empty = np.flatnonzero(lens <= 0).tolist()
-        order, bounds, o, e = _arena_windows(offs, lens, window_bytes // itemsize)
+        order, bounds, o, e = _arena_windows(offs, lens, window_bytes // (src_itemsize or itemsize))
         live = order
         self.windows = [order[a:b].tolist() for a, b in bounds]      # recording indices of each window (arena order)
         self.span = [(int(o[a]), int(e[b - 1])) for a, b in bounds]  # (first, last + 1) sample
@@ -334,7 +338,7 @@ def _as_packed(audios):
     if isinstance(audios, PackedRecordings) or len(audios) < 2:
         return None
     first = audios[0]
-    if not torch.is_tensor(first) or first.is_cuda or first.dtype not in (torch.int16, torch.float32):
+    if not torch.is_tensor(first) or first.is_cuda or first.dtype not in (torch.int16, torch.float32, torch.uint8):
         return None
     st = first.untyped_storage()
     key, dtype, esz = st.data_ptr(), first.dtype, first.element_size()
@@ -356,6 +360,74 @@ def _describe(audios):
         return audios.base.dtype == torch.int16, audios.lengths.tolist()
     as_i16 = len(audios) > 0 and all(torch.is_tensor(a) and a.dtype == torch.int16 for a in audios)
     return as_i16, [int(a.shape[0]) if hasattr(a, "shape") else len(a) for a in audios]
+
+
+def _sample_kind(dtype):
+    """what a recording's samples are: G.711 codes (uint8), int16 PCM, or something that is converted to float32"""
+    return 0 if dtype == torch.uint8 else 1 if dtype == torch.int16 else 2
+
+
+_MIXED_U8 = "mixed uint8 (G.711) / int16 / float recordings in one call"
+
+
+def _is_u8(a):
+    return str(getattr(a, "dtype", "")) in ("torch.uint8", "uint8")
+
+
+def _codec_of(audios, codec):
+    """The `codec` argument of a corpus call, checked against its recordings: -> None (int16 / float recordings, no codec) or the codec
+    of every recording as uint8 ids (1 mu-law, 2 A-law).  uint8 recordings without a codec are refused -- bytes are never guessed at --
+    and so is uint8 mixed with int16 / float."""
+    n = len(audios)
+    u8 = [audios.base.dtype == torch.uint8] * n if isinstance(audios, PackedRecordings) else [_is_u8(a) for a in audios]
+    if codec is None:
+        if any(u8):
+            raise TypeError("uint8 recordings need codec='ulaw' | 'alaw' (or one per recording): bytes are never guessed at")
+        return None
+    cd = np.full(n, _codec_id(codec), np.uint8) if isinstance(codec, (str, int, np.integer)) else _codec_rows(codec)
+    if len(cd) != n:
+        raise ValueError(f"codec needs one entry per recording: {len(cd)} for {n}")
+    if n and (cd.min() < _PCM["ulaw"] or cd.max() > _PCM["alaw"]):
+        raise ValueError("a corpus codec is 'ulaw' or 'alaw'")
+    if not all(u8):
+        raise TypeError(_MIXED_U8 if any(u8) else "codec given, but the recordings are not uint8 G.711 codes")
+    return cd
+
+
+def _coded_input(audios, codec, model):
+    """(recordings, codec ids per recording or None) as the schedulers take them.  A model whose engine has the device expansion
+    (Engine.upload_rows_coded) gets the G.711 bytes as they are; any other (a CPU stand-in) gets them expanded on the host (g711_expand)
+    as int16 recordings -- the definition of what the device route computes."""
+    cd = _codec_of(audios, codec)
+    if cd is None or hasattr(getattr(model, "engine", None), "upload_rows_coded"):
+        return audios, cd
+    out = []
+    for a, c in zip(audios, cd):
+        a = a if torch.is_tensor(a) else torch.as_tensor(a)
+        out.append(torch.from_numpy(g711_expand(a.contiguous().numpy(), int(c))))
+    return out, None
+
+
+def _slot_bytes(nbytes, direct, coded):
+    """(pinned staging, device) bytes of a staging slot for a device batch of nbytes: pinned sources need no staging; pageable G.711 is
+    staged as bytes (half the int16 batch) and keeps a device copy of them BEHIND the batch, which the expansion reads."""
+    if direct:
+        return 0, nbytes
+    return (nbytes // 2, nbytes + nbytes // 2) if coded else (nbytes, nbytes)
+
+
+def _upload_rows(engine, rows_p, lens_p, codecs, n, width, esz, dst, how):
+    """vad_upload_rows, or vad_upload_rows_coded when the rows carry codecs (uint8 ids per row; dst is then int16)"""
+    if codecs is not None:
+        engine.upload_rows_coded(rows_p, lens_p, codecs, n, width, dst, how)
+    else:
+        engine.upload_rows(rows_p, lens_p, n, width, esz, dst, how)
+
+
+def _gather_instead_of_dma():
+    import warnings
+    warnings.warn("SILERO_VAD_AMD_UPLOAD=dma: a DMA cannot expand G.711 -- such recordings take the gather kernel")
+    return 1
 
 
 class _Sources:
@@ -382,9 +454,9 @@ class _Sources:
             a = a if torch.is_tensor(a) else torch.as_tensor(a)
             if a.dim() != 1:
                 raise ValueError("More than one dimension in audio. Are you trying to process audio with 2 channels?")
-            if (a.dtype == torch.int16) != (dtype == torch.int16):
+            if _sample_kind(a.dtype) != _sample_kind(dtype):
                 # (an int16 recording among float ones would be read as floats in [-32768, 32767]: never silently)
-                raise TypeError("mixed int16 / float recordings in one call")
+                raise TypeError("mixed int16 / float recordings in one call" if torch.uint8 not in (a.dtype, dtype) else _MIXED_U8)
             if a.dtype != dtype or not a.is_contiguous() or a.is_cuda:
                 a = a.to("cpu", dtype).contiguous()      # (a strided view of int16 PCM lands here: same dtype, new layout)
             self.keep.append(a)
@@ -421,7 +493,8 @@ def _stage_into(src: "_Sources", idxs, width, dst: torch.Tensor):
 
 
 def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
-                   max_bytes: int = 256 << 20, plan: RaggedPlan = None, post=None, meta=None, lanes: int = 2, prepare_only: bool = False):
+                   max_bytes: int = 256 << 20, plan: RaggedPlan = None, post=None, meta=None, lanes: int = 2, prepare_only: bool = False,
+                   codec=None):
     """Generator over the plan's buckets: yields (indices, probs[len(indices), T_bucket] on the CPU).
     Recording i of a bucket owns the first ceil(len_i / N) entries of its row.
 
@@ -435,12 +508,20 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     and stop (ragged_reserve): a run over the same recordings then allocates nothing.
 
     Ingest: recordings in pinned host memory go straight to the device batch (vad_upload_rows: no host copy);
-    pageable ones are packed into pinned staging by the native threaded copy and copied from there."""
+    pageable ones are packed into pinned staging by the native threaded copy and copied from there.
+
+    `codec` ("ulaw" / "alaw", or one per recording): the recordings are uint8 G.711 codes.  They take the same routes at ONE byte a
+    sample -- the arena windows' DMAs, the gather over PCIe, the staging buffers carry the codes -- and the gather kernel expands them
+    into the int16 batch (vad_upload_rows_coded); the buckets are planned on the batch's bytes, so the call forms the buckets of its
+    int16 twin and every result is that of the same call on the `g711_expand`ed recordings."""
     t_setup = time.perf_counter()
     n = _rates(sampling_rate)[2]                          # input samples per chunk (512 k for a multiple of 16 kHz)
+    audios, cd = _coded_input(audios, codec, model)
     as_i16, lengths = _describe(audios)
-    dtype = torch.int16 if as_i16 else torch.float32
-    esz = 2 if as_i16 else 4
+    coded = cd is not None
+    dtype = torch.int16 if as_i16 or coded else torch.float32
+    esz = 2 if as_i16 or coded else 4                     # the DEVICE batch; the source: 1 byte a sample for G.711
+    src_dtype, src_esz = (torch.uint8, 1) if coded else (dtype, esz)
     fast = model.audio_forward_device
     dev = getattr(model, "device", None)
     on_gpu = dev is not None and torch.device(dev).type == "cuda"
@@ -464,7 +545,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             v = win["next"]
             a, b = win["span"][v]
             j = v % 3
-            nb = (b - a) * esz
+            nb = (b - a) * src_esz
             if win["buf"][j] is None or win["buf"][j].numel() < nb:
                 # (the old block goes back to the caching allocator: its cuts on pool.stream were recorded against it
                 #  -- record_stream below -- and the copy stream waits for the last of them before anything else)
@@ -479,7 +560,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             with torch.cuda.stream(win["stream"]):
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record(win["stream"])
-                win["buf"][j][:nb].view(dtype).copy_(win["base"][a:b], non_blocking=True)
+                win["buf"][j][:nb].view(src_dtype).copy_(win["base"][a:b], non_blocking=True)
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record(win["stream"])
             copies.append((e0, e1))
@@ -507,11 +588,11 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
                 win["stream"].wait_stream(cur)            # (the arena was written before this call in stream order, if at all)
                 ensure_window(2)
 
-            wp = WindowedPlan(packed, max_waste, max_bytes, esz, window_bytes=wbytes, on_windows=first_windows)
+            wp = WindowedPlan(packed, max_waste, max_bytes, esz, window_bytes=wbytes, on_windows=first_windows, src_itemsize=src_esz)
             if takes_windows(wp):
                 plan, audios = wp, packed
     plan = plan or RaggedPlan(lengths, max_waste, max_bytes, esz)
-    src = _Sources(audios, dtype, check_pinned=on_gpu and mode != "stage" and hasattr(getattr(model, "engine", None), "upload_rows"))
+    src = _Sources(audios, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(getattr(model, "engine", None), "upload_rows"))
     if not on_gpu:                                        # CPU stand-in models (tests)
         if prepare_only:
             return
@@ -523,7 +604,10 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         return
     direct = src.pinned
     how = 0 if mode == "dma" else 1
+    if coded and how == 0:
+        how = _gather_instead_of_dma()
     windowed = direct and isinstance(plan, WindowedPlan)
+
     if windowed:
         if win["stream"] is None:                          # (a plan handed in by the caller, or prepare_only: nothing was started early)
             win["span"], win["base"] = plan.span, audios.base
@@ -548,9 +632,9 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             big_b = max(plan.buckets, key=lambda b: len(b) * ((max(plan.lengths[b[0]], n) + align - 1) // align * align))
             nb = len(big_b) * ((max(plan.lengths[big_b[0]], n) + align - 1) // align * align) * esz
             for k in range(pool.slots):
-                pool.get(k, nb if not direct else 0, nb)
+                pool.get(k, *_slot_bytes(nb, direct, coded))
             if windowed:                                   # the three window buffers: warm torch's allocator with blocks of the largest window
-                wb = max((b - a) * esz for a, b in plan.span)
+                wb = max((b - a) * src_esz for a, b in plan.span)
                 with torch.cuda.stream(win["stream"]):
                     warm = [torch.empty(max(wb, 1 << 20), dtype=torch.uint8, device=dev) for _ in range(3)]
                 del warm
@@ -593,9 +677,10 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         L = max(plan.lengths[idxs[0]], n)
         width = (L + align - 1) // align * align          # row pitch
         nbytes = len(idxs) * width * esz
-        i = pool.get(k, nbytes if not direct else 0, nbytes)
+        host_b, dev_b = _slot_bytes(nbytes, direct, coded)
+        i = pool.get(k, host_b, dev_b)
         if not windowed:
-            STATS["h2d_bytes"] += nbytes
+            STATS["h2d_bytes"] += nbytes * src_esz // esz
         STATS["buckets"] += 1
         STATS["padded"] += len(idxs) * L
         STATS["real"] += sum(plan.lengths[j] for j in idxs)
@@ -613,7 +698,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             m_host.copy_(mt)
         t0 = time.perf_counter()
         if not direct:
-            host = pool.host[i][:nbytes].view(dtype).view(len(idxs), width)
+            host = pool.host[i][:host_b].view(src_dtype).view(len(idxs), width)
             _stage_into(src, idxs, width, host)
             STATS["stage_s"] += time.perf_counter() - t0
             if late_wait is not None:
@@ -626,14 +711,18 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             ensure_window(w + 2)                          # this bucket's window and the two after it are on their way
             pool.stream.wait_event(win["ev"][w])
             a0 = plan.span[w][0]
-            rows = np.ascontiguousarray(win["buf"][w % 3].data_ptr() + (audios.offsets[idxs] - a0) * esz, dtype=np.uint64)
+            rows = np.ascontiguousarray(win["buf"][w % 3].data_ptr() + (audios.offsets[idxs] - a0) * src_esz, dtype=np.uint64)
             lens = np.ascontiguousarray(src.len[idxs])
+        cd_k = np.ascontiguousarray(cd[idxs]) if coded else None
+
+        def upload(rows_p, lens_p, how_):
+            _upload_rows(model.engine, rows_p, lens_p, cd_k, len(idxs), width, esz, d, how_)
+
         with torch.cuda.stream(pool.stream):
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record(pool.stream)
             if windowed:
-                model.engine.upload_rows(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)),
-                                         lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)), len(idxs), width, esz, d, 2)
+                upload(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)), 2)
                 if last_bucket_of[w] == k:                # the window's buffer may take another window once this cut is done
                     win["free"][w % 3] = torch.cuda.Event()
                     win["free"][w % 3].record(pool.stream)
@@ -642,8 +731,15 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
                 if late_wait is not None:                 # (the per-row DMA route: the same rule)
                     late_wait.synchronize()
                 tabs = src.tables(idxs)
-                model.engine.upload_rows(tabs[2], tabs[3], len(idxs), width, esz, d, how)
+                upload(tabs[2], tabs[3], how)
                 STATS["upload_call_s"] += time.perf_counter() - t0
+            elif coded:
+                # the staged codes cross the link in one copy, into the slot's device block behind the batch; the expansion reads
+                # them there with the recordings' TRUE lengths (the staging's zero bytes are not audio)
+                codes = pool.dev[i][nbytes:nbytes + host_b].view(len(idxs), width)
+                codes.copy_(host, non_blocking=True)
+                rows = np.ascontiguousarray(codes.data_ptr() + np.arange(len(idxs), dtype=np.int64) * width, dtype=np.uint64)
+                upload(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), src.tables(idxs)[3], 2)
             else:
                 d.copy_(host, non_blocking=True)
             m_dev = m_host.to(dev, non_blocking=True) if m_host is not None else None
@@ -717,28 +813,29 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
 
 
 def ragged_reserve(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15, max_bytes: int = 256 << 20,
-                   lanes: int = 2):
+                   lanes: int = 2, codec=None):
     """Everything a `ragged_probs` / `ragged_speech_segments` run over these recordings would allocate -- the compute lanes and their
     streams, every lane's scratch (vad_reserve: a later growth synchronises the device and, on some boxes, costs 0.1-0.2 s of
     hipFree / hipMalloc for the multi-GB gx scratch: profiles/r05_ingest_routes.md), the staging slots -- sized for the plan's
     largest bucket, up front.  Call it once before a corpus run (or a timed region); the run itself then allocates nothing."""
-    for _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, lanes=lanes, prepare_only=True):
+    for _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, lanes=lanes, prepare_only=True, codec=codec):
         pass
 
 
 def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
-                 max_bytes: int = 256 << 20, plan: RaggedPlan = None) -> List[torch.Tensor]:
+                 max_bytes: int = 256 << 20, plan: RaggedPlan = None, codec=None) -> List[torch.Tensor]:
     """Speech probabilities of many recordings of different lengths.
 
     Returns one 1-D CPU float tensor per recording (ceil(len / N) entries), bit-identical to
     ``model.audio_forward(audio[None], sr)[0]`` on that recording alone.  ``audios`` may be float
     tensors in [-1, 1] or int16 PCM (all of one kind).  `model` needs ``audio_forward_device``
     (HipSileroVAD); staging + H2D of bucket k+1 overlap the kernels of bucket k.  `sampling_rate` may be a multiple of 16000: the
-    recordings then stay at their raw rate all the way into HBM (_rates)."""
+    recordings then stay at their raw rate all the way into HBM (_rates).  `codec` ("ulaw" / "alaw", or one per recording): the
+    recordings are uint8 G.711 codes and cross the link as such (ragged_buckets); the result is that of the `g711_expand`ed recordings."""
     n = _rates(sampling_rate)[2]
     lengths = _describe(audios)[1]
     out: List[torch.Tensor] = [torch.empty(0)] * len(audios)
-    for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, plan):
+    for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, plan, codec=codec):
         for row, i in enumerate(idxs):
             out[i] = probs[row, : (lengths[i] + n - 1) // n].clone()
     return out
@@ -746,9 +843,9 @@ def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste:
 
 def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                            max_bytes: int = 256 << 20, threads: int = 0, device_scan: bool = None,
-                           as_arrays: bool = False, **scan_kw) -> List[list]:
+                           as_arrays: bool = False, codec=None, **scan_kw) -> List[list]:
     """Speech segments (sample indices) of many recordings: bucketed GPU batches, then the segmenter.
-    scan_kw: the threshold/duration arguments of get_speech_timestamps.  `audios`: a list of 1-D tensors or a
+    scan_kw: the threshold/duration arguments of get_speech_timestamps.  codec: as in ragged_probs (uint8 G.711 recordings).  `audios`: a list of 1-D tensors or a
     PackedRecordings.  as_arrays: return (counts int64[n], segments int64[sum(counts), 2]) -- recording i owns rows
     cumsum(counts)[i-1] .. -- instead of a list of lists of dicts (for corpora of 10^5+ recordings the dicts cost more
     host time than the GPU work; the arrays are also what a host-side gather to rank 0 wants).
@@ -780,7 +877,7 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
             return [counts, segs]
 
         for idxs, (counts, segs), probs_dev in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes,
-                                                              post=post, meta=meta):
+                                                              post=post, meta=meta, codec=codec):
             t0 = time.perf_counter()
             cnt = counts.numpy()
             if len(cnt) and int(cnt.max()) > cap0:             # rare: rescan this bucket with room for all
@@ -790,7 +887,7 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
             parts.append((np.asarray(idxs, dtype=np.int64), cnt.copy(), segs.numpy()))
             STATS["scan_s"] += time.perf_counter() - t0
     else:
-        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes):
+        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec):
             lens = [lengths[i] for i in idxs]
             t0 = time.perf_counter()
             segs = segment_probs_batch(probs, [(m + n - 1) // n for m in lens], [(m + dec - 1) // dec for m in lens], net_sr,
@@ -1043,7 +1140,7 @@ def _assign_window_buffers(first: np.ndarray, last: np.ndarray, ahead: int, slac
 
 
 def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_chunks: int, plan: "RefillPlan" = None, on_slab=None,
-                 prepare_only: bool = False):
+                 prepare_only: bool = False, codec=None):
     """The continuous-refill loop (RefillPlan) as a generator: stages slab k + 1 while the kernels of slab k run, scatters every slab's
     probabilities into one flat device tensor (recording i owns out_flat[base[i] : base[i + 1]]) and yields k once slab k has been
     ENQUEUED.  `on_slab(k, finished, out_flat, base)` is called right before that, with the recordings whose last chunk lies in slab k
@@ -1051,14 +1148,18 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     value is (out_flat, base, plan).  `prepare_only`: plan the run and make everything that allocates -- the window buffers, the staging
     slots, the engine's scratch, the flat probability tensor -- then stop (refill_reserve): a run over the same recordings allocates
     nothing (7 GiB of window buffers for a 1 263 h shard are 60 ms when they come fresh from the driver, 0.5 s when an outgrown block
-    has to go back first)."""
+    has to go back first).  `codec`: the recordings are uint8 G.711 codes (ragged_buckets: the same rules -- every route carries
+    the codes at one byte a sample and the gather kernel expands them into the int16 slab)."""
     t_setup = time.perf_counter()
     net_sr, _, n = _rates(sampling_rate)
     eng = model.engine
+    audios, cd = _coded_input(audios, codec, model)
+    coded = cd is not None
     dev = torch.device(getattr(eng, "torch_device", None) or torch.device("cuda", eng.device))
     on_gpu = dev.type == "cuda"
     as_i16, lengths = _describe(audios)
-    dtype, esz = (torch.int16, 2) if as_i16 else (torch.float32, 4)
+    dtype, esz = (torch.int16, 2) if as_i16 or coded else (torch.float32, 4)     # the DEVICE slab; the source: 1 byte a sample for G.711
+    src_dtype, src_esz = (torch.uint8, 1) if coded else (dtype, esz)
     lens_np = np.asarray(lengths, dtype=np.int64).reshape(-1)
     slots = max(1, min(int(slots), int((lens_np > 0).sum())))
     mode = _upload_mode()
@@ -1072,12 +1173,12 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     if plan is None and on_gpu and mode in ("", "window") and hasattr(eng, "upload_rows"):
         packed = audios if isinstance(audios, PackedRecordings) else _as_packed(audios)
         if packed is not None and packed.base.is_pinned() and int((lens_np > 0).sum()):
-            slab_bytes = slots * slab_chunks * n * esz
+            slab_bytes = slots * slab_chunks * n * src_esz                                      # (of the arena: what a slab reads of a window)
             wbytes = int(os.environ.get("SILERO_VAD_AMD_REFILL_WINDOW", 0)) or (1 << 30)        # (256 MiB windows: 0.92 of the link, 1 GiB: 0.95)
             # (the slots start over `ramp` slabs and the first windows are small -- 1/8, 1/4, 1/2 of a window: the first kernel runs
             #  after 7 ms of link time instead of 37, the first recordings retire that much earlier)
             ramp = max(1, int(os.environ.get("SILERO_VAD_AMD_REFILL_RAMP", "8")))
-            order, bounds, o_, e_ = _arena_windows(packed.offsets, packed.lengths, wbytes // esz, lead_limit=(wbytes // esz) // 8 if int(os.environ.get("SILERO_VAD_AMD_REFILL_LEAD", ramp > 1)) else 0)
+            order, bounds, o_, e_ = _arena_windows(packed.offsets, packed.lengths, wbytes // src_esz, lead_limit=(wbytes // src_esz) // 8 if int(os.environ.get("SILERO_VAD_AMD_REFILL_LEAD", ramp > 1)) else 0)
             spans = np.asarray([(o_[a], e_[b - 1]) for a, b in bounds], dtype=np.int64).reshape(-1, 2)
             copied = int((spans[:, 1] - spans[:, 0]).sum())
             dense = mode == "window" or float(lens_np[lens_np > 0].sum()) >= 0.6 * copied
@@ -1088,7 +1189,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     win_of[order[a:b]] = w
                 w_first = np.asarray([wplan.first_slab[order[a:b]].min() for a, b in bounds], dtype=np.int64)
                 w_last = np.asarray([wplan.last_slab[order[a:b]].max() for a, b in bounds], dtype=np.int64)
-                wmax = int((spans[:, 1] - spans[:, 0]).max()) * esz
+                wmax = int((spans[:, 1] - spans[:, 0]).max()) * src_esz
                 wmax = (wmax + 255) // 256 * 256
                 ahead = max(2, -(-2 * wmax // max(slab_bytes, 1))) + 1          # two windows' worth of slabs in front of the reader
                 slack = int(os.environ.get("SILERO_VAD_AMD_REFILL_SLACK", "2"))      # (1: A/B -- the DMAs may then wait on the device)
@@ -1106,9 +1207,11 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     STATS["refill_window_buffers"] = max(STATS["refill_window_buffers"], n_buf)
     plan = plan or RefillPlan(lens_np, slots, slab_chunks, n)
     B, S, width = plan.slots, plan.slab_chunks, plan.slab_chunks * n
-    src = _Sources(audios, dtype, check_pinned=on_gpu and mode != "stage" and hasattr(eng, "upload_rows"))
+    src = _Sources(audios, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(eng, "upload_rows"))
     direct = src.pinned                                # pinned recordings: one gather kernel per slab, no host copy
     how = 0 if mode == "dma" else 1
+    if coded and how == 0:
+        how = _gather_instead_of_dma()
     base = np.zeros(len(audios) + 1, dtype=np.int64)   # recording i owns out_flat[base[i] : base[i] + n_chunks(i)]
     np.cumsum(np.where(lens_np > 0, (lens_np + n - 1) // n, 0), out=base[1:])
     total = int(base[-1])
@@ -1156,7 +1259,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
             livem = w_ >= 0
             dptr = np.zeros(len(lens_np), dtype=np.uint64)
             dptr[livem] = (blk.data_ptr() + wf["buf_of"][w_[livem]] * wf["wmax"]
-                           + (wf["packed"].offsets[livem] - wf["spans"][w_[livem], 0]) * esz).astype(np.uint64)
+                           + (wf["packed"].offsets[livem] - wf["spans"][w_[livem], 0]) * src_esz).astype(np.uint64)
             ptr0 = dptr
 
         def issue_windows(upto):
@@ -1166,7 +1269,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                 v = wf["next"]
                 j = int(wf["buf_of"][v])
                 a, b = (int(x) for x in wf["spans"][v])
-                nb = (b - a) * esz
+                nb = (b - a) * src_esz
                 prev = wf["holder"].get(j)
                 if prev is not None:
                     # recorded behind the last cut that read window `prev`, at least two slabs ago: complete by now (stage() has waited
@@ -1177,7 +1280,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     else:
                         wf["stream"].wait_event(rel)
                 with torch.cuda.stream(wf["stream"]):
-                    wf["blk"][j * wf["wmax"]: j * wf["wmax"] + nb].view(dtype).copy_(wf["packed"].base[a:b], non_blocking=True)
+                    wf["blk"][j * wf["wmax"]: j * wf["wmax"] + nb].view(src_dtype).copy_(wf["packed"].base[a:b], non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(wf["stream"])
                 wf["ev"][v] = ev
@@ -1263,19 +1366,24 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
             sl, rec, at, take = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
             rows = np.zeros(B, dtype=np.uint64)
             lens = np.zeros(B, dtype=np.int64)
-            rows[sl] = ptr0[rec] + (at * esz).astype(np.uint64)
+            rows[sl] = ptr0[rec] + (at * src_esz).astype(np.uint64)
             lens[sl] = take
             rows_p = rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
             lens_p = lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
+            cd_k = None
+            if coded:
+                cd_k = np.zeros(B, dtype=np.uint8)                            # (a slot without a recording: an empty row, zeros)
+                cd_k[sl] = cd[rec]
             nbytes = B * width * esz
             t0 = time.perf_counter()
             if on_gpu:
-                i = pool.get(k, 0 if direct else nbytes, nbytes)
-                host = None if direct else pool.host[i][:nbytes].view(dtype).view(B, width)
+                host_b, dev_b = _slot_bytes(nbytes, direct, coded)
+                i = pool.get(k, host_b, dev_b)
+                host = None if direct else pool.host[i][:host_b].view(src_dtype).view(B, width)
             else:
                 i, host = 0, torch.empty((B, width), dtype=dtype)
             if host is not None:
-                rc = lib().vad_stage_rows(rows_p, lens_p, B, width, esz, host.data_ptr(), 0)
+                rc = lib().vad_stage_rows(rows_p, lens_p, B, width, src_esz, host.data_ptr(), 0)
                 if rc:
                     raise _lib.VadError(rc, "vad_stage_rows")
                 STATS["stage_s"] += time.perf_counter() - t0
@@ -1284,7 +1392,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                 idx_k, rs_k = slab_meta(k)
                 return host, None, i, idx_k, rs_k
             if wf is None:
-                STATS["h2d_bytes"] += nbytes
+                STATS["h2d_bytes"] += nbytes * src_esz // esz
             else:
                 issue_windows(k)
                 for v in wf["by_first"].pop(k, ()):                         # the windows this slab is the first to read
@@ -1301,15 +1409,20 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     pool.stream.wait_event(pool.consumed[i])
             with torch.cuda.stream(pool.stream):
                 if wf is not None:
-                    eng.upload_rows(rows_p, lens_p, B, width, esz, d, 2)      # (2: the rows are device addresses)
+                    _upload_rows(eng, rows_p, lens_p, cd_k, B, width, esz, d, 2)    # (2: the rows are device addresses)
                     STATS["upload_call_s"] += time.perf_counter() - t0
                     for v in wf["by_last"].pop(k, ()):                         # the windows this slab is the last to read: released
                         rel = torch.cuda.Event()
                         rel.record(pool.stream)
                         wf["release"][v] = rel
                 elif direct:
-                    eng.upload_rows(rows_p, lens_p, B, width, esz, d, how)
+                    _upload_rows(eng, rows_p, lens_p, cd_k, B, width, esz, d, how)
                     STATS["upload_call_s"] += time.perf_counter() - t0
+                elif coded:                                                    # staged codes: one copy, expanded from the slot's device block
+                    codes = pool.dev[i][nbytes:nbytes + host_b].view(B, width)
+                    codes.copy_(host, non_blocking=True)
+                    at_dev = np.ascontiguousarray(codes.data_ptr() + np.arange(B, dtype=np.int64) * width, dtype=np.uint64)
+                    _upload_rows(eng, at_dev.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens_p, cd_k, B, width, esz, d, 2)
                 else:
                     d.copy_(host, non_blocking=True)
                 ev = torch.cuda.Event()
@@ -1322,7 +1435,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
         if prepare_only:
             if on_gpu:
                 for k in range(pool.slots):
-                    pool.get(k, 0 if direct else B * width * esz, B * width * esz)
+                    pool.get(k, *_slot_bytes(B * width * esz, direct, coded))
                 torch.cuda.synchronize(dev)
             return None, base, plan
         staged = stage(0) if n_slabs else None
@@ -1352,8 +1465,8 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     return out_flat, base, plan
 
 
-def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None):
-    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan)
+def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, codec=None):
+    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec)
     while True:
         try:
             next(it)
@@ -1361,10 +1474,10 @@ def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None):
             return stop.value
 
 
-def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32):
+def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None):
     """Everything a refill run over these recordings allocates, allocated now (`ragged_reserve`'s twin): the arena windows' device
     buffers, the staging slots, the engine's scratch, the block the flat probability tensor will take.  Returns the plan."""
-    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True)
+    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True, codec=codec)
     while True:
         try:
             next(it)
@@ -1373,35 +1486,37 @@ def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: i
 
 
 def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32,
-                 plan: RefillPlan = None, _keep_on_device: bool = False):
+                 plan: RefillPlan = None, _keep_on_device: bool = False, codec=None):
     """Speech probabilities of many recordings of different lengths through `slots` persistent stream slots
     (RefillPlan).  Returns one 1-D CPU float tensor per recording, bit-identical to
     ``model.audio_forward(audio[None], sr)[0]``: the state and context a slot carries from slab to slab are exactly
     what a single call carries from chunk to chunk, and a re-admitted slot starts from zeros like `reset_states()`.
     Staging of slab k+1 (native threaded copy into pinned memory + H2D on a side stream) overlaps the kernels of
     slab k.  `audios`: float tensors in [-1, 1] or int16 PCM (all of one kind); `sampling_rate` may be a multiple of 16000 (raw
-    recordings, _rates: a slab is slab_chunks x 512 k raw samples, the carried context is the 16 kHz net's)."""
-    out_flat, base, plan = _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan)
+    recordings, _rates: a slab is slab_chunks x 512 k raw samples, the carried context is the 16 kHz net's).  `codec` ("ulaw" / "alaw",
+    or one per recording): uint8 G.711 recordings, as in ragged_probs."""
+    out_flat, base, plan = _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec)
     if _keep_on_device:
         return out_flat, base, plan
     flat = out_flat.cpu()
     return [flat[base[i]:base[i + 1]].clone() for i in range(len(audios))]
 
 
-def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, **scan_kw):
+def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None,
+                           **scan_kw):
     """The continuous-refill scheduler with RESULTS AS RECORDINGS RETIRE -- what the reference's worker pool does, each file's
     timestamps handed back when that file is done (examples/parallel_example.ipynb cell 7).  Generator of
     (recording indices int64[m], counts int64[m], segments int64[m, cap, 2]) batches: behind the slab in which a recording's last
     chunk was computed, ONE device scan (vad_segment_probs_device, a lane per recording, over the recording's own row of the flat
     probability tensor) turns the retired recordings into segment lists, which ride back over PCIe asynchronously; a batch is
     yielded as soon as its copy has landed (a slab or two behind the kernels; nothing here blocks the pipeline).  Probabilities
-    never leave the GPU.  Segments are in samples of the net's rate (x[::k] for raw 32 / 48 kHz recordings)."""
+    never leave the GPU.  Segments are in samples of the net's rate (x[::k] for raw 32 / 48 kHz recordings).  codec: as in refill_probs."""
     net_sr, dec, _ = _rates(sampling_rate)
     lengths = (np.asarray(_describe(audios)[1], dtype=np.int64).reshape(-1) + dec - 1) // dec     # samples at the net's rate: the scan's unit
     eng = model.engine
     on_gpu = hasattr(eng, "_h")
     if not on_gpu:                                                        # CPU stand-in engines (tests): scan at the end, on the host
-        flat, base, _ = _refill_run(audios, model, sampling_rate, slots, slab_chunks)
+        flat, base, _ = _refill_run(audios, model, sampling_rate, slots, slab_chunks, codec=codec)
         from .timestamps import segment_probs
         for i in range(len(lengths)):
             sg = segment_probs(flat[base[i]:base[i + 1]], int(lengths[i]), net_sr, **scan_kw) if lengths[i] > 0 else []
@@ -1496,7 +1611,7 @@ def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, 
             pending.append((finished.copy(), bufs, m, ev, out_flat, meta))
             STATS["scan_s"] += time.perf_counter() - t0
 
-    for _ in _refill_iter(audios, model, sampling_rate, slots, slab_chunks, None, on_slab):
+    for _ in _refill_iter(audios, model, sampling_rate, slots, slab_chunks, None, on_slab, codec=codec):
         while ready:
             yield ready.pop(0)
     if acc["lists"]:
@@ -1512,14 +1627,14 @@ def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, 
 
 
 def refill_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024,
-                           slab_chunks: int = 32, as_arrays: bool = False, **scan_kw) -> List[list]:
+                           slab_chunks: int = 32, as_arrays: bool = False, codec=None, **scan_kw) -> List[list]:
     """`ragged_speech_segments` over the continuous-refill scheduler (refill_segments_stream: every recording is scanned on the GPU
     behind the slab it retires in, its segment list crosses PCIe while later slabs run).  as_arrays: (counts int64[n], segments
     int64[sum(counts), 2]) like ragged_speech_segments, instead of a list of lists of dicts."""
     n_rec = len(audios)
     counts_all = np.zeros(n_rec, dtype=np.int64)
     parts = []
-    for idx, cnt, segs in refill_segments_stream(audios, model, sampling_rate, slots, slab_chunks, **scan_kw):
+    for idx, cnt, segs in refill_segments_stream(audios, model, sampling_rate, slots, slab_chunks, codec=codec, **scan_kw):
         counts_all[idx] = cnt
         parts.append((idx, cnt, segs))
     t0 = time.perf_counter()
