@@ -63,7 +63,7 @@ void vad_destroy(vad_engine *e);
  * (tests/test_concurrency.py).  What the engine does not arrange: a hipGraph capture is a process-wide state of the runtime --
  * while one thread captures (global capture mode), allocating calls of other threads (vad_create / vad_clone / vad_pump_create, a
  * scratch growth) fail; capture while the other threads make no such call.
- * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed and vad_g711_expand are re-entrant (no shared state);
+ * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed, vad_g711_expand and vad_decimate are re-entrant (no shared state);
  * vad_stage_rows and vad_segment_probs_batch serialise themselves on the process-wide helper pool (tests/test_host_concurrency.py). */
 int  vad_clone(const vad_engine *e, vad_engine **out);
 const char *vad_strerror(int status);
@@ -413,6 +413,47 @@ int  vad_pump_submit_burst(vad_pump *p, int r, const int32_t *stream_of_row, con
                            const uint8_t *codec_of_row, long n_rows);
 int  vad_pump_burst_steps(const vad_pump *p, int r);
 const float *vad_pump_burst_probs(const vad_pump *p, int r, int j);
+/* WIDE packet ticks -- WebRTC and Opus decoders deliver 32 / 48 kHz PCM, and the rest of the library takes any multiple of 16 kHz by the
+ * reference's rule x[::sr / 16000] (src/silero_vad/utils_vad.py:39-42, :301-304).  A wide tick's rows are int16 samples at step x 16 kHz,
+ * and the device keeps every step-th of them on their way into the stream's chunk: no host pass, no per-stream comb bookkeeping in the
+ * caller.
+ * vad_pump_set_wideband(p, max_step): max_step = 2 (32 kHz) or 3 (48 kHz); anything else, 1 included, is VAD_ERR_ARG.  Only on a 16 kHz
+ * pump (VAD_ERR_SAMPLE_RATE on an 8 kHz one: the reference decimates multiples of 16000 only) and only while no tick is in flight
+ * (VAD_ERR_ARG otherwise).  It allocates a second page-locked ring of ring_slots WIDE slots and three device landing buffers, each
+ * [row table | flags | streams * N * max_step int16] (75 MB on the device, 101 MB page-locked at 8 192 streams, 4 slots, 48 kHz): every
+ * stream can deliver a full 32 ms at max_step in the same tick.  Another max_step reallocates (and zeroes every comb phase); the same
+ * one is a no-op.  A pump on which it was never called allocates none of that and runs every other route through the code it always
+ * ran.  vad_pump_wide_slot(p, r): wide slot r's sample area, streams * N * max_step * 2 bytes; NULL when wideband is not enabled or r is
+ * bad.  Ring slot r and wide slot r are the same tick slot: one tick at a time uses r, through either.
+ * vad_pump_submit_wide_packets: row i of wide slot r's sample area holds len_of_row[i] int16 INPUT samples of stream stream_of_row[i],
+ * sampled at 16000 * step_of_row[i] Hz, starting at BYTE offset byte_off_of_row[i], a multiple of 16.  step = 1 ... max_step;
+ * step_of_row == NULL: every row is at max_step.  A row with step 1 is an ordinary 16 kHz packet, so one tick carries 16, 32 and 48 kHz
+ * clients side by side.  Rows are int16 only (G.711 is an 8 kHz format).  1 <= len <= step * N: a stream completes at most one chunk per
+ * tick, as in vad_pump_submit_packets (a 60 ms Opus frame at 48 kHz goes in over two ticks; there are no wide bursts).
+ * Every stream carries a COMB PHASE: input sample number g of the stream is kept iff g % step == 0, g counted from vad_pump_open (or
+ * vad_pump_create), or from the row at which the stream's step last changed.  The phase (g % step of the stream's next input sample) is
+ * host bookkeeping like the pending count; after a tick is queued it becomes (phase + len) % step.  A row may keep no sample at all
+ * (len = 1 at a phase other than 0): it advances the phase and nothing else.  The kept samples are appended to the stream's pending
+ * samples -- the same ones every packet route uses, always decimated int16, so a stream may move between wide, packet, coded and burst
+ * ticks from one tick to the next (those routes leave the phase alone).  A stream whose pending samples reach N is stepped once, the rest
+ * stays pending, every other stream is absent.  Results are bit for bit those of vad_pump_submit_packets fed the rows decimated on the
+ * host (vad_decimate with the carried phase).  vad_iter_event.sample and the iterator's current_sample count 16 kHz samples, whatever
+ * rate the rows came in at: the reference's VADIterator refuses other rates (utils_vad.py:492), there is no other convention to follow.
+ * The chunk routes' refusal of streams with pending samples stays; vad_pump_open / vad_pump_close drop a stream's pending samples, and
+ * vad_pump_open zeroes its phase.  Invalid input is VAD_ERR_ARG, nothing is queued, phases and pending counts are untouched: wideband
+ * not enabled, a step of 0 or above max_step, a stream out of range or listed twice, a length out of range, a misaligned offset, a row
+ * that runs past the area, n_rows above `streams`.  One H2D copy per tick: row table, flags, rows.
+ * vad_pump_wide_phase: the stream's phase, 0 ... step - 1; < 0: bad argument (wideband not enabled included).                         */
+int  vad_pump_set_wideband(vad_pump *p, int max_step);
+uint8_t *vad_pump_wide_slot(vad_pump *p, int r);
+int  vad_pump_submit_wide_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
+                                  const uint8_t *step_of_row, long n_rows);
+int  vad_pump_wide_phase(const vad_pump *p, int stream);
+/* The host twin of the device's decimation, from the same definition: the samples of in[0 .. n) that the comb keeps -- in[k] with
+ * (phase + k) % step == 0, i.e. in[(-phase) % step :: step] -- are written to out, and their number is returned.  phase = the number of
+ * the stream's samples in front of in[0], modulo step; the next piece's phase is (phase + n) % step.  Host only, re-entrant.
+ * -VAD_ERR_ARG for step < 1, phase out of 0 ... step - 1, n < 0 or a NULL buffer with n > 0.                                       */
+long vad_decimate(int step, int phase, const int16_t *in, long n, int16_t *out);
 /* n samples in format `codec` at `in` (n bytes for G.711, n int16 for VAD_PCM_S16: copied) -> out[0 .. n) int16 on the host: ITU-T
  * G.711 expansion, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2), from the same definition the device uses.  VAD_OK, or
  * VAD_ERR_ARG for a bad codec, n < 0 or a NULL buffer with n > 0.                                                               */

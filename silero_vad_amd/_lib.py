@@ -88,6 +88,11 @@ SYMBOLS = {
     "vad_pump_submit_burst": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
     "vad_pump_burst_steps": (c_int, [c_void_p, c_int]),
     "vad_pump_burst_probs": (c_void_p, [c_void_p, c_int, c_int]),
+    "vad_pump_set_wideband": (c_int, [c_void_p, c_int]),
+    "vad_pump_wide_slot": (c_void_p, [c_void_p, c_int]),
+    "vad_pump_submit_wide_packets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
+    "vad_pump_wide_phase": (c_int, [c_void_p, c_int]),
+    "vad_decimate": (c_long, [c_int, c_int, c_void_p, c_long, c_void_p]),
     "vad_pump_play_compact": (c_long, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_long, c_int, c_int, c_void_p, c_long,
                                        POINTER(PumpStats)]),
     "vad_pump_poll": (c_long, [c_void_p, c_int, c_void_p, c_long, POINTER(c_int)]),

@@ -140,6 +140,21 @@ hipError_t launch_assemble_burst(const int32_t *table, long n_rows, const uint8_
 // The flag rows of a burst tick's sub-steps 1 ... steps - 1: the tick's flag row holds k[b] (0 for a stream that completes no chunk),
 // flags[(j - 1) * ld + b] = k[b] > j.
 hipError_t launch_burst_flags(const uint8_t *k_of_stream, uint8_t *flags, long ld, int steps, int streams, hipStream_t s);
+// A wide packet tick of the pump (vad_pump_submit_wide_packets): int16 rows sampled at step x 16 kHz, decimated to 16 kHz on their way
+// into the carry / the batch row.  table[i] = {stream b, BYTE offset into `pkt` (a multiple of 16), len | step << kCodecShift | k0 <<
+// kCombShift, pending c}: len = 1 ... step * N INPUT samples, step = 1 ... kMaxWideStep, k0 = comb_first(step, the stream's phase) = the
+// row's first kept sample.  The row's kept samples pkt[k0], pkt[k0 + step], ... (comb_kept of them, <= N) are what assemble_packets'
+// packet is: appended to carry[b][0:c], a chunk leaves when c + kept >= N.  At most one row per stream.  N <= 512.
+constexpr int kCombShift = kCodecShift + 4;
+constexpr int kMaxWideStep = 3;
+hipError_t launch_assemble_wide_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
+                                        hipStream_t s);
+
+// The comb of the reference's decimation x[::step] (src/silero_vad/utils_vad.py:39-42) over a stream that arrives in pieces: input sample g
+// of the stream is kept iff g % step == 0; `phase` = (samples that came before the piece) % step.  The one definition the pump's
+// assembly kernel (kernel_present.hip), its host bookkeeping and the host export vad_decimate (pump.hip) share.
+__host__ __device__ inline int comb_first(int step, int phase) { return phase ? step - phase : 0; }        // the piece's first kept sample
+__host__ __device__ inline int comb_kept(int step, int k0, int len) { return len > k0 ? (len - k0 + step - 1) / step : 0; }
 
 // ITU-T G.711 code -> 16-bit linear PCM, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2).  The one definition the pump's
 // assembly kernel (kernel_present.hip) and the host export vad_g711_expand (pump.hip) share.

@@ -26,6 +26,10 @@
 // assemble_coded_packets (packet ticks with G.711 rows, vad_pump_submit_coded_packets): the same splice, with mu-law / A-law rows
 // crossing the link at 1 byte a sample and expanded to int16 in registers between their 16-byte load and the LDS row.  Ticks with
 // only int16 rows keep taking assemble_packets.
+//
+// assemble_wide_packets (wide packet ticks, vad_pump_submit_wide_packets): the same splice, with int16 rows sampled at 32 / 48 kHz (WebRTC,
+// Opus decoders) decimated to 16 kHz by the reference's rule x[::step] (utils_vad.py:39-42, :301-304) between their 16-byte loads and the
+// LDS row.  The comb's phase is carried per stream by the host and arrives in the row table.  Ticks of the other routes never take it.
 #include <hip/hip_runtime.h>
 
 #include "device_api.hpp"
@@ -127,7 +131,54 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_coded_packe
     if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
 }
 
-// assemble_burst (burst ticks, vad_pump_submit_burst): several rows per stream, rows longer than N.  The two kernels above are one wave
+// assemble_packets for a wide tick (vad_pump_submit_wide_packets): int16 rows sampled at step x 16 kHz, of which the comb k0, k0 + step,
+// ... is kept (device_api.hpp comb_first / comb_kept; step and k0 ride in the high bits of len, uniform across the wave).  Lane l owns
+// the input samples [8 step l, 8 step (l + 1)) of its row: `step` consecutive 16-byte loads.  The span starts on a multiple of step, so
+// whatever k0 is it holds exactly 8 kept samples and 8 l kept samples lie in front of it: the lane writes them at c + 8 l + j of the
+// LDS row without a scan, each guarded by the row's length.  N / 8 lanes cover the longest row (step * N), at most N samples are kept,
+// and what follows the second barrier is assemble_packets with `kept` for len.
+template <int STEP>
+__device__ inline void keep_comb(const i16x8 (&v)[kMaxWideStep], int k0, int left, short *dst) {
+#pragma unroll
+    for (int q = 0; q < STEP; ++q) {             // (k0 is uniform: one of the STEP bodies runs, its indices are constants)
+        if (k0 != q) continue;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (q + STEP * j < left) dst[j] = v[(q + STEP * j) >> 3][(q + STEP * j) & 7];
+    }
+}
+
+__global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_wide_packets_kernel(const int4 *__restrict__ table, long n_rows,
+                                                                                          const uint8_t *__restrict__ pkt, int16_t *carry,
+                                                                                          i16x8 *__restrict__ batch, int N) {
+    __shared__ __attribute__((aligned(16))) short joined[kPacketRowsPerBlock][2 * 512];      // carry[0:c] ++ kept samples, < 2N samples
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * kPacketRowsPerBlock + w;
+    const bool live = i < n_rows;                // (no early return: the barriers are the workgroup's)
+    const int4 e = live ? table[i] : make_int4(0, 0, 1 << kCodecShift, 0);
+    const int b = e.x, off = e.y, len = e.z & ((1 << kCodecShift) - 1), step = (e.z >> kCodecShift) & 15, k0 = e.z >> kCombShift, c = e.w;
+    const int at = lane * 8, from = at * step;   // the lane's first kept sample of the row, its first input sample
+    const int kept = comb_kept(step, k0, len);
+    short *row = joined[w];
+    i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
+    const i16x8 *src = reinterpret_cast<const i16x8 *>(pkt + off) + step * lane;
+    i16x8 v[kMaxWideStep] = {};
+#pragma unroll
+    for (int m = 0; m < kMaxWideStep; ++m)
+        if (m < step && from + 8 * m < len) v[m] = __builtin_nontemporal_load(src + m);
+    if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
+    __syncthreads();
+    // the kept samples behind the pending ones, at the unaligned offset c
+    if (step == 1) keep_comb<1>(v, k0, len - from, row + c + at);
+    else if (step == 2) keep_comb<2>(v, k0, len - from, row + c + at);
+    else keep_comb<3>(v, k0, len - from, row + c + at);
+    __syncthreads();
+    const int base = c + kept >= N ? N : 0, rest = c + kept - base;   // base N: a chunk is complete, the rest is the new carry
+    if (base && at < N) batch[(size_t)b * (N / 8) + lane] = *reinterpret_cast<const i16x8 *>(row + at);
+    if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
+}
+
+// assemble_burst (burst ticks, vad_pump_submit_burst): several rows per stream, rows longer than N.  The kernels above are one wave
 // per ROW and rely on nobody else touching the row's carry; with several rows of one stream in a tick the wave that writes the new carry
 // would race the wave that reads the old one.  Here the work unit is the STREAM.  The host grouped the table's rows by stream; the wave
 // whose row is the first of its stream walks that stream's rows in order, the waves of its other rows have nothing to do.  One wave is
@@ -228,6 +279,16 @@ hipError_t launch_assemble_coded_packets(const int32_t *table, long n_rows, cons
     if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
     const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
     hipLaunchKernelGGL(assemble_coded_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
+                       reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_wide_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
+                                        hipStream_t s) {
+    if (n_rows <= 0) return hipSuccess;
+    if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
+    const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
+    hipLaunchKernelGGL(assemble_wide_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
                        reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
     return hipGetLastError();
 }

@@ -56,6 +56,13 @@
 // k) masked steps back to back on the compute stream, sub-step j over d_more[j - 1] with its probabilities in h_prob_more.  d_more and its
 // flag rows are written and read on the compute stream only, in order: one buffer, not three.  Still ONE copy per tick.
 //
+// WIDE packet ticks (vad_pump_set_wideband + vad_pump_submit_wide_packets): WebRTC and Opus decoders deliver 32 / 48 kHz PCM.  A second
+// page-locked ring of wide slots ([row table | flags | streams * N * max_step int16]) and its device landing buffers take rows sampled at
+// step x 16 kHz; the host keeps each stream's comb phase beside its pending count and writes the row's first kept sample into the row
+// table, and kernel_present.hip assemble_wide_packets keeps every step-th sample (the reference's x[::step]) on the way into the carry /
+// the batch row.  The carry holds decimated int16: a stream may change route from tick to tick.  Still ONE copy per tick; everything
+// behind the assembly is the masked tick, bit for bit.
+//
 // Waits block.  A source thread of a real server sleeps in its socket; the source threads of vad_pump_play, and its server loop, spin
 // for at most 20 us on the counter they wait for and then sleep on it (futex), whatever the CPU budget: one of eight ranks under a
 // 16-CPU quota has two CPUs for a server loop, a source thread and the HIP runtime's own threads, and a spinning (or yielding) thread
@@ -139,12 +146,23 @@ struct vad_pump {
     std::vector<int32_t> b_touched;              // the streams a burst tick lists, by first appearance
     struct Held { int32_t stream, now; };
     std::vector<Held> b_new;                     // ... and what each has pending after the tick
+    // wide packet ticks (vad_pump_set_wideband; max_step == 0: not enabled, none of this is allocated)
+    int max_step = 0;                            // the largest decimation step a row may have (2: 32 kHz, 3: 48 kHz)
+    // a wide slot / a wide landing buffer: [wtab bytes: the row table, ending where the flags start][hdr bytes: present[streams], padded]
+    // [streams][N * max_step] int16
+    size_t wtab = 0, wide_bytes = 0;
+    uint8_t *h_wide = nullptr;                   // [R] wide slots, page-locked
+    uint8_t *d_wide = nullptr;                   // [NB] where a wide tick's copy lands
+    std::vector<uint8_t> w_step, w_phase;        // [streams] the step of the stream's last wide row (0: none yet) and its comb phase (host bookkeeping)
+    struct Comb { int32_t stream, now; uint8_t step, phase; };
+    std::vector<Comb> w_new;                     // what each listed stream has pending, and its step and phase, after the tick
     bool poisoned = false;                       // a tick failed half-way: the carried state is no longer what any caller expects
     std::string err;
 
     int32_t *slot_pos(int r) const { return reinterpret_cast<int32_t *>(h_ring + (size_t)r * slot_bytes + htab); }
     uint8_t *slot_present(int r) const { return h_ring + (size_t)r * slot_bytes + htab + hpos; }
     int16_t *slot_pcm(int r) const { return reinterpret_cast<int16_t *>(h_ring + (size_t)r * slot_bytes + htab + hpos + hdr); }
+    uint8_t *wide_present(int r) const { return h_wide + (size_t)r * wide_bytes + wtab; }
     float *step_probs(int r, int j) const {      // host side; the device aliases have the same layout
         return j == 0 ? h_prob + (size_t)r * streams : h_prob_more + ((size_t)r * (max_burst - 1) + (j - 1)) * streams;
     }
@@ -314,6 +332,8 @@ void vad_pump_destroy(vad_pump *p) {
     if (p->d_more) (void)hipFree(p->d_more);
     if (p->d_more_flags) (void)hipFree(p->d_more_flags);
     if (p->h_prob_more) (void)hipHostFree(p->h_prob_more);
+    if (p->d_wide) (void)hipFree(p->d_wide);
+    if (p->h_wide) (void)hipHostFree(p->h_wide);
     if (p->h_ring) (void)hipHostFree(p->h_ring);
     if (p->h_prob) (void)hipHostFree(p->h_prob);
     for (hipStream_t cs : p->copy)
@@ -454,6 +474,8 @@ struct Packets {
     bool coded = false;
     const uint8_t *codec = nullptr;
     bool burst = false;                          // vad_pump_submit_burst: a stream may have several rows, a row may be longer than N
+    bool wide = false;                           // vad_pump_submit_wide_packets: int16 rows of the WIDE slot, sampled at step x 16 kHz
+    const uint8_t *step = nullptr;               // ... the step per row, or null (every row at max_step)
 };
 
 // Validate a packet tick's rows and write its row table (ending where slot r's flags start) and its flags (the streams that complete
@@ -566,6 +588,49 @@ long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps)
     return end;
 }
 
+// The same for a wide tick (vad_pump_submit_wide_packets): the table and the flags go into WIDE slot r, table[i] = {stream, byte offset,
+// len | step << kCodecShift | first kept sample << kCombShift, pending before}.  A stream completes a chunk when its pending samples plus
+// the row's KEPT samples reach N.  Neither the pending counts nor the phases are touched: p->w_new holds them for the caller to apply
+// once the tick is queued.
+long build_wide(vad_pump *p, int r, const Packets &pk, long n_rows) {
+    const long S = p->streams, N = p->N, M = p->max_step;
+    const std::string fn = "vad_pump_submit_wide_packets: ";
+    if (M < 2) return pfail(p, VAD_ERR_ARG, fn + "wideband is not enabled on this pump (vad_pump_set_wideband)"), -1;
+    if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
+        return pfail(p, VAD_ERR_ARG, fn + "bad row list (a tick holds at most `streams` rows)"), -1;
+    uint8_t *fl = p->wide_present(r);
+    int32_t *tab = reinterpret_cast<int32_t *>(fl) - 4 * n_rows;
+    std::memset(fl, 0, (size_t)S);
+    p->w_new.clear();
+    const long area = S * N * M * 2;             // bytes of the wide slot's sample area
+    long end = 0, i = 0;
+    const char *why = nullptr;
+    for (; i < n_rows && !why; ++i) {
+        const int32_t b = pk.stream[i];
+        const long at = pk.off[i], len = pk.len[i], step = pk.step ? pk.step[i] : M;
+        if (step < 1 || step > M) why = "a step out of 1 ... max_step";
+        else if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
+        else if (len < 1 || len > step * N) why = "a row length out of 1 ... step * N (a longer row goes in over two ticks)";
+        else if (at < 0 || at % 16 || at + 2 * len > area) why = "a row byte offset that is not a multiple of 16, or a row that runs past the wide slot";
+        else {
+            p->seen[b] = 1;
+            const int32_t c = p->held[b], phase = step == p->w_step[b] ? p->w_phase[b] : 0;      // (another step: the comb starts anew)
+            const int32_t k0 = vad::comb_first((int)step, phase), total = c + vad::comb_kept((int)step, k0, (int)len);
+            tab[4 * i] = b, tab[4 * i + 1] = (int32_t)at, tab[4 * i + 2] = (int32_t)(len | step << vad::kCodecShift | (long)k0 << vad::kCombShift), tab[4 * i + 3] = c;
+            fl[b] = total >= N;
+            p->w_new.push_back(vad_pump::Comb{b, (int32_t)(total >= N ? total - N : total), (uint8_t)step, (uint8_t)((phase + len) % step)});
+            end = std::max(end, (at + 2 * len + 15) / 16 * 16);
+        }
+    }
+    for (long k = 0; k < i; ++k)                 // (only valid streams were marked)
+        if (pk.stream[k] >= 0 && pk.stream[k] < S) p->seen[pk.stream[k]] = 0;
+    if (why) {
+        std::memset(fl, 0, (size_t)S);
+        return pfail(p, VAD_ERR_ARG, fn + why), -1;
+    }
+    return end;
+}
+
 // rows != nullptr: a compact tick whose rows lie in ARRIVAL order -- row i of the slot is the chunk of stream rows[i] (n_rows of them);
 // flags and positions are built here.  rows == nullptr && compact: row i is the i-th stream (ascending) whose flag is set.
 // pk != nullptr: a packet tick of n_rows rows (compact: its copy lands in the compact buffers, and masked).
@@ -582,8 +647,11 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     bool g711 = false;                           // ... and it has a mu-law / A-law row
     int steps = 1;                               // a burst tick: the masked steps it runs
     if (pk) {
-        if ((pk_bytes = pk->burst ? build_burst(p, r, *pk, n_rows, &steps) : build_packets(p, r, *pk, n_rows, &g711)) < 0) return VAD_ERR_ARG;
-        present = p->slot_present(r);
+        if ((pk_bytes = pk->wide    ? build_wide(p, r, *pk, n_rows)
+                        : pk->burst ? build_burst(p, r, *pk, n_rows, &steps)
+                                    : build_packets(p, r, *pk, n_rows, &g711)) < 0)
+            return VAD_ERR_ARG;
+        present = pk->wide ? p->wide_present(r) : p->slot_present(r);      // (a wide tick's flags: copied to the slot's own row for vad_pump_poll)
     } else if (rows != nullptr || n_rows != 0) {
         if (!rows || n_rows < 0 || n_rows > (long)S) return pfail(p, VAD_ERR_ARG, "vad_pump_submit_rows: bad row list");
         uint8_t *fl = p->slot_present(r);
@@ -620,7 +688,9 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         // the position table: row of the slot that holds stream b's chunk (the i-th delivering stream's chunk is row i)
         const uint8_t *fl = p->slot_present(r);
         int32_t *pos = p->slot_pos(r);
-        if (pk) {
+        if (pk && pk->wide) {
+            d_present = p->d_wide + (size_t)buf * p->wide_bytes + p->wtab;      // (its copy lands in the wide buffer, flags included)
+        } else if (pk) {
             // (no position table: the row table written with the flags lies over it)
         } else if (rows != nullptr) {
             n_present = (size_t)n_rows;                  // (positions were written with the flags)
@@ -650,12 +720,15 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         // ONE copy: row table + flags + the packets; the assembly pass on the compute stream splices the completing streams' rows out
         // of their carries and their packets (the carry's previous users and the batch buffer's previous readers are earlier there)
         const size_t tab_bytes = (size_t)n_rows * 4 * sizeof(int32_t);
-        TICK_TRY(hipMemcpyAsync(cbuf + p->hpos - tab_bytes, p->slot_present(r) - tab_bytes, tab_bytes + p->hdr + pk_bytes,
-                                hipMemcpyHostToDevice, copy));
+        const uint8_t *h_fl = pk->wide ? p->wide_present(r) : p->slot_present(r);                  // the flags of the slot the rows lie in
+        uint8_t *d_fl = pk->wide ? p->d_wide + (size_t)buf * p->wide_bytes + p->wtab : cbuf + p->hpos;     // ... and of the buffer they land in
+        TICK_TRY(hipMemcpyAsync(d_fl - tab_bytes, h_fl - tab_bytes, tab_bytes + p->hdr + pk_bytes, hipMemcpyHostToDevice, copy));
         TICK_TRY(hipEventRecord(p->h2d_done[buf][0], copy));
         TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));
-        const int32_t *table = reinterpret_cast<const int32_t *>(cbuf + p->hpos - tab_bytes);
-        if (pk->burst) {                         // (chunk 0 of every stream into `batch`, chunks 1 ... into d_more; flags_j = k > j)
+        const int32_t *table = reinterpret_cast<const int32_t *>(d_fl - tab_bytes);
+        if (pk->wide) {                          // (the rows are decimated on the way; the carry holds 16 kHz samples)
+            TICK_TRY(vad::launch_assemble_wide_packets(table, n_rows, d_fl + p->hdr, p->d_carry, batch, p->N, p->compute));
+        } else if (pk->burst) {                  // (chunk 0 of every stream into `batch`, chunks 1 ... into d_more; flags_j = k > j)
             TICK_TRY(vad::launch_assemble_burst(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->d_more, p->max_burst, p->streams, p->N,
                                                 p->compute));
             TICK_TRY(vad::launch_burst_flags(d_present, p->d_more_flags, (long)p->hdr, steps, p->streams, p->compute));
@@ -700,7 +773,13 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     TICK_TRY(hipEventRecord(p->batch_free[buf], p->compute));
     TICK_TRY(hipEventRecord(p->tick_done[r], p->compute));
 #undef TICK_TRY
-    if (pk && pk->burst)                         // the pending counts after this tick
+    if (pk && pk->wide)                          // the pending counts and comb phases after this tick
+        for (const vad_pump::Comb &w : p->w_new) {
+            p->n_held += (w.now > 0) - (p->held[w.stream] > 0);
+            p->held[w.stream] = w.now;
+            p->w_step[w.stream] = w.step, p->w_phase[w.stream] = w.phase;
+        }
+    else if (pk && pk->burst)                    // the pending counts after this tick
         for (const vad_pump::Held &h : p->b_new) {
             p->n_held += (h.now > 0) - (p->held[h.stream] > 0);
             p->held[h.stream] = h.now;
@@ -808,6 +887,61 @@ const float *vad_pump_burst_probs(const vad_pump *p, int r, int j) {
     return p->step_probs(r, j);
 }
 
+int vad_pump_submit_wide_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
+                                 const uint8_t *step_of_row, long n_rows) {
+    Packets pk{stream_of_row, byte_off_of_row, len_of_row, true};
+    pk.wide = true;
+    pk.step = step_of_row;
+    return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_pump_set_wideband(vad_pump *p, int max_step) {
+    if (!p) return VAD_ERR_ARG;
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (max_step < 2 || max_step > vad::kMaxWideStep) return pfail(p, VAD_ERR_ARG, "vad_pump_set_wideband: max_step is 2 (32 kHz) or 3 (48 kHz)");
+    if (p->sr != 16000)                          // (the reference decimates multiples of 16000 only: utils_vad.py:39-42)
+        return pfail(p, VAD_ERR_SAMPLE_RATE, "vad_pump_set_wideband: only a 16 kHz pump takes 32 / 48 kHz rows");
+    if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, "vad_pump_set_wideband: ticks in flight (retire them with vad_pump_poll first)");
+    if (max_step == p->max_step) return VAD_OK;
+    PUMP_TRY(p, hipSetDevice(p->device));
+    PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    if (p->d_wide) (void)hipFree(p->d_wide);
+    if (p->h_wide) (void)hipHostFree(p->h_wide);
+    p->d_wide = p->h_wide = nullptr;
+    p->max_step = 0;
+    const size_t S = (size_t)p->streams;
+    p->wtab = (S * 4 * sizeof(int32_t) + 4095) / 4096 * 4096;
+    p->wide_bytes = p->wtab + p->hdr + S * p->N * max_step * sizeof(int16_t);
+    if (hipHostMalloc((void **)&p->h_wide, (size_t)p->R * p->wide_bytes, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void **)&p->d_wide, vad_pump::NB * p->wide_bytes) != hipSuccess) {
+        if (p->h_wide) (void)hipHostFree(p->h_wide);
+        p->d_wide = p->h_wide = nullptr;
+        return pfail(p, VAD_ERR_ALLOC, "vad_pump_set_wideband: no memory for the wide slots");
+    }
+    std::memset(p->h_wide, 0, (size_t)p->R * p->wide_bytes);
+    p->w_step.assign(S, 0);
+    p->w_phase.assign(S, 0);
+    p->w_new.reserve(S);
+    p->max_step = max_step;
+    return VAD_OK;
+}
+
+uint8_t *vad_pump_wide_slot(vad_pump *p, int r) {
+    return (p && p->max_step && r >= 0 && r < p->R) ? p->wide_present(r) + p->hdr : nullptr;
+}
+
+int vad_pump_wide_phase(const vad_pump *p, int stream) {
+    if (!p || !p->max_step || stream < 0 || stream >= p->streams) return -VAD_ERR_ARG;
+    return p->w_phase[stream];
+}
+
+long vad_decimate(int step, int phase, const int16_t *in, long n, int16_t *out) {
+    if (step < 1 || phase < 0 || phase >= step || n < 0 || (n > 0 && (!in || !out))) return -VAD_ERR_ARG;
+    long m = 0;
+    for (long k = vad::comb_first(step, phase); k < n; k += step) out[m++] = in[k];
+    return m;
+}
+
 int vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out) {
     if (codec < VAD_PCM_S16 || codec > VAD_PCM_ALAW || n < 0 || (n > 0 && (!in || !out))) return VAD_ERR_ARG;
     if (codec == VAD_PCM_S16) {
@@ -877,6 +1011,7 @@ int vad_pump_open(vad_pump *p, int stream) {
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + (n + row) * 128, 0, 128 * sizeof(float), p->compute));
     PUMP_TRY(p, hipMemsetAsync(p->d_ctx[p->flips & 1] + (size_t)stream * p->C, 0, (size_t)p->C * sizeof(float), p->compute));
     p->drop_held(stream);                        // (the device carry needs nothing: the next packet tick's table says 0 samples pending)
+    if (p->max_step) p->w_step[stream] = p->w_phase[stream] = 0;                // ... and the new stream's comb starts at its first sample
     // ... and the host side (iterator state, active flag) when those ticks have been retired: their probabilities belong to the slot's
     // previous occupant and must neither advance the new stream's sample counter nor open a segment for it
     p->pending.push_back(vad_pump::Op{p->ticks, stream, true});

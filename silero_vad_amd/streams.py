@@ -1986,6 +1986,22 @@ def g711_expand(data, codec) -> np.ndarray:
     return out
 
 
+def decimate(x, step: int, phase: int = 0) -> np.ndarray:
+    """The samples of a 1-D int16 piece that the reference's decimation x[::step] keeps (vad_decimate, from the definition the pump's
+    device decimation uses): `phase` = the number of the stream's samples in front of x[0], modulo step, so the result is
+    x[(-phase) % step::step] and the next piece's phase is (phase + len(x)) % step."""
+    x = np.ascontiguousarray(x)
+    if x.dtype != np.int16 or x.ndim != 1:
+        raise ValueError(f"x must be a 1-D int16 array, got {x.dtype} of shape {x.shape}")
+    if not isinstance(step, (int, np.integer)) or step < 1 or not isinstance(phase, (int, np.integer)) or not 0 <= phase < step:
+        raise ValueError(f"step must be >= 1 and phase in 0 ... step - 1, got step {step!r}, phase {phase!r}")
+    out = np.empty((len(x) + int(step) - 1) // int(step), np.int16)
+    m = lib().vad_decimate(int(step), int(phase), x.ctypes.data if x.size else None, x.size, out.ctypes.data if out.size else None)
+    if m < 0:
+        raise _lib.VadError(-m, "vad_decimate")
+    return out[:m]
+
+
 class StreamPump:
     """BASELINE configs[4] through the native pump (include/silero_vad_hip.h "live streams: the pump", csrc/pump.hip): `streams`
     live streams on one GPU, host int16 chunks in, VADIterator events out, with no Python and no torch on the per-tick path
@@ -2005,6 +2021,10 @@ class StreamPump:
     `pump.write_burst(r, [(stream, packet[, codec]), ...])` takes any number of packets of one stream and packets longer than a chunk (a
     60 ms Opus frame, what a jitter buffer releases after a stall); a stream that completes k <= M chunks is stepped k times inside the
     tick, `burst_steps(r)` / `burst_probs(r)` give the sub-steps, and `poll` returns their events one sub-step after the other.
+
+    32 / 48 kHz clients (WebRTC, Opus decoders): after `pump.set_wideband(3)` the rows of `wide_slot(r)` +
+    `submit_wide_packets(r, streams, lengths, steps)` are int16 samples at steps[i] x 16 kHz, and the device keeps every steps[i]-th one
+    (the reference's `x[::step]`); the pump carries each stream's comb phase (`wide_phase(stream)`), events count 16 kHz samples.
 
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
@@ -2050,7 +2070,7 @@ class StreamPump:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._slots = self._probs = self._present = self._probs_more = None
+            self._slots = self._probs = self._present = self._probs_more = self._wide = None
             self._L.vad_pump_destroy(self._h)
             self._h = None
 
@@ -2235,6 +2255,55 @@ class StreamPump:
             offsets.append(at)
             at += (x.nbytes + 15) // 16 * 16
         self.submit_burst(r, streams, lengths, np.array(codecs, np.uint8), offsets)
+
+    def set_wideband(self, max_step: int):
+        """Enable WIDE packet ticks (vad_pump_set_wideband): rows sampled at up to max_step x 16 kHz -- 2 (32 kHz) or 3 (48 kHz) -- on a
+        16 kHz pump with no tick in flight.  Allocates the wide slots ([streams * N * max_step] int16 each) and their device buffers."""
+        self._check(self._L.vad_pump_set_wideband(self._h, int(max_step)))
+        self.max_step = int(max_step)
+        nbytes = self.streams * self.n * self.max_step * 2
+        self._wide = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_wide_slot(self._h, r), ctypes.POINTER(ctypes.c_uint8)),
+                                            shape=(nbytes,)) for r in range(self.ring_slots)]
+
+    def wide_slot(self, r: int) -> np.ndarray:
+        """Wide slot r's sample area as one flat uint8 array of streams * N * max_step * 2 bytes (page-locked): where a wide tick's rows
+        go."""
+        if getattr(self, "_wide", None) is None:
+            raise ValueError("wideband is not enabled on this pump (set_wideband)")
+        return self._wide[r]
+
+    def submit_wide_packets(self, r: int, streams, lengths, steps=None, byte_offsets=None):
+        """A WIDE packet tick (vad_pump_submit_wide_packets; needs `set_wideband`): row i of `wide_slot(r)` holds lengths[i] int16
+        samples (1 ... steps[i] * N) of stream streams[i], sampled at steps[i] x 16 kHz (1 ... max_step; None = every row at max_step),
+        at byte offset byte_offsets[i] (a multiple of 16; None = the rows back to back, each rounded up to 16 bytes).  The device keeps
+        the samples of the stream's comb (input sample g iff g % step == 0) and appends them to what the stream has pending: the same
+        results, bit for bit, as `submit_packets` with the rows cut by `decimate` at the carried phase.  A bad step, stream, length or
+        offset raises and queues nothing."""
+        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
+        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
+        sp = None
+        if steps is not None:
+            sp = np.asarray(steps)
+            if sp.ndim != 1 or (sp.size and (not np.issubdtype(sp.dtype, np.integer) or sp.min() < 0 or sp.max() > 255)):
+                raise ValueError(f"steps must be a 1-D sequence of uint8 values, got {sp.dtype} of shape {sp.shape}")
+            sp = np.ascontiguousarray(sp, dtype=np.uint8)
+        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (sp is not None and len(sp) != len(st)):
+            raise ValueError(f"streams, lengths, steps and byte_offsets must have one entry per row, got {len(st)}, {len(ln)}, "
+                             f"{len(st) if sp is None else len(sp)}, {len(st) if off is None else len(off)}")
+        if off is None:
+            off = np.zeros(len(st), np.int32)
+            if len(st):
+                off[1:] = np.cumsum((ln[:-1].astype(np.int64) * 2 + 15) // 16 * 16)
+        n = len(st)
+        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [sp.ctypes.data if n and sp is not None else None]
+        self._check(self._L.vad_pump_submit_wide_packets(self._h, int(r), *ptrs, n))
+
+    def wide_phase(self, stream: int) -> int:
+        """The comb phase of `stream`: the input samples it has delivered since its comb started, modulo its step (0 ... step - 1)."""
+        v = self._L.vad_pump_wide_phase(self._h, int(stream))
+        if v < 0:
+            raise ValueError(f"no such stream, or wideband is not enabled: {stream}")
+        return int(v)
 
     def burst_steps(self, r: int) -> int:
         """The sub-steps slot r's last tick ran: max(1, the most chunks a stream completed) for a burst tick, 1 for any other."""

@@ -5,7 +5,7 @@ ticks in flight.  The ring slots are written once before the timed window: this 
 path's host writes.  Prints one JSON line: per-tick time, link bytes per tick, the share of a plain pinned -> HBM copy's rate that
 reaches, and the time per second of audio of every route (equal audio throughput).
 
-    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs] [burst_share d]
+    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs] [burst_share d] [--wide]
 
 sr: 16000 (default) or 8000.  codecs: a comma-separated list of packet formats, timed alternately with the chunk route -- "s16" (the
 default: int16 packets through vad_pump_submit_packets), "ulaw" / "alaw" (G.711 packets, 1 byte a sample, through
@@ -18,7 +18,11 @@ is what the same streams cost an integrator without bursts: the withheld packets
 d ticks behind.  Share, d and the sub-steps per tick are in the output, and so is
 "packets_on_burst_pump": the ordinary packet ticks of a burst-enabled pump, which must cost what "packets" costs.
 
-assemble_packets_kernel's / assemble_coded_packets_kernel's / assemble_burst_kernel's own time: run it under
+--wide (16 kHz only): adds the route "wide" -- every stream delivers a 20 ms 48 kHz packet (960 int16 samples) a tick through
+vad_pump_submit_wide_packets on a pump with vad_pump_set_wideband(3), the device keeps every third sample -- and "packets_on_wide_pump",
+the ordinary 16 kHz packet ticks of that same pump.  A wide tick carries the same audio as a packet tick in 3 x the packet bytes.
+
+assemble_packets_kernel's / assemble_coded_packets_kernel's / assemble_burst_kernel's / assemble_wide_packets_kernel's own time: run it under
 `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/packet_pump_time.py ...` (in a run of its own) and read the
 kernels' lines of the stats file."""
 import json
@@ -49,14 +53,16 @@ def main():
     import torch
     import bench
     from silero_vad_amd import Engine, StreamPump
+    wide = "--wide" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--wide"]
     ticks = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     sr = int(sys.argv[3]) if len(sys.argv) > 3 else 16000
     codecs = sys.argv[4].split(",") if len(sys.argv) > 4 else ["s16"]
     share = float(sys.argv[5]) if len(sys.argv) > 6 else 0.0
     d = int(sys.argv[6]) if len(sys.argv) > 6 else 0
-    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw"} or not 0.0 <= share <= 1.0 or not 0 <= d <= 11:
-        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw] [burst_share d (0 ... 11)]")
+    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw"} or not 0.0 <= share <= 1.0 or not 0 <= d <= 11 or (wide and sr != 16000):
+        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw] [burst_share d (0 ... 11)] [--wide (16000 only)]")
     S, R = 8192, 4
     N, P = (512 if sr == 16000 else 256), sr // 50                     # a chunk, a 20 ms packet (samples)
     dev = torch.device("cuda", 0)
@@ -73,9 +79,14 @@ def main():
     if share > 0:
         fmt["burst"] = "burst"
         fmt["packets_on_burst_pump"] = "s16"                              # ordinary packet ticks of a pump that has bursts enabled
+    if wide:
+        fmt["wide"] = "wide"
+        fmt["packets_on_wide_pump"] = "s16"                               # ordinary packet ticks of the pump that has wideband enabled
     routes = {}
     for name, c in fmt.items():
-        if c == "burst":                                                # row table + flags + the same samples as a tick of int16 packets
+        if c == "wide":                                                 # row table + flags + the packets at 3 samples for one
+            routes[name] = {"bytes": 16 * S + page(S) + S * P * 3 * 2, "ms_audio": 1000.0 * P / sr}
+        elif c == "burst":                                                # row table + flags + the same samples as a tick of int16 packets
             routes[name] = {"bytes": 16 * S + page(S) + S * P * 2, "ms_audio": 1000.0 * P / sr}
         elif c is None:                                                 # position table + flags + the chunks
             routes[name] = {"bytes": page(4 * S) + page(S) + S * N * 2, "ms_audio": 1000.0 * N / sr}
@@ -84,9 +95,16 @@ def main():
             routes[name] = {"bytes": 16 * S + page(S) + S * ((row + 15) // 16 * 16), "ms_audio": 1000.0 * P / sr}
     pumps = {}
     for name, c in fmt.items():
-        pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R, max_burst=8 if "burst" in name else 1)
+        if name == "packets_on_wide_pump":                              # (the same pump object: its ordinary slots)
+            pump = pumps["wide"]
+        else:
+            pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R, max_burst=8 if "burst" in name else 1)
+        if c == "wide":
+            pump.set_wideband(3)
         for r in range(R):
-            if c == "burst":
+            if c == "wide":                                             # sample-and-hold: the kept comb is the fixture
+                pump.wide_slot(r)[:S * P * 6].view(np.int16).reshape(S, 3 * P)[:] = np.repeat(rows[order, :P], 3, axis=1)
+            elif c == "burst":
                 pump.packet_area(r)[:S * P].reshape(S, P)[:] = rows[order, :P]
             elif c is None:
                 pump.slot(r)[:] = rows[order]
@@ -97,6 +115,7 @@ def main():
         pumps[name] = pump
     lengths = np.full(S, P, np.int32)
     offsets = (np.arange(S) * P).astype(np.int32)                       # samples (s16) or bytes (G.711): 16-byte aligned either way
+    wide_lengths, wide_offsets = np.full(S, 3 * P, np.int32), (np.arange(S) * P * 6).astype(np.int32)
     codec_rows = {"ulaw": np.full(S, 1, np.uint8), "alaw": np.full(S, 2, np.uint8)}
 
     # burst mode: the first `share` of the arrival order stalls, in d + 1 phases; phase f delivers (d + 1) packets as ONE row at ticks
@@ -116,7 +135,9 @@ def main():
         inflight = 0
         t0 = time.perf_counter()
         for t in range(n):
-            if c == "burst":
+            if c == "wide":
+                pump.submit_wide_packets(t % R, order, wide_lengths, None, wide_offsets)
+            elif c == "burst":
                 pump.submit_burst(t % R, phases[t % (d + 1)][0], phases[t % (d + 1)][1], None, phases[t % (d + 1)][2])
             elif c is None:
                 pump.submit_rows(t % R, order)
