@@ -367,7 +367,23 @@ int  vad_pump_submit_rows(vad_pump *p, int r, const int32_t *stream_of_row, long
  * (e.g. a 60 ms Opus frame at 16 kHz) is refused, not split: submit it over two ticks.  Invalid input is VAD_ERR_ARG and nothing is
  * queued: a stream out of range or listed twice, a length out of range, an offset that is misaligned or runs past the slot.  The chunk
  * routes (vad_pump_submit / _present / _compact / _rows) refuse (VAD_ERR_ARG, nothing queued) a chunk for a stream with samples
- * pending; vad_pump_open / vad_pump_close drop a stream's pending samples.  One copy per tick: row table, flags, packet samples.       */
+ * pending; vad_pump_open / vad_pump_close drop a stream's pending samples.  One copy per tick: row table, flags, packet samples.
+ * SILENT rows -- time that passes without a payload.  A lost packet, a G.711 trunk with silence suppression (RFC 3389 comfort-noise
+ * periods) and an Opus stream in DTX deliver nothing for 20 ms ... several seconds while the stream's clock runs.  A row whose offset
+ * entry is VAD_ROW_SILENT stands for len_of_row[i] samples of digital silence (int16 0) of its stream and occupies NO bytes of the slot:
+ * nothing is written on the host, nothing crosses the link for it (the tick's copy carries the row table, the flags and the payload
+ * rows only; a tick of silent rows copies not one byte of the sample area).  It is a row in every other respect: appended behind the
+ * stream's pending samples, it completes chunks, leaves a residue, counts as the stream's row of the tick ("listed twice") and towards
+ * n_rows <= streams, and vad_pump_pending reports what it would after a payload row of that length; the alignment and fits-the-area
+ * checks do not apply to it.  Every other negative offset stays VAD_ERR_ARG.  Probabilities, events, (h, c), context, pending samples
+ * and comb phases are bit for bit those of the same pump fed, in the same row position and through the same route, a payload row of
+ * len int16 zeros.  Here: off_of_row[i] == VAD_ROW_SILENT, 1 <= len <= N.
+ * ABSENT against SILENT.  A stream whose packet is LATE is listed in no row: it is absent, and its (h, c), context, sample counter
+ * and the iterator's silence timer freeze until the packet arrives.  A stream whose packet is LOST, or that is in DTX, is listed in a
+ * silent row: its clock runs, min_silence_duration_ms counts on, the 'end' event of the segment before the gap is emitted during the
+ * gap and every later vad_iter_event.sample stays true.  Only the caller's jitter buffer knows late from lost; the pump never fills a
+ * gap by itself.                                                                                                                   */
+#define VAD_ROW_SILENT (-1)
 int  vad_pump_submit_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *off_of_row, const int32_t *len_of_row,
                              long n_rows);
 /* Sample formats of a packet row: 16-bit linear PCM, ITU-T G.711 mu-law (PCMU) or A-law (PCMA), 1 byte per sample (SIP trunks,
@@ -380,7 +396,10 @@ enum { VAD_PCM_S16 = 0, VAD_PCM_ULAW = 1, VAD_PCM_ALAW = 2 };
  * the expanded int16 packets, and a stream may change its format from one packet to the next.  The payload of an RTP packet goes into
  * the slot as it came off the wire: half the host and link bytes of int16.  Invalid input is VAD_ERR_ARG and nothing is queued: a
  * bad codec, a stream out of range or listed twice, a length out of 1 ... N, a byte offset that is not a multiple of 16 or a row that
- * runs past the slot.  Pending samples, open / close and the chunk routes' refusal behave as for vad_pump_submit_packets.           */
+ * runs past the slot.  Pending samples, open / close and the chunk routes' refusal behave as for vad_pump_submit_packets.
+ * A row with byte_off_of_row[i] == VAD_ROW_SILENT is a silent row of 1 ... N samples (see vad_pump_submit_packets): int16 zeros,
+ * also in a G.711 tick (A-law has no code for 0).  Its codec_of_row entry is not looked at -- any byte value is accepted -- and it
+ * does not make the tick a G.711 tick.                                                                                            */
 int  vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
                                    const int32_t *len_of_row, const uint8_t *codec_of_row, long n_rows);
 /* BURST ticks -- a 60 ms Opus frame is longer than a chunk, a jitter buffer that waited out a stall releases several packets of one
@@ -406,7 +425,10 @@ int  vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_
  * steps x streams of them, and one stream may have a start and an end in the same poll.  vad_pump_burst_steps: the sub-steps slot r's
  * last tick ran (1 for every tick of another route; < 0: bad argument).  vad_pump_burst_probs(p, r, j): [streams] of sub-step j
  * (j = 0: vad_pump_probs(p, r)), VAD_PROB_ABSENT where k <= j; NULL on a bad argument (j beyond max_chunks - 1 included).
- * vad_pump_pending, vad_pump_open / _close and the chunk routes' refusal behave as for packet ticks.                                */
+ * vad_pump_pending, vad_pump_open / _close and the chunk routes' refusal behave as for packet ticks.
+ * A row with byte_off_of_row[i] == VAD_ROW_SILENT is a silent row (see vad_pump_submit_packets) of any length >= 1, longer than N
+ * included (after a stall the whole gap may arrive as one row), subject to the max_chunks rule like any row; its codec_of_row entry
+ * is not looked at.                                                                                                               */
 #define VAD_PUMP_MAX_BURST 8
 int  vad_pump_set_burst(vad_pump *p, int max_chunks);
 int  vad_pump_submit_burst(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
@@ -443,6 +465,9 @@ const float *vad_pump_burst_probs(const vad_pump *p, int r, int j);
  * vad_pump_open zeroes its phase.  Invalid input is VAD_ERR_ARG, nothing is queued, phases and pending counts are untouched: wideband
  * not enabled, a step of 0 or above max_step, a stream out of range or listed twice, a length out of range, a misaligned offset, a row
  * that runs past the area, n_rows above `streams`.  One H2D copy per tick: row table, flags, rows.
+ * A row with byte_off_of_row[i] == VAD_ROW_SILENT is a silent row (see vad_pump_submit_packets) of 1 ... step * N INPUT samples at
+ * step_of_row[i], which is validated and used as for any row: the phase advances by len and the stream gains the zeros the comb keeps
+ * of them; a silent row that keeps no sample advances only the phase.
  * vad_pump_wide_phase: the stream's phase, 0 ... step - 1; < 0: bad argument (wideband not enabled included).                         */
 int  vad_pump_set_wideband(vad_pump *p, int max_step);
 uint8_t *vad_pump_wide_slot(vad_pump *p, int r);

@@ -30,6 +30,14 @@
 // assemble_wide_packets (wide packet ticks, vad_pump_submit_wide_packets): the same splice, with int16 rows sampled at 32 / 48 kHz (WebRTC,
 // Opus decoders) decimated to 16 kHz by the reference's rule x[::step] (utils_vad.py:39-42, :301-304) between their 16-byte loads and the
 // LDS row.  The comb's phase is carried per stream by the host and arrives in the row table.  Ticks of the other routes never take it.
+//
+// SILENT rows (VAD_ROW_SILENT, all four assembly kernels): a row that stands for `len` samples of digital silence and has no bytes in the
+// slot -- a lost packet, a DTX / comfort-noise period.  The table carries the marker where a payload row carries its offset: the offset
+// column (table[i].y) holds VAD_ROW_SILENT (-1), every payload offset is >= 0, and the length word keeps its fields (len, kCodecShift,
+// kCombShift) with the meanings they have; the host writes VAD_PCM_S16 into the codec field of a silent row, so a G.711 tick never
+// expands a zero register (mu-law 0x00 is -32124).  A lane's vector starts as {} and a silent row simply does not overwrite it: one
+// compare of the offset per row, uniform across the wave, in front of the guarded load; no address is formed from the marker that is
+// dereferenced.  The zeros are spliced at the unaligned pending length like samples.
 #include <hip/hip_runtime.h>
 
 #include "device_api.hpp"
@@ -80,7 +88,7 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_packets_ker
     short *row = joined[w];
     i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
     i16x8 v = {};
-    if (at < len) v = __builtin_nontemporal_load(reinterpret_cast<const i16x8 *>(pkt + off) + lane);
+    if (off >= 0 && at < len) v = __builtin_nontemporal_load(reinterpret_cast<const i16x8 *>(pkt + off) + lane);      // (a silent row: zeros)
     if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
     __syncthreads();
     // the packet behind the pending samples, at the unaligned offset c
@@ -112,7 +120,7 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_coded_packe
     i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
     const int from = codec == VAD_PCM_S16 ? at : lane * 16;         // the lane's first sample of the packet: 16 bytes hold 8 or 16
     u32x4 v = {};
-    if (from < len) v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(pkt + off) + lane);
+    if (off >= 0 && from < len) v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(pkt + off) + lane);     // (a silent row: S16 zeros)
     if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
     __syncthreads();
     // the packet behind the pending samples, at the unaligned offset c
@@ -161,11 +169,11 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_wide_packet
     const int kept = comb_kept(step, k0, len);
     short *row = joined[w];
     i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
-    const i16x8 *src = reinterpret_cast<const i16x8 *>(pkt + off) + step * lane;
+    const i16x8 *src = reinterpret_cast<const i16x8 *>(pkt + off) + step * lane;     // (a silent row: never dereferenced)
     i16x8 v[kMaxWideStep] = {};
 #pragma unroll
     for (int m = 0; m < kMaxWideStep; ++m)
-        if (m < step && from + 8 * m < len) v[m] = __builtin_nontemporal_load(src + m);
+        if (off >= 0 && m < step && from + 8 * m < len) v[m] = __builtin_nontemporal_load(src + m);      // (a silent row: zeros)
     if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
     __syncthreads();
     // the kept samples behind the pending ones, at the unaligned offset c
@@ -204,11 +212,12 @@ __global__ void __launch_bounds__(64) assemble_burst_kernel(const int4 *__restri
         if (i != i0 && (e.x != b || e.w >= 0)) break;                           // the next stream's first row
         const int len = e.z & ((1 << kCodecShift) - 1), codec = e.z >> kCodecShift;
         const int per = codec == VAD_PCM_S16 ? 8 : 16;                         // samples in a lane's 16 bytes
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(pkt + e.y);
+        const bool quiet = e.y < 0;                                             // a silent row: its pieces are zeros, pkt is not touched
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(pkt + e.y);                     // (... nor is this)
         for (int s0 = 0; s0 < len; s0 += N) {                                   // a piece: samples [s0, s0 + n) of the row
             const int n = min(N, len - s0), from = lane * per;
             u32x4 v = {};
-            if (from < n) v = __builtin_nontemporal_load(src + s0 / per + lane);
+            if (!quiet && from < n) v = __builtin_nontemporal_load(src + s0 / per + lane);
             short *dst = joined + fill + from;
             if (codec == VAD_PCM_S16) {
 #pragma unroll

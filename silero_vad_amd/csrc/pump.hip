@@ -482,6 +482,9 @@ struct Packets {
 // a chunk).  -> the bytes of the slot's sample area the copy has to carry, or < 0 (VAD_ERR_ARG, p->err says why; nothing queued).
 // *g711: a row is mu-law or A-law -- the table then holds byte offsets and each row's codec in the high bits of its length, for
 // assemble_coded_packets; otherwise it holds sample offsets, for assemble_packets, whichever entry point was called.
+// A SILENT row (offset VAD_ROW_SILENT: len samples of digital silence, no bytes in the slot) keeps the marker in the table's offset
+// column, is S16 whatever codec_of_row says (its entry is not looked at, it does not make the tick a G.711 tick), passes neither the
+// alignment nor the fits-the-area check and does not count towards the bytes the copy carries; everything else applies to it.
 long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g711) {
     const long S = p->streams, N = p->N;
     const char *fn = pk.coded ? "vad_pump_submit_coded_packets: " : "vad_pump_submit_packets: ";
@@ -489,6 +492,7 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
         return pfail(p, VAD_ERR_ARG, std::string(fn) + "bad row list"), -1;
     *g711 = false;
     for (long i = 0; pk.codec && i < n_rows; ++i) {
+        if (pk.off[i] == VAD_ROW_SILENT) continue;
         if (pk.codec[i] > VAD_PCM_ALAW)
             return pfail(p, VAD_ERR_ARG, std::string(fn) + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) +
                                              " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW"), -1;
@@ -501,19 +505,20 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
     const char *why = nullptr;
     for (; i < n_rows && !why; ++i) {
         const int32_t b = pk.stream[i], off = pk.off[i], len = pk.len[i];
-        const int codec = pk.codec ? pk.codec[i] : VAD_PCM_S16;
+        const bool silent = off == VAD_ROW_SILENT;
+        const int codec = pk.codec && !silent ? pk.codec[i] : VAD_PCM_S16;
         const long at = pk.coded ? off : 2L * off, bytes = codec == VAD_PCM_S16 ? 2L * len : len;      // the row, in bytes
         if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
         else if (len < 1 || len > N) why = "a packet length out of 1 ... N (a longer packet goes in over two ticks)";
-        else if (at < 0 || at % 16 || at + bytes > S * N * 2)
+        else if (!silent && (at < 0 || at % 16 || at + bytes > S * N * 2))
             why = pk.coded ? "a packet byte offset that is not a multiple of 16, or a row that runs past the slot"
                            : "a packet offset that is not a multiple of 8 samples, or runs past the slot";
         else {
             p->seen[b] = 1;
             const int32_t c = p->held[b];
-            tab[4 * i] = b, tab[4 * i + 1] = (int32_t)(*g711 ? at : at / 2), tab[4 * i + 2] = len | codec << vad::kCodecShift, tab[4 * i + 3] = c;
+            tab[4 * i] = b, tab[4 * i + 1] = silent ? VAD_ROW_SILENT : (int32_t)(*g711 ? at : at / 2), tab[4 * i + 2] = len | codec << vad::kCodecShift, tab[4 * i + 3] = c;
             fl[b] = c + len >= N;
-            end = std::max(end, (at + bytes + 15) / 16 * 16);
+            if (!silent) end = std::max(end, (at + bytes + 15) / 16 * 16);
         }
     }
     for (long k = 0; k < i; ++k)                 // (only valid streams were marked)
@@ -529,7 +534,8 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
 // streams by first appearance, a stream's rows in arrival order): {stream, byte offset, len | codec, w}, w = pending before | k <<
 // kCodecShift on a stream's first row, -1 on its others -- assemble_burst's work unit is the stream.  The flag byte of a listed stream
 // holds k, the chunks it completes (0 ... max_burst).  *steps = max(1, largest k).  The pending counts are NOT touched: p->b_new holds
-// them for the caller to apply once the tick is queued.
+// them for the caller to apply once the tick is queued.  A SILENT row (offset VAD_ROW_SILENT) is a row of any length >= 1 like another:
+// S16 in the table whatever its codec entry says, no offset checks, no bytes of the copy.
 long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps) {
     const long S = p->streams, N = p->N, M = p->max_burst;
     const std::string fn = "vad_pump_submit_burst: ";
@@ -537,7 +543,7 @@ long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps)
     if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
         return pfail(p, VAD_ERR_ARG, fn + "bad row list (a tick holds at most `streams` rows)"), -1;
     for (long i = 0; pk.codec && i < n_rows; ++i)
-        if (pk.codec[i] > VAD_PCM_ALAW)
+        if (pk.off[i] != VAD_ROW_SILENT && pk.codec[i] > VAD_PCM_ALAW)
             return pfail(p, VAD_ERR_ARG, fn + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) +
                                              " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW"), -1;
     p->b_touched.clear();
@@ -547,14 +553,15 @@ long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps)
     for (long i = 0; i < n_rows && !why; ++i) {
         const int32_t b = pk.stream[i];
         const long at = pk.off[i], len = pk.len[i], bytes = (pk.codec ? pk.codec[i] : VAD_PCM_S16) == VAD_PCM_S16 ? 2 * len : len;
+        const bool silent = at == VAD_ROW_SILENT;
         if (b < 0 || b >= S) why = "a stream out of range";
         else if (len < 1) why = "a row length below 1";
-        else if (at < 0 || at % 16 || at + bytes > S * N * 2) why = "a row byte offset that is not a multiple of 16, or a row that runs past the slot";
+        else if (!silent && (at < 0 || at % 16 || at + bytes > S * N * 2)) why = "a row byte offset that is not a multiple of 16, or a row that runs past the slot";
         else {
             if (p->b_cnt[b]++ == 0) p->b_touched.push_back(b);
             if (p->held[b] + p->b_len[b] + len >= (M + 1) * N) why = "a stream would complete more than max_chunks chunks in one tick";
             else p->b_len[b] += (int32_t)len;
-            end = std::max(end, (at + bytes + 15) / 16 * 16);
+            if (!silent) end = std::max(end, (at + bytes + 15) / 16 * 16);
         }
     }
     if (why) {
@@ -574,7 +581,7 @@ long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps)
         const bool first = p->b_cnt[b] != 0;                 // (the row count has done its work: positions are assigned)
         p->b_cnt[b] = 0;
         int32_t *e = tab + 4 * (size_t)p->b_pos[b]++;
-        e[0] = b, e[1] = pk.off[i], e[2] = pk.len[i] | (pk.codec ? pk.codec[i] : VAD_PCM_S16) << vad::kCodecShift;
+        e[0] = b, e[1] = pk.off[i], e[2] = pk.len[i] | (pk.codec && pk.off[i] != VAD_ROW_SILENT ? pk.codec[i] : VAD_PCM_S16) << vad::kCodecShift;
         e[3] = first ? c | k << vad::kCodecShift : -1;
     }
     for (const int32_t b : p->b_touched) {
@@ -591,7 +598,8 @@ long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps)
 // The same for a wide tick (vad_pump_submit_wide_packets): the table and the flags go into WIDE slot r, table[i] = {stream, byte offset,
 // len | step << kCodecShift | first kept sample << kCombShift, pending before}.  A stream completes a chunk when its pending samples plus
 // the row's KEPT samples reach N.  Neither the pending counts nor the phases are touched: p->w_new holds them for the caller to apply
-// once the tick is queued.
+// once the tick is queued.  A SILENT row (offset VAD_ROW_SILENT) stands for len input samples of silence at its step: the phase advances
+// by len and comb_kept zeros are appended, as for a payload row; no offset checks, no bytes of the copy.
 long build_wide(vad_pump *p, int r, const Packets &pk, long n_rows) {
     const long S = p->streams, N = p->N, M = p->max_step;
     const std::string fn = "vad_pump_submit_wide_packets: ";
@@ -608,10 +616,11 @@ long build_wide(vad_pump *p, int r, const Packets &pk, long n_rows) {
     for (; i < n_rows && !why; ++i) {
         const int32_t b = pk.stream[i];
         const long at = pk.off[i], len = pk.len[i], step = pk.step ? pk.step[i] : M;
+        const bool silent = at == VAD_ROW_SILENT;
         if (step < 1 || step > M) why = "a step out of 1 ... max_step";
         else if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
         else if (len < 1 || len > step * N) why = "a row length out of 1 ... step * N (a longer row goes in over two ticks)";
-        else if (at < 0 || at % 16 || at + 2 * len > area) why = "a row byte offset that is not a multiple of 16, or a row that runs past the wide slot";
+        else if (!silent && (at < 0 || at % 16 || at + 2 * len > area)) why = "a row byte offset that is not a multiple of 16, or a row that runs past the wide slot";
         else {
             p->seen[b] = 1;
             const int32_t c = p->held[b], phase = step == p->w_step[b] ? p->w_phase[b] : 0;      // (another step: the comb starts anew)
@@ -619,7 +628,7 @@ long build_wide(vad_pump *p, int r, const Packets &pk, long n_rows) {
             tab[4 * i] = b, tab[4 * i + 1] = (int32_t)at, tab[4 * i + 2] = (int32_t)(len | step << vad::kCodecShift | (long)k0 << vad::kCombShift), tab[4 * i + 3] = c;
             fl[b] = total >= N;
             p->w_new.push_back(vad_pump::Comb{b, (int32_t)(total >= N ? total - N : total), (uint8_t)step, (uint8_t)((phase + len) % step)});
-            end = std::max(end, (at + 2 * len + 15) / 16 * 16);
+            if (!silent) end = std::max(end, (at + 2 * len + 15) / 16 * 16);
         }
     }
     for (long k = 0; k < i; ++k)                 // (only valid streams were marked)

@@ -1963,6 +1963,22 @@ def _codec_rows(codecs) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+# the offset entry of a SILENT row (include/silero_vad_hip.h VAD_ROW_SILENT): lengths[i] samples of digital silence, no bytes in the slot
+ROW_SILENT = -1
+
+
+def _silent_len(x):
+    """A write_* helper's row payload: None for a sample array, the row's length for an int (a silent row).  bool, 0, negative values
+    and floats are refused: they are neither."""
+    if isinstance(x, (bool, np.bool_, float, np.floating)):
+        raise ValueError(f"a packet is a 1-D sample array, or an int >= 1 for a silent row of that many samples, got {x!r}")
+    if not isinstance(x, (int, np.integer)):
+        return None
+    if x < 1:
+        raise ValueError(f"a silent row holds at least 1 sample, got {x!r}")
+    return int(x)
+
+
 def _int32_rows(x, name) -> np.ndarray:
     a = np.asarray(x)
     if a.ndim != 1 or (a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < -2**31 or a.max() >= 2**31)):
@@ -2015,7 +2031,9 @@ class StreamPump:
 
     Streams that arrive in 10 / 20 / 30 ms packets: `pump.write_packets(r, [(stream, int16 packet), ...])` (or the packets written
     into `packet_area(r)` + `submit_packets(r, streams, lengths, offsets)`); the device cuts each stream's concatenated packets into
-    chunks, and `pending(stream)` says how many samples wait for the next one.  G.711 (PCMU / PCMA) packets go in as they came off
+    chunks, and `pending(stream)` says how many samples wait for the next one.  Time without a payload (a lost packet, DTX, a
+    comfort-noise period) is a SILENT row: `(stream, 160)` in a `write_*` list, or `ROW_SILENT` as the row's offset -- that many zero
+    samples of the stream, no bytes written or sent; a stream listed in no row is absent (late) and stands still instead.  G.711 (PCMU / PCMA) packets go in as they came off
     the wire, 1 byte a sample: `pump.write_coded_packets(r, [(stream, packet, "ulaw" | "alaw" | "s16"), ...])` (or `packet_bytes(r)` +
     `submit_coded_packets(...)`); the device expands them.  With `max_burst=M` (2 ... 8) a tick may be a BURST:
     `pump.write_burst(r, [(stream, packet[, codec]), ...])` takes any number of packets of one stream and packets longer than a chunk (a
@@ -2123,7 +2141,10 @@ class StreamPump:
         """A PACKET tick (vad_pump_submit_packets): row i of `packet_area(r)` holds lengths[i] samples (1 ... N) of stream streams[i]
         at sample offset offsets[i] (a multiple of 8; None = the rows back to back, each rounded up to 8 samples).  Each stream's
         packets are appended to what it has pending; a stream whose pending samples reach N is stepped on the first N of them, every
-        other stream is absent this tick.  A stream listed twice or out of range, a bad length or offset raises and queues nothing."""
+        other stream is absent this tick.  A stream listed twice or out of range, a bad length or offset raises and queues nothing.
+        offsets[i] == ROW_SILENT (-1): a SILENT row -- lengths[i] samples of digital silence, no bytes of the area, exempt from the
+        alignment and fit checks, a row in every other respect; results are those of a row of int16 zeros.  Every other negative
+        offset is refused.  With offsets=None every row has a payload."""
         def table(x, name):
             a = np.asarray(x)
             if a.ndim != 1 or (a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < -2**31 or a.max() >= 2**31)):
@@ -2144,10 +2165,21 @@ class StreamPump:
 
     def write_packets(self, r: int, packets):
         """Pack [(stream, int16 samples), ...] back to back (each rounded up to 8 samples) into `packet_area(r)` and submit the packet
-        tick -- the convenience form for tests and small servers."""
+        tick -- the convenience form for tests and small servers.  An int in place of the samples, `(stream, 160)`, is a silent row of
+        that many samples (1 ... N): it takes no room in the area and advances no offset."""
         area = self.packet_area(r)
+        packets = list(packets)
+        for _, x in packets:                                     # (the silent rows first: nothing is written when one is bad)
+            n = _silent_len(x)
+            if n is not None and n > self.n:
+                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {n} (submit a longer one over two ticks)")
         streams, lengths, offsets, at = [], [], [], 0
         for s, x in packets:
+            if _silent_len(x) is not None:
+                streams.append(s)
+                lengths.append(int(x))
+                offsets.append(ROW_SILENT)
+                continue
             x = np.asarray(x)
             if x.dtype != np.int16 or x.ndim != 1:
                 raise ValueError("a packet must be a 1-D int16 array")
@@ -2171,7 +2203,9 @@ class StreamPump:
         (1 ... N) of stream streams[i] in format codecs[i] -- "s16" (2 bytes a sample), "ulaw" or "alaw" (1 byte), or the VAD_PCM_*
         numbers; None = every row "s16" -- at byte offset byte_offsets[i] (a multiple of 16; None = the rows back to back, each
         rounded up to 16 bytes).  The device expands G.711 to int16: the same results, bit for bit, as `submit_packets` with the rows
-        expanded by `g711_expand`.  A bad codec, stream, length or offset raises and queues nothing."""
+        expanded by `g711_expand`.  A bad codec, stream, length or offset raises and queues nothing.
+        byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] int16 zeros (see `submit_packets`); its codecs[i] is not looked
+        at by the pump.  With byte_offsets=None every row has a payload."""
         st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
         off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
         cd = None if codecs is None else _codec_rows(codecs)
@@ -2189,11 +2223,23 @@ class StreamPump:
 
     def write_coded_packets(self, r: int, packets):
         """Pack [(stream, samples, codec), ...] back to back (each rounded up to 16 bytes) into `packet_bytes(r)` and submit the tick:
-        codec "s16" takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes (an RTP payload as it came off the wire)."""
+        codec "s16" takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes (an RTP payload as it came off the wire).  An int
+        in place of the samples, `(stream, 160, codec)`, is a silent row of that many samples (1 ... N), whatever the codec."""
         area = self.packet_bytes(r)
+        packets = list(packets)
+        for _, x, _ in packets:                                  # (the silent rows first: nothing is written when one is bad)
+            n = _silent_len(x)
+            if n is not None and n > self.n:
+                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {n} (submit a longer one over two ticks)")
         streams, lengths, codecs, offsets, at = [], [], [], [], 0
         for s, x, codec in packets:
             c = _codec_id(codec)
+            if _silent_len(x) is not None:
+                streams.append(s)
+                lengths.append(int(x))
+                codecs.append(c)
+                offsets.append(ROW_SILENT)
+                continue
             x = np.asarray(x)
             want = np.int16 if c == _PCM["s16"] else np.uint8
             if x.dtype != want or x.ndim != 1:
@@ -2215,7 +2261,9 @@ class StreamPump:
         listed any number of times and a row may be longer than N.  Each stream's rows are appended, in row order, to what it has
         pending; a stream that completes k chunks (k <= max_burst) is stepped k times, in order, inside this tick.  The results are
         those of the same audio fed chunk by chunk, bit for bit.  A stream that would complete more than max_burst chunks, more rows
-        than `streams`, a bad codec, stream, length or offset raises and queues nothing."""
+        than `streams`, a bad codec, stream, length or offset raises and queues nothing.
+        byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] >= 1 int16 zeros (see `submit_packets`), longer than N if the
+        gap was; it counts towards max_burst like any row.  With byte_offsets=None every row has a payload."""
         st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
         off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
         cd = None if codecs is None else _codec_rows(codecs)
@@ -2234,12 +2282,22 @@ class StreamPump:
     def write_burst(self, r: int, packets):
         """Pack [(stream, samples) | (stream, samples, codec), ...] back to back in arrival order (each rounded up to 16 bytes) into
         `packet_bytes(r)` and submit the burst tick: packets of any length, streams repeated as often as they delivered.  codec "s16"
-        (the default) takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes."""
+        (the default) takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes.  An int in place of the samples,
+        `(stream, 3 * N + 5)`, is a silent row of that many samples."""
         area = self.packet_bytes(r)
+        packets = list(packets)
+        for pk in packets:                                       # (the silent rows first: nothing is written when one is bad)
+            _silent_len(pk[1])
         streams, lengths, codecs, offsets, at = [], [], [], [], 0
         for pk in packets:
             s, x, codec = pk if len(pk) == 3 else (pk[0], pk[1], "s16")
             c = _codec_id(codec)
+            if _silent_len(x) is not None:
+                streams.append(s)
+                lengths.append(int(x))
+                codecs.append(c)
+                offsets.append(ROW_SILENT)
+                continue
             x = np.asarray(x)
             want = np.int16 if c == _PCM["s16"] else np.uint8
             if x.dtype != want or x.ndim != 1:
@@ -2278,7 +2336,9 @@ class StreamPump:
         at byte offset byte_offsets[i] (a multiple of 16; None = the rows back to back, each rounded up to 16 bytes).  The device keeps
         the samples of the stream's comb (input sample g iff g % step == 0) and appends them to what the stream has pending: the same
         results, bit for bit, as `submit_packets` with the rows cut by `decimate` at the carried phase.  A bad step, stream, length or
-        offset raises and queues nothing."""
+        offset raises and queues nothing.
+        byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] input samples of silence at steps[i] (see `submit_packets`): the
+        phase advances by lengths[i], the stream gains the zeros the comb keeps.  With byte_offsets=None every row has a payload."""
         st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
         off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
         sp = None

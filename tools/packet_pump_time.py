@@ -5,7 +5,7 @@ ticks in flight.  The ring slots are written once before the timed window: this 
 path's host writes.  Prints one JSON line: per-tick time, link bytes per tick, the share of a plain pinned -> HBM copy's rate that
 reaches, and the time per second of audio of every route (equal audio throughput).
 
-    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs] [burst_share d] [--wide]
+    python tools/packet_pump_time.py [ticks] [reps] [sr] [codecs] [burst_share d] [--wide] [--silent SHARE [--zeros]]
 
 sr: 16000 (default) or 8000.  codecs: a comma-separated list of packet formats, timed alternately with the chunk route -- "s16" (the
 default: int16 packets through vad_pump_submit_packets), "ulaw" / "alaw" (G.711 packets, 1 byte a sample, through
@@ -21,6 +21,13 @@ d ticks behind.  Share, d and the sub-steps per tick are in the output, and so i
 --wide (16 kHz only): adds the route "wide" -- every stream delivers a 20 ms 48 kHz packet (960 int16 samples) a tick through
 vad_pump_submit_wide_packets on a pump with vad_pump_set_wideband(3), the device keeps every third sample -- and "packets_on_wide_pump",
 the ordinary 16 kHz packet ticks of that same pump.  A wide tick carries the same audio as a packet tick in 3 x the packet bytes.
+
+--silent SHARE (0 ... 1): that share of the streams (the first of the arrival order) is in a gap -- lost packets, DTX -- in every tick of
+the routes "packets" / "packets_ulaw" / "packets_alaw": their rows are SILENT rows (offset ROW_SILENT, no bytes in the slot), the payload
+rows lie back to back, and the tick's copy ends behind the last of them.  With --zeros the same streams deliver payload rows of int16
+zeros instead, each where its packet would lie: what a caller without silent rows sends (and what a library without them can be timed
+with).  Both give the same chunks to the step kernels.  "link_bytes_per_tick" is what the tick's one copy carries either way, and
+"tick_ms_p50" the median time from a tick's submission to its retirement, two ticks in flight.
 
 assemble_packets_kernel's / assemble_coded_packets_kernel's / assemble_burst_kernel's / assemble_wide_packets_kernel's own time: run it under
 `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/packet_pump_time.py ...` (in a run of its own) and read the
@@ -54,7 +61,15 @@ def main():
     import bench
     from silero_vad_amd import Engine, StreamPump
     wide = "--wide" in sys.argv
-    sys.argv = [a for a in sys.argv if a != "--wide"]
+    zeros = "--zeros" in sys.argv
+    silent = 0.0
+    if "--silent" in sys.argv:
+        k = sys.argv.index("--silent")
+        silent = float(sys.argv[k + 1])
+        del sys.argv[k:k + 2]
+    if not 0.0 <= silent <= 1.0 or (zeros and not silent):
+        raise SystemExit("--silent SHARE: a share of 0 ... 1; --zeros goes with it")
+    sys.argv = [a for a in sys.argv if a not in ("--wide", "--zeros")]
     ticks = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     sr = int(sys.argv[3]) if len(sys.argv) > 3 else 16000
@@ -72,6 +87,8 @@ def main():
     rng = np.random.default_rng(0)
     order = rng.permutation(S).astype(np.int32)
     page = lambda b: (b + 4095) // 4096 * 4096                          # noqa: E731  (the slot's header areas, csrc/pump.hip)
+    n_gap = int(S * silent)                                             # rows 0 ... n_gap - 1 of the arrival order are in a gap
+    packed = n_gap > 0 and not zeros                                    # silent rows: the payload rows move up, back to back
     # route -> packet format (None: the chunk route)
     names = {"s16": "packets", "ulaw": "packets_ulaw", "alaw": "packets_alaw"}
     fmt = {names[c]: c for c in codecs}
@@ -92,7 +109,10 @@ def main():
             routes[name] = {"bytes": page(4 * S) + page(S) + S * N * 2, "ms_audio": 1000.0 * N / sr}
         else:                                                           # row table (16 bytes a row) + flags + the packets
             row = P * (2 if c == "s16" else 1)
-            routes[name] = {"bytes": 16 * S + page(S) + S * ((row + 15) // 16 * 16), "ms_audio": 1000.0 * P / sr}
+            carried = S - n_gap if packed and "_on_" not in name else S
+            if zeros and c != "s16":                                    # (the rows of zeros are int16 among 1-byte rows: see below)
+                carried = n_gap * 2 + (S - n_gap)
+            routes[name] = {"bytes": 16 * S + page(S) + carried * ((row + 15) // 16 * 16), "ms_audio": 1000.0 * P / sr}
     pumps = {}
     for name, c in fmt.items():
         if name == "packets_on_wide_pump":                              # (the same pump object: its ordinary slots)
@@ -115,6 +135,28 @@ def main():
         pumps[name] = pump
     lengths = np.full(S, P, np.int32)
     offsets = (np.arange(S) * P).astype(np.int32)                       # samples (s16) or bytes (G.711): 16-byte aligned either way
+    gap_offsets, gap_codecs = {}, {}                                    # per packet format, with `silent`
+    if n_gap:
+        ROW_SILENT = -1                                                 # (silero_vad_amd.ROW_SILENT, include/silero_vad_hip.h VAD_ROW_SILENT)
+        for c in codecs:
+            cd = np.full(S, {"s16": 0, "ulaw": 1, "alaw": 2}[c], np.uint8)
+            if packed:                                                  # payload row k lies where row k - n_gap lay
+                off = np.concatenate([np.full(n_gap, ROW_SILENT), offsets[:S - n_gap]]).astype(np.int32)
+                for r in range(R):
+                    area = pumps[names[c]].packet_area(r) if c == "s16" else pumps[names[c]].packet_bytes(r)
+                    area[:(S - n_gap) * P] = area[n_gap * P:S * P].copy()
+            elif c == "s16":
+                off = offsets
+                for r in range(R):
+                    pumps[names[c]].packet_area(r)[:n_gap * P] = 0
+            else:                                                       # int16 zeros in front (2 bytes a sample), the G.711 rows behind them
+                off = np.concatenate([np.arange(n_gap) * 2 * P, n_gap * 2 * P + np.arange(S - n_gap) * P]).astype(np.int32)
+                cd[:n_gap] = 0
+                for r in range(R):
+                    area = pumps[names[c]].packet_bytes(r)
+                    area[n_gap * 2 * P:n_gap * 2 * P + (S - n_gap) * P] = area[n_gap * P:S * P].copy()
+                    area[:n_gap * 2 * P] = 0
+            gap_offsets[c], gap_codecs[c] = off, cd
     wide_lengths, wide_offsets = np.full(S, 3 * P, np.int32), (np.arange(S) * P * 6).astype(np.int32)
     codec_rows = {"ulaw": np.full(S, 1, np.uint8), "alaw": np.full(S, 2, np.uint8)}
 
@@ -133,9 +175,17 @@ def main():
     def run(name, n):
         pump, c = pumps[name], fmt[name]
         inflight = 0
+        gap = n_gap and name in (names.get(c), ) and c in gap_offsets
+        sent, lat = [], lats.setdefault(name, [])
+        lat.clear()
         t0 = time.perf_counter()
         for t in range(n):
-            if c == "wide":
+            sent.append(time.perf_counter())
+            if gap and c == "s16":
+                pump.submit_packets(t % R, order, lengths, gap_offsets[c])
+            elif gap:
+                pump.submit_coded_packets(t % R, order, lengths, gap_codecs[c], gap_offsets[c])
+            elif c == "wide":
                 pump.submit_wide_packets(t % R, order, wide_lengths, None, wide_offsets)
             elif c == "burst":
                 pump.submit_burst(t % R, phases[t % (d + 1)][0], phases[t % (d + 1)][1], None, phases[t % (d + 1)][2])
@@ -148,11 +198,15 @@ def main():
             inflight += 1
             if inflight >= 2:
                 pump.poll()
+                lat.append(time.perf_counter() - sent[len(lat)])
                 inflight -= 1
         while inflight:
             pump.poll()
+            lat.append(time.perf_counter() - sent[len(lat)])
             inflight -= 1
         return time.perf_counter() - t0
+
+    lats = {}
 
     for name in routes:                                                 # warm-up: code objects, the carry's first fill
         run(name, 200)
@@ -161,6 +215,8 @@ def main():
         for name in routes:
             best[name] = min(best[name], run(name, ticks))
     out = {"streams": S, "sr": sr, "packet_samples": P, "ticks": ticks, "reps": reps, "h2d_GBps": round(link, 2)}
+    if n_gap:
+        out.update({"silent_share": round(n_gap / S, 4), "gap_rows": "int16 zeros" if zeros else "silent"})
     if share > 0:
         out.update({"burst_share": round(group / S, 4), "withheld_ticks": d,
                     "burst_steps_last_ticks": sorted({pumps["burst"].burst_steps(r) for r in range(R)})})
@@ -168,7 +224,8 @@ def main():
         tick_s = best[name] / ticks
         out[name] = {"tick_us": round(tick_s * 1e6, 1), "link_bytes_per_tick": info["bytes"],
                      "link_GBps": round(info["bytes"] / tick_s / 1e9, 2), "of_link": round(info["bytes"] / tick_s / 1e9 / link, 3),
-                     "ms_per_s_audio": round(tick_s * 1e3 / (info["ms_audio"] / 1000.0), 2)}
+                     "ms_per_s_audio": round(tick_s * 1e3 / (info["ms_audio"] / 1000.0), 2),
+                     "tick_ms_p50": round(float(np.median(lats[name])) * 1e3, 4)}
     for name in routes:
         if name != "chunks":
             out[f"{name}_over_chunks_per_s_audio"] = round(out[name]["ms_per_s_audio"] / out["chunks"]["ms_per_s_audio"], 3)
