@@ -500,6 +500,80 @@ int  vad_pump_open(vad_pump *p, int stream);
 int  vad_pump_close(vad_pump *p, int stream);
 /* Test / migration hook: copy stream's carried h[128], c[128], ctx[C] to the host (any may be NULL).  Synchronises.        */
 int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
+
+/* SNAPSHOT AND RESTORE of live streams: everything a stream carries from one tick to the next leaves a pump as plain bytes and enters
+ * any slot of any pump of the same sample rate -- another GPU, another process, another machine -- for a drain, a rebalancing of
+ * streams between per-GPU ranks, a rolling restart or a failover.  The reference treats this state as the resumable unit of the model
+ * (_state and _context are explicit inputs and outputs of its graph; the VADIterator adds triggered / temp_end / current_sample,
+ * utils_vad.py:500-503).  Every probability, event, state and pending count after an import is bit for bit what the uninterrupted
+ * stream would have produced, PROVIDED the destination pump was created with the iterator parameters of the source (see below).
+ *
+ * THE BLOB (version 1).  Little-endian; this layout is the contract between a blob's writer and its readers.
+ *   header, VAD_SNAPSHOT_HEADER_BYTES = 64:
+ *      0  char    magic[8]       "SVADSNAP"
+ *      8  uint32  version        VAD_SNAPSHOT_VERSION
+ *     12  uint32  header_bytes   64
+ *     16  int32   sr             8000 / 16000
+ *     20  int32   N              samples per chunk at sr (256 / 512)
+ *     24  int32   C              context samples at sr (32 / 64)
+ *     28  uint32  stride         bytes per record: 32 + 4 * (128 + 128 + C) + 2 * N = 1696 / 2336, a multiple of 16
+ *     32  int64   n_records
+ *     40  float64 threshold      \  the source pump's iterator parameters as the iterator compares them: the threshold, and
+ *     48  float64 min_silence     > min_silence_duration_ms and speech_pad_ms in SAMPLES at sr.  INFORMATIONAL: import does not compare
+ *     56  float64 pad            /  them with the destination's, and the continuation is bit-identical only if they are the same.
+ *   then n_records records of `stride` bytes, each:
+ *      0  vad_stream_info (32 bytes, below)
+ *     32  float32 h[128]
+ *    544  float32 c[128]
+ *   1056  float32 ctx[C]                  the context the stream's NEXT chunk is computed behind
+ *   1056 + 4 C  int16 pending_samples[N]  the stream's samples that wait for their chunk (at the pump's rate: G.711 rows expanded,
+ *                                         wide rows decimated), pending_samples[0 : pending]; everything behind them is ZERO
+ * A record does not name the slot it came from.  Reserved bytes are written as zero and a reader refuses a record in which they are not;
+ * samples behind `pending` are written as zero and ignored when read.  Two exports with no tick between them are byte for byte the same.
+ * NOT carried: ticks in flight (there are none: see below), the position counter of the vad_pump_play* helpers (it restarts as after
+ * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), and the model weights.                   */
+#define VAD_SNAPSHOT_VERSION 1
+#define VAD_SNAPSHOT_HEADER_BYTES 64
+typedef struct vad_stream_info {
+    int64_t current_sample;      /* VADIterator.current_sample: samples stepped since vad_pump_open; >= 0                            */
+    int64_t temp_end;            /* VADIterator.temp_end: 0 ... current_sample                                                       */
+    int32_t pending;             /* samples that wait for their chunk, 0 ... N - 1 (vad_pump_pending)                                */
+    uint8_t active;              /* 1: open (emits events); 0: closed (vad_pump_close)                                               */
+    uint8_t triggered;           /* VADIterator.triggered, 0 / 1: inside a speech segment                                            */
+    uint8_t wide_step;           /* the step of the stream's last wide row: 0 = it never had one, else 1 ... 3                       */
+    uint8_t wide_phase;          /* its comb phase (vad_pump_wide_phase), 0 ... max(1, wide_step) - 1                                */
+    uint8_t reserved[8];         /* zero                                                                                             */
+} vad_stream_info;
+/* Bytes of a blob of n records at sample rate sr: 64 + n * stride.  0 for a bad sr or n < 0.  Host only.                            */
+size_t vad_pump_snapshot_bytes(int sr, long n);
+/* EXPORT: the records of streams[0 ... n - 1] (distinct slots; NULL = every slot in ascending order, and n must be the pump's stream
+ * count) into blob[0 : vad_pump_snapshot_bytes(sr, n)], ordinary host memory of `cap` bytes.  Read-only: the pump and the exported
+ * streams go on exactly as if the call had not happened; the caller closes them when it wants to.  Synchronous: the blob is complete on
+ * return.  One gather kernel on the pump's compute stream packs the records on the device and ONE copy brings them over the link.
+ * IMPORT: record records[i] of the blob (NULL = record i) replaces the whole carried state of slot streams[i], i = 0 ... n - 1
+ * (distinct slots; records may repeat and may be any subset, so one blob can be dealt out to several pumps): h, c, the context the next
+ * tick reads, the pending samples and their count, the comb step and phase, the iterator state and the open / closed flag; the
+ * position counter of vad_pump_play* restarts.  Synchronous.  ONE copy takes the records blob[min record ... max record] over the link
+ * and one scatter kernel on the compute stream puts them in place.
+ * BOTH work only on an IDLE pump -- no tick in flight (retire them with vad_pump_poll first: at most ring_slots - 1), VAD_ERR_ARG
+ * otherwise, as vad_pump_set_burst / vad_pump_set_wideband: then no deferred open / close is waiting and the host bookkeeping, which
+ * advances partly at submit time (pending counts, comb phases) and partly at retire time (iterator state), is at ONE point of every
+ * stream's timeline.  A poisoned pump refuses them like every other call (VAD_ERR_HIP).
+ * Export refuses (VAD_ERR_ARG, blob untouched): a slot out of range or listed twice, n < 0, cap too small.
+ * Import refuses, with NOTHING queued and NOTHING changed: a blob vad_snapshot_inspect refuses (VAD_ERR_ARG: bad magic / version /
+ * geometry, shorter than its header claims, any record field out of its range -- a blob is untrusted input, and all of it is checked on
+ * the host before a value from it can steer a device address or a loop bound); a sample rate other than the pump's
+ * (VAD_ERR_SAMPLE_RATE); a record index out of range, a slot out of range or listed twice, a record with wide_step >= 2 for a pump
+ * whose wideband max_step is smaller (a pump without wideband included) (VAD_ERR_ARG).  A record with wide_step 1 enters a pump
+ * without wideband as a stream that never had a wide row: a step-1 comb has no phase to lose.                                       */
+int  vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap);
+int  vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const int32_t *records, const int32_t *streams, long n);
+/* Readers of a blob; host only, no pump and no device needed.  vad_snapshot_inspect: validate ALL of blob[0 : nbytes] (header and every
+ * record's fields) -> VAD_OK and *n_records, *sr (either may be NULL), or VAD_ERR_ARG.  vad_snapshot_stream: record i of a valid blob
+ * -> *info, h[128], c[128], ctx[C], pending[N] (any may be NULL); VAD_ERR_ARG for an invalid blob or i out of range.                */
+int  vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr);
+int  vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info *info, float *h, float *c, float *ctx, int16_t *pending);
+
 /* The whole loop in one native call -- for tests, benchmarks and file-fed servers: stream b plays rows[b * ld ...] circularly with
  * period `period` samples (a multiple of N): at tick t its chunk is rows[b * ld + (t * N) % period ...].  `fill_threads` SOURCE
  * threads (0: min(8, vad_host_threads() - 2); < 0: the sources are silent, the slots keep their content -- isolates the device

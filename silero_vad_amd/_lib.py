@@ -49,6 +49,12 @@ class PumpStats(Structure):
                 ("fill_threads", c_int), ("depth", c_int), ("chunks", c_long)]
 
 
+class StreamInfo(Structure):
+    """vad_stream_info: the host's part of a snapshot record (include/silero_vad_hip.h "SNAPSHOT AND RESTORE")."""
+    _fields_ = [("current_sample", c_int64), ("temp_end", c_int64), ("pending", ctypes.c_int32), ("active", ctypes.c_uint8),
+                ("triggered", ctypes.c_uint8), ("wide_step", ctypes.c_uint8), ("wide_phase", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 8)]
+
+
 # every symbol include/silero_vad_hip.h declares: name -> (restype, argtypes)
 f32p, i16p = POINTER(c_float), POINTER(c_int16)
 SYMBOLS = {
@@ -100,6 +106,11 @@ SYMBOLS = {
     "vad_pump_open": (c_int, [c_void_p, c_int]),
     "vad_pump_close": (c_int, [c_void_p, c_int]),
     "vad_pump_state": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vad_pump_snapshot_bytes": (c_size_t, [c_int, c_long]),
+    "vad_pump_export_streams": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_size_t]),
+    "vad_pump_import_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_long]),
+    "vad_snapshot_inspect": (c_int, [c_void_p, c_size_t, POINTER(c_long), POINTER(c_int)]),
+    "vad_snapshot_stream": (c_int, [c_void_p, c_size_t, c_long, POINTER(StreamInfo), c_void_p, c_void_p, c_void_p, c_void_p]),
     "vad_pump_play": (c_long, [c_void_p, c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_void_p, c_long, POINTER(PumpStats)]),
     "vad_forward_audio": (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_long, c_void_p, c_void_p,
                                   c_void_p, c_long, c_void_p]),

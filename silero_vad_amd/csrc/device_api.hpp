@@ -149,6 +149,19 @@ constexpr int kCombShift = kCodecShift + 4;
 constexpr int kMaxWideStep = 3;
 hipError_t launch_assemble_wide_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
                                         hipStream_t s);
+// Snapshot and restore of the pump's streams (vad_pump_export_streams / vad_pump_import_streams; kernel_snapshot.hip).  table[i] = {slot b,
+// its part k, pending c (0 ... N - 1), record r}, all range-checked by the host; parts[k] = part k's state block [2][n][128] and its
+// first slot.  gather: record r of `records` (the blob's record layout, 32 + 4 * (256 + C) + 2 * N bytes each) <- zeros for the info
+// block, h, c, ctx[b], carry[b][0:c] ++ zeros.  scatter: the reverse (the info block is the host's; the carry row gets the record's first
+// c samples ++ zeros).  `ctx` is the context buffer the pump's next tick reads.  HBM to HBM.
+struct SnapPart {
+    float *state;
+    int32_t lo, n;
+};
+hipError_t launch_snapshot_gather(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, int N, int C,
+                                  uint8_t *records, hipStream_t s);
+hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, int N, int C,
+                                   const uint8_t *records, hipStream_t s);
 
 // The comb of the reference's decimation x[::step] (src/silero_vad/utils_vad.py:39-42) over a stream that arrives in pieces: input sample g
 // of the stream is kept iff g % step == 0; `phase` = (samples that came before the piece) % step.  The one definition the pump's

@@ -156,6 +156,12 @@ struct vad_pump {
     std::vector<uint8_t> w_step, w_phase;        // [streams] the step of the stream's last wide row (0: none yet) and its comb phase (host bookkeeping)
     struct Comb { int32_t stream, now; uint8_t step, phase; };
     std::vector<Comb> w_new;                     // what each listed stream has pending, and its step and phase, after the tick
+    // snapshot / restore (vad_pump_export_streams / vad_pump_import_streams; allocated by the first of them, none of it touched by a tick)
+    int32_t *h_snap_tab = nullptr;               // [streams] x {slot, part, pending, record}: page-locked, mapped -- the kernels read it in place
+    int32_t *d_snap_tab = nullptr;               // device alias of h_snap_tab
+    vad::SnapPart *d_snap_parts = nullptr;       // [parts] each part's state block and first slot
+    uint8_t *d_snap = nullptr;                   // the packed records on the device: what the one copy of a call carries
+    size_t snap_cap = 0;                         // ... its bytes
     bool poisoned = false;                       // a tick failed half-way: the carried state is no longer what any caller expects
     std::string err;
 
@@ -334,6 +340,9 @@ void vad_pump_destroy(vad_pump *p) {
     if (p->h_prob_more) (void)hipHostFree(p->h_prob_more);
     if (p->d_wide) (void)hipFree(p->d_wide);
     if (p->h_wide) (void)hipHostFree(p->h_wide);
+    if (p->d_snap) (void)hipFree(p->d_snap);
+    if (p->d_snap_parts) (void)hipFree(p->d_snap_parts);
+    if (p->h_snap_tab) (void)hipHostFree(p->h_snap_tab);
     if (p->h_ring) (void)hipHostFree(p->h_ring);
     if (p->h_prob) (void)hipHostFree(p->h_prob);
     for (hipStream_t cs : p->copy)
@@ -1056,6 +1065,237 @@ int vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx) {
     if (h) PUMP_TRY(p, hipMemcpy(h, p->d_state[k] + row * 128, 128 * sizeof(float), hipMemcpyDeviceToHost));
     if (c) PUMP_TRY(p, hipMemcpy(c, p->d_state[k] + (n + row) * 128, 128 * sizeof(float), hipMemcpyDeviceToHost));
     if (ctx) PUMP_TRY(p, hipMemcpy(ctx, p->d_ctx[p->flips & 1] + (size_t)stream * p->C, (size_t)p->C * sizeof(float), hipMemcpyDeviceToHost));
+    return VAD_OK;
+}
+
+}  // extern "C"
+
+// Snapshot and restore (include/silero_vad_hip.h "SNAPSHOT AND RESTORE"; kernel_snapshot.hip).  The blob's header and record layout:
+namespace {
+
+#if __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
+#error "the snapshot blob is little-endian and is written from the host's own representation"
+#endif
+struct SnapHeader {
+    char magic[8];
+    uint32_t version, header_bytes;
+    int32_t sr, N, C;
+    uint32_t stride;
+    int64_t n_records;
+    double threshold, min_silence, pad;
+};
+static_assert(sizeof(SnapHeader) == VAD_SNAPSHOT_HEADER_BYTES && sizeof(vad_stream_info) == 32, "the blob layout is the documented one");
+const char kSnapMagic[8] = {'S', 'V', 'A', 'D', 'S', 'N', 'A', 'P'};
+
+size_t snap_stride(int N, int C) { return sizeof(vad_stream_info) + (size_t)(2 * 128 + C) * sizeof(float) + (size_t)N * sizeof(int16_t); }
+
+const char *snap_info_fault(const vad_stream_info &f, int N) {
+    if (f.pending < 0 || f.pending >= N) return "pending out of 0 ... N - 1";
+    if (f.active > 1 || f.triggered > 1) return "active / triggered other than 0 / 1";
+    if (f.wide_step > vad::kMaxWideStep) return "wide_step above 3";
+    if (f.wide_phase >= std::max<int>(1, f.wide_step)) return "wide_phase not below max(1, wide_step)";
+    if (f.current_sample < 0 || f.temp_end < 0 || f.temp_end > f.current_sample) return "current_sample / temp_end out of range";
+    for (const uint8_t z : f.reserved)
+        if (z) return "reserved bytes that are not zero";
+    return nullptr;
+}
+
+// The whole blob, header and every record's fields (the blob may lie at any address: everything is read through memcpy).
+// -> nullptr and *hd, or what is wrong with it.
+const char *snap_check(const void *blob, size_t nbytes, SnapHeader *hd) {
+    if (!blob || nbytes < sizeof(SnapHeader)) return "shorter than a header";
+    std::memcpy(hd, blob, sizeof(SnapHeader));
+    if (std::memcmp(hd->magic, kSnapMagic, sizeof(kSnapMagic)) != 0) return "not a snapshot (magic)";
+    if (hd->version != VAD_SNAPSHOT_VERSION || hd->header_bytes != sizeof(SnapHeader)) return "a version this library does not read";
+    int N = 0, C = 0;
+    if (vad_geometry(hd->sr, &N, &C) != VAD_OK || hd->N != N || hd->C != C || hd->stride != snap_stride(N, C)) return "a sample rate / geometry that does not exist";
+    if (hd->n_records < 0 || (uint64_t)hd->n_records > (nbytes - sizeof(SnapHeader)) / hd->stride) return "shorter than its header claims";
+    const uint8_t *rec = static_cast<const uint8_t *>(blob) + sizeof(SnapHeader);
+    for (int64_t i = 0; i < hd->n_records; ++i) {
+        vad_stream_info f;
+        std::memcpy(&f, rec + (size_t)i * hd->stride, sizeof(f));
+        if (const char *why = snap_info_fault(f, N)) return why;
+    }
+    return nullptr;
+}
+
+int part_of(const vad_pump *p, int b) { return (int)(std::upper_bound(p->hi.begin(), p->hi.end(), b) - p->hi.begin()); }
+
+// the work table and the part table (first call), and room for `bytes` of records on the device
+int snap_reserve(vad_pump *p, size_t bytes) {
+    PUMP_TRY(p, hipSetDevice(p->device));
+    if (!p->h_snap_tab) {
+        void *dv = nullptr;
+        int32_t *tab = nullptr;
+        vad::SnapPart *dp = nullptr;
+        std::vector<vad::SnapPart> parts;
+        for (int k = 0; k < p->parts; ++k) parts.push_back(vad::SnapPart{p->d_state[k], p->lo[k], p->hi[k] - p->lo[k]});
+        const bool ok = hipHostMalloc((void **)&tab, (size_t)p->streams * 4 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess &&
+                        hipHostGetDevicePointer(&dv, tab, 0) == hipSuccess && dv &&
+                        hipMalloc((void **)&dp, parts.size() * sizeof(vad::SnapPart)) == hipSuccess &&
+                        hipMemcpy(dp, parts.data(), parts.size() * sizeof(vad::SnapPart), hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) {
+            if (dp) (void)hipFree(dp);
+            if (tab) (void)hipHostFree(tab);
+            return pfail(p, VAD_ERR_ALLOC, "snapshot: no memory for the work tables");
+        }
+        p->h_snap_tab = tab, p->d_snap_tab = static_cast<int32_t *>(dv), p->d_snap_parts = dp;
+    }
+    if (bytes > p->snap_cap) {
+        if (p->d_snap) (void)hipFree(p->d_snap);
+        p->d_snap = nullptr, p->snap_cap = 0;
+        if (hipMalloc((void **)&p->d_snap, bytes) != hipSuccess) return pfail(p, VAD_ERR_ALLOC, "snapshot: no device memory for the records");
+        p->snap_cap = bytes;
+    }
+    return VAD_OK;
+}
+
+// both calls: not on a poisoned pump, not with a tick in flight
+int snap_idle(vad_pump *p, const std::string &fn) {
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, fn + "ticks in flight (retire them with vad_pump_poll first)");
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t vad_pump_snapshot_bytes(int sr, long n) {
+    int N = 0, C = 0;
+    if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
+    return sizeof(SnapHeader) + (size_t)n * snap_stride(N, C);
+}
+
+int vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr) {
+    SnapHeader hd;
+    if (snap_check(blob, nbytes, &hd)) return VAD_ERR_ARG;
+    if (n_records) *n_records = (long)hd.n_records;
+    if (sr) *sr = hd.sr;
+    return VAD_OK;
+}
+
+int vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info *info, float *h, float *c, float *ctx, int16_t *pending) {
+    SnapHeader hd;
+    if (snap_check(blob, nbytes, &hd) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
+    const uint8_t *rec = static_cast<const uint8_t *>(blob) + sizeof(SnapHeader) + (size_t)i * hd.stride;
+    const size_t st = 128 * sizeof(float), cx = (size_t)hd.C * sizeof(float);
+    if (info) std::memcpy(info, rec, sizeof(*info));
+    if (h) std::memcpy(h, rec + sizeof(vad_stream_info), st);
+    if (c) std::memcpy(c, rec + sizeof(vad_stream_info) + st, st);
+    if (ctx) std::memcpy(ctx, rec + sizeof(vad_stream_info) + 2 * st, cx);
+    if (pending) std::memcpy(pending, rec + sizeof(vad_stream_info) + 2 * st + cx, (size_t)hd.N * sizeof(int16_t));
+    return VAD_OK;
+}
+
+int vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) {
+    if (!p) return VAD_ERR_ARG;
+    const std::string fn = "vad_pump_export_streams: ";
+    if (const int rc = snap_idle(p, fn)) return rc;
+    const long S = p->streams;
+    if (n < 0 || n > S || (!streams && n != S && n != 0) || !blob) return pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count) or no blob");
+    const size_t stride = snap_stride(p->N, p->C), need = sizeof(SnapHeader) + (size_t)n * stride;
+    if (cap < need) return pfail(p, VAD_ERR_ARG, fn + "the blob needs vad_pump_snapshot_bytes(sr, n) bytes");
+    bool bad = false;
+    long i = 0;
+    for (; streams && i < n && !bad; ++i) {
+        const int32_t b = streams[i];
+        if (!(bad = b < 0 || b >= S || p->seen[b])) p->seen[b] = 1;
+    }
+    for (long k = 0; streams && k < i; ++k)      // (only valid slots were marked)
+        if (streams[k] >= 0 && streams[k] < S) p->seen[streams[k]] = 0;
+    if (bad) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
+    uint8_t *rec = static_cast<uint8_t *>(blob) + sizeof(SnapHeader);
+    if (n > 0) {
+        if (const int rc = snap_reserve(p, (size_t)n * stride)) return rc;
+        for (long k = 0; k < n; ++k) {
+            const int32_t b = streams ? streams[k] : (int32_t)k;
+            int32_t *e = p->h_snap_tab + 4 * k;
+            e[0] = b, e[1] = part_of(p, b), e[2] = p->held[b], e[3] = (int32_t)k;
+        }
+        // (read-only, behind everything the compute stream has run: a failure leaves the pump as it was)
+        PUMP_TRY(p, vad::launch_snapshot_gather(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute));
+        PUMP_TRY(p, hipMemcpyAsync(rec, p->d_snap, (size_t)n * stride, hipMemcpyDeviceToHost, p->compute));
+        PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    }
+    SnapHeader hd;
+    std::memcpy(hd.magic, kSnapMagic, sizeof(kSnapMagic));
+    hd.version = VAD_SNAPSHOT_VERSION, hd.header_bytes = sizeof(SnapHeader);
+    hd.sr = p->sr, hd.N = p->N, hd.C = p->C, hd.stride = (uint32_t)stride, hd.n_records = n;
+    hd.threshold = p->threshold, hd.min_silence = p->min_silence, hd.pad = p->pad;
+    std::memcpy(blob, &hd, sizeof(hd));
+    for (long k = 0; k < n; ++k) {               // the host's part of a record (the gather left it zero)
+        const int32_t b = streams ? streams[k] : (int32_t)k;
+        vad_stream_info f{};
+        f.current_sample = p->current[b], f.temp_end = p->temp_end[b], f.pending = p->held[b];
+        f.active = p->active[b], f.triggered = p->triggered[b];
+        if (p->max_step) f.wide_step = p->w_step[b], f.wide_phase = p->w_phase[b];
+        std::memcpy(rec + (size_t)k * stride, &f, sizeof(f));
+    }
+    return VAD_OK;
+}
+
+int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const int32_t *records, const int32_t *streams, long n) {
+    if (!p) return VAD_ERR_ARG;
+    const std::string fn = "vad_pump_import_streams: ";
+    if (const int rc = snap_idle(p, fn)) return rc;
+    SnapHeader hd;
+    if (const char *why = snap_check(blob, nbytes, &hd)) return pfail(p, VAD_ERR_ARG, fn + "the blob is " + why);
+    if (hd.sr != p->sr) return pfail(p, VAD_ERR_SAMPLE_RATE, fn + "the blob's sample rate is not the pump's");
+    const long S = p->streams;
+    if (n < 0 || n > S || (n > 0 && !streams)) return pfail(p, VAD_ERR_ARG, fn + "bad slot list");
+    const uint8_t *rec = static_cast<const uint8_t *>(blob) + sizeof(SnapHeader);
+    const size_t stride = hd.stride;
+    auto info_of = [&](long r) {
+        vad_stream_info f;
+        std::memcpy(&f, rec + (size_t)r * stride, sizeof(f));
+        return f;
+    };
+    // everything is decided here, on the host, from values snap_check has range-checked: nothing is queued before the last check
+    const char *why = nullptr;
+    long i = 0, first = hd.n_records, last = -1;
+    for (; i < n && !why; ++i) {
+        const long r = records ? records[i] : i;
+        const int32_t b = streams[i];
+        if (r < 0 || r >= hd.n_records) why = "a record index out of range";
+        else if (b < 0 || b >= S || p->seen[b]) why = "a slot out of range, or listed twice";
+        else if (info_of(r).wide_step >= 2 && info_of(r).wide_step > p->max_step) why = "a record of a 32 / 48 kHz stream, and the pump's wideband max_step is smaller (vad_pump_set_wideband)";
+        else {
+            p->seen[b] = 1;
+            first = std::min(first, r), last = std::max(last, r);
+        }
+    }
+    for (long k = 0; k < i; ++k)                 // (only valid slots were marked)
+        if (streams[k] >= 0 && streams[k] < S) p->seen[streams[k]] = 0;
+    if (why) return pfail(p, VAD_ERR_ARG, fn + why);
+    if (n == 0) return VAD_OK;
+    const size_t bytes = (size_t)(last - first + 1) * stride;
+    if (const int rc = snap_reserve(p, bytes)) return rc;
+    for (long k = 0; k < n; ++k) {
+        const long r = records ? records[k] : k;
+        int32_t *e = p->h_snap_tab + 4 * k;
+        e[0] = streams[k], e[1] = part_of(p, streams[k]), e[2] = info_of(r).pending, e[3] = (int32_t)(r - first);
+    }
+    // ONE copy: the records first ... last; the scatter behind it on the compute stream.  From the copy on a failure leaves slots
+    // half-replaced: the pump says so from then on.
+    const hipError_t rc = [&] {
+        hipError_t e = hipMemcpyAsync(p->d_snap, rec + (size_t)first * stride, bytes, hipMemcpyHostToDevice, p->compute);
+        if (e == hipSuccess) e = vad::launch_snapshot_scatter(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute);
+        return e == hipSuccess ? hipStreamSynchronize(p->compute) : e;
+    }();
+    if (rc != hipSuccess) {
+        p->poisoned = true;
+        return pfail(p, VAD_ERR_HIP, fn + hipGetErrorString(rc));
+    }
+    for (long k = 0; k < n; ++k) {               // the host's part of the slot
+        const vad_stream_info f = info_of(records ? records[k] : k);
+        const int32_t b = streams[k];
+        p->active[b] = f.active, p->triggered[b] = f.triggered, p->temp_end[b] = f.temp_end, p->current[b] = f.current_sample;
+        p->n_held += (f.pending > 0) - (p->held[b] > 0);
+        p->held[b] = f.pending;
+        if (p->max_step) p->w_step[b] = f.wide_step, p->w_phase[b] = f.wide_phase;
+        p->src_pos[b] = 0;
+    }
     return VAD_OK;
 }
 

@@ -2018,6 +2018,45 @@ def decimate(x, step: int, phase: int = 0) -> np.ndarray:
     return out[:m]
 
 
+def _blob_bytes(blob) -> np.ndarray:
+    a = np.asarray(blob)
+    if a.dtype != np.uint8 or a.ndim != 1:
+        raise ValueError(f"a snapshot blob is a 1-D uint8 array, got {a.dtype} of shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _distinct_slots(x, name) -> np.ndarray:
+    a = _int32_rows(x, name)
+    if len(np.unique(a)) != len(a):
+        raise ValueError(f"{name} lists a slot twice")
+    return a
+
+
+def snapshot_info(blob) -> list:
+    """The records of a snapshot blob (`StreamPump.export_streams`), host only (vad_snapshot_inspect / vad_snapshot_stream): per record a
+    dict of the vad_stream_info fields (`active`, `triggered`, `temp_end`, `current_sample`, `pending`, `wide_step`, `wide_phase`) plus
+    `h` [128], `c` [128], `ctx` [C] float32 and `pending_samples` [N] int16 (zeros behind `pending`).  A blob the library refuses --
+    bad magic or version, truncated, a field out of range -- raises."""
+    a = _blob_bytes(blob)
+    L = lib()
+    n, sr = ctypes.c_long(), ctypes.c_int()
+    rc = L.vad_snapshot_inspect(a.ctypes.data if a.size else None, a.size, ctypes.byref(n), ctypes.byref(sr))
+    if rc:
+        raise _lib.VadError(rc, "vad_snapshot_inspect: not a valid snapshot blob")
+    N = chunk_size(sr.value)
+    out = []
+    for i in range(n.value):
+        f = _lib.StreamInfo()
+        h, c, x, pend = np.empty(128, np.float32), np.empty(128, np.float32), np.empty(N // 8, np.float32), np.empty(N, np.int16)
+        rc = L.vad_snapshot_stream(a.ctypes.data, a.size, i, ctypes.byref(f), h.ctypes.data, c.ctypes.data, x.ctypes.data, pend.ctypes.data)
+        if rc:
+            raise _lib.VadError(rc, "vad_snapshot_stream")
+        d = {k: int(getattr(f, k)) for k in ("active", "triggered", "temp_end", "current_sample", "pending", "wide_step", "wide_phase")}
+        d.update(h=h, c=c, ctx=x, pending_samples=pend)
+        out.append(d)
+    return out
+
+
 class StreamPump:
     """BASELINE configs[4] through the native pump (include/silero_vad_hip.h "live streams: the pump", csrc/pump.hip): `streams`
     live streams on one GPU, host int16 chunks in, VADIterator events out, with no Python and no torch on the per-tick path
@@ -2043,6 +2082,11 @@ class StreamPump:
     32 / 48 kHz clients (WebRTC, Opus decoders): after `pump.set_wideband(3)` the rows of `wide_slot(r)` +
     `submit_wide_packets(r, streams, lengths, steps)` are int16 samples at steps[i] x 16 kHz, and the device keeps every steps[i]-th one
     (the reference's `x[::step]`); the pump carries each stream's comb phase (`wide_phase(stream)`), events count 16 kHz samples.
+
+    Moving live streams (a drain, a rebalancing between per-GPU ranks, a restart): with no tick in flight `blob = pump.export_streams([3, 7])`
+    packs everything those streams carry into one uint8 array, `other.import_streams(blob, [0, 5])` puts the records into slots of any
+    pump of the same sample rate (another GPU, another process), and `snapshot_info(blob)` reads a blob without a pump; the streams go
+    on bit for bit.
 
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
@@ -2405,6 +2449,31 @@ class StreamPump:
         h, c, x = np.empty(128, np.float32), np.empty(128, np.float32), np.empty(self.n // 8, np.float32)
         self._check(self._L.vad_pump_state(self._h, int(stream), h.ctypes.data, c.ctypes.data, x.ctypes.data))
         return h, c, x
+
+    def export_streams(self, streams=None) -> np.ndarray:
+        """Everything `streams` (distinct slots; None = every slot, ascending) carry, as one self-describing uint8 blob
+        (vad_pump_export_streams; layout: include/silero_vad_hip.h): (h, c), the context the next tick reads, the pending samples, the
+        comb step and phase, the iterator state and the open / closed flag.  Only with no tick in flight (poll them first).  Read-only:
+        the pump and the streams go on as if nothing had happened."""
+        st = None if streams is None else _distinct_slots(streams, "streams")
+        n = self.streams if st is None else len(st)
+        blob = np.zeros(int(self._L.vad_pump_snapshot_bytes(self.sr, n)), np.uint8)
+        self._check(self._L.vad_pump_export_streams(self._h, st.ctypes.data if st is not None and n else None, n, blob.ctypes.data, blob.size))
+        return blob
+
+    def import_streams(self, blob, slots, records=None):
+        """Record records[i] of `blob` (None = record i) replaces the whole carried state of slot slots[i] (vad_pump_import_streams); the
+        stream continues bit for bit if this pump has the iterator parameters of the pump that wrote the blob.  Only with no tick in
+        flight.  A blob of another sample rate, a malformed blob, a bad record index or slot, or a 32 / 48 kHz stream for a pump without
+        that wideband step raises, and nothing has changed."""
+        a = _blob_bytes(blob)
+        sl = _distinct_slots(slots, "slots")
+        rc = None if records is None else _int32_rows(records, "records")
+        if rc is not None and len(rc) != len(sl):
+            raise ValueError(f"slots and records must have one entry per stream, got {len(sl)} and {len(rc)}")
+        n = len(sl)
+        self._check(self._L.vad_pump_import_streams(self._h, a.ctypes.data if a.size else None, a.size, rc.ctypes.data if rc is not None and n else None,
+                                                    sl.ctypes.data if n else None, n))
 
     def play(self, rows: np.ndarray, n_ticks: int, first_tick: int = 0, depth: int = 2, fill_threads: int = 0, max_events: int = 0,
              pattern: np.ndarray = None, compact: bool = False):
