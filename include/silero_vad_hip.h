@@ -63,7 +63,7 @@ void vad_destroy(vad_engine *e);
  * (tests/test_concurrency.py).  What the engine does not arrange: a hipGraph capture is a process-wide state of the runtime --
  * while one thread captures (global capture mode), allocating calls of other threads (vad_create / vad_clone / vad_pump_create, a
  * scratch growth) fail; capture while the other threads make no such call.
- * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed, vad_g711_expand and vad_decimate are re-entrant (no shared state);
+ * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed, vad_g711_expand, vad_deinterleave and vad_decimate are re-entrant (no shared state);
  * vad_stage_rows and vad_segment_probs_batch serialise themselves on the process-wide helper pool (tests/test_host_concurrency.py). */
 int  vad_clone(const vad_engine *e, vad_engine **out);
 const char *vad_strerror(int status);
@@ -633,6 +633,27 @@ int  vad_upload_rows(vad_engine *e, const void *const *rows, const long *lens, l
  * null row with a length, a misaligned dst or pitch, an S16 row at an odd address.                                            */
 int  vad_upload_rows_coded(vad_engine *e, const void *const *rows, const long *lens, const uint8_t *codec_of_row, long n, long width,
                            void *dst_i16, int how, void *stream);
+/* vad_upload_rows_coded for recordings that are still INTERLEAVED -- a recorded call is one file with the agent on the left channel and
+ * the customer on the right, frame by frame, G.711 or 16-bit PCM: the data chunk stays as it lies on disk in page-locked memory
+ * (how = 1) or crosses the link in one large DMA of its arena (how = 2), once, and the gather kernel writes one batch row per wanted
+ * channel.  Source i is frames[i] frames of channels_of_row[i] (1 ... VAD_MAX_CHANNELS; NULL = every source has 1) samples each in
+ * format codec_of_row[i] (NULL = every source is S16) at rows[i]: any byte address for G.711, any EVEN address for S16 (a stereo frame
+ * may sit at 2 mod 4).  dst_row[VAD_MAX_CHANNELS * i + c] is the row of dst = DEVICE int16 [n_dst][width] (16-byte aligned, width a
+ * multiple of 8; frames and width in FRAMES = samples of one channel) that channel c goes to, or -1 for a channel nobody wants.  That
+ * row becomes vad_deinterleave(codec_i, channels_i, c, rows[i], frames[i]) followed by int16 zeros to `width`, bit for bit; rows of dst
+ * that no entry names are not touched.  With every source at one channel and dst_row[2 i] = i the batch is that of
+ * vad_upload_rows_coded.  how = 1 or 2 as in vad_upload_rows.
+ * No engine: VAD_ERR_ARG; a host-only engine: VAD_ERR_NO_DEVICE, before the rows are looked at.  VAD_ERR_ARG, with nothing queued and
+ * the batch untouched: how = 0 (a DMA neither expands nor splits), a codec above VAD_PCM_ALAW, a channel count outside
+ * 1 ... VAD_MAX_CHANNELS, a dst_row entry below -1 or >= n_dst, a batch row named twice, an entry other than -1 for a channel the
+ * source does not have, frames[i] > width, a null row with a length, an S16 source at an odd address, a misaligned dst or pitch.   */
+#define VAD_MAX_CHANNELS 2
+int  vad_upload_rows_channels(vad_engine *e, const void *const *rows, const long *frames, const uint8_t *codec_of_row,
+                              const uint8_t *channels_of_row, const int32_t *dst_row /* [n][VAD_MAX_CHANNELS] */,
+                              long n, long n_dst, long width, void *dst_i16, int how, void *stream);
+/* host twin, re-entrant: channel `channel` of `frames` interleaved frames -> out[0 .. frames) int16 (G.711 expanded: the values of
+ * vad_g711_expand); returns frames, or -VAD_ERR_ARG (bad codec, channels not 1 .. VAD_MAX_CHANNELS, channel out of range, frames < 0, NULL with frames > 0) */
+long vad_deinterleave(int codec, int channels, int channel, const void *in, long frames, int16_t *out);
 /* Page-lock / unlock a host range so that it can be a vad_upload_rows source (hipHostRegister; a decoder's output
  * buffers, a memory-mapped corpus shard).  Process-wide.                                                              */
 int  vad_host_register(void *p, size_t bytes);

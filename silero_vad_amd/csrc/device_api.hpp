@@ -210,6 +210,19 @@ hipError_t launch_gather_rows(const RowDesc *rows, long n, long width, int esz, 
 // g711_to_s16 on the way); dst[i][0 .. width) int16, zero padded behind the row's last sample; width a multiple of 8.
 constexpr int kRowCodecShift = 56;
 hipError_t launch_gather_expand_rows(const RowDesc *rows, long n, long width, void *dst_i16, bool rows_on_device, hipStream_t s);
+// The same over SOURCES of one or two interleaved channels (vad_upload_rows_channels): src[i].tag = frames | channels << kRowChanShift
+// | codec << kRowCodecShift; channel c of source i becomes batch row src[i].dst[c] of dst[n_dst][width] (-1: not wanted), de-interleaved,
+// expanded if G.711 and zero padded behind its last frame; batch rows nobody names are not written.  frame_bytes: the most bytes a frame
+// of any source of the table has (1 ... 4), which sizes the launch.
+constexpr int kRowChanShift = 48;
+struct ChanRowDesc {
+    const void *ptr;
+    long tag;
+    int32_t dst[2];
+    int32_t pad[2];                  // 32 bytes: an entry never straddles a 64-byte line of the pinned table
+};
+hipError_t launch_gather_channels(const ChanRowDesc *src, long n, long width, int frame_bytes, void *dst_i16, bool rows_on_device,
+                                  hipStream_t s);
 
 // Segmenter on the device (kernel_scan.hip): lane i scans probs[i * ldp ...] (or probs[row_off[i] ...] if row_off is
 // not null), n_chunks[i] entries (or n_chunks_all if n_chunks is null), writes its segments to out[i * cap ...] and

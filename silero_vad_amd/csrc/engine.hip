@@ -1059,9 +1059,12 @@ const void *device_view(const void *p) {
 // The row table of a gather launch (vad_upload_rows / vad_upload_rows_coded, how = 1 or 2): the next pinned slot of the ring -- the kernel
 // reads it itself; a slot is reused once its kernel is done -- filled with every row's DEVICE address and len_tag(i); row i is
 // row_bytes(i) bytes long.  Returns a status; *slot_out is the slot (the caller launches, records tab_ev[slot] and sets tab_busy).
-extern "C++" template <typename Bytes, typename Tag>
-int fill_row_table(vad_engine *e, const void *const *rows, const long *lens, long n, int how, const char *who, Bytes row_bytes,
-                          Tag len_tag, int *slot_out) {
+// Desc: the kernel's table entry -- vad::RowDesc, or vad::ChanRowDesc (vad_upload_rows_channels: the same ring, the slots' capacity
+// counts RowDesc units) -- which entry(i, device address) makes.
+extern "C++" template <typename Desc, typename Bytes, typename Entry>
+int fill_table(vad_engine *e, const void *const *rows, const long *lens, long n_desc, int how, const char *who, Bytes row_bytes,
+               Entry entry, int *slot_out) {
+    const long n = (long)(((size_t)n_desc * sizeof(Desc) + sizeof(vad::RowDesc) - 1) / sizeof(vad::RowDesc));   // RowDesc units
     const int slot = e->tab_next;
     e->tab_next = (slot + 1) % vad_engine::kTabSlots;
     if (e->tab_busy[slot]) {
@@ -1081,8 +1084,9 @@ int fill_row_table(vad_engine *e, const void *const *rows, const long *lens, lon
         e->tab_cap[slot] = cap;
     }
     if (!e->tab_ev[slot]) HIP_TRY(e, hipEventCreateWithFlags(&e->tab_ev[slot], hipEventDisableTiming));
+    Desc *tab = reinterpret_cast<Desc *>(e->h_tab[slot]);
     if (how == 2) {                                    // rows[] are device addresses already
-        for (long i = 0; i < n; ++i) e->h_tab[slot][i] = vad::RowDesc{lens[i] ? rows[i] : nullptr, len_tag(i)};
+        for (long i = 0; i < n_desc; ++i) tab[i] = entry(i, lens[i] ? rows[i] : nullptr);
     } else {
         // Resolving a host address costs a runtime call (~1 us): thousands of short rows per slab, 92 slabs per 100 h of audio, made the
         // refill route's upload call 190 ms of its 245.  The rows of a corpus lie in a few page-locked allocations, and inside ONE
@@ -1090,7 +1094,7 @@ int fill_row_table(vad_engine *e, const void *const *rows, const long *lens, lon
         // extent from hipMemGetAddressRange on the device view) and the rows that fall inside it are translated by arithmetic.
         const uint8_t *c_host = nullptr, *c_dev = nullptr;       // [c_host, c_host + c_bytes) -> c_dev + offset
         size_t c_bytes = 0;
-        for (long i = 0; i < n; ++i) {
+        for (long i = 0; i < n_desc; ++i) {
             const void *dv = nullptr;
             if (lens[i]) {
                 const uint8_t *hp = static_cast<const uint8_t *>(rows[i]);
@@ -1116,11 +1120,18 @@ int fill_row_table(vad_engine *e, const void *const *rows, const long *lens, lon
                     }
                 }
             }
-            e->h_tab[slot][i] = vad::RowDesc{dv, len_tag(i)};
+            tab[i] = entry(i, dv);
         }
     }
     *slot_out = slot;
     return VAD_OK;
+}
+
+extern "C++" template <typename Bytes, typename Tag>
+int fill_row_table(vad_engine *e, const void *const *rows, const long *lens, long n, int how, const char *who, Bytes row_bytes,
+                   Tag len_tag, int *slot_out) {
+    return fill_table<vad::RowDesc>(e, rows, lens, n, how, who, row_bytes,
+                                    [&](long i, const void *dv) { return vad::RowDesc{dv, len_tag(i)}; }, slot_out);
 }
 }  // namespace
 
@@ -1247,6 +1258,55 @@ int vad_upload_rows_coded(vad_engine *e, const void *const *rows, const long *le
                                 [&](long i) { return lens[i] | (long)codec_of_row[i] << vad::kRowCodecShift; }, &slot))
         return rc;
     HIP_TRY(e, vad::launch_gather_expand_rows(e->h_tab[slot], n, width, dst, how == 2, stream));
+    HIP_TRY(e, hipEventRecord(e->tab_ev[slot], stream));
+    e->tab_busy[slot] = true;
+    return VAD_OK;
+}
+
+int vad_upload_rows_channels(vad_engine *e, const void *const *rows, const long *frames, const uint8_t *codec_of_row,
+                             const uint8_t *channels_of_row, const int32_t *dst_row, long n, long n_dst, long width, void *dst,
+                             int how, void *stream_v) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (n < 0 || n_dst < 0 || width < 0 || how < 0 || how > 2) return fail(e, VAD_ERR_ARG, "bad argument");
+    if (how == 0)
+        return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: the copy engines (how = 0) are not a route: a DMA neither expands nor splits");
+    if (n == 0 || width == 0) return VAD_OK;
+    if (!rows || !frames || !dst_row || !dst) return fail(e, VAD_ERR_ARG, "null pointer");
+    if (((size_t)dst & 15) || (width * 2) % 16) return fail(e, VAD_ERR_ARG, "dst and its row pitch must be 16-byte aligned");
+    if (n_dst > 0x7fffffffL) return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: too many batch rows");
+    std::vector<uint8_t> named((size_t)n_dst, 0);
+    int frame_bytes = 1;
+    for (long i = 0; i < n; ++i) {
+        const int c = codec_of_row ? codec_of_row[i] : VAD_PCM_S16, ch = channels_of_row ? channels_of_row[i] : 1;
+        if (c > VAD_PCM_ALAW) return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: unknown codec");
+        if (ch < 1 || ch > VAD_MAX_CHANNELS) return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: a source has 1 or 2 channels");
+        if (frames[i] < 0 || frames[i] > width || (frames[i] > 0 && !rows[i])) return fail(e, VAD_ERR_ARG, "bad row");
+        if (c == VAD_PCM_S16 && frames[i] > 0 && ((size_t)rows[i] & 1)) return fail(e, VAD_ERR_ARG, "an int16 row at an odd address");
+        for (int k = 0; k < VAD_MAX_CHANNELS; ++k) {
+            const long r = dst_row[i * VAD_MAX_CHANNELS + k];
+            if (r == -1) continue;
+            if (r < -1 || r >= n_dst) return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: a batch row out of range");
+            if (k >= ch) return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: a batch row for a channel the source does not have");
+            if (named[(size_t)r]) return fail(e, VAD_ERR_ARG, "vad_upload_rows_channels: a batch row named twice");
+            named[(size_t)r] = 1;
+        }
+        frame_bytes = std::max(frame_bytes, ch * (c == VAD_PCM_S16 ? 2 : 1));
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(e, hipSetDevice(e->device));
+    auto bytes_of = [&](long i) {
+        return (size_t)frames[i] * (channels_of_row ? channels_of_row[i] : 1) * ((codec_of_row ? codec_of_row[i] : VAD_PCM_S16) == VAD_PCM_S16 ? 2 : 1);
+    };
+    int slot = 0;
+    if (int rc = fill_table<vad::ChanRowDesc>(e, rows, frames, n, how, "vad_upload_rows_channels", bytes_of,
+                                              [&](long i, const void *dv) {
+                                                  const long c = codec_of_row ? codec_of_row[i] : VAD_PCM_S16, ch = channels_of_row ? channels_of_row[i] : 1;
+                                                  return vad::ChanRowDesc{dv, frames[i] | ch << vad::kRowChanShift | c << vad::kRowCodecShift,
+                                                                          {dst_row[2 * i], dst_row[2 * i + 1]}, {0, 0}};
+                                              }, &slot))
+        return rc;
+    HIP_TRY(e, vad::launch_gather_channels(reinterpret_cast<const vad::ChanRowDesc *>(e->h_tab[slot]), n, width, frame_bytes, dst, how == 2, stream));
     HIP_TRY(e, hipEventRecord(e->tab_ev[slot], stream));
     e->tab_busy[slot] = true;
     return VAD_OK;

@@ -171,10 +171,64 @@ __device__ __forceinline__ void put_vector(u32x4 x, uint8_t *d, long p, long kee
     }
 }
 
+// The 16 source bytes x of one lane, whole interleaved STEREO frames (source position p is a multiple of 16, a frame is 4 or 2 bytes)
+// -> the two batch rows d0 (channel 0) and d1 (channel 1); a null row is a channel nobody wants.  keep as in put_vector: source bytes
+// of x that belong to the recording, a whole number of frames; the samples behind them leave as int16 zeros (zeroed after the expansion).
+// Every lane of the wave executes this (the S16 form trades halves with the neighbour lane); `on`: this lane's vector lies inside the
+// row and is stored.
+//   * G.711: 8 frames.  v_perm_b32 picks the even bytes (channel 0) and the odd ones (channel 1) of two dwords at a time; 8 codes of a
+//     channel expand to 16 bytes: ONE 16-byte store per channel and lane, at byte p of the channel's row.
+//   * S16: 4 frames = 8 bytes a channel.  v_perm_b32 picks the low halfwords (channel 0) and the high ones (channel 1); lanes 2 i and
+//     2 i + 1 hold the 8 consecutive frames at p, so the even lane hands its channel-1 half to the odd one and takes the odd one's
+//     channel-0 half (two DPP / bpermute moves): the even lane stores 16 bytes of channel 0, the odd lane 16 bytes of channel 1.
+template <int CODEC, bool NT>
+__device__ __forceinline__ void put_stereo(u32x4 x, uint8_t *d0, uint8_t *d1, long p, long keep, bool on, int lane) {
+    auto store = [](u32x4 v, uint8_t *at) {
+        if (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(at));
+        else *reinterpret_cast<u32x4 *>(at) = v;
+    };
+    if (CODEC == 0) {
+        constexpr unsigned kLo = 0x05040100u, kHi = 0x07060302u;          // halfwords 0, 2 / 1, 3 of the 8 bytes {S0 : S1}
+        unsigned l0 = __builtin_amdgcn_perm(x.y, x.x, kLo), l1 = __builtin_amdgcn_perm(x.w, x.z, kLo);
+        unsigned r0 = __builtin_amdgcn_perm(x.y, x.x, kHi), r1 = __builtin_amdgcn_perm(x.w, x.z, kHi);
+        if (keep < 16) {
+            const long f = keep >> 2;                                    // frames of x that exist
+            const unsigned m0 = f >= 2 ? ~0u : f == 1 ? 0xffffu : 0u, m1 = f >= 4 ? ~0u : f == 3 ? 0xffffu : 0u;
+            l0 &= m0, r0 &= m0, l1 &= m1, r1 &= m1;
+        }
+        const bool odd = lane & 1;
+        const unsigned g0 = __shfl_xor(odd ? l0 : r0, 1), g1 = __shfl_xor(odd ? l1 : r1, 1);
+        uint8_t *d = odd ? d1 : d0;
+        if (on && d) store(odd ? u32x4{g0, g1, r0, r1} : u32x4{l0, l1, g0, g1}, d + ((odd ? p - 16 : p) >> 1));
+    } else {
+        constexpr unsigned kEven = 0x06040200u, kOdd = 0x07050301u;      // bytes 0, 2, 4, 6 / 1, 3, 5, 7 of the 8 bytes {S0 : S1}
+        unsigned o[8];
+        expand4<CODEC>(__builtin_amdgcn_perm(x.y, x.x, kEven), o[0], o[1]);
+        expand4<CODEC>(__builtin_amdgcn_perm(x.w, x.z, kEven), o[2], o[3]);
+        expand4<CODEC>(__builtin_amdgcn_perm(x.y, x.x, kOdd), o[4], o[5]);
+        expand4<CODEC>(__builtin_amdgcn_perm(x.w, x.z, kOdd), o[6], o[7]);
+        if (keep < 16) {
+            const long f = keep >> 1;                                    // frames of x that exist
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long k = f - 2 * j;
+                const unsigned mk = k >= 2 ? ~0u : k == 1 ? 0xffffu : 0u;
+                o[j] &= mk, o[4 + j] &= mk;
+            }
+        }
+        if (on && d0) store(u32x4{o[0], o[1], o[2], o[3]}, d0 + p);
+        if (on && d1) store(u32x4{o[4], o[5], o[6], o[7]}, d1 + p);
+    }
+}
+
 // One (row, segment) item.  A: the aligned granule that holds the row's first byte, m: the first byte's place in it, live: source bytes
 // of the row, wsb: source bytes of a full batch row (a multiple of 16 for a copy, of 8 for G.711), d: the batch row.
-template <int CODEC>
-__device__ __forceinline__ void move_segment(const uint8_t *A, int m, long live, long wsb, uint8_t *d, long lo, int lane) {
+// CH = 2 (gather_channels_kernel): the source is interleaved stereo -- live and wsb count its bytes, 2 x those of a channel, so wsb is a
+// multiple of 16 whatever the codec; the loads and the shuffle are the same, every vector leaves through put_stereo into d (channel 0)
+// and d1 (channel 1).
+template <int CODEC, int CH = 1>
+__device__ __forceinline__ void move_segment(const uint8_t *A, int m, long live, long wsb, uint8_t *d, long lo, int lane,
+                                             uint8_t *d1 = nullptr) {
     if (lo >= wsb) return;                                     // (a G.711 row has half the segments of an S16 row of its width)
     const u32x4 zero{0u, 0u, 0u, 0u};
     if (lo + kSegBytes <= live) {
@@ -190,7 +244,10 @@ __device__ __forceinline__ void move_segment(const uint8_t *A, int m, long live,
             for (int k = 0; k < 8; ++k) v[k] = shift_bytes(v[k], next_lane(v[k], lane0_of(k < 7 ? v[k + 1] : extra), lane), m);
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) put_vector<CODEC, true>(v[k], d, lo + (k * 64 + lane) * 16L, 16, 16);
+        for (int k = 0; k < 8; ++k) {
+            if (CH == 1) put_vector<CODEC, true>(v[k], d, lo + (k * 64 + lane) * 16L, 16, 16);
+            else put_stereo<CODEC, true>(v[k], d, d1, lo + (k * 64 + lane) * 16L, 16, true, lane);
+        }
         return;
     }
     // the segment with the recording's end and / or the padding: one wave-load at a time.  Granule p is read iff it holds a byte of the
@@ -208,7 +265,11 @@ __device__ __forceinline__ void move_segment(const uint8_t *A, int m, long live,
             if (lane == 63 && p < hi && p + 16 < end) n = *reinterpret_cast<const u32x4 *>(A + p + 16);
             c = shift_bytes(c, next_lane(c, n, lane), m);
         }
-        if (p < hi) put_vector<CODEC, false>(c, d, p, live - p, hi - p);
+        if (CH == 1) {
+            if (p < hi) put_vector<CODEC, false>(c, d, p, live - p, hi - p);
+        } else {
+            put_stereo<CODEC, false>(c, d, d1, p, live - p, p < hi, lane);     // (hi is a multiple of 32: a lane pair is inside or outside)
+        }
     }
 }
 
@@ -226,6 +287,49 @@ __global__ void __launch_bounds__(64) gather_expand_rows_kernel(const RowDesc *r
         if (codec == VAD_PCM_S16) move_segment<0>(A, m, len * 2, width * 2, d, lo, lane);
         else if (codec == VAD_PCM_ULAW) move_segment<VAD_PCM_ULAW>(A, m, len, width, d, lo, lane);
         else move_segment<VAD_PCM_ALAW>(A, m, len, width, d, lo, lane);
+    }
+}
+
+// ---- interleaved stereo recordings: gather, expand AND split -------------------------------------------------------------
+// The same gather over a table of SOURCES (vad_upload_rows_channels): a source is a recorded call as its WAV data chunk holds it, one
+// or two channels interleaved frame by frame, S16 at any even address (a stereo frame may sit at 2 mod 4) or G.711 at any byte address,
+// and every wanted channel leaves as one row of the int16 batch: src[i].dst[c] is the batch row of channel c, -1 a channel nobody
+// wants.  The source crosses the link once, as it lies on disk; the de-interleaving that the host would otherwise do -- a strided byte
+// pass over the whole corpus -- happens in the lanes' registers between the shuffle and the stores (put_stereo).  src[i].tag = frames |
+// channels << kRowChanShift | codec << kRowCodecShift, all wave-uniform per source.
+//   * a one-channel source is move_segment as gather_expand_rows_kernel calls it: the same loads, the same stores, the same bits;
+//   * a two-channel source takes the same aligned granule loads and the same neighbour-lane shuffle on its interleaved bytes -- 16
+//     source bytes at a multiple of 16 behind the first frame are whole frames -- and a segment is 8 KiB of SOURCE: 2 048 frames of
+//     stereo S16, 4 096 of stereo G.711;
+//   * the items are sized for the widest source of the table (frame_bytes: 4 for stereo S16); narrower ones leave their spare items
+//     at once, as a G.711 row does in gather_expand_rows_kernel;
+//   * footprint as above.  No LDS; 95 VGPRs, one more than gather_expand_rows_kernel (the whole-segment path holds its 8 vectors and the
+//     granule behind them; a lane splits one vector at a time).
+constexpr long kChanLenMask = (1L << kRowChanShift) - 1;
+
+__global__ void __launch_bounds__(64) gather_channels_kernel(const ChanRowDesc *src, long n, long width, uint8_t *dst, long segs_per_row) {
+    const long items = n * segs_per_row;
+    const int lane = threadIdx.x;
+    __builtin_amdgcn_s_setprio(3);          // as in gather_rows_kernel
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+        const long row = item / segs_per_row, lo = (item % segs_per_row) * kSegBytes;
+        const size_t s = (size_t)src[row].ptr;
+        const long tag = src[row].tag, frames = tag & kChanLenMask;
+        const int codec = (int)(tag >> kRowCodecShift), ch = (int)(tag >> kRowChanShift) & 0xff, m = (int)(s & 15);
+        const int r0 = src[row].dst[0], r1 = src[row].dst[1];
+        const uint8_t *A = reinterpret_cast<const uint8_t *>(s - m);
+        uint8_t *d0 = r0 >= 0 ? dst + r0 * width * 2 : nullptr, *d1 = r1 >= 0 ? dst + r1 * width * 2 : nullptr;
+        if (ch == 1) {
+            if (!d0) continue;
+            if (codec == VAD_PCM_S16) move_segment<0>(A, m, frames * 2, width * 2, d0, lo, lane);
+            else if (codec == VAD_PCM_ULAW) move_segment<VAD_PCM_ULAW>(A, m, frames, width, d0, lo, lane);
+            else move_segment<VAD_PCM_ALAW>(A, m, frames, width, d0, lo, lane);
+        } else {
+            if (!d0 && !d1) continue;
+            if (codec == VAD_PCM_S16) move_segment<0, 2>(A, m, frames * 4, width * 4, d0, lo, lane, d1);
+            else if (codec == VAD_PCM_ULAW) move_segment<VAD_PCM_ULAW, 2>(A, m, frames * 2, width * 2, d0, lo, lane, d1);
+            else move_segment<VAD_PCM_ALAW, 2>(A, m, frames * 2, width * 2, d0, lo, lane, d1);
+        }
     }
 }
 
@@ -255,6 +359,18 @@ hipError_t launch_gather_expand_rows(const RowDesc *rows, long n, long width, vo
     const long waves = rows_on_device ? 4096 : kGatherWaves;      // (as launch_gather_rows)
     const unsigned grid = (unsigned)(items < waves ? items : waves);
     hipLaunchKernelGGL(gather_expand_rows_kernel, dim3(grid), dim3(64), 0, s, rows, n, width, static_cast<uint8_t *>(dst_i16), segs);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_channels(const ChanRowDesc *src, long n, long width, int frame_bytes, void *dst_i16, bool rows_on_device,
+                                  hipStream_t s) {
+    if (n <= 0 || width <= 0) return hipSuccess;
+    const long segs = (width * frame_bytes + kSegBytes - 1) / kSegBytes;      // (of the table's widest kind of source)
+    const long items = n * segs;
+    if (items > 0x7fffffffL) return hipErrorInvalidValue;
+    const long waves = rows_on_device ? 4096 : kGatherWaves;      // (as launch_gather_rows)
+    const unsigned grid = (unsigned)(items < waves ? items : waves);
+    hipLaunchKernelGGL(gather_channels_kernel, dim3(grid), dim3(64), 0, s, src, n, width, static_cast<uint8_t *>(dst_i16), segs);
     return hipGetLastError();
 }
 

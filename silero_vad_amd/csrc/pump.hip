@@ -970,6 +970,20 @@ int vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out) {
     return VAD_OK;
 }
 
+long vad_deinterleave(int codec, int channels, int channel, const void *in, long frames, int16_t *out) {
+    if (codec < VAD_PCM_S16 || codec > VAD_PCM_ALAW || channels < 1 || channels > VAD_MAX_CHANNELS || channel < 0 || channel >= channels ||
+        frames < 0 || (frames > 0 && (!in || !out)))
+        return -VAD_ERR_ARG;
+    if (codec == VAD_PCM_S16) {
+        const uint8_t *b = static_cast<const uint8_t *>(in) + 2 * channel;       // (any even address: read bytewise)
+        for (long i = 0; i < frames; ++i) std::memcpy(out + i, b + (size_t)i * 2 * channels, 2);
+    } else {
+        const uint8_t *b = static_cast<const uint8_t *>(in) + channel;
+        for (long i = 0; i < frames; ++i) out[i] = vad::g711_to_s16(codec, b[(size_t)i * channels]);
+    }
+    return frames;
+}
+
 long vad_pump_pending(const vad_pump *p, int stream) {
     if (!p || stream < 0 || stream >= p->streams) return -1;
     return p->held[stream];

@@ -201,6 +201,17 @@ class Engine:
         cp = None if codecs is None else codecs.ctypes.data
         self._check(self._L.vad_upload_rows_coded(self._h, rows, lens, cp, n, width, dst.data_ptr(), how, self._stream()))
 
+    def upload_rows_channels(self, rows, frames, codecs, channels, dst_row, n, n_dst, width, dst, how=1):
+        """`upload_rows_coded` for sources that are still INTERLEAVED (vad_upload_rows_channels): source i is frames[i] frames of
+        channels[i] (1 or 2; uint8 numpy array, None: all 1) samples each, int16 or G.711 (codecs as in upload_rows_coded), and its
+        channel c becomes row dst_row[i, c] (int32 numpy array [n, 2]; -1: not wanted) of dst, the int16 [n_dst, width] device batch --
+        de-interleaved, expanded and zero padded on the device; rows nobody names are not touched.  frames / width in frames.
+        how 1: pinned host sources, 2: device addresses."""
+        cp = None if codecs is None else codecs.ctypes.data
+        hp = None if channels is None else channels.ctypes.data
+        self._check(self._L.vad_upload_rows_channels(self._h, rows, frames, cp, hp, dst_row.ctypes.data, n, n_dst, width, dst.data_ptr(), how,
+                                                     self._stream()))
+
     def streams_overlap(self, a, b) -> bool:
         """vad_streams_overlap: do kernels on torch streams a and b run beside each other (distinct hardware queues)?"""
         rc = self._L.vad_streams_overlap(self._h, a.cuda_stream, b.cuda_stream)

@@ -58,7 +58,7 @@ def gather_to_rank0(obj, group=None):
 
 def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate: int = 16000,
                             rank: int = 0, world_size: int = 1, balance: str = "duration",
-                            scheduler: str = "buckets", codec=None, **kwargs) -> List[list]:
+                            scheduler: str = "buckets", codec=None, channels=None, **kwargs) -> List[list]:
     """`get_speech_timestamps` over many recordings (the reference's pattern is one worker process
     per file, examples/parallel_example.ipynb cells 5, 7): this rank processes its shard --
     `balance="duration"` (default) deals recordings out by total audio length, `"count"` by contiguous
@@ -67,10 +67,13 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
     `streams.refill_speech_segments`), both scanned on the GPU -- and rank 0 receives every result in
     input order (other ranks get None).  kwargs are those of get_speech_timestamps.  `codec` ("ulaw" / "alaw", or one per
     recording): the recordings are uint8 G.711 codes; they go to the scheduler as they are (one byte a sample over the link, expanded on
-    the device) and the result is that of the `g711_expand`ed recordings."""
+    the device) and the result is that of the `g711_expand`ed recordings.  `channels` (1 or 2, or one per recording): the recordings
+    are interleaved int16 samples or G.711 codes, as a WAV data chunk holds a recorded call; a recording goes to one rank whole, is
+    split on the device, and the result has one entry per (recording, channel), recording-major (`streams.channel_rows`): that of the
+    call on the `deinterleave`d recordings."""
     import warnings
 
-    from .streams import _codec_of, g711_expand, ragged_speech_segments, refill_speech_segments
+    from .streams import _Fanned, _channels_of, _codec_of, deinterleave, g711_expand, ragged_speech_segments, refill_speech_segments
     from .timestamps import get_speech_timestamps
 
     if balance not in ("duration", "count") or scheduler not in ("buckets", "refill"):
@@ -80,6 +83,11 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
     else:
         mine = list(shard_range(len(audios), world_size, rank))
     cd = _codec_of(audios, codec)                          # (uint8 without a codec, uint8 among int16 / float: refused here)
+    ch = _channels_of(audios, channels)                    # (None: every recording is mono)
+    if ch is not None:
+        _Fanned(audios, ch, cd)                            # (float recordings, an odd length: refused here)
+    n_ch = np.ones(len(audios), dtype=np.int64) if ch is None else ch
+    row0 = np.concatenate([[0], np.cumsum(n_ch)]).astype(np.int64)      # recording i owns results row0[i] ... row0[i + 1] - 1
     results = {}
     scan_kw = {k: kwargs[k] for k in kwargs if k not in ("return_seconds", "time_resolution",
                                                          "visualize_probs", "progress_tracking_callback",
@@ -88,6 +96,11 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
     if fast is None or kwargs.get("visualize_probs") or kwargs.get("progress_tracking_callback"):
         for i in mine:
             a = audios[i]                                  # (a list's entry, or a PackedRecordings' view of its arena)
+            if ch is not None:                             # interleaved: split (and expanded) here, one channel at a time
+                for c in range(int(n_ch[i])):
+                    x = torch.from_numpy(deinterleave(np.ascontiguousarray(a), int(n_ch[i]), c, None if cd is None else int(cd[i])))
+                    results[int(row0[i]) + c] = get_speech_timestamps(x, model, sampling_rate=sampling_rate, **kwargs)
+                continue
             if cd is not None:                             # G.711 codes: expanded here, the per-recording path has no device batch
                 a = torch.from_numpy(g711_expand(np.ascontiguousarray(a), int(cd[i])))
             results[i] = get_speech_timestamps(a, model, sampling_rate=sampling_rate, **kwargs)
@@ -106,11 +119,13 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
         # recordings are read by the DMA / the gather kernel where they lie) and the frontend's loads take every step-th sample
         # (streams._rates) -- the reference's x[::step] (utils_vad.py:301-307) without the copy.  Segments come back in samples of
         # the 16 kHz signal, like the reference's before its final `* step`.
-        lens = [(int(a.shape[0]) + step - 1) // step for a in local]
+        flat = [(i, c) for i in mine for c in range(int(n_ch[i]))]      # the scheduler's results: one per (recording, channel)
+        lens = [(int(local[r].shape[0]) // int(n_ch[i]) + step - 1) // step for r, i in enumerate(mine) for _ in range(int(n_ch[i]))]
         segs = (ragged_speech_segments if scheduler == "buckets" else refill_speech_segments)(
-            local, model, sampling_rate, codec=None if cd is None else cd[mine], **scan_kw)
+            local, model, sampling_rate, codec=None if cd is None else cd[mine], channels=None if ch is None else ch[mine], **scan_kw)
         seconds, res = kwargs.get("return_seconds", False), kwargs.get("time_resolution", 1)
-        for r, i in enumerate(mine):
+        for r, (rec_i, c) in enumerate(flat):
+            i = int(row0[rec_i]) + c
             out = segs[r]
             if seconds:                                    # utils_vad.py:442-446
                 total = lens[r] / sr
@@ -128,4 +143,4 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
     merged = {}
     for part in gathered:
         merged.update(part)
-    return [merged[i] for i in range(len(audios))]
+    return [merged[i] for i in range(int(row0[-1]))]

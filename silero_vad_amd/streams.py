@@ -58,7 +58,7 @@ def _rates(sr: int):
 
 
 # ---- offline: ragged corpora ------------------------------------------------------------------------
-def _bucket_cuts(L: np.ndarray, max_waste: float, max_bytes: int, itemsize: int):
+def _bucket_cuts(L: np.ndarray, max_waste: float, max_bytes: int, itemsize: int, mate=None):
     """The greedy bucketing of RaggedPlan on arrays: -> (order, cuts) with order = the non-empty recordings by descending length (ties in
     index order) and bucket k = order[cuts[k] : cuts[k + 1]].  A bucket takes recordings while the zero padding to its first (longest)
     member wastes at most max_waste of its samples and its padded size stays within max_bytes; the waste grows with every (shorter)
@@ -84,6 +84,10 @@ def _bucket_cuts(L: np.ndarray, max_waste: float, max_bytes: int, itemsize: int)
                 break
             k0 += blk
             blk *= 2
+        # mate[i]: entry i + 1 is the other channel of entry i's recording (equal lengths: neighbours after the sort).  A bucket does not
+        # end between them -- the pair opens the next one -- so that one source of the upload serves both rows.
+        if mate is not None and cnt > 1 and s + cnt < n and mate[order[s + cnt - 1]] and order[s + cnt] == order[s + cnt - 1] + 1:
+            cnt -= 1
         s += cnt
         cuts.append(s)
     return order, cuts
@@ -97,11 +101,11 @@ class RaggedPlan:
     staged PCM (``itemsize`` bytes per sample)."""
 
     def __init__(self, lengths: Sequence[int], max_waste: float = 0.15, max_bytes: int = 1 << 30,
-                 itemsize: int = 4):
+                 itemsize: int = 4, mate=None):
         L = np.asarray(lengths, dtype=np.int64).reshape(-1)
         self.lengths = L.tolist()
         self.empty = np.flatnonzero(L <= 0).tolist()
-        order, cuts = _bucket_cuts(L, max_waste, max_bytes, itemsize)
+        order, cuts = _bucket_cuts(L, max_waste, max_bytes, itemsize, mate)
         self.buckets: List[List[int]] = [order[cuts[k]:cuts[k + 1]].tolist() for k in range(len(cuts) - 1)]
 
     def padded_samples(self) -> int:
@@ -303,17 +307,21 @@ class WindowedPlan:
     `density` = live bytes / copied bytes: a sparse set (recordings scattered over a large arena) is better served by the
     gather kernel (streams.ragged_buckets)."""
 
-    def __init__(self, rec: PackedRecordings, max_waste, max_bytes, itemsize, window_bytes, on_windows=None, src_itemsize=None):
+    def __init__(self, rec: PackedRecordings, max_waste, max_bytes, itemsize, window_bytes, on_windows=None, src_itemsize=None, fan=None):
         """itemsize: bytes per sample of the DEVICE batch (what the buckets are planned on); src_itemsize (default: the same): bytes per
         sample in the arena, what a window's span is measured in -- 1 for G.711 recordings, whose batch is int16.
         on_windows(plan): called as soon as the windows, their spans and the density are known and BEFORE the buckets are planned --
-        the hook for starting the first windows' DMA while the rest of the planning runs."""
-        self.lengths = rec.lengths.tolist()
+        the hook for starting the first windows' DMA while the rest of the planning runs.
+        fan (_Fanned over rec): the recordings are interleaved -- the windows are those of the recordings, the buckets (and lengths,
+        empty, windows) are of the batch ROWS they fan out to, a recording's channels in one bucket."""
         offs, lens = rec.offsets, rec.lengths
-        self.empty = np.flatnonzero(lens <= 0).tolist()
+        row_lens = lens if fan is None else fan.lengths
+        self.lengths = row_lens.tolist()
+        self.empty = np.flatnonzero(row_lens <= 0).tolist()
         order, bounds, o, e = _arena_windows(offs, lens, window_bytes // (src_itemsize or itemsize))
         live = order
-        self.windows = [order[a:b].tolist() for a, b in bounds]      # recording indices of each window (arena order)
+        rows_in = (lambda r: r) if fan is None else fan.rows_of
+        self.windows = [rows_in(order[a:b]).tolist() for a, b in bounds]      # recording (row) indices of each window (arena order)
         self.span = [(int(o[a]), int(e[b - 1])) for a, b in bounds]  # (first, last + 1) sample
         copied = sum(b - a for a, b in self.span)
         self.density = float(lens[live].sum()) / copied if copied else 0.0
@@ -321,8 +329,8 @@ class WindowedPlan:
         if on_windows is not None:
             on_windows(self)
         for w, (a, b) in enumerate(bounds):
-            idx = order[a:b]
-            sub_order, cuts = _bucket_cuts(lens[idx], max_waste, max_bytes, itemsize)
+            idx = rows_in(order[a:b])
+            sub_order, cuts = _bucket_cuts(row_lens[idx], max_waste, max_bytes, itemsize, None if fan is None else fan.mate[idx])
             glob = idx[sub_order]
             for k in range(len(cuts) - 1):
                 self.buckets.append(glob[cuts[k]:cuts[k + 1]].tolist())
@@ -358,6 +366,8 @@ def _describe(audios):
     """(is int16, lengths as a list of ints) of a list of recordings or a PackedRecordings."""
     if isinstance(audios, PackedRecordings):
         return audios.base.dtype == torch.int16, audios.lengths.tolist()
+    if isinstance(audios, _Fanned):
+        return True, audios.lengths.tolist()
     as_i16 = len(audios) > 0 and all(torch.is_tensor(a) and a.dtype == torch.int16 for a in audios)
     return as_i16, [int(a.shape[0]) if hasattr(a, "shape") else len(a) for a in audios]
 
@@ -408,11 +418,152 @@ def _coded_input(audios, codec, model):
     return out, None
 
 
-def _slot_bytes(nbytes, direct, coded):
+MAX_CHANNELS = 2         # include/silero_vad_hip.h VAD_MAX_CHANNELS
+
+
+def _channels_of(audios, channels):
+    """The `channels` argument of a corpus call, checked: -> None (every recording is mono: the call is today's) or the channel count
+    of every recording as int64."""
+    if channels is None:
+        return None
+    n = len(audios)
+    if isinstance(channels, (int, np.integer)) and not isinstance(channels, (bool, np.bool_)):
+        ch = np.full(n, int(channels), np.int64)
+    else:
+        ch = np.asarray(channels)
+        if ch.ndim != 1 or (ch.size and not np.issubdtype(ch.dtype, np.integer)):
+            raise ValueError("channels must be an int or one int per recording")
+        ch = ch.astype(np.int64)
+    if len(ch) != n:
+        raise ValueError(f"channels needs one entry per recording: {len(ch)} for {n}")
+    if n and (ch.min() < 1 or ch.max() > MAX_CHANNELS):
+        raise ValueError(f"a recording has 1 ... {MAX_CHANNELS} channels")
+    return ch if n and ch.max() > 1 else None
+
+
+def channel_rows(channels, n: int = None) -> list:
+    """The (recording, channel) pairs that the flat indices of a `channels=` call stand for, recording-major: entry k of a result -- a
+    probability tensor, a segment list, an index that `ragged_buckets` or `refill_segments_stream` yields -- belongs to
+    channel_rows(channels, n)[k].  channels: an int (then n recordings) or one int per recording."""
+    if isinstance(channels, (bool, np.bool_)):
+        raise ValueError("channels must be an int or one int per recording")
+    if isinstance(channels, (int, np.integer)):
+        if n is None:
+            raise ValueError("channels as one int needs the number of recordings")
+        channels = [int(channels)] * int(n)
+    ch = np.asarray(channels)
+    if ch.ndim != 1 or ch.dtype == np.bool_ or (ch.size and not np.issubdtype(ch.dtype, np.integer)):
+        raise ValueError("channels must be an int or one int per recording")
+    if n is not None and len(ch) != n:
+        raise ValueError(f"channels needs one entry per recording: {len(ch)} for {n}")
+    if ch.size and (ch.min() < 1 or ch.max() > MAX_CHANNELS):
+        raise ValueError(f"a recording has 1 ... {MAX_CHANNELS} channels")
+    return [(i, c) for i, m in enumerate(ch.tolist()) for c in range(int(m))]
+
+
+class _Fanned:
+    """The recordings of a `channels=` call beside the flat list of batch rows they fan out to: row k is channel ch_of[k] of recording
+    rec_of[k], recording-major (channel_rows), `lengths[k]` FRAMES long.  The schedulers plan on the rows -- len(), lengths and every
+    index they yield are the rows' -- and read the recordings (`audios`: a list or a PackedRecordings of interleaved int16 samples or
+    G.711 codes, `cd` their codec ids or None) only to build the sources of an upload (table)."""
+
+    def __init__(self, audios, ch, cd):
+        if isinstance(audios, PackedRecordings):
+            kinds, elems = {_sample_kind(audios.base.dtype)}, audios.lengths
+        else:
+            audios = [a if torch.is_tensor(a) else torch.as_tensor(a) for a in audios]
+            if any(a.dim() != 1 for a in audios):
+                raise ValueError("a recording with channels is a 1-D tensor of interleaved samples, as in a WAV data chunk")
+            kinds, elems = {_sample_kind(a.dtype) for a in audios}, np.asarray([a.shape[0] for a in audios], dtype=np.int64)
+        if 2 in kinds:
+            raise TypeError("float recordings with more than one channel: the device batch the channels are split into is int16 -- "
+                            "hand over int16 samples, or G.711 codes with `codec`")
+        if ((elems % ch) != 0).any():
+            raise ValueError("an interleaved recording of 2 channels has an even number of samples")
+        self.audios, self.C, self.cd = audios, ch, cd
+        self.frames = elems // ch
+        self.row0 = np.concatenate([[0], np.cumsum(ch)[:-1]]).astype(np.int64)       # a recording's first row
+        self.rec_of = np.repeat(np.arange(len(ch), dtype=np.int64), ch)
+        self.ch_of = np.arange(len(self.rec_of), dtype=np.int64) - self.row0[self.rec_of]
+        self.lengths = self.frames[self.rec_of]
+        self.mate = (self.C[self.rec_of] == 2) & (self.ch_of == 0)                   # row k + 1 is row k's sibling channel
+
+    def __len__(self):
+        return len(self.rec_of)
+
+    def rows_of(self, recs):
+        """the rows of recordings `recs`, in their order"""
+        recs = np.asarray(recs, dtype=np.int64)
+        reps = self.C[recs]
+        first = np.repeat(self.row0[recs], reps)
+        within = np.arange(int(reps.sum()), dtype=np.int64) - np.repeat(np.cumsum(reps) - reps, reps)
+        return first + within
+
+    def table(self, rows, at=None, batch_rows=None):
+        """The sources of an upload whose batch row batch_rows[j] (default: j) is row rows[j], from sample at[j] (default: 0) of its
+        channel on: -> (recording of every source, first frame of every source, position in `rows` of every source's first row,
+        int32 [n_src, 2] batch row of each channel or -1).  Rows that want the same frames of one recording share ONE source: every
+        source byte is read once."""
+        rows = np.asarray(rows, dtype=np.int64)
+        rec, ch = self.rec_of[rows], self.ch_of[rows]
+        at = np.zeros(len(rows), dtype=np.int64) if at is None else np.asarray(at, dtype=np.int64)
+        key = rec * (int(self.frames.max()) + 1 if len(self.frames) else 1) + at
+        _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+        dst = np.full((len(first), MAX_CHANNELS), -1, dtype=np.int32)
+        dst[inv.reshape(-1), ch] = np.arange(len(rows)) if batch_rows is None else batch_rows
+        return rec[first], at[first], first, dst
+
+
+def _channel_input(audios, codec, channels, model):
+    """(recordings, codec, fan) as the schedulers take them; the public corpus calls resolve `channels=` here, once, and hand `fan` down
+    through the schedulers' private `_fan=`.  Mono (channels None or all 1): as handed over, fan None.  Otherwise a model whose engine
+    splits on the device (Engine.upload_rows_channels) keeps the interleaved recordings, with fan = the _Fanned over them (it carries
+    the codecs: codec None); any other (a CPU stand-in) gets the flat list of de-interleaved int16 recordings, fan None -- the
+    definition of what the device route computes."""
+    ch = _channels_of(audios, channels)
+    if ch is None:
+        return audios, codec, None
+    cd = _codec_of(audios, codec)
+    fan = _Fanned(audios, ch, cd)
+    if hasattr(getattr(model, "engine", None), "upload_rows_channels"):
+        return fan.audios, None, fan
+    out = []
+    for i, a in enumerate(fan.audios):
+        x = a.contiguous().numpy()
+        for c in range(int(ch[i])):
+            out.append(torch.from_numpy(deinterleave(x, int(ch[i]), c, None if cd is None else int(cd[i]))))
+    return out, None, None
+
+
+def _stage_sources(ptr, frames, ch, width, src_esz, host):
+    """Pageable interleaved sources into the pinned staging block `host` (uint8) as the bytes they are: the one-channel sources at a
+    pitch of `width` elements, behind them the two-channel ones at 2 x width (vad_stage_rows, once per pitch) -> byte offset of every
+    source in the block.  The block holds what the batch rows of these sources hold, no more."""
+    off = np.zeros(len(ptr), dtype=np.int64)
+    at = 0
+    for c in range(1, MAX_CHANNELS + 1):
+        sel = np.flatnonzero(ch == c)
+        if not len(sel):
+            continue
+        rows = np.ascontiguousarray(ptr[sel], dtype=np.uint64)
+        lens = np.ascontiguousarray(frames[sel] * c, dtype=np.int64)
+        rc = lib().vad_stage_rows(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)),
+                                  len(sel), width * c, src_esz, host.data_ptr() + at, 0)
+        if rc:
+            raise _lib.VadError(rc, "vad_stage_rows")
+        off[sel] = at + np.arange(len(sel), dtype=np.int64) * width * c * src_esz
+        at += len(sel) * width * c * src_esz
+    return off
+
+
+def _slot_bytes(nbytes, direct, coded, staged=None):
     """(pinned staging, device) bytes of a staging slot for a device batch of nbytes: pinned sources need no staging; pageable G.711 is
-    staged as bytes (half the int16 batch) and keeps a device copy of them BEHIND the batch, which the expansion reads."""
+    staged as bytes (half the int16 batch) and keeps a device copy of them BEHIND the batch, which the expansion reads; so do pageable
+    interleaved sources, whatever their codec (staged: their bytes), which the split reads."""
     if direct:
         return 0, nbytes
+    if staged is not None:
+        return staged, nbytes + staged
     return (nbytes // 2, nbytes + nbytes // 2) if coded else (nbytes, nbytes)
 
 
@@ -494,7 +645,7 @@ def _stage_into(src: "_Sources", idxs, width, dst: torch.Tensor):
 
 def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                    max_bytes: int = 256 << 20, plan: RaggedPlan = None, post=None, meta=None, lanes: int = 2, prepare_only: bool = False,
-                   codec=None):
+                   codec=None, channels=None, _fan=None):
     """Generator over the plan's buckets: yields (indices, probs[len(indices), T_bucket] on the CPU).
     Recording i of a bucket owns the first ceil(len_i / N) entries of its row.
 
@@ -513,11 +664,25 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     `codec` ("ulaw" / "alaw", or one per recording): the recordings are uint8 G.711 codes.  They take the same routes at ONE byte a
     sample -- the arena windows' DMAs, the gather over PCIe, the staging buffers carry the codes -- and the gather kernel expands them
     into the int16 batch (vad_upload_rows_coded); the buckets are planned on the batch's bytes, so the call forms the buckets of its
-    int16 twin and every result is that of the same call on the `g711_expand`ed recordings."""
+    int16 twin and every result is that of the same call on the `g711_expand`ed recordings.
+
+    `channels` (1 or 2, or one per recording; with `codec` or with int16 recordings): a recording is INTERLEAVED, as a WAV data chunk
+    holds a recorded call, and every channel is a stream of its own.  The interleaved bytes take the same routes, once -- the windows'
+    DMAs, the gather over PCIe, the staging buffers carry them as they are -- and the gather kernel writes one batch row per channel
+    (vad_upload_rows_channels).  Buckets are planned on the batch rows, a recording's channels in one bucket; every result is that of
+    the same call on the flat list [deinterleave(a_i, C_i, c) for i for c in range(C_i)], and the indices yielded are indices into
+    that list (channel_rows)."""
     t_setup = time.perf_counter()
     n = _rates(sampling_rate)[2]                          # input samples per chunk (512 k for a multiple of 16 kHz)
-    audios, cd = _coded_input(audios, codec, model)
-    as_i16, lengths = _describe(audios)
+    fan = _fan                                            # (a public caller resolved `channels=` already)
+    if fan is None:
+        audios, codec, fan = _channel_input(audios, codec, channels, model)
+    if fan is not None:                                   # interleaved recordings: `audios` the sources, lengths / plan / indices the rows'
+        audios, cd = fan.audios, fan.cd
+        as_i16, lengths = _describe(fan)
+    else:
+        audios, cd = _coded_input(audios, codec, model)
+        as_i16, lengths = _describe(audios)
     coded = cd is not None
     dtype = torch.int16 if as_i16 or coded else torch.float32
     esz = 2 if as_i16 or coded else 4                     # the DEVICE batch; the source: 1 byte a sample for G.711
@@ -588,12 +753,13 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
                 win["stream"].wait_stream(cur)            # (the arena was written before this call in stream order, if at all)
                 ensure_window(2)
 
-            wp = WindowedPlan(packed, max_waste, max_bytes, esz, window_bytes=wbytes, on_windows=first_windows, src_itemsize=src_esz)
+            wp = WindowedPlan(packed, max_waste, max_bytes, esz, window_bytes=wbytes, on_windows=first_windows, src_itemsize=src_esz, fan=fan)
             if takes_windows(wp):
                 plan, audios = wp, packed
-    plan = plan or RaggedPlan(lengths, max_waste, max_bytes, esz)
+    plan = plan or RaggedPlan(lengths, max_waste, max_bytes, esz, None if fan is None else fan.mate)
     src = _Sources(audios, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(getattr(model, "engine", None), "upload_rows"))
     if not on_gpu:                                        # CPU stand-in models (tests)
+        assert fan is None                                # (they were handed the de-interleaved recordings: _channel_input)
         if prepare_only:
             return
         for idxs in plan.buckets:
@@ -604,7 +770,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         return
     direct = src.pinned
     how = 0 if mode == "dma" else 1
-    if coded and how == 0:
+    if (coded or fan is not None) and how == 0:
         how = _gather_instead_of_dma()
     windowed = direct and isinstance(plan, WindowedPlan)
 
@@ -632,7 +798,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             big_b = max(plan.buckets, key=lambda b: len(b) * ((max(plan.lengths[b[0]], n) + align - 1) // align * align))
             nb = len(big_b) * ((max(plan.lengths[big_b[0]], n) + align - 1) // align * align) * esz
             for k in range(pool.slots):
-                pool.get(k, *_slot_bytes(nb, direct, coded))
+                pool.get(k, *_slot_bytes(nb, direct, coded, None if fan is None else nb * src_esz // esz))
             if windowed:                                   # the three window buffers: warm torch's allocator with blocks of the largest window
                 wb = max((b - a) * src_esz for a, b in plan.span)
                 with torch.cuda.stream(win["stream"]):
@@ -677,7 +843,14 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         L = max(plan.lengths[idxs[0]], n)
         width = (L + align - 1) // align * align          # row pitch
         nbytes = len(idxs) * width * esz
-        host_b, dev_b = _slot_bytes(nbytes, direct, coded)
+        staged = None
+        if fan is not None:
+            # the bucket's sources: one per recording, both channels wanted (a bucket does not end between them: _bucket_cuts)
+            recs_k, _, _, dst_k = fan.table(idxs)
+            fr_k, ch_k = np.ascontiguousarray(fan.frames[recs_k]), np.ascontiguousarray(fan.C[recs_k], dtype=np.uint8)
+            fr_p = fr_k.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
+            staged = int(ch_k.sum()) * width * src_esz
+        host_b, dev_b = _slot_bytes(nbytes, direct, coded, staged)
         i = pool.get(k, host_b, dev_b)
         if not windowed:
             STATS["h2d_bytes"] += nbytes * src_esz // esz
@@ -698,8 +871,12 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             m_host.copy_(mt)
         t0 = time.perf_counter()
         if not direct:
-            host = pool.host[i][:host_b].view(src_dtype).view(len(idxs), width)
-            _stage_into(src, idxs, width, host)
+            if fan is not None:
+                host = pool.host[i][:host_b]
+                at_k = _stage_sources(src.ptr[recs_k], fr_k, ch_k, width, src_esz, host)
+            else:
+                host = pool.host[i][:host_b].view(src_dtype).view(len(idxs), width)
+                _stage_into(src, idxs, width, host)
             STATS["stage_s"] += time.perf_counter() - t0
             if late_wait is not None:
                 # the H2D copy below is a DMA: issued behind an OPEN device-side wait it leaves the copy engines' fast path (the refill
@@ -711,12 +888,16 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             ensure_window(w + 2)                          # this bucket's window and the two after it are on their way
             pool.stream.wait_event(win["ev"][w])
             a0 = plan.span[w][0]
-            rows = np.ascontiguousarray(win["buf"][w % 3].data_ptr() + (audios.offsets[idxs] - a0) * src_esz, dtype=np.uint64)
-            lens = np.ascontiguousarray(src.len[idxs])
-        cd_k = np.ascontiguousarray(cd[idxs]) if coded else None
+            from_ = idxs if fan is None else recs_k
+            rows = np.ascontiguousarray(win["buf"][w % 3].data_ptr() + (audios.offsets[from_] - a0) * src_esz, dtype=np.uint64)
+            lens = np.ascontiguousarray(src.len[idxs]) if fan is None else fr_k
+        cd_k = np.ascontiguousarray(cd[idxs if fan is None else recs_k]) if coded else None
 
         def upload(rows_p, lens_p, how_):
-            _upload_rows(model.engine, rows_p, lens_p, cd_k, len(idxs), width, esz, d, how_)
+            if fan is not None:
+                model.engine.upload_rows_channels(rows_p, lens_p, cd_k, ch_k, dst_k, len(recs_k), len(idxs), width, d, how_)
+            else:
+                _upload_rows(model.engine, rows_p, lens_p, cd_k, len(idxs), width, esz, d, how_)
 
         with torch.cuda.stream(pool.stream):
             ev0 = torch.cuda.Event(enable_timing=True)
@@ -730,9 +911,16 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             elif direct:
                 if late_wait is not None:                 # (the per-row DMA route: the same rule)
                     late_wait.synchronize()
-                tabs = src.tables(idxs)
-                upload(tabs[2], tabs[3], how)
+                tabs = src.tables(idxs if fan is None else recs_k)
+                upload(tabs[2], tabs[3] if fan is None else fr_p, how)
                 STATS["upload_call_s"] += time.perf_counter() - t0
+            elif fan is not None:
+                # the staged interleaved bytes cross the link in one copy, into the slot's device block behind the batch; the split
+                # reads them there
+                block = pool.dev[i][nbytes:nbytes + host_b]
+                block.copy_(host, non_blocking=True)
+                rows = np.ascontiguousarray(block.data_ptr() + at_k, dtype=np.uint64)
+                upload(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), fr_p, 2)
             elif coded:
                 # the staged codes cross the link in one copy, into the slot's device block behind the batch; the expansion reads
                 # them there with the recordings' TRUE lengths (the staging's zero bytes are not audio)
@@ -813,17 +1001,17 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
 
 
 def ragged_reserve(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15, max_bytes: int = 256 << 20,
-                   lanes: int = 2, codec=None):
+                   lanes: int = 2, codec=None, channels=None):
     """Everything a `ragged_probs` / `ragged_speech_segments` run over these recordings would allocate -- the compute lanes and their
     streams, every lane's scratch (vad_reserve: a later growth synchronises the device and, on some boxes, costs 0.1-0.2 s of
     hipFree / hipMalloc for the multi-GB gx scratch: profiles/r05_ingest_routes.md), the staging slots -- sized for the plan's
     largest bucket, up front.  Call it once before a corpus run (or a timed region); the run itself then allocates nothing."""
-    for _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, lanes=lanes, prepare_only=True, codec=codec):
+    for _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, lanes=lanes, prepare_only=True, codec=codec, channels=channels):
         pass
 
 
 def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
-                 max_bytes: int = 256 << 20, plan: RaggedPlan = None, codec=None) -> List[torch.Tensor]:
+                 max_bytes: int = 256 << 20, plan: RaggedPlan = None, codec=None, channels=None) -> List[torch.Tensor]:
     """Speech probabilities of many recordings of different lengths.
 
     Returns one 1-D CPU float tensor per recording (ceil(len / N) entries), bit-identical to
@@ -831,11 +1019,14 @@ def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste:
     tensors in [-1, 1] or int16 PCM (all of one kind).  `model` needs ``audio_forward_device``
     (HipSileroVAD); staging + H2D of bucket k+1 overlap the kernels of bucket k.  `sampling_rate` may be a multiple of 16000: the
     recordings then stay at their raw rate all the way into HBM (_rates).  `codec` ("ulaw" / "alaw", or one per recording): the
-    recordings are uint8 G.711 codes and cross the link as such (ragged_buckets); the result is that of the `g711_expand`ed recordings."""
+    recordings are uint8 G.711 codes and cross the link as such (ragged_buckets); the result is that of the `g711_expand`ed recordings.
+    `channels` (1 or 2, or one per recording): the recordings are interleaved and split on the device (ragged_buckets); the result has
+    one entry per (recording, channel), recording-major (channel_rows) -- that of the call on the `deinterleave`d recordings."""
     n = _rates(sampling_rate)[2]
-    lengths = _describe(audios)[1]
-    out: List[torch.Tensor] = [torch.empty(0)] * len(audios)
-    for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, plan, codec=codec):
+    audios, codec, fan = _channel_input(audios, codec, channels, model)
+    lengths = _describe(audios if fan is None else fan)[1]
+    out: List[torch.Tensor] = [torch.empty(0)] * len(lengths)
+    for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, plan, codec=codec, _fan=fan):
         for row, i in enumerate(idxs):
             out[i] = probs[row, : (lengths[i] + n - 1) // n].clone()
     return out
@@ -843,9 +1034,10 @@ def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste:
 
 def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                            max_bytes: int = 256 << 20, threads: int = 0, device_scan: bool = None,
-                           as_arrays: bool = False, codec=None, **scan_kw) -> List[list]:
+                           as_arrays: bool = False, codec=None, channels=None, **scan_kw) -> List[list]:
     """Speech segments (sample indices) of many recordings: bucketed GPU batches, then the segmenter.
-    scan_kw: the threshold/duration arguments of get_speech_timestamps.  codec: as in ragged_probs (uint8 G.711 recordings).  `audios`: a list of 1-D tensors or a
+    scan_kw: the threshold/duration arguments of get_speech_timestamps.  codec / channels: as in ragged_probs (uint8 G.711 recordings;
+    interleaved recordings, one result per channel).  `audios`: a list of 1-D tensors or a
     PackedRecordings.  as_arrays: return (counts int64[n], segments int64[sum(counts), 2]) -- recording i owns rows
     cumsum(counts)[i-1] .. -- instead of a list of lists of dicts (for corpora of 10^5+ recordings the dicts cost more
     host time than the GPU work; the arrays are also what a host-side gather to rank 0 wants).
@@ -856,7 +1048,8 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
     Both give the same segments (one source, csrc/scanner.hpp).  `sampling_rate` may be a multiple of 16000 (raw recordings, _rates):
     the segments are then in samples of the 16 kHz signal x[::k], as the reference's scan sees it (utils_vad.py:301-307)."""
     net_sr, dec, n = _rates(sampling_rate)
-    lengths = _describe(audios)[1]
+    audios, codec, fan = _channel_input(audios, codec, channels, model)
+    lengths = _describe(audios if fan is None else fan)[1]
     dev = getattr(model, "device", None)
     on_gpu = dev is not None and torch.device(dev).type == "cuda"
     if device_scan is None:
@@ -877,7 +1070,7 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
             return [counts, segs]
 
         for idxs, (counts, segs), probs_dev in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes,
-                                                              post=post, meta=meta, codec=codec):
+                                                              post=post, meta=meta, codec=codec, _fan=fan):
             t0 = time.perf_counter()
             cnt = counts.numpy()
             if len(cnt) and int(cnt.max()) > cap0:             # rare: rescan this bucket with room for all
@@ -887,7 +1080,7 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
             parts.append((np.asarray(idxs, dtype=np.int64), cnt.copy(), segs.numpy()))
             STATS["scan_s"] += time.perf_counter() - t0
     else:
-        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec):
+        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec, _fan=fan):
             lens = [lengths[i] for i in idxs]
             t0 = time.perf_counter()
             segs = segment_probs_batch(probs, [(m + n - 1) // n for m in lens], [(m + dec - 1) // dec for m in lens], net_sr,
@@ -1140,7 +1333,7 @@ def _assign_window_buffers(first: np.ndarray, last: np.ndarray, ahead: int, slac
 
 
 def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_chunks: int, plan: "RefillPlan" = None, on_slab=None,
-                 prepare_only: bool = False, codec=None):
+                 prepare_only: bool = False, codec=None, channels=None, _fan=None):
     """The continuous-refill loop (RefillPlan) as a generator: stages slab k + 1 while the kernels of slab k run, scatters every slab's
     probabilities into one flat device tensor (recording i owns out_flat[base[i] : base[i + 1]]) and yields k once slab k has been
     ENQUEUED.  `on_slab(k, finished, out_flat, base)` is called right before that, with the recordings whose last chunk lies in slab k
@@ -1149,15 +1342,27 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     slots, the engine's scratch, the flat probability tensor -- then stop (refill_reserve): a run over the same recordings allocates
     nothing (7 GiB of window buffers for a 1 263 h shard are 60 ms when they come fresh from the driver, 0.5 s when an outgrown block
     has to go back first).  `codec`: the recordings are uint8 G.711 codes (ragged_buckets: the same rules -- every route carries
-    the codes at one byte a sample and the gather kernel expands them into the int16 slab)."""
+    the codes at one byte a sample and the gather kernel expands them into the int16 slab).  `channels`: the recordings are interleaved
+    (ragged_buckets: the same rules).  Every channel is a queue entry of its own, next to its sibling and with the same need, so the
+    schedule is that of the flat list of de-interleaved recordings; where a slab's slots want the same frames of both channels of a
+    recording that is ONE source of the slab's upload, where the schedule admitted the two at different slabs each slab names the
+    channel it wants (_Fanned.table)."""
     t_setup = time.perf_counter()
     net_sr, _, n = _rates(sampling_rate)
     eng = model.engine
-    audios, cd = _coded_input(audios, codec, model)
+    fan = _fan                                         # (a public caller resolved `channels=` already)
+    if fan is None:
+        audios, codec, fan = _channel_input(audios, codec, channels, model)
+    if fan is not None:                                # interleaved recordings: `recs` the sources; lengths, plan, base, results the rows'
+        recs, cd = fan.audios, fan.cd
+    else:
+        audios, cd = _coded_input(audios, codec, model)
+        recs = audios
+    n_rows = len(audios) if fan is None else len(fan)
     coded = cd is not None
     dev = torch.device(getattr(eng, "torch_device", None) or torch.device("cuda", eng.device))
     on_gpu = dev.type == "cuda"
-    as_i16, lengths = _describe(audios)
+    as_i16, lengths = _describe(audios if fan is None else fan)
     dtype, esz = (torch.int16, 2) if as_i16 or coded else (torch.float32, 4)     # the DEVICE slab; the source: 1 byte a sample for G.711
     src_dtype, src_esz = (torch.uint8, 1) if coded else (dtype, esz)
     lens_np = np.asarray(lengths, dtype=np.int64).reshape(-1)
@@ -1171,7 +1376,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     # buffers (SILERO_VAD_AMD_REFILL_WINDOW_BUDGET, 16 GiB of the 288) keeps the gather route.
     wf = None
     if plan is None and on_gpu and mode in ("", "window") and hasattr(eng, "upload_rows"):
-        packed = audios if isinstance(audios, PackedRecordings) else _as_packed(audios)
+        packed = recs if isinstance(recs, PackedRecordings) else _as_packed(recs)
         if packed is not None and packed.base.is_pinned() and int((lens_np > 0).sum()):
             slab_bytes = slots * slab_chunks * n * src_esz                                      # (of the arena: what a slab reads of a window)
             wbytes = int(os.environ.get("SILERO_VAD_AMD_REFILL_WINDOW", 0)) or (1 << 30)        # (256 MiB windows: 0.92 of the link, 1 GiB: 0.95)
@@ -1181,14 +1386,15 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
             order, bounds, o_, e_ = _arena_windows(packed.offsets, packed.lengths, wbytes // src_esz, lead_limit=(wbytes // src_esz) // 8 if int(os.environ.get("SILERO_VAD_AMD_REFILL_LEAD", ramp > 1)) else 0)
             spans = np.asarray([(o_[a], e_[b - 1]) for a, b in bounds], dtype=np.int64).reshape(-1, 2)
             copied = int((spans[:, 1] - spans[:, 0]).sum())
-            dense = mode == "window" or float(lens_np[lens_np > 0].sum()) >= 0.6 * copied
+            dense = mode == "window" or float(packed.lengths[packed.lengths > 0].sum()) >= 0.6 * copied
             if dense:
-                wplan = RefillPlan(lens_np, slots, slab_chunks, n, order=order, ramp=ramp)
-                win_of = np.full(len(lens_np), -1, dtype=np.int64)
+                rows_in = (lambda r: r) if fan is None else fan.rows_of       # (the rows of recordings, in their order)
+                wplan = RefillPlan(lens_np, slots, slab_chunks, n, order=rows_in(order), ramp=ramp)
+                win_of = np.full(len(packed), -1, dtype=np.int64)
                 for w, (a, b) in enumerate(bounds):
                     win_of[order[a:b]] = w
-                w_first = np.asarray([wplan.first_slab[order[a:b]].min() for a, b in bounds], dtype=np.int64)
-                w_last = np.asarray([wplan.last_slab[order[a:b]].max() for a, b in bounds], dtype=np.int64)
+                w_first = np.asarray([wplan.first_slab[rows_in(order[a:b])].min() for a, b in bounds], dtype=np.int64)
+                w_last = np.asarray([wplan.last_slab[rows_in(order[a:b])].max() for a, b in bounds], dtype=np.int64)
                 wmax = int((spans[:, 1] - spans[:, 0]).max()) * src_esz
                 wmax = (wmax + 255) // 256 * 256
                 ahead = max(2, -(-2 * wmax // max(slab_bytes, 1))) + 1          # two windows' worth of slabs in front of the reader
@@ -1207,18 +1413,18 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     STATS["refill_window_buffers"] = max(STATS["refill_window_buffers"], n_buf)
     plan = plan or RefillPlan(lens_np, slots, slab_chunks, n)
     B, S, width = plan.slots, plan.slab_chunks, plan.slab_chunks * n
-    src = _Sources(audios, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(eng, "upload_rows"))
+    src = _Sources(recs, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(eng, "upload_rows"))
     direct = src.pinned                                # pinned recordings: one gather kernel per slab, no host copy
     how = 0 if mode == "dma" else 1
-    if coded and how == 0:
+    if (coded or fan is not None) and how == 0:
         how = _gather_instead_of_dma()
-    base = np.zeros(len(audios) + 1, dtype=np.int64)   # recording i owns out_flat[base[i] : base[i] + n_chunks(i)]
+    base = np.zeros(n_rows + 1, dtype=np.int64)   # recording i owns out_flat[base[i] : base[i] + n_chunks(i)]
     np.cumsum(np.where(lens_np > 0, (lens_np + n - 1) // n, 0), out=base[1:])
     total = int(base[-1])
     out_flat = torch.zeros(total + 1, dtype=torch.float32, device=dev)      # [+1]: sink for the padding chunks
     ctx = torch.zeros((B, chunk_size(net_sr) // 8), dtype=torch.float32, device=dev)
     state = torch.zeros((2, B, 128), dtype=torch.float32, device=dev)
-    done = np.zeros(len(audios), dtype=np.int64)       # chunks of each recording already produced
+    done = np.zeros(n_rows, dtype=np.int64)       # chunks of each recording already produced
     ctxm = contextlib.nullcontext() if not on_gpu else torch.cuda.device(dev)
     with ctxm:
         if on_gpu:
@@ -1257,7 +1463,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
             # every recording's device address, once: its window's buffer + its place in the window's span
             w_ = wf["win_of"]
             livem = w_ >= 0
-            dptr = np.zeros(len(lens_np), dtype=np.uint64)
+            dptr = np.zeros(len(w_), dtype=np.uint64)
             dptr[livem] = (blk.data_ptr() + wf["buf_of"][w_[livem]] * wf["wmax"]
                            + (wf["packed"].offsets[livem] - wf["spans"][w_[livem], 0]) * src_esz).astype(np.uint64)
             ptr0 = dptr
@@ -1364,25 +1570,55 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
         def stage(k):
             e = plan.slab_arrays[k]                                        # [entries, 5], vectorised bookkeeping
             sl, rec, at, take = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
-            rows = np.zeros(B, dtype=np.uint64)
-            lens = np.zeros(B, dtype=np.int64)
-            rows[sl] = ptr0[rec] + (at * src_esz).astype(np.uint64)
-            lens[sl] = take
+            staged = None
+            if fan is not None:
+                # the slab's sources: the slots that read the same frames of one recording -- its two channels, admitted together --
+                # share one
+                src_k, at_k, _, dst_k = fan.table(rec, at, sl)
+                ch_k = np.ascontiguousarray(fan.C[src_k], dtype=np.uint8)
+                rows = np.ascontiguousarray(ptr0[src_k] + (at_k * fan.C[src_k] * src_esz).astype(np.uint64))
+                lens = np.ascontiguousarray(np.minimum(fan.frames[src_k] - at_k, width))
+                cd_k = np.ascontiguousarray(cd[src_k]) if coded else None
+                if len(sl) < B:
+                    # a slot without a recording: an empty one-channel source names it, so the row is zeros as on the mono path
+                    idle = np.setdiff1d(np.arange(B, dtype=np.int64), sl)
+                    ch_k = np.concatenate([ch_k, np.ones(len(idle), dtype=np.uint8)])
+                    rows = np.concatenate([rows, np.zeros(len(idle), dtype=np.uint64)])
+                    lens = np.concatenate([lens, np.zeros(len(idle), dtype=np.int64)])
+                    cd_k = None if cd_k is None else np.concatenate([cd_k, np.zeros(len(idle), dtype=np.uint8)])
+                    dst_k = np.ascontiguousarray(np.concatenate([dst_k, np.stack([idle, np.full(len(idle), -1)], axis=1).astype(np.int32)]))
+                staged = int(ch_k.sum()) * width * src_esz
+            else:
+                rows = np.zeros(B, dtype=np.uint64)
+                lens = np.zeros(B, dtype=np.int64)
+                rows[sl] = ptr0[rec] + (at * src_esz).astype(np.uint64)
+                lens[sl] = take
+                cd_k = None
+                if coded:
+                    cd_k = np.zeros(B, dtype=np.uint8)                        # (a slot without a recording: an empty row, zeros)
+                    cd_k[sl] = cd[rec]
             rows_p = rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
             lens_p = lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
-            cd_k = None
-            if coded:
-                cd_k = np.zeros(B, dtype=np.uint8)                            # (a slot without a recording: an empty row, zeros)
-                cd_k[sl] = cd[rec]
+
+            def upload(rows_p_, how_):
+                if fan is None:
+                    _upload_rows(eng, rows_p_, lens_p, cd_k, B, width, esz, d, how_)
+                    return
+                eng.upload_rows_channels(rows_p_, lens_p, cd_k, ch_k, dst_k, len(ch_k), B, width, d, how_)
+
             nbytes = B * width * esz
             t0 = time.perf_counter()
             if on_gpu:
-                host_b, dev_b = _slot_bytes(nbytes, direct, coded)
+                host_b, dev_b = _slot_bytes(nbytes, direct, coded, staged)
                 i = pool.get(k, host_b, dev_b)
-                host = None if direct else pool.host[i][:host_b].view(src_dtype).view(B, width)
+                host = None if direct else pool.host[i][:host_b] if fan is not None else pool.host[i][:host_b].view(src_dtype).view(B, width)
             else:
+                assert fan is None                                            # (a CPU stand-in was handed the de-interleaved recordings)
                 i, host = 0, torch.empty((B, width), dtype=dtype)
-            if host is not None:
+            if host is not None and fan is not None:
+                off_k = _stage_sources(rows, lens, ch_k, width, src_esz, host)
+                STATS["stage_s"] += time.perf_counter() - t0
+            elif host is not None:
                 rc = lib().vad_stage_rows(rows_p, lens_p, B, width, src_esz, host.data_ptr(), 0)
                 if rc:
                     raise _lib.VadError(rc, "vad_stage_rows")
@@ -1409,20 +1645,25 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     pool.stream.wait_event(pool.consumed[i])
             with torch.cuda.stream(pool.stream):
                 if wf is not None:
-                    _upload_rows(eng, rows_p, lens_p, cd_k, B, width, esz, d, 2)    # (2: the rows are device addresses)
+                    upload(rows_p, 2)                                          # (2: the rows are device addresses)
                     STATS["upload_call_s"] += time.perf_counter() - t0
                     for v in wf["by_last"].pop(k, ()):                         # the windows this slab is the last to read: released
                         rel = torch.cuda.Event()
                         rel.record(pool.stream)
                         wf["release"][v] = rel
                 elif direct:
-                    _upload_rows(eng, rows_p, lens_p, cd_k, B, width, esz, d, how)
+                    upload(rows_p, how)
                     STATS["upload_call_s"] += time.perf_counter() - t0
+                elif fan is not None:                                          # staged interleaved bytes: one copy, split from the slot's device block
+                    block = pool.dev[i][nbytes:nbytes + host_b]
+                    block.copy_(host, non_blocking=True)
+                    at_dev = np.ascontiguousarray(block.data_ptr() + off_k, dtype=np.uint64)
+                    upload(at_dev.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), 2)
                 elif coded:                                                    # staged codes: one copy, expanded from the slot's device block
                     codes = pool.dev[i][nbytes:nbytes + host_b].view(B, width)
                     codes.copy_(host, non_blocking=True)
                     at_dev = np.ascontiguousarray(codes.data_ptr() + np.arange(B, dtype=np.int64) * width, dtype=np.uint64)
-                    _upload_rows(eng, at_dev.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens_p, cd_k, B, width, esz, d, 2)
+                    upload(at_dev.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), 2)
                 else:
                     d.copy_(host, non_blocking=True)
                 ev = torch.cuda.Event()
@@ -1435,7 +1676,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
         if prepare_only:
             if on_gpu:
                 for k in range(pool.slots):
-                    pool.get(k, *_slot_bytes(B * width * esz, direct, coded))
+                    pool.get(k, *_slot_bytes(B * width * esz, direct, coded, None if fan is None else B * width * src_esz))
                 torch.cuda.synchronize(dev)
             return None, base, plan
         staged = stage(0) if n_slabs else None
@@ -1465,8 +1706,8 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     return out_flat, base, plan
 
 
-def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, codec=None):
-    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec)
+def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, codec=None, _fan=None):
+    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec, _fan=_fan)
     while True:
         try:
             next(it)
@@ -1474,10 +1715,10 @@ def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, cod
             return stop.value
 
 
-def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None):
+def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None, channels=None):
     """Everything a refill run over these recordings allocates, allocated now (`ragged_reserve`'s twin): the arena windows' device
     buffers, the staging slots, the engine's scratch, the block the flat probability tensor will take.  Returns the plan."""
-    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True, codec=codec)
+    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True, codec=codec, channels=channels)
     while True:
         try:
             next(it)
@@ -1486,7 +1727,7 @@ def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: i
 
 
 def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32,
-                 plan: RefillPlan = None, _keep_on_device: bool = False, codec=None):
+                 plan: RefillPlan = None, _keep_on_device: bool = False, codec=None, channels=None):
     """Speech probabilities of many recordings of different lengths through `slots` persistent stream slots
     (RefillPlan).  Returns one 1-D CPU float tensor per recording, bit-identical to
     ``model.audio_forward(audio[None], sr)[0]``: the state and context a slot carries from slab to slab are exactly
@@ -1494,29 +1735,35 @@ def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int
     Staging of slab k+1 (native threaded copy into pinned memory + H2D on a side stream) overlaps the kernels of
     slab k.  `audios`: float tensors in [-1, 1] or int16 PCM (all of one kind); `sampling_rate` may be a multiple of 16000 (raw
     recordings, _rates: a slab is slab_chunks x 512 k raw samples, the carried context is the 16 kHz net's).  `codec` ("ulaw" / "alaw",
-    or one per recording): uint8 G.711 recordings, as in ragged_probs."""
-    out_flat, base, plan = _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec)
+    or one per recording): uint8 G.711 recordings, as in ragged_probs.  `channels`: interleaved recordings, one result per (recording,
+    channel) as in ragged_probs."""
+    audios, codec, fan = _channel_input(audios, codec, channels, model)
+    out_flat, base, plan = _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec, _fan=fan)
     if _keep_on_device:
         return out_flat, base, plan
     flat = out_flat.cpu()
-    return [flat[base[i]:base[i + 1]].clone() for i in range(len(audios))]
+    return [flat[base[i]:base[i + 1]].clone() for i in range(len(base) - 1)]
 
 
 def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None,
-                           **scan_kw):
+                           channels=None, _fan=None, **scan_kw):
     """The continuous-refill scheduler with RESULTS AS RECORDINGS RETIRE -- what the reference's worker pool does, each file's
     timestamps handed back when that file is done (examples/parallel_example.ipynb cell 7).  Generator of
     (recording indices int64[m], counts int64[m], segments int64[m, cap, 2]) batches: behind the slab in which a recording's last
     chunk was computed, ONE device scan (vad_segment_probs_device, a lane per recording, over the recording's own row of the flat
     probability tensor) turns the retired recordings into segment lists, which ride back over PCIe asynchronously; a batch is
     yielded as soon as its copy has landed (a slab or two behind the kernels; nothing here blocks the pipeline).  Probabilities
-    never leave the GPU.  Segments are in samples of the net's rate (x[::k] for raw 32 / 48 kHz recordings).  codec: as in refill_probs."""
+    never leave the GPU.  Segments are in samples of the net's rate (x[::k] for raw 32 / 48 kHz recordings).  codec: as in refill_probs.
+    channels: interleaved recordings; the indices yielded are those of channel_rows."""
     net_sr, dec, _ = _rates(sampling_rate)
-    lengths = (np.asarray(_describe(audios)[1], dtype=np.int64).reshape(-1) + dec - 1) // dec     # samples at the net's rate: the scan's unit
+    fan = _fan                                                            # (refill_speech_segments resolved `channels=` already)
+    if fan is None:
+        audios, codec, fan = _channel_input(audios, codec, channels, model)
+    lengths = (np.asarray(_describe(audios if fan is None else fan)[1], dtype=np.int64).reshape(-1) + dec - 1) // dec     # samples at the net's rate: the scan's unit
     eng = model.engine
     on_gpu = hasattr(eng, "_h")
     if not on_gpu:                                                        # CPU stand-in engines (tests): scan at the end, on the host
-        flat, base, _ = _refill_run(audios, model, sampling_rate, slots, slab_chunks, codec=codec)
+        flat, base, _ = _refill_run(audios, model, sampling_rate, slots, slab_chunks, codec=codec, _fan=fan)
         from .timestamps import segment_probs
         for i in range(len(lengths)):
             sg = segment_probs(flat[base[i]:base[i + 1]], int(lengths[i]), net_sr, **scan_kw) if lengths[i] > 0 else []
@@ -1611,7 +1858,7 @@ def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, 
             pending.append((finished.copy(), bufs, m, ev, out_flat, meta))
             STATS["scan_s"] += time.perf_counter() - t0
 
-    for _ in _refill_iter(audios, model, sampling_rate, slots, slab_chunks, None, on_slab, codec=codec):
+    for _ in _refill_iter(audios, model, sampling_rate, slots, slab_chunks, None, on_slab, codec=codec, _fan=fan):
         while ready:
             yield ready.pop(0)
     if acc["lists"]:
@@ -1627,14 +1874,15 @@ def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, 
 
 
 def refill_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024,
-                           slab_chunks: int = 32, as_arrays: bool = False, codec=None, **scan_kw) -> List[list]:
+                           slab_chunks: int = 32, as_arrays: bool = False, codec=None, channels=None, **scan_kw) -> List[list]:
     """`ragged_speech_segments` over the continuous-refill scheduler (refill_segments_stream: every recording is scanned on the GPU
     behind the slab it retires in, its segment list crosses PCIe while later slabs run).  as_arrays: (counts int64[n], segments
-    int64[sum(counts), 2]) like ragged_speech_segments, instead of a list of lists of dicts."""
-    n_rec = len(audios)
+    int64[sum(counts), 2]) like ragged_speech_segments, instead of a list of lists of dicts.  codec / channels: as in refill_probs."""
+    audios, codec, fan = _channel_input(audios, codec, channels, model)
+    n_rec = len(audios) if fan is None else len(fan)
     counts_all = np.zeros(n_rec, dtype=np.int64)
     parts = []
-    for idx, cnt, segs in refill_segments_stream(audios, model, sampling_rate, slots, slab_chunks, codec=codec, **scan_kw):
+    for idx, cnt, segs in refill_segments_stream(audios, model, sampling_rate, slots, slab_chunks, codec=codec, _fan=fan, **scan_kw):
         counts_all[idx] = cnt
         parts.append((idx, cnt, segs))
     t0 = time.perf_counter()
@@ -1999,6 +2247,30 @@ def g711_expand(data, codec) -> np.ndarray:
     rc = lib().vad_g711_expand(c, x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None)
     if rc:
         raise _lib.VadError(rc, "vad_g711_expand")
+    return out
+
+
+def deinterleave(x, channels: int, channel: int, codec=None) -> np.ndarray:
+    """Channel `channel` of a 1-D array of interleaved samples, as a WAV data chunk holds them, as int16 (vad_deinterleave, from the
+    definition the device split uses): x[channel::channels] for int16 samples (codec None or "s16"), g711_expand(x[channel::channels])
+    for uint8 codes with codec "ulaw" / "alaw".  What a corpus call with `channels=` computes is, by definition, what it computes on
+    these."""
+    c = _PCM["s16"] if codec is None else _codec_id(codec)
+    x = np.ascontiguousarray(x)
+    want = np.int16 if c == _PCM["s16"] else np.uint8
+    if x.ndim != 1 or x.dtype != want:
+        raise ValueError(f"{'s16' if codec is None else codec!r} data must be 1-D {np.dtype(want).name}, got {x.dtype} of shape {x.shape}")
+    if isinstance(channels, (bool, np.bool_)) or not isinstance(channels, (int, np.integer)) or not 1 <= channels <= MAX_CHANNELS:
+        raise ValueError(f"channels must be 1 ... {MAX_CHANNELS}, got {channels!r}")
+    if not 0 <= channel < channels:
+        raise ValueError(f"channel must be 0 ... {channels - 1}, got {channel!r}")
+    if x.size % channels:
+        raise ValueError("an interleaved recording of 2 channels has an even number of samples")
+    frames = x.size // channels
+    out = np.empty(frames, np.int16)
+    rc = lib().vad_deinterleave(c, int(channels), int(channel), x.ctypes.data if frames else None, frames, out.ctypes.data if frames else None)
+    if rc != frames:
+        raise _lib.VadError(-rc, "vad_deinterleave")
     return out
 
 

@@ -270,6 +270,47 @@ def read_audio(path: str, sampling_rate: int = 16000) -> torch.Tensor:
     return torch.from_numpy(pcm.astype(np.float32).mean(axis=1) / 32768.0)
 
 
+def read_wav_raw(path: str):
+    """A WAV file's data chunk exactly as it lies in the file -> (samples, sampling_rate, channels, codec): a 1-D tensor of INTERLEAVED
+    samples, int16 with codec None for 16-bit PCM (format tag 1), uint8 with codec "ulaw" / "alaw" for G.711 (tags 7 / 6, which Python's
+    `wave` module refuses) -- what the corpus calls take with `codec=` and `channels=`: a recorded call, the agent on one channel and the
+    customer on the other, is split on the device and never averaged.  (`read_audio` is the reference's reader: float, mono, channels
+    averaged.)  Anything else -- another tag, another sample size, more channels than the corpus calls split -- is a ValueError that
+    names the format.  The chunk headers are walked by seeking; the samples are read once, straight into the array returned."""
+    import os
+    import struct
+
+    import numpy as np
+    with open(str(path), "rb") as f:
+        size = os.fstat(f.fileno()).st_size
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise ValueError(f"read_wav_raw: {path}: not a RIFF / WAVE file")
+        fmt = None
+        while True:
+            hdr = f.read(8)
+            if len(hdr) < 8:
+                raise ValueError(f"read_wav_raw: {path}: no fmt / data chunk")
+            tag, n = hdr[:4], struct.unpack("<I", hdr[4:])[0]
+            if tag == b"data":
+                break
+            if tag == b"fmt ":
+                fmt = f.read(min(n, 16))
+            f.seek(f.tell() - (len(fmt) if tag == b"fmt " else 0) + n + (n & 1))       # chunks are word aligned
+        if fmt is None or len(fmt) < 16:
+            raise ValueError(f"read_wav_raw: {path}: no fmt chunk in front of the data")
+        tag, channels, rate, _, _, bits = struct.unpack("<HHIIHH", fmt)
+        kinds = {(1, 16): (np.int16, None), (7, 8): (np.uint8, "ulaw"), (6, 8): (np.uint8, "alaw")}
+        if (tag, bits) not in kinds or not 1 <= channels <= 2:
+            raise ValueError(f"read_wav_raw: {path}: format tag {tag}, {bits} bits, {channels} channels -- 16-bit PCM (tag 1), G.711 mu-law "
+                             "(7) and A-law (6) with 1 or 2 channels are read")
+        dtype, codec = kinds[(tag, bits)]
+        frame = channels * np.dtype(dtype).itemsize
+        n = min(n, size - f.tell())                        # (a truncated file: what is there)
+        samples = np.fromfile(f, dtype=dtype, count=n // frame * channels)
+    return torch.from_numpy(samples), int(rate), int(channels), codec
+
+
 def save_audio(path: str, tensor: torch.Tensor, sampling_rate: int = 16000):
     """float tensor in [-1, 1] -> PCM16 mono WAV (the reference writes through torchaudio, utils_vad.py:175-191; same file)."""
     import wave
