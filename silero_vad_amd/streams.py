@@ -24,6 +24,7 @@ import contextlib
 import ctypes
 import os
 import time
+import types
 from typing import List, Sequence
 
 import numpy as np
@@ -421,43 +422,39 @@ def _coded_input(audios, codec, model):
 MAX_CHANNELS = 2         # include/silero_vad_hip.h VAD_MAX_CHANNELS
 
 
-def _channels_of(audios, channels):
-    """The `channels` argument of a corpus call, checked: -> None (every recording is mono: the call is today's) or the channel count
-    of every recording as int64."""
-    if channels is None:
-        return None
-    n = len(audios)
+def _channel_counts(channels, n):
+    """`channels` as one int64 count per recording, checked (the one checker of `_channels_of` and `channel_rows`).  n: the number of
+    recordings, None if the caller does not know it (a single int then cannot be spread)."""
     if isinstance(channels, (int, np.integer)) and not isinstance(channels, (bool, np.bool_)):
-        ch = np.full(n, int(channels), np.int64)
+        if n is None:
+            raise ValueError("channels as one int needs the number of recordings")
+        ch = np.full(int(n), int(channels), np.int64)
     else:
         ch = np.asarray(channels)
         if ch.ndim != 1 or (ch.size and not np.issubdtype(ch.dtype, np.integer)):
             raise ValueError("channels must be an int or one int per recording")
         ch = ch.astype(np.int64)
-    if len(ch) != n:
+    if n is not None and len(ch) != n:
         raise ValueError(f"channels needs one entry per recording: {len(ch)} for {n}")
-    if n and (ch.min() < 1 or ch.max() > MAX_CHANNELS):
+    if ch.size and (ch.min() < 1 or ch.max() > MAX_CHANNELS):
         raise ValueError(f"a recording has 1 ... {MAX_CHANNELS} channels")
-    return ch if n and ch.max() > 1 else None
+    return ch
+
+
+def _channels_of(audios, channels):
+    """The `channels` argument of a corpus call, checked: -> None (every recording is mono: the call is today's) or the channel count
+    of every recording as int64."""
+    if channels is None:
+        return None
+    ch = _channel_counts(channels, len(audios))
+    return ch if ch.size and ch.max() > 1 else None
 
 
 def channel_rows(channels, n: int = None) -> list:
     """The (recording, channel) pairs that the flat indices of a `channels=` call stand for, recording-major: entry k of a result -- a
     probability tensor, a segment list, an index that `ragged_buckets` or `refill_segments_stream` yields -- belongs to
     channel_rows(channels, n)[k].  channels: an int (then n recordings) or one int per recording."""
-    if isinstance(channels, (bool, np.bool_)):
-        raise ValueError("channels must be an int or one int per recording")
-    if isinstance(channels, (int, np.integer)):
-        if n is None:
-            raise ValueError("channels as one int needs the number of recordings")
-        channels = [int(channels)] * int(n)
-    ch = np.asarray(channels)
-    if ch.ndim != 1 or ch.dtype == np.bool_ or (ch.size and not np.issubdtype(ch.dtype, np.integer)):
-        raise ValueError("channels must be an int or one int per recording")
-    if n is not None and len(ch) != n:
-        raise ValueError(f"channels needs one entry per recording: {len(ch)} for {n}")
-    if ch.size and (ch.min() < 1 or ch.max() > MAX_CHANNELS):
-        raise ValueError(f"a recording has 1 ... {MAX_CHANNELS} channels")
+    ch = _channel_counts(channels, n)
     return [(i, c) for i, m in enumerate(ch.tolist()) for c in range(int(m))]
 
 
@@ -535,6 +532,35 @@ def _channel_input(audios, codec, channels, model):
     return out, None, None
 
 
+def _corpus_input(audios, model, codec, channels, fan):
+    """What both corpus schedulers open with: `channels=` and `codec=` resolved (_channel_input -- unless a public caller did that
+    already and hands its `fan` down --, _coded_input) and the sample formats that follow.  -> recs (the recordings to read), lengths
+    (of the batch ROWS: the recordings', or with interleaved recordings their channels'), cd (codec ids per recording or None), fan
+    (_Fanned or None), coded, and dtype / esz of the DEVICE batch beside src_dtype / src_esz of the source (1 byte a sample for G.711).
+    The sources themselves are read later, once the plan is known (_Ingest): a window route swaps a list for its PackedRecordings."""
+    if fan is None:
+        audios, codec, fan = _channel_input(audios, codec, channels, model)
+    if fan is not None:                                   # interleaved recordings: `recs` the sources, lengths / plan / indices the rows'
+        recs, cd = fan.audios, fan.cd
+    else:
+        recs, cd = _coded_input(audios, codec, model)
+    as_i16, lengths = _describe(recs if fan is None else fan)
+    coded = cd is not None
+    dtype, esz = (torch.int16, 2) if as_i16 or coded else (torch.float32, 4)
+    src_dtype, src_esz = (torch.uint8, 1) if coded else (dtype, esz)
+    return types.SimpleNamespace(recs=recs, lengths=lengths, cd=cd, fan=fan, coded=coded, dtype=dtype, esz=esz, src_dtype=src_dtype, src_esz=src_esz)
+
+
+def _pack_rows(ptr, lens, pitch, esz, dst_ptr):
+    """Rows at host addresses `ptr` (uint64), `lens` elements of `esz` bytes each, into [len(ptr)][pitch] at host address dst_ptr, zero
+    padded, with the native threaded copy."""
+    ptr, lens = np.ascontiguousarray(ptr, dtype=np.uint64), np.ascontiguousarray(lens, dtype=np.int64)
+    rc = lib().vad_stage_rows(ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)),
+                              len(ptr), pitch, esz, dst_ptr, 0)
+    if rc:
+        raise _lib.VadError(rc, "vad_stage_rows")
+
+
 def _stage_sources(ptr, frames, ch, width, src_esz, host):
     """Pageable interleaved sources into the pinned staging block `host` (uint8) as the bytes they are: the one-channel sources at a
     pitch of `width` elements, behind them the two-channel ones at 2 x width (vad_stage_rows, once per pitch) -> byte offset of every
@@ -545,40 +571,140 @@ def _stage_sources(ptr, frames, ch, width, src_esz, host):
         sel = np.flatnonzero(ch == c)
         if not len(sel):
             continue
-        rows = np.ascontiguousarray(ptr[sel], dtype=np.uint64)
-        lens = np.ascontiguousarray(frames[sel] * c, dtype=np.int64)
-        rc = lib().vad_stage_rows(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)),
-                                  len(sel), width * c, src_esz, host.data_ptr() + at, 0)
-        if rc:
-            raise _lib.VadError(rc, "vad_stage_rows")
+        _pack_rows(ptr[sel], frames[sel] * c, width * c, src_esz, host.data_ptr() + at)
         off[sel] = at + np.arange(len(sel), dtype=np.int64) * width * c * src_esz
         at += len(sel) * width * c * src_esz
     return off
 
 
-def _slot_bytes(nbytes, direct, coded, staged=None):
-    """(pinned staging, device) bytes of a staging slot for a device batch of nbytes: pinned sources need no staging; pageable G.711 is
-    staged as bytes (half the int16 batch) and keeps a device copy of them BEHIND the batch, which the expansion reads; so do pageable
-    interleaved sources, whatever their codec (staged: their bytes), which the split reads."""
-    if direct:
-        return 0, nbytes
-    if staged is not None:
-        return staged, nbytes + staged
-    return (nbytes // 2, nbytes + nbytes // 2) if coded else (nbytes, nbytes)
+def _ingest_route(windowed, direct, interleaved, coded, nbytes, staged=0):
+    """How a device batch of `nbytes` gets into HBM, and the staging slot it needs: -> (route, (pinned staging bytes, device bytes)).
+      "cut"     the sources are device addresses inside an arena window's copy: the gather kernel cuts the batch out of it (how 2);
+      "pinned"  the sources sit in page-locked memory: the gather kernel reads them over the link, or one DMA per row (how 1 / 0);
+    neither needs staging.  Pageable sources are packed into the slot's pinned staging and cross the link in ONE copy:
+      "copy"    plain samples, straight into the batch;
+      "codes"   G.711 codes, staged as bytes (half the int16 batch) into a device block BEHIND the batch, which the expansion reads;
+      "sources" interleaved sources, whatever their codec (`staged`: their bytes), into such a block, which the split reads."""
+    if windowed or direct:
+        return "cut" if windowed else "pinned", (0, nbytes)
+    if interleaved:
+        return "sources", (staged, nbytes + staged)
+    if coded:
+        return "codes", (nbytes // 2, nbytes + nbytes // 2)
+    return "copy", (nbytes, nbytes)
 
 
-def _upload_rows(engine, rows_p, lens_p, codecs, n, width, esz, dst, how):
-    """vad_upload_rows, or vad_upload_rows_coded when the rows carry codecs (uint8 ids per row; dst is then int16)"""
-    if codecs is not None:
-        engine.upload_rows_coded(rows_p, lens_p, codecs, n, width, dst, how)
-    else:
-        engine.upload_rows(rows_p, lens_p, n, width, esz, dst, how)
+class _Batch:
+    """What a scheduler says about one batch of an upload, as plain arrays: `ptr` (uint64) the sources' addresses -- host ones, or
+    device ones on the window routes --, `lens` (int64) their samples (frames, where interleaved), `codecs` (uint8 ids) or None,
+    `channels` (uint8 counts: the sources are interleaved) or None with `rows_of` the int32 [sources, 2] batch row of each channel
+    (-1: not wanted), into a batch of n_rows x pitch samples.  Without channels, source j IS batch row j."""
+    __slots__ = ("ptr", "lens", "codecs", "channels", "rows_of", "n_rows", "pitch")
+
+    def __init__(self, ptr, lens, codecs, channels, rows_of, n_rows, pitch):
+        def arr(x, dtype):
+            return None if x is None else np.ascontiguousarray(x, dtype=dtype)
+
+        self.ptr, self.lens, self.codecs = arr(ptr, np.uint64), arr(lens, np.int64), arr(codecs, np.uint8)
+        self.channels, self.rows_of, self.n_rows, self.pitch = arr(channels, np.uint8), arr(rows_of, np.int32), n_rows, pitch
 
 
-def _gather_instead_of_dma():
-    import warnings
-    warnings.warn("SILERO_VAD_AMD_UPLOAD=dma: a DMA cannot expand G.711 -- such recordings take the gather kernel")
-    return 1
+class _Ingest:
+    """The one place that knows how a batch of rows gets into HBM (_ingest_route: the matrix of sample format x where the bytes lie);
+    the schedulers only say which rows (_Batch).  Made once per corpus call, after the plan: it holds the call's _Sources (`src`) and
+    what follows from them -- `direct` (every recording is page-locked: no host copy) and `how` (1 the gather kernel, 0 one DMA per row).
+    A scheduler that took a window route sets `windowed`.  Staging a batch has a host half (`host`) and a device half (`device`, inside
+    the scheduler's own `with torch.cuda.stream(pool.stream)`); the stream choreography around them is the scheduler's."""
+
+    def __init__(self, inp, recs, pool, engine, on_gpu):
+        self.pool, self.engine = pool, engine
+        self.dtype, self.esz, self.src_dtype, self.src_esz = inp.dtype, inp.esz, inp.src_dtype, inp.src_esz
+        self.coded, self.interleaved = inp.coded, inp.fan is not None
+        mode = _upload_mode()
+        self.src = _Sources(recs, inp.src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(engine, "upload_rows"))
+        self.direct = self.src.pinned
+        self.windowed = False
+        self.how = 0 if mode == "dma" else 1
+        if (self.coded or self.interleaved) and self.how == 0:
+            import warnings
+            warnings.warn("SILERO_VAD_AMD_UPLOAD=dma: a DMA cannot expand G.711 -- such recordings take the gather kernel")
+            self.how = 1
+        self.stage_sync = os.environ.get("SILERO_VAD_AMD_STAGE_SYNC", "1") != "0"   # (0: A/B -- the staged copies wait on the device)
+
+    def reserve(self, nbytes):
+        """every staging slot, sized for a batch of nbytes (prepare_only)"""
+        for k in range(self.pool.slots):
+            self.pool.get(k, *_ingest_route(self.windowed, self.direct, self.interleaved, self.coded, nbytes, nbytes * self.src_esz // self.esz)[1])
+
+    def host(self, k, b, since=None):
+        """The host half of staging batch k: its slot, pageable sources packed into the slot's pinned staging, the wait for the slot's
+        previous reader.  -> a handle, `d` its device batch [n_rows, pitch] and `slot` the slot's index.  since: where the caller's
+        clock for stage_s / upload_call_s started, if before the slot was taken (the refill loop has always counted the wait for the
+        slot into them, the bucket loop has not)."""
+        pool = self.pool
+        nbytes = b.n_rows * b.pitch * self.esz
+        staged = int(b.channels.sum()) * b.pitch * self.src_esz if self.interleaved else 0
+        route, (host_b, dev_b) = _ingest_route(self.windowed, self.direct, self.interleaved, self.coded, nbytes, staged)
+        i = pool.get(k, host_b, dev_b)
+        if route != "cut":
+            STATS["h2d_bytes"] += nbytes * self.src_esz // self.esz
+        STATS["buckets"] += 1
+        h = types.SimpleNamespace(slot=i, route=route, nbytes=nbytes, host=None, at=None,
+                                  d=pool.dev[i][:nbytes].view(self.dtype).view(b.n_rows, b.pitch))
+        # The slot's previous reader is done before anything is written: the cuts and the gather kernels wait for it on the stream.  A
+        # DMA -- the staged copy, the per-row copies -- issued behind an OPEN device-side wait leaves the copy engines' fast path (the
+        # refill window feed's finding, profiles/r06_refill_window_feed.md); the reader of this slot's previous batch started a few
+        # batches ago and is normally done by the time this one is staged, so it is waited for on the HOST, behind the staging, and the
+        # copy is issued without a dependency.
+        late_wait = None
+        if pool.consumed[i] is not None:
+            if route == "cut" or (route == "pinned" and self.how != 0) or not self.stage_sync:
+                pool.stream.wait_event(pool.consumed[i])
+            else:
+                late_wait = pool.consumed[i]
+        h.t0 = time.perf_counter() if since is None else since
+        if host_b:
+            h.host = pool.host[i][:host_b]
+            if route == "sources":
+                h.at = _stage_sources(b.ptr, b.lens, b.channels, b.pitch, self.src_esz, h.host)
+            else:
+                h.host = h.host.view(self.src_dtype).view(b.n_rows, b.pitch)
+                _pack_rows(b.ptr, b.lens, b.pitch, self.src_esz, h.host.data_ptr())
+            STATS["stage_s"] += time.perf_counter() - h.t0
+        if late_wait is not None:
+            late_wait.synchronize()
+        return h
+
+    def device(self, h, b):
+        """The device half: batch b into h.d -- enqueued on the current stream, the staging pool's."""
+        if h.route == "cut":
+            self._upload(b, b.ptr, 2, h.d)                # (2: the sources are device addresses)
+        elif h.route == "pinned":
+            self._upload(b, b.ptr, self.how, h.d)
+        elif h.route == "copy":
+            h.d.copy_(h.host, non_blocking=True)
+            return
+        else:
+            # the staged bytes cross the link in one copy, into the slot's device block behind the batch; the expansion / the split
+            # reads them there, the codes with the recordings' TRUE lengths (the staging's zero bytes are not audio)
+            block = self.pool.dev[h.slot][h.nbytes:h.nbytes + h.host.numel()]
+            block.view(h.host.shape).copy_(h.host, non_blocking=True)
+            at = h.at if h.route == "sources" else np.arange(b.n_rows, dtype=np.int64) * b.pitch
+            self._upload(b, block.data_ptr() + at, 2, h.d)
+            return
+        STATS["upload_call_s"] += time.perf_counter() - h.t0
+
+    def _upload(self, b, ptr, how, d):
+        """vad_upload_rows; vad_upload_rows_coded when the rows carry codecs (d is then int16); vad_upload_rows_channels when the
+        sources are interleaved"""
+        ptr = np.ascontiguousarray(ptr, dtype=np.uint64)
+        rows_p, lens_p = ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), b.lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
+        if b.channels is not None:
+            self.engine.upload_rows_channels(rows_p, lens_p, b.codecs, b.channels, b.rows_of, len(b.channels), b.n_rows, b.pitch, d, how)
+        elif b.codecs is not None:
+            self.engine.upload_rows_coded(rows_p, lens_p, b.codecs, b.n_rows, b.pitch, d, how)
+        else:
+            self.engine.upload_rows(rows_p, lens_p, b.n_rows, b.pitch, self.esz, d, how)
 
 
 class _Sources:
@@ -634,15 +760,6 @@ def _upload_mode():
     return os.environ.get("SILERO_VAD_AMD_UPLOAD", "")
 
 
-def _stage_into(src: "_Sources", idxs, width, dst: torch.Tensor):
-    """Pack recordings `idxs` into dst[len(idxs), width] (zero padded) with the native threaded copy."""
-    _, _, rows_p, lens_p = tabs = src.tables(idxs)
-    rc = lib().vad_stage_rows(rows_p, lens_p, len(idxs), width, dst.element_size(), dst.data_ptr(), 0)
-    del tabs
-    if rc:
-        raise _lib.VadError(rc, "vad_stage_rows")
-
-
 def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                    max_bytes: int = 256 << 20, plan: RaggedPlan = None, post=None, meta=None, lanes: int = 2, prepare_only: bool = False,
                    codec=None, channels=None, _fan=None):
@@ -674,19 +791,9 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     that list (channel_rows)."""
     t_setup = time.perf_counter()
     n = _rates(sampling_rate)[2]                          # input samples per chunk (512 k for a multiple of 16 kHz)
-    fan = _fan                                            # (a public caller resolved `channels=` already)
-    if fan is None:
-        audios, codec, fan = _channel_input(audios, codec, channels, model)
-    if fan is not None:                                   # interleaved recordings: `audios` the sources, lengths / plan / indices the rows'
-        audios, cd = fan.audios, fan.cd
-        as_i16, lengths = _describe(fan)
-    else:
-        audios, cd = _coded_input(audios, codec, model)
-        as_i16, lengths = _describe(audios)
-    coded = cd is not None
-    dtype = torch.int16 if as_i16 or coded else torch.float32
-    esz = 2 if as_i16 or coded else 4                     # the DEVICE batch; the source: 1 byte a sample for G.711
-    src_dtype, src_esz = (torch.uint8, 1) if coded else (dtype, esz)
+    inp = _corpus_input(audios, model, codec, channels, _fan)
+    audios, lengths, cd, fan = inp.recs, inp.lengths, inp.cd, inp.fan
+    dtype, esz, src_dtype, src_esz = inp.dtype, inp.esz, inp.src_dtype, inp.src_esz
     fast = model.audio_forward_device
     dev = getattr(model, "device", None)
     on_gpu = dev is not None and torch.device(dev).type == "cuda"
@@ -757,7 +864,8 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             if takes_windows(wp):
                 plan, audios = wp, packed
     plan = plan or RaggedPlan(lengths, max_waste, max_bytes, esz, None if fan is None else fan.mate)
-    src = _Sources(audios, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(getattr(model, "engine", None), "upload_rows"))
+    ing = _Ingest(inp, audios, pool, getattr(model, "engine", None), on_gpu)      # (after the plan: the window route reads the arena)
+    src = ing.src
     if not on_gpu:                                        # CPU stand-in models (tests)
         assert fan is None                                # (they were handed the de-interleaved recordings: _channel_input)
         if prepare_only:
@@ -765,14 +873,10 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         for idxs in plan.buckets:
             width = max(plan.lengths[idxs[0]], n)
             host = torch.empty((len(idxs), width), dtype=dtype)
-            _stage_into(src, idxs, width, host)
+            _pack_rows(src.ptr[idxs], src.len[idxs], width, host.element_size(), host.data_ptr())
             yield idxs, fast(host, sampling_rate).cpu()
         return
-    direct = src.pinned
-    how = 0 if mode == "dma" else 1
-    if (coded or fan is not None) and how == 0:
-        how = _gather_instead_of_dma()
-    windowed = direct and isinstance(plan, WindowedPlan)
+    windowed = ing.windowed = ing.direct and isinstance(plan, WindowedPlan)
 
     if windowed:
         if win["stream"] is None:                          # (a plan handed in by the caller, or prepare_only: nothing was started early)
@@ -797,8 +901,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         if plan.buckets:
             big_b = max(plan.buckets, key=lambda b: len(b) * ((max(plan.lengths[b[0]], n) + align - 1) // align * align))
             nb = len(big_b) * ((max(plan.lengths[big_b[0]], n) + align - 1) // align * align) * esz
-            for k in range(pool.slots):
-                pool.get(k, *_slot_bytes(nb, direct, coded, None if fan is None else nb * src_esz // esz))
+            ing.reserve(nb)
             if windowed:                                   # the three window buffers: warm torch's allocator with blocks of the largest window
                 wb = max((b - a) * src_esz for a, b in plan.span)
                 with torch.cuda.stream(win["stream"]):
@@ -812,8 +915,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     # kernel_rec.hip) beside the other lane's frontend.  The matrix-vector form of the recurrence (kernel_rec_small.hip) finishes a
     # bucket of a few hundred recordings 2-3 x sooner but spreads it over the whole chip, with nothing left to overlap with: the
     # pipelined corpus runs 4 % (window route) to 30 % (gather kernel) slower with it.  Lanes therefore pin the MFMA form.
-    import os as _os
-    lane_form = _os.environ.get("SILERO_VAD_AMD_LANE_REC", "mfma")     # (A/B: "auto" lets the lanes take the matrix-vector form)
+    lane_form = os.environ.get("SILERO_VAD_AMD_LANE_REC", "mfma")     # (A/B: "auto" lets the lanes take the matrix-vector form)
     lane_engines = []
     if len(lane_list) > 1 and lane_form != "auto":
         lane_engines = [e for e in (getattr(m, "engine", None) for m, _ in lane_list) if e is not None and hasattr(e, "set_transient")]
@@ -834,103 +936,41 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
                     eng_l.set_transient("rec_form", before)
 
     pin_lanes(True)
-    import os as _os
-    stage_sync = _os.environ.get("SILERO_VAD_AMD_STAGE_SYNC", "1") != "0"      # (0: A/B -- the staged copies wait on the device)
 
     def stage(k):
         idxs = plan.buckets[k]
         # at least one full window: audio_forward rejects shorter inputs (vad_annotator.py:124)
         L = max(plan.lengths[idxs[0]], n)
         width = (L + align - 1) // align * align          # row pitch
-        nbytes = len(idxs) * width * esz
-        staged = None
+        from_, lens, ch_k, rows_of = idxs, src.len, None, None
         if fan is not None:
             # the bucket's sources: one per recording, both channels wanted (a bucket does not end between them: _bucket_cuts)
-            recs_k, _, _, dst_k = fan.table(idxs)
-            fr_k, ch_k = np.ascontiguousarray(fan.frames[recs_k]), np.ascontiguousarray(fan.C[recs_k], dtype=np.uint8)
-            fr_p = fr_k.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
-            staged = int(ch_k.sum()) * width * src_esz
-        host_b, dev_b = _slot_bytes(nbytes, direct, coded, staged)
-        i = pool.get(k, host_b, dev_b)
-        if not windowed:
-            STATS["h2d_bytes"] += nbytes * src_esz // esz
-        STATS["buckets"] += 1
+            from_, _, _, rows_of = fan.table(idxs)
+            lens, ch_k = fan.frames, fan.C[from_]
+        # (a windowed bucket's sources are device addresses, known once its window is on its way: below)
+        b = _Batch(None if windowed else src.ptr[from_], lens[from_], None if cd is None else cd[from_], ch_k, rows_of, len(idxs), width)
         STATS["padded"] += len(idxs) * L
         STATS["real"] += sum(plan.lengths[j] for j in idxs)
-        d = pool.dev[i][:nbytes].view(dtype).view(len(idxs), width)
-        late_wait = None
-        if pool.consumed[i] is not None:                  # the device buffer's previous reader is done
-            if windowed or (direct and how != 0) or not stage_sync:
-                pool.stream.wait_event(pool.consumed[i])
-            else:
-                late_wait = pool.consumed[i]              # (a DMA: waited for on the HOST, behind the staging -- see below)
-        m_host = None
-        if meta is not None:                              # in the slot's own pinned scratch (meta_buffer: why)
-            mt = meta(idxs)
-            m_host = pool.meta_buffer(i, mt.numel()).view(mt.shape)
-            m_host.copy_(mt)
-        t0 = time.perf_counter()
-        if not direct:
-            if fan is not None:
-                host = pool.host[i][:host_b]
-                at_k = _stage_sources(src.ptr[recs_k], fr_k, ch_k, width, src_esz, host)
-            else:
-                host = pool.host[i][:host_b].view(src_dtype).view(len(idxs), width)
-                _stage_into(src, idxs, width, host)
-            STATS["stage_s"] += time.perf_counter() - t0
-            if late_wait is not None:
-                # the H2D copy below is a DMA: issued behind an OPEN device-side wait it leaves the copy engines' fast path (the refill
-                # window feed's finding, profiles/r06_refill_window_feed.md).  The reader of this slot's previous bucket started three
-                # buckets ago and is normally done by the time this one is staged: wait for it here, issue the copy without a dependency
-                late_wait.synchronize()
+        mt = meta(idxs) if meta is not None else None
+        h = ing.host(k, b)
+        i, d = h.slot, h.d
         if windowed:
             w = plan.window_of[k]
             ensure_window(w + 2)                          # this bucket's window and the two after it are on their way
             pool.stream.wait_event(win["ev"][w])
-            a0 = plan.span[w][0]
-            from_ = idxs if fan is None else recs_k
-            rows = np.ascontiguousarray(win["buf"][w % 3].data_ptr() + (audios.offsets[from_] - a0) * src_esz, dtype=np.uint64)
-            lens = np.ascontiguousarray(src.len[idxs]) if fan is None else fr_k
-        cd_k = np.ascontiguousarray(cd[idxs if fan is None else recs_k]) if coded else None
-
-        def upload(rows_p, lens_p, how_):
-            if fan is not None:
-                model.engine.upload_rows_channels(rows_p, lens_p, cd_k, ch_k, dst_k, len(recs_k), len(idxs), width, d, how_)
-            else:
-                _upload_rows(model.engine, rows_p, lens_p, cd_k, len(idxs), width, esz, d, how_)
-
+            b.ptr = np.ascontiguousarray(win["buf"][w % 3].data_ptr() + (audios.offsets[from_] - plan.span[w][0]) * src_esz, dtype=np.uint64)
         with torch.cuda.stream(pool.stream):
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record(pool.stream)
-            if windowed:
-                upload(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)), 2)
-                if last_bucket_of[w] == k:                # the window's buffer may take another window once this cut is done
-                    win["free"][w % 3] = torch.cuda.Event()
-                    win["free"][w % 3].record(pool.stream)
-                STATS["upload_call_s"] += time.perf_counter() - t0
-            elif direct:
-                if late_wait is not None:                 # (the per-row DMA route: the same rule)
-                    late_wait.synchronize()
-                tabs = src.tables(idxs if fan is None else recs_k)
-                upload(tabs[2], tabs[3] if fan is None else fr_p, how)
-                STATS["upload_call_s"] += time.perf_counter() - t0
-            elif fan is not None:
-                # the staged interleaved bytes cross the link in one copy, into the slot's device block behind the batch; the split
-                # reads them there
-                block = pool.dev[i][nbytes:nbytes + host_b]
-                block.copy_(host, non_blocking=True)
-                rows = np.ascontiguousarray(block.data_ptr() + at_k, dtype=np.uint64)
-                upload(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), fr_p, 2)
-            elif coded:
-                # the staged codes cross the link in one copy, into the slot's device block behind the batch; the expansion reads
-                # them there with the recordings' TRUE lengths (the staging's zero bytes are not audio)
-                codes = pool.dev[i][nbytes:nbytes + host_b].view(len(idxs), width)
-                codes.copy_(host, non_blocking=True)
-                rows = np.ascontiguousarray(codes.data_ptr() + np.arange(len(idxs), dtype=np.int64) * width, dtype=np.uint64)
-                upload(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), src.tables(idxs)[3], 2)
-            else:
-                d.copy_(host, non_blocking=True)
-            m_dev = m_host.to(dev, non_blocking=True) if m_host is not None else None
+            ing.device(h, b)
+            if windowed and last_bucket_of[w] == k:       # the window's buffer may take another window once this cut is done
+                win["free"][w % 3] = torch.cuda.Event()
+                win["free"][w % 3].record(pool.stream)
+            m_dev = m_host = None
+            if mt is not None:                            # through the slot's own pinned scratch (meta_buffer: why)
+                m_host = pool.meta_buffer(i, mt.numel()).view(mt.shape)
+                m_host.copy_(mt)
+                m_dev = m_host.to(dev, non_blocking=True)
             ev = torch.cuda.Event(enable_timing=True)
             ev.record(pool.stream)
         if not windowed:
@@ -1350,21 +1390,12 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     t_setup = time.perf_counter()
     net_sr, _, n = _rates(sampling_rate)
     eng = model.engine
-    fan = _fan                                         # (a public caller resolved `channels=` already)
-    if fan is None:
-        audios, codec, fan = _channel_input(audios, codec, channels, model)
-    if fan is not None:                                # interleaved recordings: `recs` the sources; lengths, plan, base, results the rows'
-        recs, cd = fan.audios, fan.cd
-    else:
-        audios, cd = _coded_input(audios, codec, model)
-        recs = audios
-    n_rows = len(audios) if fan is None else len(fan)
-    coded = cd is not None
+    inp = _corpus_input(audios, model, codec, channels, _fan)
+    recs, lengths, cd, fan = inp.recs, inp.lengths, inp.cd, inp.fan     # (interleaved: `recs` the sources; lengths, plan, base, results the rows')
+    dtype, esz, src_dtype, src_esz = inp.dtype, inp.esz, inp.src_dtype, inp.src_esz
+    n_rows = len(lengths)
     dev = torch.device(getattr(eng, "torch_device", None) or torch.device("cuda", eng.device))
     on_gpu = dev.type == "cuda"
-    as_i16, lengths = _describe(audios if fan is None else fan)
-    dtype, esz = (torch.int16, 2) if as_i16 or coded else (torch.float32, 4)     # the DEVICE slab; the source: 1 byte a sample for G.711
-    src_dtype, src_esz = (torch.uint8, 1) if coded else (dtype, esz)
     lens_np = np.asarray(lengths, dtype=np.int64).reshape(-1)
     slots = max(1, min(int(slots), int((lens_np > 0).sum())))
     mode = _upload_mode()
@@ -1413,11 +1444,6 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     STATS["refill_window_buffers"] = max(STATS["refill_window_buffers"], n_buf)
     plan = plan or RefillPlan(lens_np, slots, slab_chunks, n)
     B, S, width = plan.slots, plan.slab_chunks, plan.slab_chunks * n
-    src = _Sources(recs, src_dtype, check_pinned=on_gpu and mode != "stage" and hasattr(eng, "upload_rows"))
-    direct = src.pinned                                # pinned recordings: one gather kernel per slab, no host copy
-    how = 0 if mode == "dma" else 1
-    if (coded or fan is not None) and how == 0:
-        how = _gather_instead_of_dma()
     base = np.zeros(n_rows + 1, dtype=np.int64)   # recording i owns out_flat[base[i] : base[i] + n_chunks(i)]
     np.cumsum(np.where(lens_np > 0, (lens_np + n - 1) // n, 0), out=base[1:])
     total = int(base[-1])
@@ -1426,6 +1452,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     state = torch.zeros((2, B, 128), dtype=torch.float32, device=dev)
     done = np.zeros(n_rows, dtype=np.int64)       # chunks of each recording already produced
     ctxm = contextlib.nullcontext() if not on_gpu else torch.cuda.device(dev)
+    pool = None
     with ctxm:
         if on_gpu:
             pool = getattr(model, "_stage_pool", None)
@@ -1437,7 +1464,9 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
         STATS["padded"] += plan.padded_chunks() * n
         STATS["real"] += int(lens_np[lens_np > 0].sum())
 
-        ptr0 = src.ptr
+        ing = _Ingest(inp, recs, pool, eng, on_gpu)    # (pinned recordings: one gather kernel per slab, no host copy)
+        ing.windowed = wf is not None
+        ptr0 = ing.src.ptr
         if on_gpu and hasattr(eng, "reserve"):
             eng.reserve(sampling_rate, B, S)
         if wf is not None:
@@ -1505,8 +1534,7 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
         # known when its first slab is staged).  A small copy per slab costs the large transfers beside it far more than its bytes:
         # the refill route's window DMAs ran at 0.907 of the link with a 2 MB copy per slab and the scans' three small ones, 0.949
         # without them (profiles/r06_refill_window_feed.md).
-        import os as _os
-        G = max(1, int(_os.environ.get("SILERO_VAD_AMD_REFILL_GROUP", "8")))
+        G = max(1, int(os.environ.get("SILERO_VAD_AMD_REFILL_GROUP", "8")))
         n_slabs_all = len(plan.slab_arrays)
         grp = {"g": -1, "host": [None, None], "ev": [None, None], "dev": None, "roff": {}, "next": 0}
 
@@ -1570,15 +1598,14 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
         def stage(k):
             e = plan.slab_arrays[k]                                        # [entries, 5], vectorised bookkeeping
             sl, rec, at, take = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
-            staged = None
             if fan is not None:
                 # the slab's sources: the slots that read the same frames of one recording -- its two channels, admitted together --
                 # share one
                 src_k, at_k, _, dst_k = fan.table(rec, at, sl)
-                ch_k = np.ascontiguousarray(fan.C[src_k], dtype=np.uint8)
-                rows = np.ascontiguousarray(ptr0[src_k] + (at_k * fan.C[src_k] * src_esz).astype(np.uint64))
-                lens = np.ascontiguousarray(np.minimum(fan.frames[src_k] - at_k, width))
-                cd_k = np.ascontiguousarray(cd[src_k]) if coded else None
+                ch_k = fan.C[src_k].astype(np.uint8)
+                rows = ptr0[src_k] + (at_k * fan.C[src_k] * src_esz).astype(np.uint64)
+                lens = np.minimum(fan.frames[src_k] - at_k, width)
+                cd_k = None if cd is None else cd[src_k]
                 if len(sl) < B:
                     # a slot without a recording: an empty one-channel source names it, so the row is zeros as on the mono path
                     idle = np.setdiff1d(np.arange(B, dtype=np.int64), sl)
@@ -1586,97 +1613,50 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
                     rows = np.concatenate([rows, np.zeros(len(idle), dtype=np.uint64)])
                     lens = np.concatenate([lens, np.zeros(len(idle), dtype=np.int64)])
                     cd_k = None if cd_k is None else np.concatenate([cd_k, np.zeros(len(idle), dtype=np.uint8)])
-                    dst_k = np.ascontiguousarray(np.concatenate([dst_k, np.stack([idle, np.full(len(idle), -1)], axis=1).astype(np.int32)]))
-                staged = int(ch_k.sum()) * width * src_esz
+                    dst_k = np.concatenate([dst_k, np.stack([idle, np.full(len(idle), -1)], axis=1).astype(np.int32)])
+                b = _Batch(rows, lens, cd_k, ch_k, dst_k, B, width)
             else:
                 rows = np.zeros(B, dtype=np.uint64)
                 lens = np.zeros(B, dtype=np.int64)
                 rows[sl] = ptr0[rec] + (at * src_esz).astype(np.uint64)
                 lens[sl] = take
                 cd_k = None
-                if coded:
+                if cd is not None:
                     cd_k = np.zeros(B, dtype=np.uint8)                        # (a slot without a recording: an empty row, zeros)
                     cd_k[sl] = cd[rec]
-            rows_p = rows.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
-            lens_p = lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
-
-            def upload(rows_p_, how_):
-                if fan is None:
-                    _upload_rows(eng, rows_p_, lens_p, cd_k, B, width, esz, d, how_)
-                    return
-                eng.upload_rows_channels(rows_p_, lens_p, cd_k, ch_k, dst_k, len(ch_k), B, width, d, how_)
-
-            nbytes = B * width * esz
+                b = _Batch(rows, lens, cd_k, None, None, B, width)
             t0 = time.perf_counter()
-            if on_gpu:
-                host_b, dev_b = _slot_bytes(nbytes, direct, coded, staged)
-                i = pool.get(k, host_b, dev_b)
-                host = None if direct else pool.host[i][:host_b] if fan is not None else pool.host[i][:host_b].view(src_dtype).view(B, width)
-            else:
-                assert fan is None                                            # (a CPU stand-in was handed the de-interleaved recordings)
-                i, host = 0, torch.empty((B, width), dtype=dtype)
-            if host is not None and fan is not None:
-                off_k = _stage_sources(rows, lens, ch_k, width, src_esz, host)
-                STATS["stage_s"] += time.perf_counter() - t0
-            elif host is not None:
-                rc = lib().vad_stage_rows(rows_p, lens_p, B, width, src_esz, host.data_ptr(), 0)
-                if rc:
-                    raise _lib.VadError(rc, "vad_stage_rows")
-                STATS["stage_s"] += time.perf_counter() - t0
-            STATS["buckets"] += 1
             if not on_gpu:
+                assert fan is None                                            # (a CPU stand-in was handed the de-interleaved recordings)
+                host = torch.empty((B, width), dtype=dtype)
+                _pack_rows(b.ptr, b.lens, width, src_esz, host.data_ptr())
+                STATS["stage_s"] += time.perf_counter() - t0
+                STATS["buckets"] += 1
                 idx_k, rs_k = slab_meta(k)
-                return host, None, i, idx_k, rs_k
-            if wf is None:
-                STATS["h2d_bytes"] += nbytes * src_esz // esz
-            else:
+                return host, None, 0, idx_k, rs_k
+            idx_k, rs_k = slab_meta(k)                                      # (the group's one copy goes out with its first slab)
+            h = ing.host(k, b, since=t0)
+            if wf is not None:
                 issue_windows(k)
                 for v in wf["by_first"].pop(k, ()):                         # the windows this slab is the first to read
                     pool.stream.wait_event(wf["ev"].pop(v))
-            d = pool.dev[i][:nbytes].view(dtype).view(B, width)
-            idx_k, rs_k = slab_meta(k)                                      # (the group's one copy goes out with its first slab)
-            if pool.consumed[i] is not None:
-                # (a DMA -- the staged copy, the per-row copies -- is issued behind a COMPLETE event, waited for on the host: behind an
-                #  open device-side wait it leaves the copy engines' fast path, as in the bucket routes' stage(); the upload kernels wait
-                #  on the device)
-                if wf is None and (not direct or how == 0) and os.environ.get("SILERO_VAD_AMD_STAGE_SYNC", "1") != "0":
-                    pool.consumed[i].synchronize()
-                else:
-                    pool.stream.wait_event(pool.consumed[i])
             with torch.cuda.stream(pool.stream):
+                ing.device(h, b)
                 if wf is not None:
-                    upload(rows_p, 2)                                          # (2: the rows are device addresses)
-                    STATS["upload_call_s"] += time.perf_counter() - t0
-                    for v in wf["by_last"].pop(k, ()):                         # the windows this slab is the last to read: released
+                    for v in wf["by_last"].pop(k, ()):                     # the windows this slab is the last to read: released
                         rel = torch.cuda.Event()
                         rel.record(pool.stream)
                         wf["release"][v] = rel
-                elif direct:
-                    upload(rows_p, how)
-                    STATS["upload_call_s"] += time.perf_counter() - t0
-                elif fan is not None:                                          # staged interleaved bytes: one copy, split from the slot's device block
-                    block = pool.dev[i][nbytes:nbytes + host_b]
-                    block.copy_(host, non_blocking=True)
-                    at_dev = np.ascontiguousarray(block.data_ptr() + off_k, dtype=np.uint64)
-                    upload(at_dev.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), 2)
-                elif coded:                                                    # staged codes: one copy, expanded from the slot's device block
-                    codes = pool.dev[i][nbytes:nbytes + host_b].view(B, width)
-                    codes.copy_(host, non_blocking=True)
-                    at_dev = np.ascontiguousarray(codes.data_ptr() + np.arange(B, dtype=np.int64) * width, dtype=np.uint64)
-                    upload(at_dev.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), 2)
-                else:
-                    d.copy_(host, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(pool.stream)
-            pool.done[i] = ev
-            return d, ev, i, idx_k, rs_k
+            pool.done[h.slot] = ev
+            return h.d, ev, h.slot, idx_k, rs_k
 
         n_slabs = len(plan.slab_arrays)
         STATS["setup_s"] += time.perf_counter() - t_setup
         if prepare_only:
             if on_gpu:
-                for k in range(pool.slots):
-                    pool.get(k, *_slot_bytes(B * width * esz, direct, coded, None if fan is None else B * width * src_esz))
+                ing.reserve(B * width * esz)
                 torch.cuda.synchronize(dev)
             return None, base, plan
         staged = stage(0) if n_slabs else None
@@ -1706,24 +1686,23 @@ def _refill_iter(audios: Sequence, model, sampling_rate: int, slots: int, slab_c
     return out_flat, base, plan
 
 
-def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, codec=None, _fan=None):
-    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec, _fan=_fan)
+def _drain(gen):
+    """run a generator to its end -> its return value"""
     while True:
         try:
-            next(it)
+            next(gen)
         except StopIteration as stop:
             return stop.value
+
+
+def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, codec=None, _fan=None):
+    return _drain(_refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec, _fan=_fan))
 
 
 def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None, channels=None):
     """Everything a refill run over these recordings allocates, allocated now (`ragged_reserve`'s twin): the arena windows' device
     buffers, the staging slots, the engine's scratch, the block the flat probability tensor will take.  Returns the plan."""
-    it = _refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True, codec=codec, channels=channels)
-    while True:
-        try:
-            next(it)
-        except StopIteration as stop:
-            return stop.value[2]
+    return _drain(_refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True, codec=codec, channels=channels))[2]
 
 
 def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32,

@@ -263,6 +263,72 @@ def test_corpus_routes_equal_their_twins(model, oracle, tag, kind):
                 assert np.abs(probs[i].numpy() - want).max() < TIGHT, i
 
 
+def route_corpora():
+    """Six recordings of 2 ... 6 chunks with odd tails at 16 kHz, three times over: as plain int16, as G.711 codes of both laws, as
+    interleaved int16 (every third one mono) -> {format: (recordings, codec, channels, int16 twins)}.  (The seed: packed back to back,
+    most recordings of every format start at a misaligned byte, which make_containers asserts.)"""
+    from silero_vad_amd import g711_expand
+    from test_corpus_g711 import LAWS, encode
+    recs, chans, _, twins = stereo_recordings("16k", "s16", count=6, lo=2, hi=6, seed=23, single_frame=False)
+    plain = [twins[sum(chans[:i])] for i in range(6)]           # (a recording's first channel)
+    assert chans.count(2) == 4 and all(512 < len(x) <= 6 * 512 and len(x) % 512 for x in plain)
+    laws = [LAWS[i % 2] for i in range(6)]
+    codes = [encode(x, lw) for x, lw in zip(plain, laws)]
+    expanded = [g711_expand(c, lw) for c, lw in zip(codes, laws)]
+    return {"plain": (plain, None, None, plain), "g711": (codes, laws, None, expanded), "stereo": (recs, None, chans, twins)}
+
+
+# which engine method carries a batch, and with which `how` (0 one DMA per row, 1 the gather kernel over the link, 2 the gather kernel
+# over device memory): by sample format and by where the bytes lie.  None: no upload call at all -- ONE copy straight into the batch.
+METHOD = {"plain": "upload_rows", "g711": "upload_rows_coded", "stereo": "upload_rows_channels"}
+HOW = {"arena": {"plain": 2, "g711": 2, "stereo": 2},           # cut from an arena window's device copy
+       "pinned": {"plain": 1, "g711": 1, "stereo": 1},          # scattered page-locked recordings
+       "pageable": {"plain": None, "g711": 2, "stereo": 2},     # staged: the codes / the interleaved bytes into a block behind the batch
+       "dma": {"plain": 0, "g711": 1, "stereo": 1}}             # SILERO_VAD_AMD_UPLOAD=dma: a DMA neither expands nor splits
+
+
+@pytest.mark.parametrize("kind", ["arena", "pinned", "pageable", "dma"])
+def test_every_route_calls_its_upload(model, monkeypatch, kind):
+    """Each cell of the ingest matrix -- plain int16 / G.711 / interleaved recordings x arena windows / scattered pinned / pageable --
+    reaches HBM through the engine method and the `how` that the matrix names, in the bucket scheduler and in the refill scheduler.
+    So few recordings do not pass the window routes' density rule on their own: the arena runs under SILERO_VAD_AMD_UPLOAD=window.
+    Under SILERO_VAD_AMD_UPLOAD=dma plain pinned recordings take one DMA per row; coded and interleaved ones cannot, say so in a
+    warning, take the gather kernel and give the gather run's probabilities."""
+    import warnings
+    from silero_vad_amd import ragged_probs, refill_probs
+    calls = []
+    for name in METHOD.values():
+        def counting(*a, _name=name, _real=getattr(model.engine, name), **kw):
+            calls.append((_name, kw["how"] if "how" in kw else a[-1]))
+            return _real(*a, **kw)
+        monkeypatch.setattr(model.engine, name, counting)
+    schedulers = {"ragged_probs": lambda a, **kw: ragged_probs(a, model, 16000, **kw),
+                  "refill_probs": lambda a, **kw: refill_probs(a, model, 16000, slots=4, slab_chunks=2, **kw)}
+    for fmt, (recs, codec, chans, twins) in route_corpora().items():
+        n_rows = len(twins)
+        inter, _ = make_containers("pinned" if kind == "dma" else kind, recs, chans or [1] * 6, twins)
+        results = {}
+        for name, call in schedulers.items():
+            monkeypatch.delenv("SILERO_VAD_AMD_UPLOAD", raising=False)
+            if kind == "dma":
+                results["gather"] = call(inter, codec=codec, channels=chans)
+            if kind in ("arena", "dma"):
+                monkeypatch.setenv("SILERO_VAD_AMD_UPLOAD", "window" if kind == "arena" else "dma")
+            del calls[:]
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                results[name] = got = call(inter, codec=codec, channels=chans)
+            want = HOW[kind][fmt]
+            assert len(got) == n_rows
+            assert set(calls) == (set() if want is None else {(METHOD[fmt], want)}), (fmt, name, sorted(set(calls)))
+            downgraded = [w for w in caught if "SILERO_VAD_AMD_UPLOAD=dma" in str(w.message)]
+            assert len(downgraded) == (1 if kind == "dma" and fmt != "plain" else 0), (fmt, name, [str(w.message) for w in caught])
+            for i, (p, q) in enumerate(zip(got, results.get("gather", got))):
+                assert torch.equal(p, q), (fmt, name, i)
+        for i, (p, q) in enumerate(zip(results["ragged_probs"], results["refill_probs"])):      # (both are the single call's bits)
+            assert p.numel() > 1 and torch.equal(p, q), (fmt, i)
+
+
 def test_raw_48k_stereo_arena(model):
     import warnings
     from silero_vad_amd import ragged_probs

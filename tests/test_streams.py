@@ -672,3 +672,23 @@ def test_ragged_reserve_is_harmless_without_a_gpu(built):
     got = ragged_probs(audios, m, 16000)
     want = ragged_probs(audios, OracleModel(), 16000)
     assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
+def test_ingest_route_and_slot_sizes():
+    """The ingest matrix as a pure function: for every combination of (windowed, direct, interleaved, coded) the route a batch of N
+    bytes takes into HBM and the (pinned staging, device) bytes its staging slot needs -- a batch that is cut from an arena window or
+    gathered from page-locked recordings needs no staging; a pageable plain batch is staged whole; pageable G.711 is staged as codes,
+    half the int16 batch, and keeps their device copy behind the batch; pageable interleaved sources of S bytes likewise."""
+    import itertools
+    from silero_vad_amd.streams import _ingest_route
+    N, S = 6 * 1024 * 2, 4 * 1024 * 2 + 1024
+    want = {(0, 0, 0, 0): ("copy", (N, N)), (0, 0, 0, 1): ("codes", (N // 2, N + N // 2)),
+            (0, 0, 1, 0): ("sources", (S, N + S)), (0, 0, 1, 1): ("sources", (S, N + S)),
+            (0, 1, 0, 0): ("pinned", (0, N)), (0, 1, 0, 1): ("pinned", (0, N)), (0, 1, 1, 0): ("pinned", (0, N)), (0, 1, 1, 1): ("pinned", (0, N)),
+            (1, 1, 0, 0): ("cut", (0, N)), (1, 1, 0, 1): ("cut", (0, N)), (1, 1, 1, 0): ("cut", (0, N)), (1, 1, 1, 1): ("cut", (0, N)),
+            # (a window route always reads page-locked memory; the function does not depend on being told so)
+            (1, 0, 0, 0): ("cut", (0, N)), (1, 0, 0, 1): ("cut", (0, N)), (1, 0, 1, 0): ("cut", (0, N)), (1, 0, 1, 1): ("cut", (0, N))}
+    for key in itertools.product((0, 1), repeat=4):
+        windowed, direct, interleaved, coded = (bool(v) for v in key)
+        assert _ingest_route(windowed, direct, interleaved, coded, N, S) == want[key], key
+    assert _ingest_route(False, False, False, True, N) == ("codes", (N // 2, N + N // 2))      # (staged bytes: only interleaved sources')
