@@ -278,6 +278,35 @@ int  vad_segment_probs_device(vad_engine *e, const float *probs, long ldp, const
                               const long *n_chunks, long n_chunks_all, const long *audio_len, const vad_segment_params *p,
                               vad_segment *out, long cap_per_stream, long *counts, void *stream);
 
+/* ---- the audio the segments keep ----------------------------------------------------------------------------------------------
+ * collect_chunks / drop_chunks (src/silero_vad/utils_vad.py:552-655) for every row of a batch that is still in HBM, right behind
+ * vad_segment_probs_device: the samples inside (invert = 0) or outside (invert = 1, up to audio_len[i]) row i's segments, packed, so
+ * that only the kept audio leaves the device -- or none of it, for a consumer on the same GPU.  All pointers are DEVICE pointers.
+ * pcm[n_streams][ld] of elem_size 2 (int16) or 4 (float32) is the batch as vad_forward_audio[_i16] received it; it holds raw-rate
+ * samples, 16 kHz sample s of row i is pcm[i * ld + s * step], step 1, 2 or 3 (16 / 32 / 48 kHz).  audio_len (16 kHz samples), segs,
+ * cap_per_stream (<= 512) and counts are what the scan was given and wrote.  A segment is clamped to [0, audio_len[i]] and one with
+ * end < start is empty; audio_len[i] itself is confined to the samples a row of ld elements holds.
+ * Two phases, both asynchronous on `stream`:
+ *   out == NULL  COUNT: kept[i] = the number of samples row i keeps; -1 for a row with counts[i] > cap_per_stream (its list is
+ *                incomplete: rescan it with room, or collect it on the host with vad_collect_segments).  pcm and out_offset are not read.
+ *   out != NULL  GATHER: row i's kept[i] samples go to out + out_offset[i] (in elements).  The caller derives out_offset from kept --
+ *                an exclusive sum of the kept counts, each rounded up to 16 bytes, keeps every row's start 16-byte aligned, which is
+ *                what the kernel's vector stores want (any other offset is honoured element by element) -- and sizes out by it.
+ *                Exactly kept[i] elements are written per row: the padding between rows and everything behind the last row is not
+ *                touched.  Rows with kept[i] <= 0 write nothing.
+ * Bit for bit what vad_collect_segments gives for each row.  VAD_ERR_ARG, before anything is queued: elem_size not 2 or 4, step not
+ * 1 ... 3, invert not 0 or 1, a negative size, cap_per_stream above 512, a NULL audio_len / counts / kept (segs with a cap; pcm and
+ * out_offset with out), pcm not aligned to its elements, out not 16-byte aligned.  A host-only engine: VAD_ERR_NO_DEVICE.          */
+int  vad_collect_segments_device(vad_engine *e, const void *pcm, size_t elem_size, long ld, int step, long n_streams,
+                                 const long *audio_len, const vad_segment *segs, long cap_per_stream, const long *counts,
+                                 int invert, long *kept, const long *out_offset, void *out, void *stream);
+/* host twin, one stream, re-entrant, no GPU: the same samples of pcm (a HOST pointer; sample s at element s * step) for n_segs
+ * segments, in one pass.  Returns the number of samples the segments keep: they were written to out if out is given and cap (the
+ * room of out, in samples) holds them; with out == NULL or a cap that is too small nothing is written and the number says what is
+ * needed.  -VAD_ERR_ARG for a bad elem_size / step / invert, a negative size, NULL segs with n_segs > 0, NULL pcm with samples to copy. */
+long vad_collect_segments(const void *pcm, size_t elem_size, int step, long audio_len, const vad_segment *segs, long n_segs,
+                          int invert, void *out, long cap);
+
 /* The streaming caller, VADIterator.__call__ (src/silero_vad/utils_vad.py:507-549), for every slot of a lock-step batch: probs[n]
  * = this tick's probabilities (what vad_step left, copied to the host), active (may be NULL = all) marks the slots that carry a
  * live stream.  triggered / temp_end / current_sample are the iterator's per-stream state (zero after a reset, :500-503), updated

@@ -231,6 +231,18 @@ hipError_t launch_scan(const float *probs, long ldp, const long *row_off, long n
                        const long *audio_len, const vad_segment_params &p, vad_segment *out, long cap, long *counts,
                        hipStream_t s);
 
+// The audio inside (invert 0) or outside (invert 1) every row's segments, packed (kernel_collect.hip's two phases; the parts are
+// collector.hpp).  pcm[n_rows][ld] of esz 2 | 4, 16 kHz sample s of a row at element s * step; segs[n_rows][cap] / counts[] as
+// launch_scan left them, cap <= kCollectMaxCap (the gather keeps a row's prefix of part lengths in LDS).
+//   launch_count_kept        kept[i] = samples row i keeps, -1 where counts[i] > cap
+//   launch_collect_segments  row i's kept[i] samples to out + out_offset[i] (elements); nothing else is written
+constexpr long kCollectMaxCap = 512;
+hipError_t launch_count_kept(long ld, int step, long n_rows, const long *audio_len, const vad_segment *segs, long cap, const long *counts,
+                             int invert, long *kept, hipStream_t s);
+hipError_t launch_collect_segments(const void *pcm, int esz, long ld, int step, long n_rows, const long *audio_len, const vad_segment *segs,
+                                   long cap, const long *counts, int invert, const long *kept, const long *out_offset, void *out,
+                                   hipStream_t s);
+
 // test hook: y[i] = sigmoid (kind 0) / tanh (kind 1) of x[i] exactly as the recurrent kernels evaluate them (activations.hpp)
 hipError_t launch_activation_probe(int kind, const float *x, float *y, long n, hipStream_t s);
 

@@ -851,6 +851,31 @@ int vad_segment_probs_device(vad_engine *e, const float *probs, long ldp, const 
     return VAD_OK;
 }
 
+int vad_collect_segments_device(vad_engine *e, const void *pcm, size_t elem_size, long ld, int step, long n_streams,
+                                const long *audio_len, const vad_segment *segs, long cap_per_stream, const long *counts,
+                                int invert, long *kept, const long *out_offset, void *out, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    // (the arguments first: a host-only engine refuses a malformed call for what is wrong with it)
+    if (elem_size != 2 && elem_size != 4) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: elem_size must be 2 (int16) or 4 (float32)");
+    if (step < 1 || step > 3) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: step must be 1, 2 or 3");
+    if (invert != 0 && invert != 1) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: invert must be 0 or 1");
+    if (ld < 0 || n_streams < 0 || cap_per_stream < 0) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: negative size");
+    if (cap_per_stream > vad::kCollectMaxCap) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: cap_per_stream above 512");
+    if (n_streams > 0 && (!audio_len || !counts || !kept || (cap_per_stream > 0 && !segs)))
+        return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: null audio_len, counts, kept or segs");
+    if (out && n_streams > 0 && (!pcm || !out_offset)) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: null pcm or out_offset");
+    if (((size_t)pcm) % elem_size) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: pcm is not aligned to its elements");
+    if (((size_t)out) & 15) return fail(e, VAD_ERR_ARG, "vad_collect_segments_device: out is not 16-byte aligned");
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!out)
+        HIP_TRY(e, vad::launch_count_kept(ld, step, n_streams, audio_len, segs, cap_per_stream, counts, invert, kept, (hipStream_t)stream));
+    else
+        HIP_TRY(e, vad::launch_collect_segments(pcm, (int)elem_size, ld, step, n_streams, audio_len, segs, cap_per_stream, counts, invert,
+                                                kept, out_offset, out, (hipStream_t)stream));
+    return VAD_OK;
+}
+
 int vad_reserve(vad_engine *e, int sr, int B, long T) {
     if (!e) return VAD_ERR_ARG;
     if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");

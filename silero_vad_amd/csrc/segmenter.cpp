@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/silero_vad_hip.h"
+#include "collector.hpp"
 #include "host_threads.hpp"
 #include "scanner.hpp"
 
@@ -67,6 +68,44 @@ extern "C" long vad_segment_probs_batch(const float *probs, long ldp, long n_str
     long total = 0;
     for (long i = 0; i < n_streams; ++i) total += counts[i];
     return total;
+}
+
+// collect_chunks / drop_chunks (reference src/silero_vad/utils_vad.py:552-655) for one stream, the host twin of the device gather
+// (kernel_collect.hip; one source for what a part is: collector.hpp): the samples inside (invert 0) or outside (invert 1) the segments
+// of a 16 kHz signal whose sample s is element s * step of pcm.  One pass; returns the number of samples the segments keep -- written
+// when out is given and they fit its cap, only counted otherwise.
+extern "C" long vad_collect_segments(const void *pcm, size_t elem_size, int step, long audio_len, const vad_segment *segs, long n_segs,
+                                     int invert, void *out, long cap) {
+    if ((elem_size != 2 && elem_size != 4) || step < 1 || step > 3 || (invert != 0 && invert != 1) || audio_len < 0 || n_segs < 0 ||
+        cap < 0 || (n_segs > 0 && !segs))
+        return -VAD_ERR_ARG;
+    const long parts = vad::collect_parts(n_segs, invert);
+    long need = 0;
+    for (long k = 0; k < parts; ++k) {
+        const vad::Part p = vad::collect_part(segs, n_segs, k, audio_len, invert);
+        need += p.b > p.a ? (long)(p.b - p.a) : 0;
+    }
+    if (!out || need > cap) return need;
+    if (need > 0 && !pcm) return -VAD_ERR_ARG;
+    long at = 0;
+    for (long k = 0; k < parts; ++k) {
+        const vad::Part p = vad::collect_part(segs, n_segs, k, audio_len, invert);
+        if (p.b <= p.a) continue;
+        const long m = (long)(p.b - p.a);
+        if (elem_size == 2) {
+            const int16_t *s = static_cast<const int16_t *>(pcm) + p.a * step;
+            int16_t *d = static_cast<int16_t *>(out) + at;
+            if (step == 1) std::copy(s, s + m, d);
+            else for (long j = 0; j < m; ++j) d[j] = s[j * step];
+        } else {
+            const uint32_t *s = static_cast<const uint32_t *>(pcm) + p.a * step;       // (bit patterns: a copy never touches a NaN)
+            uint32_t *d = static_cast<uint32_t *>(out) + at;
+            if (step == 1) std::copy(s, s + m, d);
+            else for (long j = 0; j < m; ++j) d[j] = s[j * step];
+        }
+        at += m;
+    }
+    return need;
 }
 
 // VADIterator (reference src/silero_vad/utils_vad.py:507-549) for every slot of a lock-step batch: one call advances all n streams

@@ -36,9 +36,11 @@ from ._lib import lib
 
 # Cumulative counters of the corpus path since the last STATS.clear() (bench.py --config corpus reads them):
 # stage_s host packing into pinned memory, h2d_bytes / h2d_s the H2D copies themselves (hipEvents on the copy
-# stream), scan_s the native segmenter, buckets, padded / real samples staged.
+# stream), scan_s the native segmenter, buckets, padded / real samples staged; ragged_speech_audio: collect_bytes the audio kept on the
+# device, audio_d2h_bytes / audio_d2h_s what of it was brought home (copy-stream events), collect_host_rows the rows left to the host.
 STATS = collections.defaultdict(float)
 TRACE = None             # bring-up: set to a list to collect (slab, t before on_slab, t after, t after stage) from the refill loop
+AUDIO_TRACE = None       # measurement: set to a list to collect (start event, end event, bytes) of ragged_speech_audio's D2H copies
 
 
 def chunk_size(sr: int) -> int:
@@ -762,7 +764,7 @@ def _upload_mode():
 
 def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                    max_bytes: int = 256 << 20, plan: RaggedPlan = None, post=None, meta=None, lanes: int = 2, prepare_only: bool = False,
-                   codec=None, channels=None, _fan=None):
+                   codec=None, channels=None, _fan=None, post_batch: bool = False):
     """Generator over the plan's buckets: yields (indices, probs[len(indices), T_bucket] on the CPU).
     Recording i of a bucket owns the first ceil(len_i / N) entries of its row.
 
@@ -770,7 +772,10 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     right after the bucket's kernels; the generator then yields (indices, [those tensors on the CPU], probs_dev) and
     the probabilities themselves never leave the GPU (ragged_speech_segments scans them there).  `meta` (indices ->
     small CPU int64 tensor) rides to the GPU with the bucket's PCM on the copy stream (pinned, asynchronous), so that
-    nothing in the loop blocks the host on the compute stream.  `lanes`: buckets are issued round-robin to this many
+    nothing in the loop blocks the host on the compute stream.  `post_batch`: `post` is called as (probs_dev, indices, meta_dev, x)
+    with x the bucket's batch [len(indices), L] as the kernels read it (int16 or float32, raw rate; its rows keep the staging slot's
+    pitch) -- valid only for the work `post` enqueues: the slot is handed to a later bucket once that work is done (the slot's
+    `consumed` event is recorded behind `post`).  `lanes`: buckets are issued round-robin to this many
     engines on their own streams (_compute_lanes); results are yielded in bucket order.  `prepare_only`: plan the run, create the lanes
     and their streams, size every lane's scratch and the staging slots for the plan's largest bucket -- everything that allocates --
     and stop (ragged_reserve): a run over the same recordings then allocates nothing.
@@ -997,9 +1002,9 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
                 if m_dev is not None:
                     m_dev.record_stream(lane_stream)
                 probs = lane_model.audio_forward_device(x, sampling_rate)   # asynchronous
-                pool.consumed[slot] = torch.cuda.Event()
+                back = [probs] if post is None else post(probs, idxs, m_dev, x) if post_batch else post(probs, idxs, m_dev)
+                pool.consumed[slot] = torch.cuda.Event()      # (behind post: with post_batch it reads x)
                 pool.consumed[slot].record(lane_stream)
-                back = [probs] if post is None else post(probs, idxs, m_dev)
                 outs = []
                 for o in back:                            # pinned blocks come from torch's caching host allocator
                     h = torch.empty(o.shape, dtype=o.dtype, pin_memory=True)
@@ -1087,6 +1092,12 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
     back over PCIe; otherwise the probabilities are copied to the host and scanned by the native threaded scanner.
     Both give the same segments (one source, csrc/scanner.hpp).  `sampling_rate` may be a multiple of 16000 (raw recordings, _rates):
     the segments are then in samples of the 16 kHz signal x[::k], as the reference's scan sees it (utils_vad.py:301-307)."""
+    return _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads, device_scan, as_arrays, codec, channels, None, scan_kw)
+
+
+def _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads, device_scan, as_arrays, codec, channels, collector, scan_kw):
+    """ragged_speech_segments; with a `collector` (_AudioCollector: ragged_speech_audio) every bucket's gather is enqueued behind its
+    scan and the collector is told each bucket's final segment table.  Without one, the calls are those of ragged_speech_segments."""
     net_sr, dec, n = _rates(sampling_rate)
     audios, codec, fan = _channel_input(audios, codec, channels, model)
     lengths = _describe(audios if fan is None else fan)[1]
@@ -1105,12 +1116,17 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
             lens = lens_t[idxs]
             return torch.stack([(lens + n - 1) // n, (lens + dec - 1) // dec])
 
-        def post(probs_dev, idxs, both):
+        def post(probs_dev, idxs, both, x=None):
             counts, segs = _device_scan(model.engine, probs_dev, both[0], both[1], params, cap0)
-            return [counts, segs]
+            if collector is None:
+                return [counts, segs]
+            return [counts, segs] + collector.enqueue(x, both[1], counts, segs)
 
-        for idxs, (counts, segs), probs_dev in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes,
-                                                              post=post, meta=meta, codec=codec, _fan=fan):
+        if collector is not None:
+            collector.open(audios, _codec_of(audios, codec) if fan is None else fan.cd, fan, lengths)
+        for idxs, outs, probs_dev in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, post=post, meta=meta,
+                                                    codec=codec, _fan=fan, post_batch=collector is not None):
+            counts, segs = outs[0], outs[1]
             t0 = time.perf_counter()
             cnt = counts.numpy()
             if len(cnt) and int(cnt.max()) > cap0:             # rare: rescan this bucket with room for all
@@ -1119,7 +1135,12 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
                 cnt, segs = c2.cpu().numpy(), s2.cpu()
             parts.append((np.asarray(idxs, dtype=np.int64), cnt.copy(), segs.numpy()))
             STATS["scan_s"] += time.perf_counter() - t0
+            if collector is not None:
+                collector.bucket(idxs, parts[-1][1], parts[-1][2], outs[2], outs[3])
     else:
+        if collector is not None:
+            raise RuntimeError("ragged_speech_audio collects on the device, behind the device scan: it needs a GPU model backed by the "
+                               "native engine (and device_scan left on); there is no host route")
         for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec, _fan=fan):
             lens = [lengths[i] for i in idxs]
             t0 = time.perf_counter()
@@ -1148,6 +1169,192 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
         return counts_all, flat
     fl = flat.tolist()
     return [[{"start": a, "end": b} for a, b in fl[first[i]:first[i + 1]]] for i in range(len(lengths))]
+
+
+def collect_chunks_device(engine, pcm_dev: torch.Tensor, segs_dev: torch.Tensor, counts_dev: torch.Tensor, audio_len_dev: torch.Tensor,
+                          step: int = 1, invert: bool = False):
+    """`collect_chunks` (invert: `drop_chunks`) for every row of a batch that is on the GPU beside its scan, asynchronous on the current
+    stream (vad_collect_segments_device: the count phase, the offsets, the gather) -> (out_dev, offsets, kept), all on the device.
+
+    pcm_dev[B, W]: int16 or float32 rows with unit stride inside a row, as `audio_forward_device` received them; `step` 1, 2 or 3: the
+    batch holds raw 16 / 32 / 48 kHz samples, 16 kHz sample s of a row is its element s * step.  segs_dev[B, cap, 2] / counts_dev[B]:
+    what the device scan wrote (cap <= 512); audio_len_dev[B]: the 16 kHz lengths the scan was given.  Row i's kept[i] samples are
+    out_dev[offsets[i] : offsets[i] + kept[i]]; every offset is a multiple of 16 bytes and the elements between rows are uninitialised.
+    kept[i] == -1: the row is left to the caller -- its segment list did not fit `cap` (rescan it), or, for hand-made overlapping
+    segments only, it keeps more than out_dev has room for (out_dev is sized like the batch itself, which lists of disjoint segments
+    cannot exceed; nothing here waits for the device to learn a size)."""
+    if not (torch.is_tensor(pcm_dev) and pcm_dev.is_cuda and pcm_dev.dim() == 2 and pcm_dev.dtype in (torch.int16, torch.float32)):
+        raise ValueError("pcm_dev must be a 2-D CUDA tensor of int16 or float32 samples")
+    B, W = pcm_dev.shape
+    if W > 1 and pcm_dev.stride(1) != 1:
+        raise ValueError("pcm_dev: the samples of a row must be contiguous")
+    if step not in (1, 2, 3):
+        raise ValueError(f"step must be 1, 2 or 3, got {step!r}")
+    dev, esz = pcm_dev.device, pcm_dev.element_size()
+    if segs_dev.dim() != 3 or segs_dev.shape[0] != B or segs_dev.shape[2] != 2 or counts_dev.shape != (B,) or audio_len_dev.shape != (B,):
+        raise ValueError("segs_dev[B, cap, 2], counts_dev[B] and audio_len_dev[B] need one entry per row of pcm_dev")
+    for t in (segs_dev, counts_dev, audio_len_dev):
+        if t.dtype != torch.int64 or t.device != dev:
+            raise ValueError("segs_dev, counts_dev and audio_len_dev must be int64 tensors on pcm_dev's device")
+    segs_dev, counts_dev = segs_dev.contiguous(), counts_dev.contiguous()
+    per = 16 // esz                                            # elements of a 16-byte granule: every row of out starts on one
+    room = (W + step - 1) // step                              # 16 kHz samples a row holds
+    alen = audio_len_dev.clamp(max=room).contiguous()
+    ld = pcm_dev.stride(0) if B > 1 else W
+    capacity = B * ((room + per - 1) // per * per)
+    out = torch.empty(capacity, dtype=pcm_dev.dtype, device=dev)
+    kept = torch.empty(B, dtype=torch.int64, device=dev)
+    offsets = torch.zeros(B, dtype=torch.int64, device=dev)
+    if B == 0:
+        return out, offsets, kept
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def phase(out_ptr):
+        _lib.check(engine._h, lib().vad_collect_segments_device(
+            engine._h, pcm_dev.data_ptr(), esz, ld, int(step), B, alen.data_ptr(), segs_dev.data_ptr(), segs_dev.shape[1],
+            counts_dev.data_ptr(), 1 if invert else 0, kept.data_ptr(), offsets.data_ptr(), out_ptr, stream))
+
+    phase(None)
+    padded = (kept.clamp(min=0) + (per - 1)) // per * per
+    ends = torch.cumsum(padded, 0)
+    offsets = (ends - padded).contiguous()
+    kept = torch.where(ends <= capacity, kept, torch.full_like(kept, -1)).contiguous()
+    phase(out.data_ptr())
+    return out, offsets, kept
+
+
+class _AudioCollector:
+    """ragged_speech_audio's half of the bucket loop (_speech_segments): `enqueue` puts a bucket's gather behind its scan on the lane's
+    stream; `bucket` is told the bucket's final segments once the host has them (and kept[] with them) and brings the kept bytes home
+    on a stream of its own -- or leaves them where they are --; rows the device left alone are collected from their recording on the
+    host (vad_collect_segments)."""
+
+    def __init__(self, model, step, invert, on_device):
+        self.model, self.step, self.invert, self.on_device = model, step, invert, on_device
+        self.held = collections.deque()                        # packed outputs of the buckets in flight, oldest first
+        self.events = []
+        self.audio = self.dtype = self.dev = None
+        self.copy_stream = None
+
+    def open(self, audios, cd, fan, lengths):
+        self.audios, self.cd, self.fan, self.lengths = audios, cd, fan, lengths
+        self.audio = [None] * len(lengths)
+
+    def enqueue(self, x, audio_len_dev, counts, segs):
+        out, offsets, kept = collect_chunks_device(self.model.engine, x, segs, counts, audio_len_dev, self.step, self.invert)
+        self.dtype, self.dev = out.dtype, out.device
+        self.held.append(out)
+        return [kept, offsets]
+
+    def _stream(self):
+        """where the audio goes home: not a compute lane, and beside the lanes where the hardware queues allow it"""
+        if self.copy_stream is None:
+            pool = self.model._stage_pool
+            st = getattr(pool, "audio_stream", None)
+            if st is None:
+                lanes = [s for _, s in _compute_lanes(self.model, pool.slots - 1)]
+                st = pool.audio_stream = _distinct_queue_stream(getattr(self.model, "engine", None), self.dev, lanes)
+            self.copy_stream = st
+        return self.copy_stream
+
+    def bucket(self, idxs, cnt, segs, kept, offsets):
+        out = self.held.popleft()
+        kept, offsets = kept.numpy(), offsets.numpy()
+        live = kept > 0
+        total = int((offsets[live] + kept[live]).max()) if live.any() else 0
+        esz = out.element_size()
+        STATS["collect_bytes"] += int(kept[live].sum()) * esz
+        if self.on_device:
+            buf = out[:total]
+            out.record_stream(torch.cuda.current_stream(self.dev))      # (allocated on a lane's stream, read by the caller's)
+        else:
+            buf = torch.empty(total, dtype=out.dtype, pin_memory=True)
+            if total:
+                # the bucket is done (the loop waited for it): nothing to wait for on the device, the copy overlaps the later buckets
+                st = self._stream()
+                with torch.cuda.stream(st):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(st)
+                    buf.copy_(out[:total], non_blocking=True)
+                    e1.record(st)
+                out.record_stream(st)
+                self.events.append((e0, e1))
+                if AUDIO_TRACE is not None:
+                    AUDIO_TRACE.append((e0, e1, total * esz))
+                STATS["audio_d2h_bytes"] += total * esz
+        # every row's view in ONE call (a slice per row costs more host time than a bucket's gather costs the device): the cuts are
+        # each row's first and one-past-last element, so the odd pieces are the rows and the even ones the padding between them
+        cuts = np.stack([offsets, offsets + np.maximum(kept, 0)], axis=1).reshape(-1)
+        cuts = np.minimum(np.maximum.accumulate(cuts), total)  # (rows the device left alone own nothing of buf)
+        views = torch.tensor_split(buf, cuts.tolist())[1::2]
+        for r, i in enumerate(idxs):
+            self.audio[i] = views[r] if kept[r] >= 0 else self._on_host(i, segs[r, :int(cnt[r])])
+
+    def _on_host(self, i, segs):
+        """row i from its recording: the twin's raw-rate samples (g711_expand / deinterleave), every step-th of them inside the segments"""
+        STATS["collect_host_rows"] += 1
+        rec, ch, C = (i, 0, 1) if self.fan is None else (int(self.fan.rec_of[i]), int(self.fan.ch_of[i]), int(self.fan.C[self.fan.rec_of[i]]))
+        a = self.audios[rec]
+        a = a if torch.is_tensor(a) else torch.as_tensor(a)
+        raw = a.detach().cpu().contiguous().numpy()
+        c = None if self.cd is None else int(self.cd[rec])
+        if self.fan is not None:
+            raw = deinterleave(raw, C, ch, c)
+        elif c is not None:
+            raw = g711_expand(raw, c)
+        raw = np.ascontiguousarray(raw, dtype=np.int16 if self.dtype == torch.int16 else np.float32)
+        alen = (len(raw) + self.step - 1) // self.step
+        sg = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 2)
+        args = (raw.ctypes.data if raw.size else None, raw.itemsize, self.step, alen, sg.ctypes.data if len(sg) else None, len(sg),
+                1 if self.invert else 0)
+        need = lib().vad_collect_segments(*args, None, 0)
+        if need < 0:
+            raise _lib.VadError(-need, "vad_collect_segments")
+        res = np.empty(need, raw.dtype)
+        if lib().vad_collect_segments(*args, res.ctypes.data if need else None, need) != need:
+            raise _lib.VadError(1, "vad_collect_segments")
+        t = torch.from_numpy(res)
+        return t.to(self.dev) if self.on_device else t
+
+    def finish(self):
+        for e0, e1 in self.events:
+            e1.synchronize()
+            STATS["audio_d2h_s"] += e0.elapsed_time(e1) / 1e3
+        dtype = self.dtype
+        if dtype is None:                                      # no bucket ran: every recording is empty
+            dtype = torch.int16
+        for i, a in enumerate(self.audio):
+            if a is None:                                      # an empty recording is in no bucket
+                self.audio[i] = torch.empty(0, dtype=dtype, device=self.dev if self.on_device and self.dev is not None else "cpu")
+        return self.audio
+
+
+def ragged_speech_audio(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15, max_bytes: int = 256 << 20,
+                        keep: str = "speech", on_device: bool = False, as_arrays: bool = False, codec=None, channels=None, **scan_kw):
+    """`ragged_speech_segments` AND the audio its segments keep -> (segments, audio): the speech of every recording (keep="speech",
+    `collect_chunks`) or everything but the speech (keep="nonspeech", `drop_chunks`), collected on the GPU from the batch rows the scan
+    ran on (vad_collect_segments_device, csrc/kernel_collect.hip) -- the recordings are not expanded, split, decimated or sliced on the
+    host again, and only the kept bytes cross the link back, on a stream of their own while the following buckets compute.
+
+    `segments` is exactly what `ragged_speech_segments` returns for the same arguments (`as_arrays` included).  `audio[i]` is a 1-D tensor
+    of the batch's sample type -- int16 for int16 and G.711 recordings, float32 for float ones.  With recording i's TWIN being the
+    recording after `g711_expand`, `deinterleave` and the reference's decimation x[::k] for a multiple of 16 kHz (`decimate`), so that
+    segments and samples share the 16 kHz axis, audio[i] == collect_chunks(segments[i], twin_i) (drop_chunks for keep="nonspeech"),
+    bit for bit.  A recording without segments gives an EMPTY tensor under keep="speech": the reference's `torch.cat([])` raises there,
+    this call does not.  With `channels=` there is one entry per (recording, channel), in `channel_rows` order.
+
+    on_device=True leaves the tensors on the GPU, as views of one packed buffer per bucket (for a consumer on the same device: nothing
+    crosses the link); otherwise they are views of one pinned host buffer per bucket.  A recording with more segments than the scan's
+    optimistic room (24) is collected on the host from its recording (vad_collect_segments) with the same result.  Needs a GPU model
+    backed by the native engine.  The continuous-refill route (refill_*) holds a recording only a slab at a time and has no such
+    call: out of scope.  STATS: collect_bytes (kept on the device), audio_d2h_bytes / audio_d2h_s (brought home)."""
+    if keep not in ("speech", "nonspeech"):
+        raise ValueError(f"keep must be 'speech' or 'nonspeech', got {keep!r}")
+    if "device_scan" in scan_kw or "threads" in scan_kw:
+        raise TypeError("ragged_speech_audio always scans on the device: device_scan / threads are not arguments of it")
+    col = _AudioCollector(model, _rates(sampling_rate)[1], keep == "nonspeech", bool(on_device))
+    segments = _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, 0, None, as_arrays, codec, channels, col, scan_kw)
+    return segments, col.finish()
 
 
 def _segment_params(sampling_rate=16000, threshold=0.5, neg_threshold=None, min_speech_duration_ms=250,
