@@ -688,6 +688,44 @@ long vad_deinterleave(int codec, int channels, int channel, const void *in, long
 int  vad_host_register(void *p, size_t bytes);
 int  vad_host_unregister(void *p);
 
+/* ---- resampling to the net's rate ---------------------------------------------------------------------------------------------
+ * The reference's front door, read_audio(path, sampling_rate) (src/silero_vad/utils_vad.py:138-172), brings a 44.1 / 22.05 / 24 /
+ * 11.025 kHz file to the model's rate with torchaudio's default Resample: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99.
+ * That function, as arithmetic (not torchaudio's bits): g = gcd(src, dst), O = src / g, N = dst / g, base = min(O, N) * 0.99,
+ * W = ceil(6 O / base); for phase j in [0, N) and tap i in [0, 2 W + O)
+ *     t = clamp((-j / N + (i - W) / O) * base, -6, 6),   h[j][i] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos(t pi / 12)^2 * base / O,
+ * evaluated in double and rounded to float32; with the input x (float32, or int16 / 32768) taken as zero outside [0, n),
+ *     out[q N + j] = sum_i h[j][i] x[q O + i - W],   cut to ceil(N n / O) samples.
+ * The clamp makes every tap outside one short run per phase exactly 0.0f; the table holds that run only: first[j], its first dense
+ * tap, and K taps, K the longest run of the pair (a shorter run is followed by 0.0f).  44100 -> 16000: O 441, N 160, W 17, K 34.
+ * Served: dst 8000 or 16000, src != dst, O <= 1024, N <= 1024, K <= 160 (88200 -> 8000 has K 134, 11025 -> 16000 has N 640; the
+ * caps bound the table and keep the span of input one tile of the kernel stages in LDS under 64 KiB).  Any other pair is
+ * VAD_ERR_SAMPLE_RATE.  NOT the same thing as a forward call's sr = 32000 / 48000: that is the reference's x[::k] inside the model
+ * (no low-pass); src = 48000 here is read_audio's low-pass resample.  Both exist in the reference.
+ * Non-finite samples poison the outputs whose K stored taps cover them; a dense convolution would poison the whole 2 W + O window
+ * (0 * NaN).  That is not emulated.
+ * The first four need no engine and no GPU.                                                                                      */
+int  vad_resample_geometry(int src, int dst, int *O, int *N, int *W, int *K);      /* any pointer may be NULL */
+/* ceil(N n / O): the samples n input samples become; -VAD_ERR_SAMPLE_RATE, -VAD_ERR_ARG (n < 0) */
+long vad_resample_length(int src, int dst, long n);
+/* The pair's table, the ONE source of it for the device, the host twin and Python: taps[N][K] row-major, first[N]. */
+int  vad_resample_table(int src, int dst, float *taps /* [N][K] */, int32_t *first /* [N] */);
+/* host twin, re-entrant: n samples of elem_size 2 (int16) or 4 (float32) at pcm -> out[0 .. vad_resample_length(src, dst, n)); the
+ * same table, every sum accumulated in double over the K stored taps in order and rounded once to float32. */
+int  vad_resample_host(int src, int dst, const void *pcm, size_t elem_size, long n, float *out);
+/* The device route: pcm = DEVICE [n][ld] at rate src, elem_size 2 or 4; lens[r] = live samples of row r, a device-visible table
+ * (device or page-locked memory, like vad_upload_rows' row table) that must stay valid until the stream has passed the call;
+ * dst_buf = DEVICE float32 [n][ldd], ldd >= width_out.  Sample m of row r is the sum above for m < ceil(N lens[r] / O) and exactly
+ * 0.0f from there to width_out (the reference cuts the resampled signal, then audio_forward zero-pads its last chunk).  A row ends
+ * at lens[r] (clamped to [0, ld]): the batch behind it is not read, whatever it holds.  fp32 accumulation in tap order, a function
+ * of the output index alone: a recording gives the same bits in any row of any batch at any pitch; each output is within
+ * (K + 1) 2^-24 sum_k |h_k x_k| of vad_resample_host's.  Asynchronous on `stream`, no synchronisation; nothing is allocated once
+ * the pair's table is on the device -- vad_resample_reserve puts it there up front (beside vad_reserve; an engine and its clones
+ * share the tables), otherwise the first call of a pair does, with two blocking copies.                                          */
+int  vad_resample_reserve(vad_engine *e, int src, int dst);
+int  vad_resample_rows_device(vad_engine *e, int src, int dst, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                              long width_out, float *dst_buf, long ldd, void *stream);
+
 /* The continuous-refill schedule of silero_vad_amd/streams.py RefillPlan (the reference's padded lock-step batch, tuning/utils.py:146-160,
  * with rows retired and re-admitted): recording q (in admission order) occupies a stream slot for need[q] time slabs; at every slab
  * boundary every free slot, lowest first, takes the next recording.  Writes the slab at which q is admitted and its slot.  Host only. */

@@ -139,6 +139,12 @@ SYMBOLS = {
     "vad_upload_rows_channels": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_long), c_void_p, c_void_p, c_void_p, c_long, c_long, c_long,
                                          c_void_p, c_int, c_void_p]),
     "vad_deinterleave": (c_long, [c_int, c_int, c_int, c_void_p, c_long, c_void_p]),
+    "vad_resample_geometry": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "vad_resample_length": (c_long, [c_int, c_int, c_long]),
+    "vad_resample_table": (c_int, [c_int, c_int, c_void_p, c_void_p]),
+    "vad_resample_host": (c_int, [c_int, c_int, c_void_p, c_size_t, c_long, c_void_p]),
+    "vad_resample_reserve": (c_int, [c_void_p, c_int, c_int]),
+    "vad_resample_rows_device": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_void_p]),
     "vad_refill_schedule": (c_int, [POINTER(c_long), c_long, c_long, POINTER(c_long), POINTER(c_long)]),
     "vad_refill_table": (c_long, [POINTER(c_long)] * 5 + [c_long, c_long, c_long, c_long, POINTER(c_long), POINTER(c_long)]),
     "vad_streams_overlap": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
+#include <vector>
 
 #include "../../include/silero_vad_hip.h"
 
@@ -223,6 +225,31 @@ struct ChanRowDesc {
 };
 hipError_t launch_gather_channels(const ChanRowDesc *src, long n, long width, int frame_bytes, void *dst_i16, bool rows_on_device,
                                   hipStream_t s);
+
+// Resampling to the net's rate (kernel_resample.hip; the function, the table and the kernel's shape are described there).
+constexpr int kResampleTile = 1024;          // outputs of one row a workgroup makes
+constexpr int kResampleMaxRatio = 1024;      // caps of the pairs served (vad_resample_geometry): O = src / gcd and N = dst / gcd ...
+constexpr int kResampleMaxTaps = 160;        // ... and K, the taps of a phase's live run
+struct ResampleGeom {
+    int O, N, W, K;
+    int dlo, dhi;                            // min / max over the phases of first[j] - floor(j O / N)
+    int span;                                // floats of LDS a tile stages at most
+};
+struct ResampleHostTable {                   // the one source of the table: taps[N][K] (a shorter run is followed by 0.0f), first[N]
+    ResampleGeom g;
+    std::vector<float> taps;
+    std::vector<int32_t> first;
+};
+std::shared_ptr<const ResampleHostTable> resample_table(int src, int dst);      // null: the pair is not served; built once per process
+struct ResampleDeviceTable {
+    ResampleGeom g;
+    float *taps;                             // TRANSPOSED, [K][N]: lanes of consecutive phases read consecutive floats
+    int32_t *first;
+};
+// dst[r][m] = output m of row r for m < ceil(N lens[r] / O), 0.0f from there to width_out; pcm[n][ld] of esz 2 (int16, / 32768) or 4
+// (float32); lens: device-visible.  Input at and past lens[r] (clamped to ld) counts as zero whatever the batch holds.
+hipError_t launch_resample_rows(const ResampleDeviceTable &t, const void *pcm, int esz, long ld, const long *lens, long n, long width_out,
+                                float *dst, long ldd, hipStream_t s);
 
 // Segmenter on the device (kernel_scan.hip): lane i scans probs[i * ldp ...] (or probs[row_off[i] ...] if row_off is
 // not null), n_chunks[i] entries (or n_chunks_all if n_chunks is null), writes its segments to out[i * cap ...] and

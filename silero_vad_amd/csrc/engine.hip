@@ -40,9 +40,17 @@ struct vad_images {
 #if VAD_AB
     float *d_front[2] = {}, *d_front_wino[2] = {};
 #endif
+    // the resampling tables in device memory, one per (src, dst) pair ever asked for (vad_resample_reserve / vad_resample_rows_device);
+    // an engine and its clones -- the lanes of a corpus run, each on a thread or stream of its own -- share them
+    std::mutex resample_mutex;
+    std::map<std::pair<int, int>, vad::ResampleDeviceTable> resample;
     ~vad_images() {
         if (device < 0) return;
         (void)hipSetDevice(device);
+        for (auto &kv : resample) {
+            if (kv.second.taps) (void)hipFree(kv.second.taps);
+            if (kv.second.first) (void)hipFree(kv.second.first);
+        }
         for (int ni = 0; ni < 2; ++ni) {
             if (d_front4[ni]) (void)hipFree(d_front4[ni]);
             if (d_whh[ni]) (void)hipFree(d_whh[ni]);
@@ -884,6 +892,65 @@ int vad_reserve(vad_engine *e, int sr, int B, long T) {
     if (B <= 0 || T <= 0) return fail(e, VAD_ERR_ARG, "bad argument");
     HIP_TRY(e, hipSetDevice(e->device));
     return ensure_scratch(e, sr, B, T, nullptr);
+}
+
+namespace {
+// The device image of the pair's table, made on first use: the transposed taps and first[] (kernel_resample.hip), two blocking copies.
+int resample_device_table(vad_engine *e, int src, int dst, const vad::ResampleDeviceTable **out) {
+    auto host = vad::resample_table(src, dst);
+    if (!host) return fail(e, VAD_ERR_SAMPLE_RATE, "resampling serves dst 8000 / 16000 from another rate whose reduced ratio O : N and taps K fit the caps (vad_resample_geometry)");
+    std::lock_guard<std::mutex> g(e->img->resample_mutex);
+    auto it = e->img->resample.find({src, dst});
+    if (it == e->img->resample.end()) {
+        const int N = host->g.N, K = host->g.K;
+        std::vector<float> tr((size_t)N * K);
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < K; ++k) tr[(size_t)k * N + j] = host->taps[(size_t)j * K + k];
+        vad::ResampleDeviceTable t{host->g, nullptr, nullptr};
+        if (hipMalloc((void **)&t.taps, tr.size() * sizeof(float)) != hipSuccess ||
+            hipMalloc((void **)&t.first, (size_t)N * sizeof(int32_t)) != hipSuccess) {
+            if (t.taps) (void)hipFree(t.taps);
+            (void)hipGetLastError();
+            return fail(e, VAD_ERR_ALLOC, "cannot allocate the resampling table");
+        }
+        if (hipMemcpy(t.taps, tr.data(), tr.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(t.first, host->first.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(t.taps);
+            (void)hipFree(t.first);
+            (void)hipGetLastError();
+            return fail(e, VAD_ERR_HIP, "cannot copy the resampling table to the device");
+        }
+        it = e->img->resample.emplace(std::make_pair(src, dst), t).first;
+    }
+    *out = &it->second;                              // (std::map: the entry stays where it is)
+    return VAD_OK;
+}
+}  // namespace
+
+int vad_resample_reserve(vad_engine *e, int src, int dst) {
+    if (!e) return VAD_ERR_ARG;
+    if (!vad::resample_table(src, dst)) return fail(e, VAD_ERR_SAMPLE_RATE, "vad_resample_reserve: the pair is not served (vad_resample_geometry)");
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    const vad::ResampleDeviceTable *t = nullptr;
+    return resample_device_table(e, src, dst, &t);
+}
+
+int vad_resample_rows_device(vad_engine *e, int src, int dst, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                             long width_out, float *dst_buf, long ldd, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (!vad::resample_table(src, dst)) return fail(e, VAD_ERR_SAMPLE_RATE, "vad_resample_rows_device: the pair is not served (vad_resample_geometry)");
+    if (elem_size != 2 && elem_size != 4) return fail(e, VAD_ERR_ARG, "vad_resample_rows_device: elem_size must be 2 (int16) or 4 (float32)");
+    if (n < 0 || width_out < 0 || ld < 0 || ldd < width_out) return fail(e, VAD_ERR_ARG, "vad_resample_rows_device: negative size, or ldd < width_out");
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (n == 0 || width_out == 0) return VAD_OK;
+    if (!pcm || !lens || !dst_buf) return fail(e, VAD_ERR_ARG, "vad_resample_rows_device: null pointer");
+    if (((size_t)pcm) % elem_size || ((size_t)dst_buf & 3)) return fail(e, VAD_ERR_ARG, "vad_resample_rows_device: pcm / dst is not aligned to its elements");
+    HIP_TRY(e, hipSetDevice(e->device));
+    const vad::ResampleDeviceTable *t = nullptr;
+    if (int rc = resample_device_table(e, src, dst, &t)) return rc;
+    HIP_TRY(e, vad::launch_resample_rows(*t, pcm, (int)elem_size, ld, lens, n, width_out, dst_buf, ldd, (hipStream_t)stream));
+    return VAD_OK;
 }
 
 unsigned long vad_scratch_generation(const vad_engine *e) { return e ? e->scratch_gen : 0; }

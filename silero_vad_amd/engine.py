@@ -212,6 +212,20 @@ class Engine:
         self._check(self._L.vad_upload_rows_channels(self._h, rows, frames, cp, hp, dst_row.ctypes.data, n, n_dst, width, dst.data_ptr(), how,
                                                      self._stream()))
 
+    def resample_reserve(self, src, dst):
+        """The (src, dst) pair's resampling table onto the device, up front (vad_resample_reserve): `resample_rows` then allocates nothing."""
+        self._check(self._L.vad_resample_reserve(self._h, int(src), int(dst)))
+
+    def resample_rows(self, src, dst, pcm, lens, width_out, out):
+        """pcm [n, L] (int16 or float32, cuda, unit sample stride) at rate `src`, lens int64 [n] device-visible (cuda or pinned): the
+        live samples of each row -> out [n, >= width_out] float32 (cuda) at rate `dst`, on the current stream (vad_resample_rows_device):
+        row r resampled up to ceil(N lens[r] / O), exact zeros from there to width_out."""
+        assert pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1 and out.is_cuda and out.dtype == torch.float32 and out.stride(1) == 1
+        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == pcm.shape[0] == out.shape[0] and out.shape[1] >= width_out
+        n = pcm.shape[0]
+        self._check(self._L.vad_resample_rows_device(self._h, int(src), int(dst), pcm.data_ptr(), pcm.element_size(), pcm.stride(0) if n > 1 else pcm.shape[1],
+                                                     lens.data_ptr(), n, width_out, out.data_ptr(), out.stride(0) if n > 1 else out.shape[1], self._stream()))
+
     def streams_overlap(self, a, b) -> bool:
         """vad_streams_overlap: do kernels on torch streams a and b run beside each other (distinct hardware queues)?"""
         rc = self._L.vad_streams_overlap(self._h, a.cuda_stream, b.cuda_stream)

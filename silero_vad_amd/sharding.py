@@ -58,7 +58,7 @@ def gather_to_rank0(obj, group=None):
 
 def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate: int = 16000,
                             rank: int = 0, world_size: int = 1, balance: str = "duration",
-                            scheduler: str = "buckets", codec=None, channels=None, **kwargs) -> List[list]:
+                            scheduler: str = "buckets", codec=None, channels=None, source_rate=None, **kwargs) -> List[list]:
     """`get_speech_timestamps` over many recordings (the reference's pattern is one worker process
     per file, examples/parallel_example.ipynb cells 5, 7): this rank processes its shard --
     `balance="duration"` (default) deals recordings out by total audio length, `"count"` by contiguous
@@ -71,6 +71,8 @@ def batch_speech_timestamps(audios: Sequence[torch.Tensor], model, sampling_rate
     are interleaved int16 samples or G.711 codes, as a WAV data chunk holds a recorded call; a recording goes to one rank whole, is
     split on the device, and the result has one entry per (recording, channel), recording-major (`streams.channel_rows`): that of the
     call on the `deinterleave`d recordings."""
+    from .streams import _no_source_rate
+    _no_source_rate(source_rate, "batch_speech_timestamps")
     import warnings
 
     from .streams import _Fanned, _channels_of, _codec_of, deinterleave, g711_expand, ragged_speech_segments, refill_speech_segments

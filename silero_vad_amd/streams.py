@@ -755,6 +755,39 @@ class _Sources:
                 lens.ctypes.data_as(ctypes.POINTER(ctypes.c_long)))
 
 
+def _resampled_len(L, rs):
+    """samples of a recording of L raw samples behind the resampler (rs = (O, N) of _source_rate, or None: no resampler)"""
+    return L if rs is None else (L * rs[1] + rs[0] - 1) // rs[0]
+
+
+def _resample_input(audios, codec, channels, model, source_rate, sampling_rate, fan=None):
+    """`source_rate=` resolved, once, where a corpus call opens: -> (audios, codec, channels, rs).  rs = (O, N) and the recordings as
+    handed over for a model whose engine resamples on the device (Engine.resample_rows); for any other (a CPU stand-in) the recordings
+    come back RESAMPLED on the host -- `channels=` and `codec=` resolved first, then `resample`: float32 at the net's rate, rs None --,
+    the definition of what the device route computes."""
+    rs = _source_rate(source_rate, sampling_rate)
+    if rs is None or hasattr(getattr(model, "engine", None), "resample_rows"):
+        return audios, codec, channels, rs
+    assert fan is None                                    # (a stand-in never gets interleaved recordings: _channel_input)
+    recs, cd = _coded_input(*_channel_input(audios, codec, channels, model)[:2], model)
+    return [torch.from_numpy(resample(a, source_rate, sampling_rate)) for a in recs], None, None, None
+
+
+def _lane_resampled_bytes(rows, width):
+    return rows * ((width + 3) // 4 * 4) * 4
+
+
+def _lane_resampled(lane_model, rows, width):
+    """[rows, width] float32 of the lane's buffer of resampled audio, rows 16-byte aligned (the frontend's vector loads); made on the
+    current stream, the lane's, which alone uses it: bucket k + lanes resamples into it behind bucket k's kernels in stream order."""
+    need = _lane_resampled_bytes(rows, width)
+    buf = getattr(lane_model, "_resample_buf", None)
+    if buf is None or buf.numel() < need:
+        buf = lane_model._resample_buf = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=lane_model.device)
+        STATS["resample_allocs"] += 1
+    return buf[:need].view(torch.float32).view(rows, -1)[:, :width]
+
+
 def _upload_mode():
     """How pinned recordings reach the GPU: "window" (a PackedRecordings whose recordings lie back to back: one DMA per arena
     window, batches cut on the device; the default where it applies), "gather" (one kernel that reads host memory; the default
@@ -764,7 +797,7 @@ def _upload_mode():
 
 def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                    max_bytes: int = 256 << 20, plan: RaggedPlan = None, post=None, meta=None, lanes: int = 2, prepare_only: bool = False,
-                   codec=None, channels=None, _fan=None, post_batch: bool = False):
+                   codec=None, channels=None, _fan=None, post_batch: bool = False, source_rate=None):
     """Generator over the plan's buckets: yields (indices, probs[len(indices), T_bucket] on the CPU).
     Recording i of a bucket owns the first ceil(len_i / N) entries of its row.
 
@@ -793,8 +826,20 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     DMAs, the gather over PCIe, the staging buffers carry them as they are -- and the gather kernel writes one batch row per channel
     (vad_upload_rows_channels).  Buckets are planned on the batch rows, a recording's channels in one bucket; every result is that of
     the same call on the flat list [deinterleave(a_i, C_i, c) for i for c in range(C_i)], and the indices yielded are indices into
-    that list (channel_rows)."""
+    that list (channel_rows).
+
+    `source_rate` (44100, 22050, 24000, 11025, ...: resample_geometry): the recordings are at THAT rate and `sampling_rate` is the net's,
+    8000 or 16000 -- what a reference user gets from read_audio(path, sampling_rate), channel averaging apart.  Planning and ingest are
+    untouched: lengths, buckets, windows, staging and every ingest route count RAW samples, the raw bytes cross the link once, `codec`
+    and `channels` compose.  Per bucket ONE resample (vad_resample_rows_device) is enqueued on the lane's stream in front of the
+    kernels, from the batch the ingest wrote into the lane's float32 buffer (sized by ragged_reserve); recording i then owns the first
+    ceil(ceil(N len_i / O) / chunk) entries of its row, and the x a `post_batch` post sees is the RESAMPLED batch.  Every result is
+    that of the same call on [resample(a) for a in audios] up to the kernel's fp32 rounding (resample_device).  A model without the
+    device route (a CPU stand-in) gets the recordings resampled on the host by `resample`: exactly that call.
+    NOT `sampling_rate=48000`: that is the reference's x[::3] inside the model, no low-pass; `source_rate=48000` is read_audio's
+    low-pass resample.  Both exist in the reference."""
     t_setup = time.perf_counter()
+    audios, codec, channels, rs = _resample_input(audios, codec, channels, model, source_rate, sampling_rate, _fan)
     n = _rates(sampling_rate)[2]                          # input samples per chunk (512 k for a multiple of 16 kHz)
     inp = _corpus_input(audios, model, codec, channels, _fan)
     audios, lengths, cd, fan = inp.recs, inp.lengths, inp.cd, inp.fan
@@ -894,7 +939,7 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
     # every lane's scratch is sized up front for the largest bucket it can meet: a growth inside the loop would
     # synchronise the device and stall all lanes (vad_reserve)
     if plan.buckets and hasattr(getattr(model, "engine", None), "reserve"):
-        shapes = [(len(b), (max(plan.lengths[b[0]], n) + n - 1) // n) for b in plan.buckets]
+        shapes = [(len(b), (max(_resampled_len(plan.lengths[b[0]], rs), n) + n - 1) // n) for b in plan.buckets]
         big = max(shapes, key=lambda bt: ((bt[0] + 15) // 16) * bt[1])
         wide = max(shapes, key=lambda bt: bt[0])
         t_res = time.perf_counter()
@@ -902,6 +947,13 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             for bt in {big, wide}:
                 lane_model.engine.reserve(sampling_rate, bt[0], bt[1])
         STATS["reserve_s"] += time.perf_counter() - t_res
+    if rs is not None and plan.buckets:
+        # the pair's table onto the device, and every lane's float32 buffer for the largest resampled bucket it can meet
+        rs_bytes = max(_lane_resampled_bytes(len(b), max(_resampled_len(plan.lengths[b[0]], rs), n)) for b in plan.buckets)
+        for lane_model, lane_stream in lane_list:
+            lane_model.engine.resample_reserve(source_rate, sampling_rate)
+            with torch.cuda.stream(lane_stream):
+                _lane_resampled(lane_model, 1, rs_bytes // 4)
     if prepare_only:
         if plan.buckets:
             big_b = max(plan.buckets, key=lambda b: len(b) * ((max(plan.lengths[b[0]], n) + align - 1) // align * align))
@@ -971,17 +1023,24 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
             if windowed and last_bucket_of[w] == k:       # the window's buffer may take another window once this cut is done
                 win["free"][w % 3] = torch.cuda.Event()
                 win["free"][w % 3].record(pool.stream)
-            m_dev = m_host = None
-            if mt is not None:                            # through the slot's own pinned scratch (meta_buffer: why)
-                m_host = pool.meta_buffer(i, mt.numel()).view(mt.shape)
+            m_dev = m_host = l_dev = None
+            mt_n = mt.numel() if mt is not None else 0
+            if mt is not None or rs is not None:          # through the slot's own pinned scratch (meta_buffer: why)
+                scratch = pool.meta_buffer(i, mt_n + (len(idxs) if rs is not None else 0))
+            if mt is not None:
+                m_host = scratch[:mt_n].view(mt.shape)
                 m_host.copy_(mt)
                 m_dev = m_host.to(dev, non_blocking=True)
+            if rs is not None:                            # the rows' live lengths, raw samples: where the resampler ends each row
+                l_host = scratch[mt_n:]
+                l_host.copy_(torch.as_tensor([plan.lengths[j] for j in idxs], dtype=torch.int64))
+                l_dev = l_host.to(dev, non_blocking=True)
             ev = torch.cuda.Event(enable_timing=True)
             ev.record(pool.stream)
         if not windowed:
             copies.append((ev0, ev))
         pool.done[i] = ev
-        return d[:, :L], ev, i, m_dev, m_host
+        return d[:, :L], ev, i, m_dev, m_host, l_dev
 
     def finish(done_bucket):
         idxs, outs, _, probs_dev = done_bucket
@@ -994,13 +1053,17 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
         staged = stage(0) if plan.buckets else None
         inflight = []                                     # buckets enqueued and not yet yielded, oldest first
         for k, idxs in enumerate(plan.buckets):
-            x, ev, slot, m_dev, _keep = staged
+            x, ev, slot, m_dev, _keep, l_dev = staged
             lane_model, lane_stream = lane_list[k % len(lane_list)]
             lane_stream.wait_event(ev)
             with torch.cuda.stream(lane_stream):
                 x.record_stream(lane_stream)              # allocated on pool.stream, read on the lane's stream
                 if m_dev is not None:
                     m_dev.record_stream(lane_stream)
+                if rs is not None:                        # the raw batch -> the lane's float32 buffer at the net's rate
+                    l_dev.record_stream(lane_stream)
+                    raw, x = x, _lane_resampled(lane_model, len(idxs), max(_resampled_len(plan.lengths[idxs[0]], rs), n))
+                    lane_model.engine.resample_rows(source_rate, sampling_rate, raw, l_dev, x.shape[1], x)
                 probs = lane_model.audio_forward_device(x, sampling_rate)   # asynchronous
                 back = [probs] if post is None else post(probs, idxs, m_dev, x) if post_batch else post(probs, idxs, m_dev)
                 pool.consumed[slot] = torch.cuda.Event()      # (behind post: with post_batch it reads x)
@@ -1046,17 +1109,19 @@ def ragged_buckets(audios: Sequence, model, sampling_rate: int = 16000, max_wast
 
 
 def ragged_reserve(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15, max_bytes: int = 256 << 20,
-                   lanes: int = 2, codec=None, channels=None):
+                   lanes: int = 2, codec=None, channels=None, source_rate=None):
     """Everything a `ragged_probs` / `ragged_speech_segments` run over these recordings would allocate -- the compute lanes and their
     streams, every lane's scratch (vad_reserve: a later growth synchronises the device and, on some boxes, costs 0.1-0.2 s of
     hipFree / hipMalloc for the multi-GB gx scratch: profiles/r05_ingest_routes.md), the staging slots -- sized for the plan's
-    largest bucket, up front.  Call it once before a corpus run (or a timed region); the run itself then allocates nothing."""
-    for _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, lanes=lanes, prepare_only=True, codec=codec, channels=channels):
+    largest bucket, up front.  Call it once before a corpus run (or a timed region); the run itself then allocates nothing.  With
+    `source_rate` (ragged_buckets) also the pair's resampling table and every lane's buffer of resampled audio."""
+    for _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, lanes=lanes, prepare_only=True, codec=codec, channels=channels,
+                            source_rate=source_rate):
         pass
 
 
 def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
-                 max_bytes: int = 256 << 20, plan: RaggedPlan = None, codec=None, channels=None) -> List[torch.Tensor]:
+                 max_bytes: int = 256 << 20, plan: RaggedPlan = None, codec=None, channels=None, source_rate=None) -> List[torch.Tensor]:
     """Speech probabilities of many recordings of different lengths.
 
     Returns one 1-D CPU float tensor per recording (ceil(len / N) entries), bit-identical to
@@ -1066,12 +1131,17 @@ def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste:
     recordings then stay at their raw rate all the way into HBM (_rates).  `codec` ("ulaw" / "alaw", or one per recording): the
     recordings are uint8 G.711 codes and cross the link as such (ragged_buckets); the result is that of the `g711_expand`ed recordings.
     `channels` (1 or 2, or one per recording): the recordings are interleaved and split on the device (ragged_buckets); the result has
-    one entry per (recording, channel), recording-major (channel_rows) -- that of the call on the `deinterleave`d recordings."""
+    one entry per (recording, channel), recording-major (channel_rows) -- that of the call on the `deinterleave`d recordings.
+    `source_rate`: the recordings are at that rate and are resampled to `sampling_rate`, the net's, on the device (ragged_buckets: what
+    read_audio(path, sampling_rate) gives a reference user); recording i has ceil(ceil(N len_i / O) / chunk) probabilities, bit-identical
+    to ``model.audio_forward(resample_device(engine, audio_on_the_gpu, None, source_rate, sampling_rate)[None], sampling_rate)[0]``."""
+    audios, codec, channels, rs = _resample_input(audios, codec, channels, model, source_rate, sampling_rate)
     n = _rates(sampling_rate)[2]
     audios, codec, fan = _channel_input(audios, codec, channels, model)
-    lengths = _describe(audios if fan is None else fan)[1]
+    lengths = [_resampled_len(m, rs) for m in _describe(audios if fan is None else fan)[1]]
     out: List[torch.Tensor] = [torch.empty(0)] * len(lengths)
-    for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, plan, codec=codec, _fan=fan):
+    for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, plan, codec=codec, _fan=fan,
+                                      source_rate=source_rate if rs else None):
         for row, i in enumerate(idxs):
             out[i] = probs[row, : (lengths[i] + n - 1) // n].clone()
     return out
@@ -1079,7 +1149,7 @@ def ragged_probs(audios: Sequence, model, sampling_rate: int = 16000, max_waste:
 
 def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
                            max_bytes: int = 256 << 20, threads: int = 0, device_scan: bool = None,
-                           as_arrays: bool = False, codec=None, channels=None, **scan_kw) -> List[list]:
+                           as_arrays: bool = False, codec=None, channels=None, source_rate=None, **scan_kw) -> List[list]:
     """Speech segments (sample indices) of many recordings: bucketed GPU batches, then the segmenter.
     scan_kw: the threshold/duration arguments of get_speech_timestamps.  codec / channels: as in ragged_probs (uint8 G.711 recordings;
     interleaved recordings, one result per channel).  `audios`: a list of 1-D tensors or a
@@ -1091,16 +1161,23 @@ def ragged_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, 
     kernels of its bucket (vad_segment_probs_device, one lane per recording) and only counts + segment lists come
     back over PCIe; otherwise the probabilities are copied to the host and scanned by the native threaded scanner.
     Both give the same segments (one source, csrc/scanner.hpp).  `sampling_rate` may be a multiple of 16000 (raw recordings, _rates):
-    the segments are then in samples of the 16 kHz signal x[::k], as the reference's scan sees it (utils_vad.py:301-307)."""
-    return _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads, device_scan, as_arrays, codec, channels, None, scan_kw)
+    the segments are then in samples of the 16 kHz signal x[::k], as the reference's scan sees it (utils_vad.py:301-307).
+    `source_rate`: the recordings are at that rate and are resampled to `sampling_rate` on the device (ragged_buckets); the segments are
+    in samples of the RESAMPLED signal, clipped to its length ceil(N len / O) -- what get_speech_timestamps gives on read_audio's
+    output."""
+    return _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads, device_scan, as_arrays, codec, channels, None, scan_kw,
+                            source_rate)
 
 
-def _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads, device_scan, as_arrays, codec, channels, collector, scan_kw):
+def _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads, device_scan, as_arrays, codec, channels, collector, scan_kw,
+                     source_rate=None):
     """ragged_speech_segments; with a `collector` (_AudioCollector: ragged_speech_audio) every bucket's gather is enqueued behind its
     scan and the collector is told each bucket's final segment table.  Without one, the calls are those of ragged_speech_segments."""
+    audios, codec, channels, rs = _resample_input(audios, codec, channels, model, source_rate, sampling_rate)
     net_sr, dec, n = _rates(sampling_rate)
     audios, codec, fan = _channel_input(audios, codec, channels, model)
-    lengths = _describe(audios if fan is None else fan)[1]
+    lengths = [_resampled_len(m, rs) for m in _describe(audios if fan is None else fan)[1]]      # (of what the net and the scan see)
+    source_rate = source_rate if rs else None
     dev = getattr(model, "device", None)
     on_gpu = dev is not None and torch.device(dev).type == "cuda"
     if device_scan is None:
@@ -1125,7 +1202,7 @@ def _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads
         if collector is not None:
             collector.open(audios, _codec_of(audios, codec) if fan is None else fan.cd, fan, lengths)
         for idxs, outs, probs_dev in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, post=post, meta=meta,
-                                                    codec=codec, _fan=fan, post_batch=collector is not None):
+                                                    codec=codec, _fan=fan, post_batch=collector is not None, source_rate=source_rate):
             counts, segs = outs[0], outs[1]
             t0 = time.perf_counter()
             cnt = counts.numpy()
@@ -1141,7 +1218,7 @@ def _speech_segments(audios, model, sampling_rate, max_waste, max_bytes, threads
         if collector is not None:
             raise RuntimeError("ragged_speech_audio collects on the device, behind the device scan: it needs a GPU model backed by the "
                                "native engine (and device_scan left on); there is no host route")
-        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec, _fan=fan):
+        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec, _fan=fan, source_rate=source_rate):
             lens = [lengths[i] for i in idxs]
             t0 = time.perf_counter()
             segs = segment_probs_batch(probs, [(m + n - 1) // n for m in lens], [(m + dec - 1) // dec for m in lens], net_sr,
@@ -1330,7 +1407,8 @@ class _AudioCollector:
 
 
 def ragged_speech_audio(audios: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15, max_bytes: int = 256 << 20,
-                        keep: str = "speech", on_device: bool = False, as_arrays: bool = False, codec=None, channels=None, **scan_kw):
+                        keep: str = "speech", on_device: bool = False, as_arrays: bool = False, codec=None, channels=None, source_rate=None,
+                        **scan_kw):
     """`ragged_speech_segments` AND the audio its segments keep -> (segments, audio): the speech of every recording (keep="speech",
     `collect_chunks`) or everything but the speech (keep="nonspeech", `drop_chunks`), collected on the GPU from the batch rows the scan
     ran on (vad_collect_segments_device, csrc/kernel_collect.hip) -- the recordings are not expanded, split, decimated or sliced on the
@@ -1348,6 +1426,7 @@ def ragged_speech_audio(audios: Sequence, model, sampling_rate: int = 16000, max
     optimistic room (24) is collected on the host from its recording (vad_collect_segments) with the same result.  Needs a GPU model
     backed by the native engine.  The continuous-refill route (refill_*) holds a recording only a slab at a time and has no such
     call: out of scope.  STATS: collect_bytes (kept on the device), audio_d2h_bytes / audio_d2h_s (brought home)."""
+    _no_source_rate(source_rate, "ragged_speech_audio")
     if keep not in ("speech", "nonspeech"):
         raise ValueError(f"keep must be 'speech' or 'nonspeech', got {keep!r}")
     if "device_scan" in scan_kw or "threads" in scan_kw:
@@ -1906,14 +1985,16 @@ def _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan=None, cod
     return _drain(_refill_iter(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec, _fan=_fan))
 
 
-def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None, channels=None):
+def refill_reserve(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None, channels=None,
+                   source_rate=None):
     """Everything a refill run over these recordings allocates, allocated now (`ragged_reserve`'s twin): the arena windows' device
     buffers, the staging slots, the engine's scratch, the block the flat probability tensor will take.  Returns the plan."""
+    _no_source_rate(source_rate, "refill_reserve")
     return _drain(_refill_iter(audios, model, sampling_rate, slots, slab_chunks, prepare_only=True, codec=codec, channels=channels))[2]
 
 
 def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32,
-                 plan: RefillPlan = None, _keep_on_device: bool = False, codec=None, channels=None):
+                 plan: RefillPlan = None, _keep_on_device: bool = False, codec=None, channels=None, source_rate=None):
     """Speech probabilities of many recordings of different lengths through `slots` persistent stream slots
     (RefillPlan).  Returns one 1-D CPU float tensor per recording, bit-identical to
     ``model.audio_forward(audio[None], sr)[0]``: the state and context a slot carries from slab to slab are exactly
@@ -1923,6 +2004,7 @@ def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int
     recordings, _rates: a slab is slab_chunks x 512 k raw samples, the carried context is the 16 kHz net's).  `codec` ("ulaw" / "alaw",
     or one per recording): uint8 G.711 recordings, as in ragged_probs.  `channels`: interleaved recordings, one result per (recording,
     channel) as in ragged_probs."""
+    _no_source_rate(source_rate, "refill_probs")
     audios, codec, fan = _channel_input(audios, codec, channels, model)
     out_flat, base, plan = _refill_run(audios, model, sampling_rate, slots, slab_chunks, plan, codec=codec, _fan=fan)
     if _keep_on_device:
@@ -1932,7 +2014,7 @@ def refill_probs(audios: Sequence, model, sampling_rate: int = 16000, slots: int
 
 
 def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024, slab_chunks: int = 32, codec=None,
-                           channels=None, _fan=None, **scan_kw):
+                           channels=None, _fan=None, source_rate=None, **scan_kw):
     """The continuous-refill scheduler with RESULTS AS RECORDINGS RETIRE -- what the reference's worker pool does, each file's
     timestamps handed back when that file is done (examples/parallel_example.ipynb cell 7).  Generator of
     (recording indices int64[m], counts int64[m], segments int64[m, cap, 2]) batches: behind the slab in which a recording's last
@@ -1941,6 +2023,7 @@ def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, 
     yielded as soon as its copy has landed (a slab or two behind the kernels; nothing here blocks the pipeline).  Probabilities
     never leave the GPU.  Segments are in samples of the net's rate (x[::k] for raw 32 / 48 kHz recordings).  codec: as in refill_probs.
     channels: interleaved recordings; the indices yielded are those of channel_rows."""
+    _no_source_rate(source_rate, "refill_segments_stream")
     net_sr, dec, _ = _rates(sampling_rate)
     fan = _fan                                                            # (refill_speech_segments resolved `channels=` already)
     if fan is None:
@@ -2060,10 +2143,11 @@ def refill_segments_stream(audios: Sequence, model, sampling_rate: int = 16000, 
 
 
 def refill_speech_segments(audios: Sequence, model, sampling_rate: int = 16000, slots: int = 1024,
-                           slab_chunks: int = 32, as_arrays: bool = False, codec=None, channels=None, **scan_kw) -> List[list]:
+                           slab_chunks: int = 32, as_arrays: bool = False, codec=None, channels=None, source_rate=None, **scan_kw) -> List[list]:
     """`ragged_speech_segments` over the continuous-refill scheduler (refill_segments_stream: every recording is scanned on the GPU
     behind the slab it retires in, its segment list crosses PCIe while later slabs run).  as_arrays: (counts int64[n], segments
     int64[sum(counts), 2]) like ragged_speech_segments, instead of a list of lists of dicts.  codec / channels: as in refill_probs."""
+    _no_source_rate(source_rate, "refill_speech_segments")
     audios, codec, fan = _channel_input(audios, codec, channels, model)
     n_rec = len(audios) if fan is None else len(fan)
     counts_all = np.zeros(n_rec, dtype=np.int64)
@@ -2476,6 +2560,100 @@ def decimate(x, step: int, phase: int = 0) -> np.ndarray:
     return out[:m]
 
 
+def resample_geometry(orig_freq: int, new_freq: int):
+    """(O, N, W, K) of the pair (vad_resample_geometry: O : N the reduced ratio, W the reference's filter half-width in input samples, K
+    the taps of a phase's live run); ValueError for a pair that is not served -- new_freq 8000 or 16000, from another rate, O and N at
+    most 1024, K at most 160."""
+    v = [ctypes.c_int() for _ in range(4)]
+    ok = all(isinstance(f, (int, np.integer)) and not isinstance(f, (bool, np.bool_)) and 0 < f < 2 ** 31 for f in (orig_freq, new_freq))
+    if not ok or lib().vad_resample_geometry(int(orig_freq), int(new_freq), *[ctypes.byref(c) for c in v]):
+        raise ValueError(f"resampling {orig_freq!r} -> {new_freq!r} Hz is not served: the target is 8000 or 16000, the source another rate "
+                         "whose reduced ratio O : N has O, N <= 1024 and at most 160 taps a phase (88200 -> 8000 and 11025 -> 16000 are)")
+    return tuple(c.value for c in v)
+
+
+def resample_table(orig_freq: int, new_freq: int):
+    """(taps float32 [N, K], first int32 [N]) of the pair (vad_resample_table): the table the device kernel and `resample` read."""
+    _, N, _, K = resample_geometry(orig_freq, new_freq)
+    taps, first = np.empty((N, K), np.float32), np.empty(N, np.int32)
+    rc = lib().vad_resample_table(int(orig_freq), int(new_freq), taps.ctypes.data, first.ctypes.data)
+    if rc:
+        raise _lib.VadError(rc, "vad_resample_table")
+    return taps, first
+
+
+def resample(x, orig_freq: int, new_freq: int) -> np.ndarray:
+    """A 1-D recording (int16 PCM, taken as x / 32768, or float) at orig_freq -> float32 at new_freq (8000 or 16000): what the reference's
+    `read_audio` does to a file of another rate, torchaudio's default Resample (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99),
+    as arithmetic: the polyphase table of vad_resample_table, every output accumulated in double and rounded once (vad_resample_host,
+    the CPU twin of the device kernel) -- ceil(N len / O) samples.  Not torchaudio's bits: its float32 convolution differs in the
+    last places.  The function and the pairs served: include/silero_vad_hip.h "resampling"."""
+    resample_geometry(orig_freq, new_freq)
+    x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError(f"x must be 1-D, got shape {x.shape}")
+    x = np.ascontiguousarray(x, dtype=np.int16 if x.dtype == np.int16 else np.float32)
+    out = np.empty(lib().vad_resample_length(int(orig_freq), int(new_freq), x.size), np.float32)
+    rc = lib().vad_resample_host(int(orig_freq), int(new_freq), x.ctypes.data if x.size else None, x.itemsize, x.size,
+                                 out.ctypes.data if out.size else None)
+    if rc:
+        raise _lib.VadError(rc, "vad_resample_host")
+    return out
+
+
+def resample_device(engine, x_dev: torch.Tensor, lens, orig_freq: int, new_freq: int, out: torch.Tensor = None) -> torch.Tensor:
+    """`resample` on the device, for a padded batch: x_dev [rows, L] (or 1-D: one row, and a 1-D result) int16 or float32 on the
+    engine's GPU at orig_freq; lens: the live samples of each row (a sequence, or an int64 tensor -- on the device or pinned --; None:
+    L for every row).  -> float32 [rows, ceil(N L / O)] on the device (or `out`, float32 [rows, width_out] with unit sample stride,
+    whatever it held): row r is its recording resampled, ceil(N lens[r] / O) samples, and exact zeros from there on.  The batch behind
+    lens[r] is not read.  Enqueued on the current stream (vad_resample_rows_device); fp32 sums in tap order, the same bits for a
+    recording in any row of any batch, each within (K + 1) 2^-24 sum |h x| of `resample`."""
+    O, N, _, _ = resample_geometry(orig_freq, new_freq)
+    x = x_dev if x_dev.dim() == 2 else x_dev.unsqueeze(0)
+    if x_dev.dim() not in (1, 2) or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
+        raise ValueError("x_dev must be a 1-D or 2-D int16 / float32 tensor on the GPU")
+    if x.stride(1) != 1 and x.shape[1] > 1:
+        x = x.contiguous()
+    rows, L = x.shape
+    if lens is None:
+        lens = torch.full((rows,), L, dtype=torch.int64, device=x.device)
+    elif not torch.is_tensor(lens):
+        host = np.asarray(lens, dtype=np.int64).reshape(-1)
+        if len(host) != rows or (len(host) and (host.min() < 0 or host.max() > L)):
+            raise ValueError(f"lens needs one entry in 0 ... {L} per row")
+        lens = torch.from_numpy(host).to(x.device)
+    elif lens.dtype != torch.int64 or lens.numel() != rows or not (lens.is_cuda or lens.is_pinned()):
+        raise ValueError("lens as a tensor is int64, one entry per row, on the device or in pinned memory")
+    width = (L * N + O - 1) // O
+    if out is None:
+        out = torch.empty((rows, width), dtype=torch.float32, device=x.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != rows or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError("out must be a float32 [rows, width_out] tensor on the GPU with unit sample stride")
+    if rows and out.shape[1]:
+        engine.resample_rows(orig_freq, new_freq, x, lens.contiguous(), out.shape[1], out)
+    return out[0] if x_dev.dim() == 1 else out
+
+
+def _source_rate(source_rate, sampling_rate):
+    """The `source_rate=` of a corpus call, checked: -> None (the recordings are at `sampling_rate`: the call is today's) or (O, N), the
+    reduced ratio of the resample in front of the net.  With a source rate, `sampling_rate` is the NET's rate, 8000 or 16000."""
+    if source_rate is None or source_rate == sampling_rate:
+        return None
+    if sampling_rate not in (8000, 16000):
+        raise ValueError(f"source_rate={source_rate!r}: sampling_rate is then the net's rate, 8000 or 16000, got {sampling_rate!r}")
+    try:
+        return resample_geometry(source_rate, sampling_rate)[:2]
+    except ValueError as e:
+        raise ValueError(f"source_rate={source_rate!r}: {e}") from None
+
+
+def _no_source_rate(source_rate, who):
+    """the corpus and stream routes that do not resample say so"""
+    if source_rate is not None:
+        raise ValueError(f"{who}: source_rate= is not served here -- resampling in front of the net is a route of ragged_buckets / "
+                         "ragged_reserve / ragged_probs / ragged_speech_segments (or `resample` the recordings first)")
+
+
 def _blob_bytes(blob) -> np.ndarray:
     a = np.asarray(blob)
     if a.dtype != np.uint8 or a.ndim != 1:
@@ -2549,7 +2727,8 @@ class StreamPump:
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
     def __init__(self, engine, sampling_rate: int = 16000, streams: int = 8192, parts: int = 0, ring_slots: int = 0,
-                 threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1):
+                 threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1, source_rate=None):
+        _no_source_rate(source_rate, "StreamPump")
         if sampling_rate not in (8000, 16000):
             raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
         if not isinstance(max_burst, (int, np.integer)) or not 1 <= max_burst <= 8:

@@ -254,20 +254,29 @@ def drop_chunks(tss: List[dict], wav: torch.Tensor, seconds: bool = False,
 
 
 def read_audio(path: str, sampling_rate: int = 16000) -> torch.Tensor:
-    """PCM16 mono/stereo WAV -> float tensor in [-1, 1] (÷32768, examples/cpp/wav.h:113-118).
-    The reference decodes through torchaudio/torchcodec (utils_vad.py:138-172), which this image
-    does not ship; other containers and resampling are out of scope here."""
+    """PCM16 mono/stereo WAV -> float tensor in [-1, 1] (÷32768, examples/cpp/wav.h:113-118) at `sampling_rate`, channels averaged.
+    The reference decodes through torchaudio/torchcodec (utils_vad.py:138-172), which this image does not ship; other containers are
+    out of scope here.  A file of another rate (44.1 / 22.05 / 24 / 11.025 kHz ...) is resampled after the averaging, as the reference
+    does with torchaudio's default Resample (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99): by `streams.resample`, the same
+    polyphase table with every output accumulated in double.  The result is torchaudio's ARITHMETIC, not its bits: each sample lies
+    within (K + 1) 2^-24 sum_k |h_k x_k| of any float32 evaluation of the same K-tap sum (K = 34 for 44.1 -> 16 kHz), which is where
+    torchaudio's float32 convolution lies.  `sampling_rate` is then 8000 or 16000 (streams.resample_geometry: the pairs served)."""
     import wave
 
     import numpy as np
     with wave.open(str(path)) as w:
         if w.getsampwidth() != 2:
             raise ValueError("read_audio: only 16-bit PCM WAV is supported in this build")
-        if w.getframerate() != sampling_rate:
-            raise ValueError(f"read_audio: file is {w.getframerate()} Hz, asked for {sampling_rate} Hz "
-                             "(resampling is not available in this build)")
+        rate = w.getframerate()
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, w.getnchannels())
-    return torch.from_numpy(pcm.astype(np.float32).mean(axis=1) / 32768.0)
+    x = pcm.astype(np.float32).mean(axis=1) / 32768.0
+    if rate != sampling_rate:
+        from .streams import resample
+        try:
+            x = resample(x, rate, sampling_rate)
+        except ValueError as e:
+            raise ValueError(f"read_audio: file is {rate} Hz, asked for {sampling_rate} Hz: {e}") from None
+    return torch.from_numpy(x)
 
 
 def read_wav_raw(path: str):
