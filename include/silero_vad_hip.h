@@ -307,6 +307,36 @@ int  vad_collect_segments_device(vad_engine *e, const void *pcm, size_t elem_siz
 long vad_collect_segments(const void *pcm, size_t elem_size, int step, long audio_len, const vad_segment *segs, long n_segs,
                           int invert, void *out, long cap);
 
+/* ---- the enter / exit threshold sweep ---------------------------------------------------------------------------------------------
+ * What tuning/search_thresholds.py computes on a labelled validation corpus (calculate_best_thresholds, tuning/utils.py:326-356), as
+ * integer counts: for every row i of probabilities and every threshold pair k the confusion counts of the hysteresis decision
+ * against per-chunk labels.  The decision starts at 0; per chunk, in order: p >= enter[k] sets it, else p <= exit[k] clears it,
+ * anything else (a NaN too) holds it; then tp += (decision && label == 1), tn += (!decision && label == 0).  labels are uint8: 0 not
+ * speech, 1 speech, any other value (VAD_LABEL_IGNORE) a chunk that is not there -- skipped, decision untouched, nothing counted.
+ * Any pair is accepted (exit >= enter is defined by the order of the two tests).  The comparisons are fp32: a caller with float64
+ * thresholds rounds enter UP and exit DOWN to float32, which decides every float32 probability as the float64 comparison does.
+ *
+ * Row i's n_chunks[i] probabilities start at probs[i * ldp] (row_offsets NULL; n_chunks[i] <= ldp) or at probs[row_offsets[i]]; its
+ * n_chunks[i] labels start at labels[label_offsets[i]], packed, no alignment required.  Nothing behind a row's n_chunks[i] entries is
+ * read.  Outputs, int32: tp, tn [n_streams][n_pairs]; n_pos[i] = labels equal to 1, n_valid[i] = labels equal to 0 or 1 (accuracy is
+ * (tp + tn) / n_valid; precision, recall and F1 follow from the same four numbers).  Exactly those cells are written.
+ *
+ * vad_threshold_counts_host: re-entrant, no GPU; rows are split over `threads` persistent host threads (<= 0: vad_host_threads()).
+ * vad_threshold_counts_device: right behind vad_forward_audio, for probabilities that are still in HBM: ALL pointers are DEVICE
+ * pointers, asynchronous on `stream`, allocates nothing, one wave per (row, 64 pairs) -- only the counts have to cross the link.
+ * The two give the same counts, as integers (one source, csrc/sweeper.hpp).  VAD_ERR_ARG: a NULL pointer (with n_streams > 0; enter
+ * and exit always), a negative size, n_pairs <= 0; on the host also a negative n_chunks[i] / offset or n_chunks[i] > ldp without
+ * row_offsets; on the device probs not aligned to 4 bytes or n_streams * ceil(n_pairs / 64) >= 2^31.  A host-only engine:
+ * VAD_ERR_NO_DEVICE.                                                                                                                */
+#define VAD_LABEL_IGNORE 255
+int  vad_threshold_counts_host(const float *probs, long ldp, const long *row_offsets, long n_streams, const long *n_chunks,
+                               const uint8_t *labels, const long *label_offsets, const float *enter, const float *exit, long n_pairs,
+                               int32_t *tp, int32_t *tn, int32_t *n_pos, int32_t *n_valid, int threads);
+int  vad_threshold_counts_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams,
+                                 const long *n_chunks, const uint8_t *labels, const long *label_offsets, const float *enter,
+                                 const float *exit, long n_pairs, int32_t *tp, int32_t *tn, int32_t *n_pos, int32_t *n_valid,
+                                 void *stream);
+
 /* The streaming caller, VADIterator.__call__ (src/silero_vad/utils_vad.py:507-549), for every slot of a lock-step batch: probs[n]
  * = this tick's probabilities (what vad_step left, copied to the host), active (may be NULL = all) marks the slots that carry a
  * live stream.  triggered / temp_end / current_sample are the iterator's per-stream state (zero after a reset, :500-503), updated

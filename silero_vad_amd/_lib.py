@@ -130,7 +130,11 @@ SYMBOLS = {
     "vad_collect_segments_device": (c_int, [c_void_p, c_void_p, c_size_t, c_long, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p,
                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vad_collect_segments": (c_long, [c_void_p, c_size_t, c_int, c_long, c_void_p, c_long, c_int, c_void_p, c_long]),
-    "vad_iterator_feed": (c_long, [c_void_p, c_void_p, c_long, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+    "vad_threshold_counts_host": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "vad_threshold_counts_device": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vad_iterator_feed":(c_long, [c_void_p, c_void_p, c_long, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_long]),
     "vad_stage_rows": (c_int, [POINTER(c_void_p), POINTER(c_long), c_long, c_long, c_size_t, c_void_p, c_int]),
     "vad_upload_rows": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_long), c_long, c_long, c_size_t, c_void_p, c_int,

@@ -270,6 +270,13 @@ hipError_t launch_collect_segments(const void *pcm, int esz, long ld, int step, 
                                    long cap, const long *counts, int invert, const long *kept, const long *out_offset, void *out,
                                    hipStream_t s);
 
+// The threshold sweep (kernel_sweep.hip; the cell is sweeper.hpp): row i's n_chunks[i] probabilities at probs + (row_off ? row_off[i]
+// : i * ldp), its packed labels at labels + label_off[i]; tp / tn [n_rows][n_pairs], n_pos / n_valid [n_rows].  One wave per (row,
+// 64 pairs): n_rows * ceil(n_pairs / 64) blocks, which the caller keeps below 2^31.
+hipError_t launch_sweep(const float *probs, long ldp, const long *row_off, long n_rows, const long *n_chunks, const uint8_t *labels,
+                        const long *label_off, const float *enter, const float *exit_, long n_pairs, int *tp, int *tn, int *n_pos,
+                        int *n_valid, hipStream_t s);
+
 // test hook: y[i] = sigmoid (kind 0) / tanh (kind 1) of x[i] exactly as the recurrent kernels evaluate them (activations.hpp)
 hipError_t launch_activation_probe(int kind, const float *x, float *y, long n, hipStream_t s);
 

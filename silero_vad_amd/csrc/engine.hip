@@ -884,6 +884,26 @@ int vad_collect_segments_device(vad_engine *e, const void *pcm, size_t elem_size
     return VAD_OK;
 }
 
+int vad_threshold_counts_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams, const long *n_chunks,
+                                const uint8_t *labels, const long *label_offsets, const float *enter, const float *exit, long n_pairs,
+                                int32_t *tp, int32_t *tn, int32_t *n_pos, int32_t *n_valid, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    // (the arguments first: a host-only engine refuses a malformed call for what is wrong with it)
+    if (n_streams < 0 || ldp < 0) return fail(e, VAD_ERR_ARG, "vad_threshold_counts_device: negative size");
+    if (n_pairs <= 0) return fail(e, VAD_ERR_ARG, "vad_threshold_counts_device: n_pairs must be positive");
+    if (!enter || !exit) return fail(e, VAD_ERR_ARG, "vad_threshold_counts_device: null enter or exit");
+    if (n_streams > 0 && (!probs || !n_chunks || !labels || !label_offsets || !tp || !tn || !n_pos || !n_valid))
+        return fail(e, VAD_ERR_ARG, "vad_threshold_counts_device: null probs, n_chunks, labels, label_offsets, tp, tn, n_pos or n_valid");
+    if (((size_t)probs) & 3) return fail(e, VAD_ERR_ARG, "vad_threshold_counts_device: probs is not aligned to its elements");
+    if (n_pairs > (1L << 24) || n_streams > 0x7fffffffL / ((n_pairs + 63) / 64))
+        return fail(e, VAD_ERR_ARG, "vad_threshold_counts_device: n_streams x ceil(n_pairs / 64) does not fit one launch");
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, vad::launch_sweep(probs, ldp, row_offsets, n_streams, n_chunks, labels, label_offsets, enter, exit, n_pairs, tp, tn, n_pos,
+                                 n_valid, (hipStream_t)stream));
+    return VAD_OK;
+}
+
 int vad_reserve(vad_engine *e, int sr, int B, long T) {
     if (!e) return VAD_ERR_ARG;
     if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");

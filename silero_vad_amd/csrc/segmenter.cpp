@@ -12,6 +12,7 @@
 #include "collector.hpp"
 #include "host_threads.hpp"
 #include "scanner.hpp"
+#include "sweeper.hpp"
 
 extern "C" void vad_segment_params_default(vad_segment_params *p, int sampling_rate) {
     if (!p) return;
@@ -68,6 +69,54 @@ extern "C" long vad_segment_probs_batch(const float *probs, long ldp, long n_str
     long total = 0;
     for (long i = 0; i < n_streams; ++i) total += counts[i];
     return total;
+}
+
+// The enter / exit threshold sweep (reference tuning/utils.py:326-356, the loops of calculate_best_thresholds) on the host, the twin of
+// the device kernel (kernel_sweep.hip; one source for the decision and the counts: sweeper.hpp).  Rows are independent and are split
+// over the pool like the batch scanner's; inside a row the chunk is the outer loop and the pair the inner one, so that a row is read
+// once and the branch-free cell vectorises along the pairs.
+extern "C" int vad_threshold_counts_host(const float *probs, long ldp, const long *row_offsets, long n_streams, const long *n_chunks,
+                                         const uint8_t *labels, const long *label_offsets, const float *enter, const float *exit,
+                                         long n_pairs, int32_t *tp, int32_t *tn, int32_t *n_pos, int32_t *n_valid, int threads) {
+    if (n_streams < 0 || ldp < 0 || n_pairs <= 0 || !enter || !exit) return VAD_ERR_ARG;
+    if (n_streams > 0 && (!probs || !n_chunks || !labels || !label_offsets || !tp || !tn || !n_pos || !n_valid)) return VAD_ERR_ARG;
+    for (long i = 0; i < n_streams; ++i)
+        if (n_chunks[i] < 0 || (!row_offsets && n_chunks[i] > ldp) || label_offsets[i] < 0 || (row_offsets && row_offsets[i] < 0)) return VAD_ERR_ARG;
+    auto work = [&](long lo, long hi) {
+        std::vector<vad::SweepCell> cells((size_t)n_pairs);
+        for (long i = lo; i < hi; ++i) {
+            const float *row = probs + (row_offsets ? row_offsets[i] : i * ldp);
+            const uint8_t *lab = labels + label_offsets[i];
+            std::fill(cells.begin(), cells.end(), vad::SweepCell());
+            vad::SweepLabels seen;
+            for (long t = 0; t < n_chunks[i]; ++t) {
+                const unsigned l = lab[t];
+                seen.feed(l);
+                if (l > 1u) continue;
+                const float p = row[t];
+                for (long k = 0; k < n_pairs; ++k) cells[(size_t)k].feed(p, l, enter[k], exit[k]);
+            }
+            for (long k = 0; k < n_pairs; ++k) {
+                tp[i * n_pairs + k] = cells[(size_t)k].tp;
+                tn[i * n_pairs + k] = cells[(size_t)k].tn;
+            }
+            n_pos[i] = seen.n_pos;
+            n_valid[i] = seen.n_valid;
+        }
+    };
+    int nt = threads > 0 ? threads : vad::default_host_threads(64);
+    nt = (int)std::max<long>(1, std::min<long>(nt, n_streams / 16 + 1));
+    if (nt == 1) {
+        work(0, n_streams);
+    } else {
+        const int blocks = (int)std::min<long>(n_streams, 4L * nt);
+        const long per = (n_streams + blocks - 1) / blocks;
+        vad::HostPool::get().run(nt, blocks, [&](int k) {
+            const long lo = k * per, hi = std::min(n_streams, lo + per);
+            if (lo < hi) work(lo, hi);
+        });
+    }
+    return VAD_OK;
 }
 
 // collect_chunks / drop_chunks (reference src/silero_vad/utils_vad.py:552-655) for one stream, the host twin of the device gather

@@ -1527,6 +1527,272 @@ def segment_probs_batch(probs: torch.Tensor, n_chunks, audio_lengths, sampling_r
     return [[{"start": int(s), "end": int(e)} for s, e in segs[i, : counts[i]]] for i in range(B)]
 
 
+# ---- offline: the enter / exit threshold search over a labelled corpus ----------------------------------------------
+LABEL_IGNORE = 255        # VAD_LABEL_IGNORE: a chunk that does not exist for the sweep (the reference's masked chunks, tuning/utils.py:317-319)
+
+ThresholdPairs = collections.namedtuple("ThresholdPairs", "enter exit enter_f32 exit_f32")
+ThresholdPairs.__doc__ = """(enter, exit) threshold pairs: `enter` / `exit` float64[P] as the caller means them, `enter_f32` / `exit_f32` their directed
+float32 roundings, which the sweep compares with (threshold_pairs)."""
+
+
+def _round_f32(x: np.ndarray, up: bool) -> np.ndarray:
+    """the smallest float32 >= x (up) / the largest float32 <= x (down), element by element"""
+    f = x.astype(np.float32)
+    with np.errstate(over="ignore"):
+        if up:
+            return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+        return np.where(f.astype(np.float64) > x, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def threshold_pairs(enter=None, exit=None) -> ThresholdPairs:
+    """The grid of the reference's threshold search (calculate_best_thresholds, tuning/utils.py:328-331): every (enter, exit) with
+    exit < enter, enter-major, from `enter` x `exit` (default: np.linspace(0, 1, 20) for both -- 190 pairs).
+
+    The reference compares a float32 probability, widened to double, with these float64 values.  double(p) >= e holds exactly when
+    p >= the smallest float32 >= e, and double(p) <= x exactly when p <= the largest float32 <= x: `enter_f32` is `enter` rounded UP
+    and `exit_f32` is `exit` rounded DOWN, and the sweep compares in fp32 with the reference's outcome for every float32 probability."""
+    en = np.linspace(0, 1, 20) if enter is None else np.asarray(enter, dtype=np.float64).reshape(-1)
+    ex = np.linspace(0, 1, 20) if exit is None else np.asarray(exit, dtype=np.float64).reshape(-1)
+    keep = ex[None, :] < en[:, None]                          # [enter, exit]: row-major is enter-major
+    e = np.ascontiguousarray(np.broadcast_to(en[:, None], keep.shape)[keep])
+    x = np.ascontiguousarray(np.broadcast_to(ex[None, :], keep.shape)[keep])
+    return ThresholdPairs(e, x, _round_f32(e, True), _round_f32(x, False))
+
+
+def _as_pairs(pairs) -> ThresholdPairs:
+    if pairs is None:
+        return threshold_pairs()
+    if isinstance(pairs, ThresholdPairs):
+        return pairs
+    p = np.asarray(pairs, dtype=np.float64)                    # [P, 2]: the pairs as they are, none left out
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("pairs: a ThresholdPairs (threshold_pairs) or an array [P, 2] of (enter, exit)")
+    e, x = np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+    return ThresholdPairs(e, x, _round_f32(e, True), _round_f32(x, False))
+
+
+def chunk_labels(speech_ts, n_samples: int, sampling_rate: int = 16000) -> np.ndarray:
+    """Per-chunk 0 / 1 labels (uint8) of a recording of `n_samples` samples from its annotation, a list of {'start': s, 'end': s} in
+    SECONDS -- the reference's rule (get_ground_truth_annotated, tuning/utils.py:113-133): samples int(start * sr) ... int(end * sr)
+    are speech, the length is padded up to a whole chunk, and a chunk is speech when more than half of its samples are."""
+    n = chunk_size(sampling_rate)
+    chunks = (int(n_samples) + n - 1) // n
+    gt = np.zeros(chunks * n, dtype=np.uint8)
+    for seg in speech_ts:
+        gt[int(seg["start"] * sampling_rate): int(seg["end"] * sampling_rate)] = 1
+    return (gt.reshape(chunks, n).sum(axis=1, dtype=np.int64) * 2 > n).astype(np.uint8)
+
+
+class ThresholdCounts:
+    """The sweep's result: `pairs` (ThresholdPairs, P of them) and, for R recordings in the caller's order, the int32 counts
+    tp[R, P], tn[R, P] (chunks decided speech / not speech and labelled so), n_pos[R] (labels equal to 1), n_valid[R] (labels equal
+    to 0 or 1).  Everything else is derived from these integers on the host."""
+
+    def __init__(self, pairs: ThresholdPairs, tp, tn, n_pos, n_valid):
+        self.pairs = pairs
+        self.tp, self.tn = np.asarray(tp, dtype=np.int32), np.asarray(tn, dtype=np.int32)
+        self.n_pos, self.n_valid = np.asarray(n_pos, dtype=np.int32), np.asarray(n_valid, dtype=np.int32)
+
+    def _scored(self):
+        if len(self.n_valid) == 0 or int(self.n_valid.min()) <= 0:
+            raise ValueError("a recording without a valid chunk cannot be scored")
+
+    def accuracy(self) -> np.ndarray:
+        """(tp + tn) / n_valid, float64[R, P]"""
+        self._scored()
+        return (self.tp.astype(np.int64) + self.tn) / self.n_valid.astype(np.int64)[:, None]
+
+    def f1(self) -> np.ndarray:
+        """2 tp / (2 tp + fp + fn) with fp = n_valid - n_pos - tn and fn = n_pos - tp, float64[R, P]; 0 where nothing is speech or
+        called speech"""
+        tp = self.tp.astype(np.int64)
+        den = tp + self.n_valid.astype(np.int64)[:, None] - self.tn
+        return np.divide(2.0 * tp, den, out=np.zeros(tp.shape, dtype=np.float64), where=den > 0)
+
+    def best(self):
+        """(enter, exit, accuracy): what the reference's calculate_best_thresholds returns on these recordings (tuning/utils.py:326-356),
+        with its roundings -- per recording round(accuracy, 4) on a Python float, per pair round(np.mean(those), 3), a strict > against
+        a running best that starts at 0, pairs in their order (enter-major), thresholds round(., 2)."""
+        acc = self.accuracy()
+        vals, inv = np.unique(acc, return_inverse=True)        # Python's round, once per distinct value
+        acc4 = np.asarray([round(v, 4) for v in vals.tolist()], dtype=np.float64)[inv.reshape(-1)].reshape(acc.shape)
+        per_pair = np.ascontiguousarray(acc4.T)                # a contiguous vector per pair: numpy sums it as it sums the reference's list
+        best_acc, found = 0, None
+        for k in range(per_pair.shape[0]):
+            mean_acc = round(np.mean(per_pair[k]), 3)
+            if mean_acc > best_acc:
+                best_acc, found = mean_acc, k
+        if found is None:
+            raise ValueError("no threshold pair scores above 0")
+        return round(self.pairs.enter[found], 2), round(self.pairs.exit[found], 2), best_acc
+
+
+def _pack_labels(labels, n_chunks, who):
+    """the rows' label arrays back to back -> (uint8[sum], int64 offsets[R]); every row's length is checked against its chunk count"""
+    arrs = []
+    for i, (lab, m) in enumerate(zip(labels, n_chunks)):
+        a = lab.cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
+        if a.dtype != np.uint8:
+            raise ValueError(f"{who}: labels must be uint8 arrays (0, 1, {LABEL_IGNORE} = ignore)")
+        if a.ndim != 1 or len(a) != int(m):
+            raise ValueError(f"{who}: row {i} has {int(m)} chunks and {a.size} labels")
+        arrs.append(a)
+    offs = np.zeros(len(arrs), dtype=np.int64)
+    if arrs:
+        offs[1:] = np.cumsum([len(a) for a in arrs[:-1]])
+    return (np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)), offs
+
+
+def _sweep_rows(n_chunks, labels, B, T, who):
+    nck = np.ascontiguousarray(n_chunks, dtype=np.int64)
+    if nck.shape != (B,) or len(labels) != B:
+        raise ValueError(f"{who}: n_chunks and labels need one entry per row of probs")
+    if B and (int(nck.min()) < 0 or int(nck.max()) > T):
+        raise ValueError(f"{who}: n_chunks must lie in [0, T]")
+    return nck
+
+
+def threshold_counts(probs, n_chunks, labels, pairs=None, threads: int = 0) -> ThresholdCounts:
+    """The sweep on the host (vad_threshold_counts_host, the twin of the device kernel: one source, csrc/sweeper.hpp): probs[B, T]
+    float32 on the CPU, row i's first n_chunks[i] entries against labels[i] (uint8[n_chunks[i]]: 0, 1, anything else = ignore) for
+    every pair of `pairs` (threshold_pairs(); or an array [P, 2] of (enter, exit), taken as it is)."""
+    pr = _as_pairs(pairs)
+    probs = torch.as_tensor(probs, dtype=torch.float32).contiguous().cpu()
+    if probs.dim() != 2:
+        raise ValueError("threshold_counts: probs[B, T]")
+    B, T = probs.shape
+    nck = _sweep_rows(n_chunks, labels, B, T, "threshold_counts")
+    lab, offs = _pack_labels(labels, nck, "threshold_counts")
+    P = len(pr.enter)
+    tp, tn = np.zeros((B, P), dtype=np.int32), np.zeros((B, P), dtype=np.int32)
+    n_pos, n_valid = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    none = np.zeros(8, dtype=np.uint8)                         # (rows of no chunks: something to point at)
+    rc = lib().vad_threshold_counts_host(probs.data_ptr() if B * T else none.ctypes.data, T, None, B, nck.ctypes.data,
+                                         lab.ctypes.data if len(lab) else none.ctypes.data, offs.ctypes.data, pr.enter_f32.ctypes.data, pr.exit_f32.ctypes.data, P,
+                                         tp.ctypes.data, tn.ctypes.data, n_pos.ctypes.data, n_valid.ctypes.data, int(threads))
+    if rc != _lib.VAD_OK:
+        raise _lib.VadError(rc, "vad_threshold_counts_host")
+    return ThresholdCounts(pr, tp, tn, n_pos, n_valid)
+
+
+def _device_sweep(engine, probs_dev, n_chunks_dev, labels_ptr, label_offs_dev, enter_dev, exit_dev, row_offsets=None):
+    """Enqueue the sweep of probs_dev[B, T] on the current stream -> one int32 device tensor holding tp[B, P], tn[B, P], n_pos[B],
+    n_valid[B] back to back (_split_counts), so that one copy brings a bucket's counts home."""
+    B, T = probs_dev.shape
+    if row_offsets is not None:
+        B = row_offsets.shape[0]
+    P = enter_dev.shape[0]
+    out = torch.empty((B * (2 * P + 2),), dtype=torch.int32, device=probs_dev.device)
+    at = out.data_ptr()
+    _lib.check(engine._h, lib().vad_threshold_counts_device(
+        engine._h, probs_dev.data_ptr(), probs_dev.stride(0) if probs_dev.shape[0] > 1 else T,
+        row_offsets.data_ptr() if row_offsets is not None else None, B, n_chunks_dev.data_ptr(), labels_ptr, label_offs_dev.data_ptr(),
+        enter_dev.data_ptr(), exit_dev.data_ptr(), P, at, at + 4 * B * P, at + 8 * B * P, at + 8 * B * P + 4 * B,
+        ctypes.c_void_p(torch.cuda.current_stream(probs_dev.device).cuda_stream)))
+    return out
+
+
+def _split_counts(flat: np.ndarray, B: int, P: int):
+    return flat[:B * P].reshape(B, P), flat[B * P:2 * B * P].reshape(B, P), flat[2 * B * P:2 * B * P + B], flat[2 * B * P + B:]
+
+
+def _label_meta(nck: np.ndarray, lab: np.ndarray, offs: np.ndarray) -> torch.Tensor:
+    """int64[2 R + ceil(bytes / 8)]: the rows' chunk counts, their label offsets, then the label bytes themselves (viewed as int64,
+    padded with ignore) -- one small tensor to the device per batch"""
+    R = len(nck)
+    words = (len(lab) + 7) // 8
+    m = np.empty(2 * R + words, dtype=np.int64)
+    m[:R], m[R:2 * R] = nck, offs
+    tail = m[2 * R:].view(np.uint8)
+    tail[:len(lab)] = lab
+    tail[len(lab):] = LABEL_IGNORE
+    return torch.from_numpy(m)
+
+
+def threshold_counts_device(engine, probs_dev: torch.Tensor, n_chunks, labels, pairs=None) -> ThresholdCounts:
+    """`threshold_counts` for probabilities that are already on the GPU (probs_dev[B, T], CUDA float32, unit stride inside a row): the
+    sweep runs there (vad_threshold_counts_device) and only the counts are copied back."""
+    pr = _as_pairs(pairs)
+    if probs_dev.dim() != 2 or probs_dev.dtype != torch.float32 or (probs_dev.shape[1] > 1 and probs_dev.stride(1) != 1):
+        raise ValueError("threshold_counts_device: probs_dev[B, T] float32 with unit stride inside a row")
+    B, T = probs_dev.shape
+    nck = _sweep_rows(n_chunks, labels, B, T, "threshold_counts_device")
+    lab, offs = _pack_labels(labels, nck, "threshold_counts_device")
+    P = len(pr.enter)
+    dev = probs_dev.device
+    meta = _label_meta(nck, lab, offs).to(dev)
+    thr = torch.from_numpy(np.stack([pr.enter_f32, pr.exit_f32])).to(dev)
+    out = _device_sweep(engine, probs_dev, meta[:B], meta.data_ptr() + 16 * B, meta[B:2 * B], thr[0], thr[1])
+    return ThresholdCounts(pr, *_split_counts(out.cpu().numpy(), B, P))
+
+
+def ragged_threshold_counts(audios: Sequence, labels: Sequence, model, sampling_rate: int = 16000, pairs=None, max_waste: float = 0.15,
+                            max_bytes: int = 256 << 20, codec=None, channels=None, source_rate=None, threads: int = 0) -> ThresholdCounts:
+    """The threshold sweep over a labelled corpus (what tuning/search_thresholds.py does with model.audio_forward and
+    calculate_best_thresholds): the recordings take the bucket route of `ragged_probs` and every bucket's sweep is enqueued right
+    behind its kernels (vad_threshold_counts_device, one wave per recording and 64 pairs) -- the probabilities never leave the GPU,
+    only the integer counts come back.  The bucket's labels ride to the device with its PCM, one byte per chunk.
+
+    labels[i]: uint8, one entry per chunk of recording i (`chunk_labels`; 0, 1, anything else = ignore); with `channels` one per
+    (recording, channel) in `channel_rows` order, with `source_rate` per chunk of the resampled recording.  ValueError if a row's
+    label count differs from its chunk count or if it has no valid chunk (the reference's accuracy_score cannot score one either).
+    The counts are, as integers, those of `threshold_counts` on `ragged_probs` of the same call.  A model without the device route (a
+    CPU stand-in) takes the host twin.  codec / channels / source_rate / max_waste / max_bytes: as in ragged_probs."""
+    pr = _as_pairs(pairs)
+    audios, codec, channels, rs = _resample_input(audios, codec, channels, model, source_rate, sampling_rate)
+    n = _rates(sampling_rate)[2]
+    audios, codec, fan = _channel_input(audios, codec, channels, model)
+    lengths = [_resampled_len(m, rs) for m in _describe(audios if fan is None else fan)[1]]
+    source_rate = source_rate if rs else None
+    R, P = len(lengths), len(pr.enter)
+    nck = np.asarray([(m + n - 1) // n for m in lengths], dtype=np.int64)
+    if len(labels) != R:
+        raise ValueError(f"ragged_threshold_counts: {R} rows and {len(labels)} label arrays")
+    lab, offs = _pack_labels(labels, nck, "ragged_threshold_counts")
+    ignored = np.flatnonzero(lab > 1)                          # (sparse: a running sum over every label costs ten times this)
+    valid = nck - (np.searchsorted(ignored, offs + nck) - np.searchsorted(ignored, offs))
+    if R and int(valid.min()) == 0:
+        raise ValueError(f"ragged_threshold_counts: row {int(np.argmin(valid))} has no valid chunk")
+    tp, tn = np.zeros((R, P), dtype=np.int32), np.zeros((R, P), dtype=np.int32)
+    n_pos, n_valid = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+    dev = getattr(model, "device", None)
+    on_gpu = dev is not None and torch.device(dev).type == "cuda"
+
+    def rows_of(idxs):
+        ix = np.asarray(idxs, dtype=np.int64)
+        return ix, [lab[offs[i]:offs[i] + nck[i]] for i in ix]
+
+    if on_gpu and hasattr(getattr(model, "engine", None), "_h"):
+        thr = torch.from_numpy(np.stack([pr.enter_f32, pr.exit_f32])).to(dev)
+
+        def meta(idxs):
+            ix, rows = rows_of(idxs)
+            b_off = np.zeros(len(ix), dtype=np.int64)
+            b_off[1:] = np.cumsum(nck[ix][:-1])
+            return _label_meta(nck[ix], np.concatenate(rows) if rows else lab[:0], b_off)
+
+        def post(probs_dev, idxs, m_dev):
+            B = len(idxs)
+            return [_device_sweep(model.engine, probs_dev, m_dev[:B], m_dev.data_ptr() + 16 * B, m_dev[B:2 * B], thr[0], thr[1])]
+
+        for idxs, outs, _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, post=post, meta=meta, codec=codec, _fan=fan,
+                                            source_rate=source_rate):
+            ix = np.asarray(idxs, dtype=np.int64)
+            tp[ix], tn[ix], n_pos[ix], n_valid[ix] = _split_counts(outs[0].numpy(), len(ix), P)
+    else:
+        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec, _fan=fan, source_rate=source_rate):
+            ix, rows = rows_of(idxs)
+            c = threshold_counts(probs, nck[ix], rows, pr, threads)
+            tp[ix], tn[ix], n_pos[ix], n_valid[ix] = c.tp, c.tn, c.n_pos, c.n_valid
+    return ThresholdCounts(pr, tp, tn, n_pos, n_valid)
+
+
+def search_thresholds(audios: Sequence, labels: Sequence, model, sampling_rate: int = 16000, **kw):
+    """(enter, exit, accuracy) of the reference's threshold search (tuning/search_thresholds.py) over a labelled corpus:
+    `ragged_threshold_counts(...).best()`."""
+    return ragged_threshold_counts(audios, labels, model, sampling_rate, **kw).best()
+
+
 # ---- offline: continuous refill ------------------------------------------------------------------------------------
 class RefillPlan:
     """A fixed number of stream slots, processed in time slabs of `slab_chunks` chunks; a slot whose recording ends
