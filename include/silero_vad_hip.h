@@ -337,6 +337,50 @@ int  vad_threshold_counts_device(vad_engine *e, const float *probs, long ldp, co
                                  const float *exit, long n_pairs, int32_t *tp, int32_t *tn, int32_t *n_pos, int32_t *n_valid,
                                  void *stream);
 
+/* ---- validation scores: masked BCE sums and the pooled ROC-AUC ---------------------------------------------------------------------
+ * What the reference's validate() reports on a labelled validation set (tuning/utils.py:252-298): the BCE loss of the per-chunk
+ * probabilities against the labels and roc_auc_score over every chunk of the set.  Two steps, each with a host twin.
+ *
+ * 1. The per-chunk rule (one source, csrc/scorer.hpp).  A chunk is VALID when its label is 0 or 1 and 0 <= p <= 1 (a NaN fails that;
+ *    -0.0f passes and counts as +0.0f).  A label above 1 (VAD_LABEL_IGNORE) is a chunk that is not there.  A label of 0 / 1 with any
+ *    other probability is BAD: counted in n_bad, in no sum, without a key.  A valid chunk's BCE term is nn.BCELoss's, the log taken
+ *    in double: label 1: -max(log((double)p), -100); label 0: -max(log((double)(1.0f - p)), -100), the subtraction in fp32.  Its key
+ *    is (v << 1) | label with v the bit pattern of p (v <= 0x3F800000, monotone in p); every other chunk's key is
+ *    VAD_SCORE_KEY_NONE.
+ *    Rows are addressed as in the threshold sweep (probs, ldp, row_offsets, n_chunks, labels, label_offsets); row i's keys go to
+ *    keys[key_offsets[i] + t], t < n_chunks[i].  Outputs per row: bce_pos[i] / bce_neg[i] (double: the sums of the terms of the valid
+ *    label-1 / label-0 chunks), n_pos[i], n_neg[i] (valid chunks by label), n_bad[i].  Exactly those cells are written; nothing behind
+ *    a row's n_chunks[i] entries is read.  The sums are accumulated in double in an order that depends on the row alone: a row gives
+ *    the same bits at any position of any batch, at any pitch and alignment.  Host and device give the same integers and keys; each
+ *    device sum lies within (2 n + 8) * 2^-53 * sum of the host's (n = n_chunks[i]: two logs of at most 2 ulp, two summations of n
+ *    non-negative terms).
+ *    vad_chunk_scores_host: re-entrant, no GPU, rows over `threads` host threads (<= 0: vad_host_threads()).
+ *    vad_chunk_scores_device: ALL pointers are DEVICE pointers, asynchronous on `stream`, allocates nothing, one wave per row.
+ *    VAD_ERR_ARG: a NULL pointer (with n_streams > 0), a negative size; on the host also a negative n_chunks[i] / offset or
+ *    n_chunks[i] > ldp without row_offsets; on the device probs not aligned to 4 bytes, bce_pos / bce_neg not to 8, or n_streams >=
+ *    2^31.  A host-only engine: VAD_ERR_NO_DEVICE.
+ *
+ * 2. The pooled rank statistic over n keys, those equal to VAD_SCORE_KEY_NONE skipped: out[3] = { U2, n_pos, n_neg } with
+ *    U2 = sum over the positive keys (low bit 1) of 2 * #{negative keys with a smaller v} + #{negative keys with an equal v}, so that
+ *    U2 / (2 n_pos n_neg) is the Mann-Whitney statistic with ties at one half: what roc_auc_score returns.  Any other uint32 is a
+ *    key (v = key >> 1); n < 2^31, so U2 fits 64 bits.
+ *    vad_auc_counts_host: re-entrant, no GPU (a sort).  vad_auc_counts_device: keys, workspace and out are DEVICE pointers (out
+ *    aligned to 8 bytes, workspace to 16), asynchronous on `stream`, allocates nothing: the caller provides a workspace of at least
+ *    vad_auc_workspace_bytes(n) bytes (host-only call; 0 for an n outside [0, 2^31)); a smaller one is VAD_ERR_ARG with nothing
+ *    written.  A counting scheme, no sort (csrc/kernel_score.hip).  Host and device give the same three integers.                   */
+#define VAD_SCORE_KEY_NONE 0xFFFFFFFFu
+int  vad_chunk_scores_host(const float *probs, long ldp, const long *row_offsets, long n_streams, const long *n_chunks,
+                           const uint8_t *labels, const long *label_offsets, const long *key_offsets, uint32_t *keys, double *bce_pos,
+                           double *bce_neg, int32_t *n_pos, int32_t *n_neg, int32_t *n_bad, int threads);
+int  vad_chunk_scores_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams,
+                             const long *n_chunks, const uint8_t *labels, const long *label_offsets, const long *key_offsets,
+                             uint32_t *keys, double *bce_pos, double *bce_neg, int32_t *n_pos, int32_t *n_neg, int32_t *n_bad,
+                             void *stream);
+size_t vad_auc_workspace_bytes(long n);
+int  vad_auc_counts_host(const uint32_t *keys, long n, uint64_t *out);
+int  vad_auc_counts_device(vad_engine *e, const uint32_t *keys, long n, void *workspace, size_t workspace_bytes, uint64_t *out,
+                           void *stream);
+
 /* The streaming caller, VADIterator.__call__ (src/silero_vad/utils_vad.py:507-549), for every slot of a lock-step batch: probs[n]
  * = this tick's probabilities (what vad_step left, copied to the host), active (may be NULL = all) marks the slots that carry a
  * live stream.  triggered / temp_end / current_sample are the iterator's per-stream state (zero after a reset, :500-503), updated

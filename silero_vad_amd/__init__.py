@@ -8,7 +8,8 @@ from .timestamps import (VADIterator, collect_chunks, drop_chunks, get_speech_ti
                          read_audio, read_wav_raw, save_audio, segment_probs)
 from .streams import (BatchVADIterator, PackedRecordings, RaggedPlan, RefillPlan, StreamPool, StreamPump, refill_probs, refill_reserve, refill_segments_stream, refill_speech_segments, ragged_buckets, ragged_probs, ragged_reserve,  # noqa: F401
                       ragged_speech_segments, ragged_speech_audio, collect_chunks_device, segment_probs_batch, segment_probs_batch_device, g711_expand, decimate, resample, resample_device, resample_geometry, resample_table, snapshot_info, ROW_SILENT, deinterleave, channel_rows,
-                      ThresholdCounts, ThresholdPairs, LABEL_IGNORE, threshold_pairs, chunk_labels, threshold_counts, threshold_counts_device, ragged_threshold_counts, search_thresholds)
+                      ThresholdCounts, ThresholdPairs, LABEL_IGNORE, threshold_pairs, chunk_labels, threshold_counts, threshold_counts_device, ragged_threshold_counts, search_thresholds,
+                      ValidationScores, SCORE_KEY_NONE, chunk_scores, chunk_scores_device, ragged_validation, validate)
 from .sharding import shard_range, shard_by_duration, gather_to_rank0, batch_speech_timestamps  # noqa: F401
 
 __version__ = "0.1.0"

@@ -277,6 +277,15 @@ hipError_t launch_sweep(const float *probs, long ldp, const long *row_off, long 
                         const long *label_off, const float *enter, const float *exit_, long n_pairs, int *tp, int *tn, int *n_pos,
                         int *n_valid, hipStream_t s);
 
+// The validation scores (kernel_score.hip; the per-chunk rule is scorer.hpp).  launch_chunk_scores: rows addressed as launch_sweep's,
+// row i's keys to keys + key_off[i]; one wave per row, n_rows < 2^31.  launch_auc_counts: out[3] = {U2, n_pos, n_neg} over the keys
+// other than VAD_SCORE_KEY_NONE; workspace: auc_workspace_bytes(n) bytes, 16-byte aligned; 0 <= n < 2^31.
+hipError_t launch_chunk_scores(const float *probs, long ldp, const long *row_off, long n_rows, const long *n_chunks, const uint8_t *labels,
+                               const long *label_off, const long *key_off, uint32_t *keys, double *bce_pos, double *bce_neg, int *n_pos,
+                               int *n_neg, int *n_bad, hipStream_t s);
+size_t auc_workspace_bytes(long n);
+hipError_t launch_auc_counts(const uint32_t *keys, long n, void *workspace, unsigned long long *out, hipStream_t s);
+
 // test hook: y[i] = sigmoid (kind 0) / tanh (kind 1) of x[i] exactly as the recurrent kernels evaluate them (activations.hpp)
 hipError_t launch_activation_probe(int kind, const float *x, float *y, long n, hipStream_t s);
 

@@ -904,6 +904,41 @@ int vad_threshold_counts_device(vad_engine *e, const float *probs, long ldp, con
     return VAD_OK;
 }
 
+int vad_chunk_scores_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams, const long *n_chunks,
+                            const uint8_t *labels, const long *label_offsets, const long *key_offsets, uint32_t *keys, double *bce_pos,
+                            double *bce_neg, int32_t *n_pos, int32_t *n_neg, int32_t *n_bad, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (n_streams < 0 || ldp < 0) return fail(e, VAD_ERR_ARG, "vad_chunk_scores_device: negative size");
+    if (n_streams > 0 && (!probs || !n_chunks || !labels || !label_offsets || !key_offsets || !keys || !bce_pos || !bce_neg || !n_pos ||
+                          !n_neg || !n_bad))
+        return fail(e, VAD_ERR_ARG, "vad_chunk_scores_device: null probs, n_chunks, labels, an offset array, keys or an output");
+    if (((size_t)probs) & 3) return fail(e, VAD_ERR_ARG, "vad_chunk_scores_device: probs is not aligned to its elements");
+    if ((((size_t)bce_pos) | ((size_t)bce_neg)) & 7) return fail(e, VAD_ERR_ARG, "vad_chunk_scores_device: bce_pos / bce_neg are not aligned to 8 bytes");
+    if (((size_t)keys) & 3) return fail(e, VAD_ERR_ARG, "vad_chunk_scores_device: keys is not aligned to its elements");
+    if (n_streams > 0x7fffffffL) return fail(e, VAD_ERR_ARG, "vad_chunk_scores_device: n_streams does not fit one launch");
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, vad::launch_chunk_scores(probs, ldp, row_offsets, n_streams, n_chunks, labels, label_offsets, key_offsets, keys, bce_pos,
+                                        bce_neg, n_pos, n_neg, n_bad, (hipStream_t)stream));
+    return VAD_OK;
+}
+
+size_t vad_auc_workspace_bytes(long n) { return n < 0 || n > 0x7fffffffL ? 0 : vad::auc_workspace_bytes(n); }
+
+int vad_auc_counts_device(vad_engine *e, const uint32_t *keys, long n, void *workspace, size_t workspace_bytes, uint64_t *out, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (n < 0 || n > 0x7fffffffL) return fail(e, VAD_ERR_ARG, "vad_auc_counts_device: n must lie in [0, 2^31)");
+    if (!out || !workspace || (n > 0 && !keys)) return fail(e, VAD_ERR_ARG, "vad_auc_counts_device: null keys, workspace or out");
+    if ((((size_t)out) & 7) || (((size_t)workspace) & 15) || (((size_t)keys) & 3))
+        return fail(e, VAD_ERR_ARG, "vad_auc_counts_device: out must be aligned to 8 bytes, workspace to 16, keys to 4");
+    if (workspace_bytes < vad::auc_workspace_bytes(n))
+        return fail(e, VAD_ERR_ARG, "vad_auc_counts_device: workspace smaller than vad_auc_workspace_bytes(n)");
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, vad::launch_auc_counts(keys, n, workspace, reinterpret_cast<unsigned long long *>(out), (hipStream_t)stream));
+    return VAD_OK;
+}
+
 int vad_reserve(vad_engine *e, int sr, int B, long T) {
     if (!e) return VAD_ERR_ARG;
     if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");

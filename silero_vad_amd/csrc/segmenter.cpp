@@ -12,6 +12,7 @@
 #include "collector.hpp"
 #include "host_threads.hpp"
 #include "scanner.hpp"
+#include "scorer.hpp"
 #include "sweeper.hpp"
 
 extern "C" void vad_segment_params_default(vad_segment_params *p, int sampling_rate) {
@@ -116,6 +117,73 @@ extern "C" int vad_threshold_counts_host(const float *probs, long ldp, const lon
             if (lo < hi) work(lo, hi);
         });
     }
+    return VAD_OK;
+}
+
+// The validation scores (reference validate(), tuning/utils.py:252-298) on the host, the twins of kernel_score.hip; the per-chunk rule is
+// scorer.hpp.  A row's two sums are accumulated in double, chunk after chunk.
+extern "C" int vad_chunk_scores_host(const float *probs, long ldp, const long *row_offsets, long n_streams, const long *n_chunks,
+                                     const uint8_t *labels, const long *label_offsets, const long *key_offsets, uint32_t *keys,
+                                     double *bce_pos, double *bce_neg, int32_t *n_pos, int32_t *n_neg, int32_t *n_bad, int threads) {
+    if (n_streams < 0 || ldp < 0) return VAD_ERR_ARG;
+    if (n_streams > 0 && (!probs || !n_chunks || !labels || !label_offsets || !key_offsets || !keys || !bce_pos || !bce_neg || !n_pos ||
+                          !n_neg || !n_bad))
+        return VAD_ERR_ARG;
+    for (long i = 0; i < n_streams; ++i)
+        if (n_chunks[i] < 0 || (!row_offsets && n_chunks[i] > ldp) || label_offsets[i] < 0 || key_offsets[i] < 0 ||
+            (row_offsets && row_offsets[i] < 0))
+            return VAD_ERR_ARG;
+    auto work = [&](long lo, long hi) {
+        for (long i = lo; i < hi; ++i) {
+            const float *row = probs + (row_offsets ? row_offsets[i] : i * ldp);
+            const uint8_t *lab = labels + label_offsets[i];
+            uint32_t *out = keys + key_offsets[i];
+            double sum[2] = {0.0, 0.0};
+            int32_t count[4] = {0, 0, 0, 0};
+            for (long t = 0; t < n_chunks[i]; ++t) {
+                const unsigned l = lab[t];
+                const vad::ScoreChunk c = vad::score_chunk(l > 1u ? 0.0f : row[t], l);
+                out[t] = c.key;
+                ++count[c.kind];
+                if (c.kind == vad::kScorePos) sum[1] += c.term;
+                else if (c.kind == vad::kScoreNeg) sum[0] += c.term;
+            }
+            bce_pos[i] = sum[1];
+            bce_neg[i] = sum[0];
+            n_pos[i] = count[vad::kScorePos];
+            n_neg[i] = count[vad::kScoreNeg];
+            n_bad[i] = count[vad::kScoreBad];
+        }
+    };
+    int nt = threads > 0 ? threads : vad::default_host_threads(64);
+    nt = (int)std::max<long>(1, std::min<long>(nt, n_streams / 16 + 1));
+    if (nt == 1) {
+        work(0, n_streams);
+    } else {
+        const int blocks = (int)std::min<long>(n_streams, 4L * nt);
+        const long per = (n_streams + blocks - 1) / blocks;
+        vad::HostPool::get().run(nt, blocks, [&](int k) {
+            const long lo = k * per, hi = std::min(n_streams, lo + per);
+            if (lo < hi) work(lo, hi);
+        });
+    }
+    return VAD_OK;
+}
+
+// out[3] = {U2, n_pos, n_neg} over the keys other than VAD_SCORE_KEY_NONE: sorted, then one walk (AucWalk).  Ascending keys put, among
+// equal probabilities, the negatives in front of the positives.
+extern "C" int vad_auc_counts_host(const uint32_t *keys, long n, uint64_t *out) {
+    if (n < 0 || n > 0x7fffffffL || !out || (n > 0 && !keys)) return VAD_ERR_ARG;
+    std::vector<uint32_t> live;
+    live.reserve((size_t)n);
+    for (long i = 0; i < n; ++i)
+        if (keys[i] != VAD_SCORE_KEY_NONE) live.push_back(keys[i]);
+    std::sort(live.begin(), live.end());
+    vad::AucWalk walk;
+    for (uint32_t k : live) walk.feed(k);
+    out[0] = walk.u2;
+    out[1] = walk.n_pos;
+    out[2] = walk.n_neg;
     return VAD_OK;
 }
 

@@ -22,6 +22,7 @@
 import collections
 import contextlib
 import ctypes
+import math
 import os
 import time
 import types
@@ -1791,6 +1792,246 @@ def search_thresholds(audios: Sequence, labels: Sequence, model, sampling_rate: 
     """(enter, exit, accuracy) of the reference's threshold search (tuning/search_thresholds.py) over a labelled corpus:
     `ragged_threshold_counts(...).best()`."""
     return ragged_threshold_counts(audios, labels, model, sampling_rate, **kw).best()
+
+
+# ---- offline: validation loss and ROC-AUC of a labelled corpus -------------------------------------------------------
+SCORE_KEY_NONE = 0xFFFFFFFF   # VAD_SCORE_KEY_NONE: the key of a chunk that is not valid (csrc/scorer.hpp)
+
+
+class ValidationScores:
+    """What the reference's validate() (tuning/utils.py:252-298) needs of a labelled validation set, for R recordings in the caller's
+    order: bce_pos[R], bce_neg[R] (float64: the sums of the BCE terms of the valid label-1 / label-0 chunks), n_pos[R], n_neg[R]
+    (int32: valid chunks by label), n_bad[R] (int32: chunks labelled 0 / 1 whose probability is not in [0, 1]), n_chunks[R] (int64),
+    and the pooled rank statistic as Python ints: u2 = sum over the positive chunks of 2 #{negatives with a smaller probability} +
+    #{negatives with an equal one}, total_pos, total_neg.  `keys` (uint32, one per chunk at the recordings' corpus offsets) is kept
+    where the caller asked for it, else None."""
+
+    def __init__(self, bce_pos, bce_neg, n_pos, n_neg, n_bad, n_chunks, u2, total_pos, total_neg, keys=None):
+        self.bce_pos, self.bce_neg = np.asarray(bce_pos, dtype=np.float64), np.asarray(bce_neg, dtype=np.float64)
+        self.n_pos, self.n_neg, self.n_bad = (np.asarray(a, dtype=np.int32) for a in (n_pos, n_neg, n_bad))
+        self.n_chunks = np.asarray(n_chunks, dtype=np.int64)
+        self.u2, self.total_pos, self.total_neg = int(u2), int(total_pos), int(total_neg)
+        self.keys = keys
+
+    def _no_bad(self):
+        bad = int(self.n_bad.astype(np.int64).sum())
+        if bad:
+            raise ValueError(f"{bad} labelled chunks have a probability outside [0, 1] (a NaN too): all elements of input should be between 0 and 1")
+
+    def roc_auc(self) -> float:
+        """u2 / (2 total_pos total_neg): the Mann-Whitney statistic with ties at one half, what roc_auc_score returns on all chunks"""
+        self._no_bad()
+        if self.total_pos == 0 or self.total_neg == 0:
+            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        return self.u2 / (2 * self.total_pos * self.total_neg)
+
+    def loss(self, noise_loss: float = 0.5, batch_size=None) -> float:
+        """The reference's losses.avg: sum(bce_pos + noise_loss bce_neg) / sum over the batches of numel, a batch being `batch_size`
+        consecutive recordings (a DataLoader without shuffling) and numel = len(batch) x its largest chunk count -- the padded count
+        (loss * masks).mean() divides by.  batch_size None: every recording is its own batch, nothing padded."""
+        self._no_bad()
+        nck = self.n_chunks
+        if batch_size is None:
+            numel = int(nck.sum())
+        else:
+            b = int(batch_size)
+            if b <= 0:
+                raise ValueError("batch_size must be positive")
+            numel = sum(len(nck[a:a + b]) * int(nck[a:a + b].max()) for a in range(0, len(nck), b))
+        if numel == 0:
+            raise ValueError("no chunk to average over")
+        return float((math.fsum(self.bce_pos.tolist()) + float(noise_loss) * math.fsum(self.bce_neg.tolist())) / numel)
+
+    def reference(self, noise_loss: float = 0.5, batch_size=None):
+        """(loss, round(roc_auc, 3)): the pair the reference's validate() returns"""
+        return self.loss(noise_loss, batch_size), round(self.roc_auc(), 3)
+
+
+def _auc_counts_host(keys: np.ndarray):
+    out = np.zeros(3, dtype=np.uint64)
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    rc = lib().vad_auc_counts_host(keys.ctypes.data if len(keys) else None, len(keys), out.ctypes.data)
+    if rc != _lib.VAD_OK:
+        raise _lib.VadError(rc, "vad_auc_counts_host")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def _key_offsets(nck: np.ndarray, who):
+    offs = np.zeros(len(nck), dtype=np.int64)
+    if len(nck):
+        offs[1:] = np.cumsum(nck[:-1])
+    total = int(nck.sum())
+    if total >= 1 << 31:
+        raise ValueError(f"{who}: {total} chunks; the pooled ROC-AUC takes fewer than 2^31")
+    return offs, total
+
+
+def _score_rows_host(probs, nck, lab, l_offs, k_offs, keys, threads):
+    """vad_chunk_scores_host on probs[B, T] (a CPU float32 tensor) -> (bce_pos, bce_neg, n_pos, n_neg, n_bad); row i's keys are written
+    to keys[k_offs[i]:]"""
+    B, T = probs.shape
+    bp, bn = np.zeros(B, dtype=np.float64), np.zeros(B, dtype=np.float64)
+    cp, cn, cb = (np.zeros(B, dtype=np.int32) for _ in range(3))
+    none = np.zeros(8, dtype=np.uint8)                         # (rows of no chunks: something to point at)
+    rc = lib().vad_chunk_scores_host(probs.data_ptr() if B * T else none.ctypes.data, T, None, B, nck.ctypes.data,
+                                     lab.ctypes.data if len(lab) else none.ctypes.data, l_offs.ctypes.data, k_offs.ctypes.data,
+                                     keys.ctypes.data if len(keys) else none.ctypes.data, bp.ctypes.data, bn.ctypes.data, cp.ctypes.data,
+                                     cn.ctypes.data, cb.ctypes.data, int(threads))
+    if rc != _lib.VAD_OK:
+        raise _lib.VadError(rc, "vad_chunk_scores_host")
+    return bp, bn, cp, cn, cb
+
+
+def chunk_scores(probs, n_chunks, labels, threads: int = 0) -> ValidationScores:
+    """The validation scores on the host (vad_chunk_scores_host + vad_auc_counts_host, the twins of the device kernels: one source,
+    csrc/scorer.hpp): probs[B, T] float32 on the CPU, row i's first n_chunks[i] entries against labels[i] (uint8[n_chunks[i]]: 0, 1,
+    anything else = ignore)."""
+    probs = torch.as_tensor(probs, dtype=torch.float32).contiguous().cpu()
+    if probs.dim() != 2:
+        raise ValueError("chunk_scores: probs[B, T]")
+    B, T = probs.shape
+    nck = _sweep_rows(n_chunks, labels, B, T, "chunk_scores")
+    lab, offs = _pack_labels(labels, nck, "chunk_scores")
+    total = _key_offsets(nck, "chunk_scores")[1]
+    keys = np.full(total, SCORE_KEY_NONE, dtype=np.uint32)
+    rows = _score_rows_host(probs, nck, lab, offs, offs, keys, threads)
+    return ValidationScores(*rows, nck, *_auc_counts_host(keys), keys=keys)
+
+
+def _score_meta(nck: np.ndarray, lab: np.ndarray, l_offs: np.ndarray, k_offs: np.ndarray) -> torch.Tensor:
+    """int64[3 R + ceil(bytes / 8)]: the rows' chunk counts, label offsets and key offsets, then the label bytes (viewed as int64,
+    padded with ignore) -- one small tensor to the device per batch"""
+    R = len(nck)
+    words = (len(lab) + 7) // 8
+    m = np.empty(3 * R + words, dtype=np.int64)
+    m[:R], m[R:2 * R], m[2 * R:3 * R] = nck, l_offs, k_offs
+    tail = m[3 * R:].view(np.uint8)
+    tail[:len(lab)] = lab
+    tail[len(lab):] = LABEL_IGNORE
+    return torch.from_numpy(m)
+
+
+def _device_scores(engine, probs_dev, m_dev, B, keys_dev):
+    """Enqueue the score kernel of probs_dev's first B rows on the current stream; m_dev is the rows' _score_meta on the device.  The
+    keys go to keys_dev (int32 storage of the uint32 keys) at the rows' key offsets; returns ONE float64 device tensor holding
+    bce_pos[B], bce_neg[B], then n_pos[B], n_neg[B], n_bad[B] as int32 (_split_scores), so that one copy brings a bucket's sums home."""
+    out = torch.empty((2 * B + (3 * B + 1) // 2,), dtype=torch.float64, device=probs_dev.device)
+    at, mp = out.data_ptr(), m_dev.data_ptr()
+    _lib.check(engine._h, lib().vad_chunk_scores_device(
+        engine._h, probs_dev.data_ptr(), probs_dev.stride(0) if probs_dev.shape[0] > 1 else probs_dev.shape[1], None, B, mp, mp + 24 * B,
+        mp + 8 * B, mp + 16 * B, keys_dev.data_ptr(), at, at + 8 * B, at + 16 * B, at + 20 * B, at + 24 * B,
+        ctypes.c_void_p(torch.cuda.current_stream(probs_dev.device).cuda_stream)))
+    return out
+
+
+def _split_scores(flat: np.ndarray, B: int):
+    ints = flat[2 * B:].view(np.int32)
+    return flat[:B], flat[B:2 * B], ints[:B], ints[B:2 * B], ints[2 * B:3 * B]
+
+
+def _device_auc(engine, keys_dev, total):
+    """vad_auc_counts_device over keys_dev[:total] on the current stream -> (u2, total_pos, total_neg); 24 bytes come home"""
+    dev = keys_dev.device
+    need = int(lib().vad_auc_workspace_bytes(total))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    out = torch.empty(3, dtype=torch.int64, device=dev)
+    _lib.check(engine._h, lib().vad_auc_counts_device(engine._h, keys_dev.data_ptr(), total, ws.data_ptr(), need, out.data_ptr(),
+                                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return tuple(int(v) for v in out.cpu().numpy().view(np.uint64))
+
+
+def chunk_scores_device(engine, probs_dev: torch.Tensor, n_chunks, labels, keep_keys: bool = False) -> ValidationScores:
+    """`chunk_scores` for probabilities that are already on the GPU (probs_dev[B, T], CUDA float32, unit stride inside a row): the score
+    kernel and the pooled count run there (vad_chunk_scores_device, vad_auc_counts_device); the per-row sums and counts and three
+    integers are copied back -- and the keys, with keep_keys."""
+    if probs_dev.dim() != 2 or probs_dev.dtype != torch.float32 or (probs_dev.shape[1] > 1 and probs_dev.stride(1) != 1):
+        raise ValueError("chunk_scores_device: probs_dev[B, T] float32 with unit stride inside a row")
+    B, T = probs_dev.shape
+    nck = _sweep_rows(n_chunks, labels, B, T, "chunk_scores_device")
+    lab, offs = _pack_labels(labels, nck, "chunk_scores_device")
+    total = _key_offsets(nck, "chunk_scores_device")[1]
+    dev = probs_dev.device
+    keys_dev = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    m_dev = _score_meta(nck, lab, offs, offs).to(dev)
+    out = _device_scores(engine, probs_dev, m_dev, B, keys_dev)
+    auc = _device_auc(engine, keys_dev, total)
+    keys = keys_dev[:total].cpu().numpy().view(np.uint32) if keep_keys else None
+    return ValidationScores(*_split_scores(out.cpu().numpy(), B), nck, *auc, keys=keys)
+
+
+def ragged_validation(audios: Sequence, labels: Sequence, model, sampling_rate: int = 16000, max_waste: float = 0.15,
+                      max_bytes: int = 256 << 20, codec=None, channels=None, source_rate=None, threads: int = 0,
+                      keep_keys: bool = False) -> ValidationScores:
+    """The validation scores of a labelled corpus (the reference's validate(), tuning/utils.py:252-298: masked BCE loss and the ROC-AUC of
+    every chunk of the set): the recordings take the bucket route of `ragged_probs` and every bucket's score kernel is enqueued right
+    behind its kernels (vad_chunk_scores_device, one wave per recording).  It leaves the per-recording BCE sums and counts, which come
+    home in one copy per bucket, and one uint32 key per chunk in ONE device array at the recording's corpus offset; after the last
+    bucket vad_auc_counts_device counts the pooled rank statistic over that array and 24 bytes come home.  The probabilities never
+    leave the GPU.
+
+    labels: as in ragged_threshold_counts (uint8 per chunk; 0, 1, anything else = ignore; with `channels` one array per (recording,
+    channel) in `channel_rows` order, with `source_rate` per chunk of the resampled recording).  ValueError if a row's label count
+    differs from its chunk count or the corpus has 2^31 chunks or more.  A model without the device route (a CPU stand-in) takes the
+    host twins over the buckets' probabilities.  keep_keys: also bring the keys home (tests).  codec / channels / source_rate /
+    max_waste / max_bytes: as in ragged_probs."""
+    audios, codec, channels, rs = _resample_input(audios, codec, channels, model, source_rate, sampling_rate)
+    n = _rates(sampling_rate)[2]
+    audios, codec, fan = _channel_input(audios, codec, channels, model)
+    lengths = [_resampled_len(m, rs) for m in _describe(audios if fan is None else fan)[1]]
+    source_rate = source_rate if rs else None
+    R = len(lengths)
+    nck = np.asarray([(m + n - 1) // n for m in lengths], dtype=np.int64)
+    if len(labels) != R:
+        raise ValueError(f"ragged_validation: {R} rows and {len(labels)} label arrays")
+    lab, offs = _pack_labels(labels, nck, "ragged_validation")
+    total = _key_offsets(nck, "ragged_validation")[1]
+    bp, bn = np.zeros(R, dtype=np.float64), np.zeros(R, dtype=np.float64)
+    cp, cn, cb = (np.zeros(R, dtype=np.int32) for _ in range(3))
+    dev = getattr(model, "device", None)
+    on_gpu = dev is not None and torch.device(dev).type == "cuda"
+
+    def rows_of(idxs):
+        ix = np.asarray(idxs, dtype=np.int64)
+        return ix, [lab[offs[i]:offs[i] + nck[i]] for i in ix]
+
+    def local_offsets(ix):
+        b_off = np.zeros(len(ix), dtype=np.int64)
+        b_off[1:] = np.cumsum(nck[ix][:-1])
+        return b_off
+
+    if on_gpu and hasattr(getattr(model, "engine", None), "_h"):
+        keys_dev = torch.empty(max(total, 1), dtype=torch.int32, device=dev)      # every chunk's key, written bucket by bucket
+
+        def meta(idxs):
+            ix, rows = rows_of(idxs)
+            return _score_meta(nck[ix], np.concatenate(rows) if rows else lab[:0], local_offsets(ix), offs[ix])
+
+        def post(probs_dev, idxs, m_dev):
+            return [_device_scores(model.engine, probs_dev, m_dev, len(idxs), keys_dev)]
+
+        for idxs, outs, _ in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, post=post, meta=meta, codec=codec, _fan=fan,
+                                            source_rate=source_rate):
+            ix = np.asarray(idxs, dtype=np.int64)
+            bp[ix], bn[ix], cp[ix], cn[ix], cb[ix] = _split_scores(outs[0].numpy(), len(ix))
+        # (the lanes' streams have been joined into the current one: every bucket's keys are in front of this)
+        auc = _device_auc(model.engine, keys_dev, total)
+        keys = keys_dev[:total].cpu().numpy().view(np.uint32) if keep_keys else None
+    else:
+        keys = np.full(total, SCORE_KEY_NONE, dtype=np.uint32)
+        for idxs, probs in ragged_buckets(audios, model, sampling_rate, max_waste, max_bytes, codec=codec, _fan=fan, source_rate=source_rate):
+            ix, rows = rows_of(idxs)
+            p = torch.as_tensor(probs, dtype=torch.float32).contiguous()
+            bp[ix], bn[ix], cp[ix], cn[ix], cb[ix] = _score_rows_host(p, np.ascontiguousarray(nck[ix]), np.concatenate(rows) if rows else lab[:0],
+                                                                      local_offsets(ix), np.ascontiguousarray(offs[ix]), keys, threads)
+        auc = _auc_counts_host(keys)
+        keys = keys if keep_keys else None
+    return ValidationScores(bp, bn, cp, cn, cb, nck, *auc, keys=keys)
+
+
+def validate(audios: Sequence, labels: Sequence, model, sampling_rate: int = 16000, noise_loss: float = 0.5, batch_size=None, **kw):
+    """(loss, ROC-AUC rounded to 3 decimals) of a labelled corpus, the pair the reference's validate() returns (tuning/utils.py:252-298):
+    `ragged_validation(...).reference(noise_loss, batch_size)`."""
+    return ragged_validation(audios, labels, model, sampling_rate, **kw).reference(noise_loss, batch_size)
 
 
 # ---- offline: continuous refill ------------------------------------------------------------------------------------
