@@ -255,12 +255,14 @@ __device__ __forceinline__ void fft_inlane(f32x2 (&z)[Q]) {
 }
 
 // The math of one frame of 16 chunks from the lanes' PCM slices s[] (load_slice): X[s] (s < Q): |Y[4s + P[g]]|;  X[Q]: |Y[4Q]| in
-// group 0, 0 elsewhere.
-template <int Q>
+// group 0, 0 elsewhere.  ARRIVE >= 0: s[] are loads still in flight (fft_frame) -- they are waited for ONCE, behind the first window
+// requests, and the wave runs at issue priority ARRIVE from there on (the caller lowers it); ARRIVE < 0: s[] are plain values.
+template <int Q, int ARRIVE = -1>
 __device__ __forceinline__ void fft_math(float (&X)[Q + 1], const float (&s)[2 * Q], const float *tab_lds, const Lane &ln);
 
-// One frame (V) of 16 chunks: load the slices, then fft_math.
-template <int Q, typename PcmT, int DEC = 1>
+// One frame (V) of 16 chunks: load the slices, then fft_math.  PRIO > 0: the wave's issue priority from the arrival of the samples
+// to the end of the pass (normal priority while it only waits for PCM).
+template <int Q, typename PcmT, int DEC = 1, int PRIO = 0>
 __device__ __forceinline__ void fft_frame(float (&X)[Q + 1], const int V, const FrontArgs &a, const float *tab_lds,
                                           const Lane &ln) {
     constexpr int SL = 2 * Q;
@@ -283,31 +285,99 @@ __device__ __forceinline__ void fft_frame(float (&X)[Q + 1], const int V, const 
         X[Q] = s[0];
         return;
     }
-    fft_math<Q>(X, s, tab_lds, ln);
+    fft_math<Q, PRIO>(X, s, tab_lds, ln);
+    if (PRIO > 0) __builtin_amdgcn_s_setprio(0);
     VAD_WAVE_STAMP(ln, 3 + 2 * V);
 }
 
-template <int Q>
+// ---- issue order of a pass ---------------------------------------------------------------------------------------------------
+// A pass shares its SIMD's one vector-issue pipe with a partner wave that mostly streams MFMAs, and every time the pass stalls
+// the pipe goes to the partner and comes back for a ~10-cycle MFMA <-> VALU switch each way (profiles/r03a_issue_pipes2.md).
+// Consuming LDS round trips one by one -- a window vector, a twiddle row, a ds_bpermute pair, each with a wait of its own -- made
+// ~135 such stalls per pass.  So the LDS traffic is issued in BATCHES, a stage ahead of its use where registers allow, and each
+// batch is waited for once; the arithmetic, its operands and the order of every floating-point operation of a bin are unchanged.
+//   lds_fence: nothing crosses it at compile time (the batches stay where the source puts them).
+//   lds_wait<N>: at most N LDS operations of this wave outstanding (they return in order): the batch issued BEFORE the last N has
+// arrived.  A hint only -- the values are ordinary C++ values, the compiler's own waits stay correct without it.
+__device__ __forceinline__ void lds_fence() { __builtin_amdgcn_sched_barrier(0); }
+template <int N>
+__device__ __forceinline__ void lds_wait() {
+    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit field");
+    lds_fence();
+    __builtin_amdgcn_s_waitcnt(0xc07f | (N << 8));             // lgkmcnt(N); vmcnt, expcnt: no wait
+    lds_fence();
+}
+__device__ __forceinline__ void lds_wait_n(int n) {           // n: a constant once the caller's loop is unrolled
+    if (n >= 15) lds_wait<15>();
+    else if (n >= 12) lds_wait<12>();
+    else if (n >= 8) lds_wait<8>();
+    else if (n >= 4) lds_wait<4>();
+    else if (n >= 2) lds_wait<2>();
+    else lds_wait<0>();
+}
+template <int N>
+__device__ __forceinline__ void lds_rows(f32x4 (&o)[N], const f32x4 *p) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = p[i];
+}
+using f32x3 = float __attribute__((ext_vector_type(3)));
+// a twiddle row is 16 bytes of which three floats are used: ds_read_b96, three registers
+__device__ __forceinline__ f32x3 tw_row(const f32x4 *p) { return *reinterpret_cast<const f32x3 *>(p); }
+
+template <int Q, int ARRIVE>
 __device__ __forceinline__ void fft_math(float (&X)[Q + 1], const float (&s)[2 * Q], const float *tab_lds, const Lane &ln) {
     constexpr int SL = 2 * Q;
     constexpr vadl::Tab tb = vadl::make_tab(8 * Q, Q);
+    // Batch sizes, set by the registers a pass has free beside 99 magnitudes and z (the 16 kHz kernels sit at the 256-VGPR limit)
+    // and by the LDS latency under load, which the arithmetic of ONE small batch does not cover: the cross-lane stage's twiddles go
+    // 4 rows at a time with three batches in flight (36 registers), the unpack 4 bins at a time with two groups in flight (2 x (8
+    // partner values + 12 of twiddles)).  Measured on the C2 shape against one batch of 4 ahead / groups of 8 bins, none ahead:
+    // 4.22 against 4.27 ms (profiles/r07a_fft_pass_order.md).
+    constexpr int TB = 4, NTB = Q / TB, T1B = 4, NT1 = Q / T1B, T1D = 3;
+    static_assert(Q % TB == 0 && SL % 16 == 0, "batches are whole");
+    const f32x4 *tw1 = reinterpret_cast<const f32x4 *>(tab_lds + tb.tw1 + ln.g * Q * 4);
+    const f32x4 *tw2 = reinterpret_cast<const f32x4 *>(tab_lds + tb.tw2 + ln.g * Q * 4);
 
     f32x2 z[Q];
-    {   // window (same taps for every frame: the lane's slice always sits at 2Q g inside the frame)
+    {   // window (same taps for every frame: the lane's slice always sits at 2Q g inside the frame), in quarters: two are
+        // requested before the first sample is touched, the others as registers come free
+        constexpr int NWB = 4, WQ = SL / 4 / NWB;
         const f32x4 *w = reinterpret_cast<const f32x4 *>(tab_lds + tb.window + SL * ln.g);
+        f32x4 wv[NWB][WQ];
+        lds_fence();                                           // (not into the caller's loads: their registers are still busy)
+        lds_rows<WQ>(wv[0], w);
+        lds_rows<WQ>(wv[1], w + WQ);
+        if (ARRIVE >= 0) {
+            lds_fence();
+            __builtin_amdgcn_s_waitcnt(0x0f70);                // vmcnt(0): the samples
+            if (ARRIVE > 0) __builtin_amdgcn_s_setprio(ARRIVE);
+        }
 #pragma unroll
-        for (int k = 0; k < SL / 4; ++k) {
-            const f32x4 wv = w[k];
-            z[2 * k] = f32x2{s[4 * k], s[4 * k + 1]} * f32x2{wv[0], wv[1]};
-            z[2 * k + 1] = f32x2{s[4 * k + 2], s[4 * k + 3]} * f32x2{wv[2], wv[3]};
+        for (int b = 0; b < NWB; ++b) {
+            if (b < NWB - 1) lds_wait<WQ>();                         // (the quarter behind this one stays in flight)
+            else lds_wait<0>();
+#pragma unroll
+            for (int i = 0; i < WQ; ++i) {
+                const int k = b * WQ + i;
+                z[2 * k] = f32x2{s[4 * k], s[4 * k + 1]} * f32x2{wv[b][i][0], wv[b][i][1]};
+                z[2 * k + 1] = f32x2{s[4 * k + 2], s[4 * k + 3]} * f32x2{wv[b][i][2], wv[b][i][3]};
+            }
+            lds_fence();
+            if (b + 2 < NWB) lds_rows<WQ>(wv[b + 2], w + (b + 2) * WQ);
         }
     }
+    // the first batches of the cross-lane stage's twiddles travel while the stage runs
+    f32x3 t1[NT1][T1B];
+#pragma unroll
+    for (int b = 0; b < T1D - 1; ++b)
+#pragma unroll
+        for (int i = 0; i < T1B; ++i) t1[b][i] = tw_row(tw1 + b * T1B + i);
+    lds_fence();
     // radix-4 across the 4 lanes of a chunk.  Stage A pairs g <-> g^2 (lanes 32 apart), stage B pairs g <-> g^1
     // (lanes 16 apart).  Each pair splits the butterflies between its two lanes with gfx950's register-pair swaps
     // (v_permlane32_swap / v_permlane16_swap: VALU, no LDS round trip, no lane selects): the lower lane trades its
     // upper Q/2 values for the upper lane's lower Q/2, both lanes form sums and differences of what they now hold,
     // and a second trade leaves all sums in the lower lane and all differences (lower minus upper) in the upper one.
-    const f32x4 *tw1 = reinterpret_cast<const f32x4 *>(tab_lds + tb.tw1 + ln.g * Q * 4);
 #if VAD_XLANE_SWAP
     constexpr int H = Q / 2;
     // lane group 3 multiplies by -i between the two stages.  Its values are the stage-A differences formed in the odd lane
@@ -335,12 +405,6 @@ __device__ __forceinline__ void fft_math(float (&X)[Q + 1], const float (&s)[2 *
     }
 #pragma unroll
     for (int q = 0; q < H; ++q) trade16(z[q], z[q + H]);
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const f32x2 x = z[q];
-        const f32x4 t = tw1[q];                        // * W_4Q^(P[g] q): (-s, s, c, 0)
-        z[q] = __builtin_elementwise_fma(swap2(x), f32x2{t[0], t[1]}, x * f32x2{t[2], t[2]});
-    }
 #else
     const f32x2 sA{ln.sgnA, ln.sgnA}, sB{ln.sgnB, ln.sgnB};
     // lane group 3 multiplies by -i between the two stages: x*rotA + swap(x)*rotB
@@ -353,35 +417,85 @@ __device__ __forceinline__ void fft_math(float (&X)[Q + 1], const float (&s)[2 *
         x = __builtin_elementwise_fma(sA, x, p);       // g<2: own + partner ; g>=2: partner - own
         x = __builtin_elementwise_fma(swap2(x), rotB, x * rotA);
         const f32x2 r{__shfl_xor(x.x, 16), __shfl_xor(x.y, 16)};
-        x = __builtin_elementwise_fma(sB, x, r);       // g even: own + partner ; g odd: partner - own
-        const f32x4 t = tw1[q];                        // * W_4Q^(P[g] q): (-s, s, c, 0)
-        z[q] = __builtin_elementwise_fma(swap2(x), f32x2{t[0], t[1]}, x * f32x2{t[2], t[2]});
+        z[q] = __builtin_elementwise_fma(sB, x, r);    // g even: own + partner ; g odd: partner - own
     }
 #endif
-    fft_inlane<Q>(z);
-    // real-FFT split: Y[k] = E + W_8Q^k O from Z[k] and conj Z[4Q - k]
+    // * W_4Q^(P[g] q), rows (-s, s, c, 0): a batch is multiplied while the next two travel
+    lds_fence();
+#pragma unroll
+    for (int b = 0; b < NT1; ++b) {
+        if (b + T1D - 1 < NT1) {
+#pragma unroll
+            for (int i = 0; i < T1B; ++i) t1[b + T1D - 1][i] = tw_row(tw1 + (b + T1D - 1) * T1B + i);
+        }
+        lds_wait_n((NT1 - 1 - b < T1D - 1 ? NT1 - 1 - b : T1D - 1) * T1B);
+#pragma unroll
+        for (int i = 0; i < T1B; ++i) {
+            const int q = b * T1B + i;
+            const f32x2 x = z[q];
+            const f32x3 t = t1[b][i];
+            z[q] = __builtin_elementwise_fma(swap2(x), f32x2{t[0], t[1]}, x * f32x2{t[2], t[2]});
+        }
+        lds_fence();
+    }
+    // the real-FFT unpack's traffic: twiddle rows and partner fetches of a group of bins (the first rows travel under the in-lane stages)
     constexpr int LG = ilog2(Q);
-    const f32x4 *tw2 = reinterpret_cast<const f32x4 *>(tab_lds + tb.tw2 + ln.g * Q * 4);
     // partner bin 8Q - k lives in the same lane for groups 0, 1 and in lane ^ 16 for groups 2, 3
     const int src_lane4 = (ln.g >= 2 ? (ln.lane ^ 16) : ln.lane) * 4;
+    f32x3 t2[NTB][TB];
+    float xr[NTB][TB], xi[NTB][TB];
+    auto bin = [&](int n, int i) { return i < TB / 2 ? (TB / 2) * n + i : Q - 1 - (TB / 2) * n - (i - TB / 2); };
+    auto rows = [&](int n) __attribute__((always_inline)) {
 #pragma unroll
-    for (int k = 0; k < Q; ++k) {
-        const f32x2 u = z[bitrev(k, LG)];
-        const int ks = bitrev((Q - k) % Q, LG), kr = bitrev(Q - 1 - k, LG);
-        const f32x2 own = z[kr], alt = z[ks];
-        const float xr = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane4, __float_as_int(own.x)));
-        const float xi = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane4, __float_as_int(own.y)));
-        const f32x2 p{ln.g == 0 ? alt.x : xr, ln.g == 0 ? alt.y : xi};
-        const f32x2 av = __builtin_elementwise_fma(p, f32x2{1.0f, -1.0f}, u);     // Z + conj(Zp)
-        const f32x2 ev = __builtin_elementwise_fma(p, f32x2{-1.0f, 1.0f}, u);     // Z - conj(Zp)
-        // y = av + (-i ev) (c + i sn) = av + ev (sn - i c)
-        const f32x4 t = tw2[k];                                                  // (c, -c, s, 0)
-        const f32x2 y = __builtin_elementwise_fma(swap2(ev), f32x2{t[0], t[1]},
-                                                  __builtin_elementwise_fma(ev, f32x2{t[2], t[2]}, av));
-        const f32x2 yy = y * y;
-        X[k] = 0.5f * __builtin_amdgcn_sqrtf(yy.x + yy.y);
-    }
+        for (int i = 0; i < TB; ++i) t2[n][i] = tw_row(tw2 + bin(n, i));
+    };
+    auto fetch = [&](int n) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TB; ++i) {
+            const f32x2 own = z[bitrev(Q - 1 - bin(n, i), LG)];
+            xr[n][i] = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane4, __float_as_int(own.x)));
+            xi[n][i] = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane4, __float_as_int(own.y)));
+        }
+    };
+    rows(0);
+    lds_fence();
+    fft_inlane<Q>(z);
     X[Q] = ln.g == 0 ? fabsf(z[0].x - z[0].y) : 0.f;           // Nyquist: Re Z0 - Im Z0
+    lds_fence();
+    // real-FFT split: Y[k] = E + W_8Q^k O from Z[k] and conj Z[4Q - k]
+    // Bins go in groups of TB: k = 2 n, 2 n + 1 with their mirrors Q-1-k.  A bin reads z[k], z[Q-1-k] and z[Q-k], so in this
+    // order z dies at the rate at which X is born (ascending k would hold all of z to the end: 33 registers the pass does not
+    // have).  A group's 2 TB partner fetches and TB twiddle rows are issued one group ahead and waited for ONCE; its bins are
+    // formed as independent chains -- the square roots, quarter rate, stand apart from one another.
+    fetch(0);
+#pragma unroll
+    for (int n = 0; n < NTB; ++n) {
+        if (n + 1 < NTB) {
+            rows(n + 1);
+            fetch(n + 1);
+            lds_wait<3 * TB>();
+        } else {
+            lds_wait<0>();
+        }
+        float m2[TB];
+#pragma unroll
+        for (int i = 0; i < TB; ++i) {
+            const int k = bin(n, i);
+            const f32x2 u = z[bitrev(k, LG)], alt = z[bitrev((Q - k) % Q, LG)];
+            const f32x2 p{ln.g == 0 ? alt.x : xr[n][i], ln.g == 0 ? alt.y : xi[n][i]};
+            const f32x2 av = __builtin_elementwise_fma(p, f32x2{1.0f, -1.0f}, u);     // Z + conj(Zp)
+            const f32x2 ev = __builtin_elementwise_fma(p, f32x2{-1.0f, 1.0f}, u);     // Z - conj(Zp)
+            // y = av + (-i ev) (c + i sn) = av + ev (sn - i c)
+            const f32x3 t = t2[n][i];                                                   // (c, -c, s, 0)
+            const f32x2 y = __builtin_elementwise_fma(swap2(ev), f32x2{t[0], t[1]},
+                                                      __builtin_elementwise_fma(ev, f32x2{t[2], t[2]}, av));
+            const f32x2 yy = y * y;
+            m2[i] = yy.x + yy.y;
+        }
+#pragma unroll
+        for (int i = 0; i < TB; ++i) X[bin(n, i)] = 0.5f * __builtin_amdgcn_sqrtf(m2[i]);
+        lds_fence();
+    }
 }
 
 // ---- non-finite input -------------------------------------------------------------------------------------------------------

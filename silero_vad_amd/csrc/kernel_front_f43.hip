@@ -139,7 +139,9 @@ __device__ __forceinline__ void gemm_r(f32x4 (&acc)[M], BF bfun, Ring &r) {
 #define VAD_F43_GEMM_PRIO 0        // A/B: issue priority of a wave from the end of its FFT passes on
 #endif
 #ifndef VAD_F43_FFT_PRIO
-#define VAD_F43_FFT_PRIO 0         // A/B (tools/variants.py fftprio*): issue priority of a wave while it transforms a frame
+#define VAD_F43_FFT_PRIO 1         // issue priority of a wave from the arrival of a frame's samples to the end of its FFT pass (fft_wave.hpp
+                                   // fft_frame).  With the pass's LDS traffic batched the pass can issue back to back, and it pays to let it:
+                                   // 5.378 against 5.420 ms per C2 step at 0; 3 reads the same as 1 (profiles/r07a_fft_pass_order.md)
 #endif
 template <int Q, typename PcmT, int DEC>
 __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
@@ -235,9 +237,7 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
 #pragma unroll
             for (int k = 0; k <= Q; ++k) X2[k] = X3[k];
         }
-        if (VAD_F43_FFT_PRIO) __builtin_amdgcn_s_setprio(VAD_F43_FFT_PRIO);
-        fft_frame<Q, PcmT, DEC>(X3, v, a, tab, ln);
-        if (VAD_F43_FFT_PRIO) __builtin_amdgcn_s_setprio(0);
+        fft_frame<Q, PcmT, DEC, VAD_F43_FFT_PRIO>(X3, v, a, tab, ln);
     }
     if (VAD_F43_GEMM_PRIO) __builtin_amdgcn_s_setprio(VAD_F43_GEMM_PRIO);
     // |Y_nyq| of chunk j lives in lane group 0 (X[Q]); every lane of the chunk needs it

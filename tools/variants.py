@@ -31,7 +31,7 @@ VARIANTS = {
     "nobvbatch": ["-DVAD_BV_BATCH=0"],                 # frontend: B-operand transforms interleaved with the MFMAs (round-2 form)
     "xbasis": ["-DVAD_F43_EF=0"],                       # F(4,3) input transform from x0..x3 instead of (E, F, x1, x2) (f43 form only)
     "trace": ["-DVAD_TRACE=1"],
-    "fftprio1": ["-DVAD_F43_FFT_PRIO=1"], "fftprio3": ["-DVAD_F43_FFT_PRIO=3"],
+    "fftprio0": ["-DVAD_F43_FFT_PRIO=0"], "fftprio1": ["-DVAD_F43_FFT_PRIO=1"], "fftprio3": ["-DVAD_F43_FFT_PRIO=3"],   # (default: 1)
     "trace_fftprio3": ["-DVAD_TRACE=1", "-DVAD_F43_FFT_PRIO=3"],
     "gemmprio3": ["-DVAD_F43_GEMM_PRIO=3"], "trace_gemmprio3": ["-DVAD_TRACE=1", "-DVAD_F43_GEMM_PRIO=3"],
     "trace_noload": ["-DVAD_TRACE=1", "-DVAD_ABLATE=4"],
