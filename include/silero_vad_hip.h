@@ -828,6 +828,53 @@ int  vad_host_threads(void);
  * afterwards follow).  Returns the node, or -1 if it is unknown or outside the process' CPU mask (nothing changed).   */
 int  vad_bind_host_to_device(int device);
 
+/* ---- decoder training -------------------------------------------------------------------------------------------------------------
+ * The reference's train() (tuning/utils.py:206-249, driven by tune.py) learns one module, VADDecoderRNNJIT: LSTMCell(128, 128),
+ * Dropout, ReLU, Conv1d(128, 1, 1), Sigmoid -- 132 225 parameters -- on the output of the frozen STFT and encoder, with the loss
+ * (BCELoss(reduction = 'none') * masks).mean() over the padded batch.  Three calls bring that to the device.
+ *
+ * vad_encode_audio: feat[b][t][0..127] = ReLU output of encoder 3 for chunk t of row b, what the reference's stft + encoder return.
+ * pcm (elem_size 2 = int16 or 4 = float32, [B][ld]), ctx ([B][64 | 32], read only: every row starts from the context given and the
+ * next context is dropped) and feat ([B][T][128], T = ceil(ceil(L / k) / N), 16-byte aligned) are device pointers.  sr as for
+ * vad_forward_audio: 8000, 16000 or a multiple of 16000, decimated the same way; long inputs run in the same time slabs.  The values
+ * are the bits of the operand the product's gate GEMM consumes; a non-finite sample makes its chunk's vector NaN.
+ * The first call builds a second set of weight images (two blocking copies, one device synchronisation); after that nothing is
+ * allocated beyond the engine's scratch (vad_reserve).  Asynchronous on `stream`.  Not with impl=reference (VAD_ERR_OPTION).        */
+int vad_encode_audio(vad_engine *e, int sr, int B, long L, const void *pcm, size_t elem_size, long ld, const float *ctx, float *feat,
+                     void *stream);
+
+/* Loss and gradients of the decoder by back-propagation through time.  The rule (csrc/trainer.hpp): row b runs from zero (h, c)
+ * over t < n_chunks[b], nothing behind that is read; aten::lstm_cell in gate order i, f, g, o; y = keep ? relu(h) keep_scale : 0
+ * (keep == NULL: y = relu(h)); z = w_out y + b_out; p = sigmoid(z).  Chunk weight w: 1 for label 1, noise_loss for label 0, 0 for
+ * any other label (VAD_LABEL_IGNORE).  loss = sum w bce(p, label) / denom with nn.BCELoss's term (log clamped at -100, taken in
+ * double); for a batch of the reference denom = len(batch) * longest row.  The head's backward is on the float32 probability,
+ * dz = (w / denom) (p - label) [p (1 - p) / max(p (1 - p), 1e-12)]: a chunk whose fp32 p is exactly 0 or 1 hands back nothing, as
+ * under torch.  The rest is plain BPTT; db_ih and db_hh are the same sums.
+ * Shapes: w_ih, w_hh [512][128]; b_ih, b_hh [512]; w_out [128]; b_out [1]; feat [B][T][128]; labels [B][ldl], ldl >= T;
+ * keep [B][T][128] bytes (0 = dropped) or NULL; probs [B][T] or NULL (0 behind n_chunks).
+ * Device call: every pointer is a device pointer; asynchronous on `stream`, allocates nothing; fp32 with the ulp-accurate
+ * activations of csrc/activations.hpp; no float atomics -- the same inputs give the same bits, and a row's probabilities do not depend on its place
+ * in the batch.  Workspace: vad_decoder_grad_workspace_bytes(B, T) bytes, 256-byte aligned, about B T (512 * 2 + 7 * 128) * 4 bytes
+ * plus at most 34 MB of split-K slabs (280 MB in all at 128 x 250); 0 = B T out of range.  n_chunks[b] is clamped to [0, T].
+ * VAD_ERR_ARG, with nothing queued and nothing written: a NULL pointer, B <= 0, T <= 0, ldl < T, denom <= 0 (or NaN), feat / w_ih /
+ * w_hh not 16-byte aligned, any other tensor not 4-byte aligned, loss / n_chunks not 8-byte aligned, a workspace that is not
+ * 256-byte aligned or too small.  A host-only engine: VAD_ERR_NO_DEVICE.
+ * Host twin: no engine, host pointers, everything in double except that p is rounded to float32 before the loss term and dz; the
+ * parameters and the gradients are DOUBLE (the reference the device call and the fixtures are compared with); n_chunks[b] outside
+ * [0, T] is VAD_ERR_ARG.  The result does not depend on `threads` (<= 0: vad_host_threads(), at most 64).                          */
+typedef struct { const float *w_ih, *w_hh, *b_ih, *b_hh, *w_out, *b_out; } vad_decoder_params;
+typedef struct { float *w_ih, *w_hh, *b_ih, *b_hh, *w_out, *b_out; } vad_decoder_grads;
+typedef struct { const double *w_ih, *w_hh, *b_ih, *b_hh, *w_out, *b_out; } vad_decoder_params_f64;
+typedef struct { double *w_ih, *w_hh, *b_ih, *b_hh, *w_out, *b_out; } vad_decoder_grads_f64;
+size_t vad_decoder_grad_workspace_bytes(int B, long T);
+int vad_decoder_grad_device(vad_engine *e, const vad_decoder_params *p, const float *feat, int B, long T, const long *n_chunks,
+                            const uint8_t *labels, long ldl, const uint8_t *keep /* [B][T][128] or NULL */, float keep_scale,
+                            float noise_loss, double denom, vad_decoder_grads *g, double *loss, float *probs /* [B][T] or NULL */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int vad_decoder_grad_host(const vad_decoder_params_f64 *p, const float *feat, int B, long T, const long *n_chunks, const uint8_t *labels,
+                          long ldl, const uint8_t *keep, float keep_scale, float noise_loss, double denom, vad_decoder_grads_f64 *g,
+                          double *loss, float *probs, int threads);
+
 /* ---- test / bring-up hooks (not part of the drop-in surface) -------------------------------------
  * Host-only: size and contents of the packed weight images the kernels consume, so CPU tests can
  * check the fragment packing without a GPU.  which: 0 = frontend GEMM stream (enc0 "direct"), 1 = recurrent

@@ -10,6 +10,8 @@ from .streams import (BatchVADIterator, PackedRecordings, RaggedPlan, RefillPlan
                       ragged_speech_segments, ragged_speech_audio, collect_chunks_device, segment_probs_batch, segment_probs_batch_device, g711_expand, decimate, resample, resample_device, resample_geometry, resample_table, snapshot_info, ROW_SILENT, deinterleave, channel_rows,
                       ThresholdCounts, ThresholdPairs, LABEL_IGNORE, threshold_pairs, chunk_labels, threshold_counts, threshold_counts_device, ragged_threshold_counts, search_thresholds,
                       ValidationScores, SCORE_KEY_NONE, chunk_scores, chunk_scores_device, ragged_validation, validate)
+from .tuning import (DecoderTrainer, decoder_grad, decoder_grad_host, decoder_grad_workspace_bytes, decoder_state_dict, replace_decoder, tune,  # noqa: F401
+                     DECODER_NAMES)
 from .sharding import shard_range, shard_by_duration, gather_to_rank0, batch_speech_timestamps  # noqa: F401
 
 __version__ = "0.1.0"

@@ -141,6 +141,12 @@ SYMBOLS = {
     "vad_auc_workspace_bytes": (c_size_t, [c_long]),
     "vad_auc_counts_host": (c_int, [c_void_p, c_long, c_void_p]),
     "vad_auc_counts_device": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "vad_encode_audio": (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_size_t, c_long, c_void_p, c_void_p, c_void_p]),
+    "vad_decoder_grad_workspace_bytes": (c_size_t, [c_int, c_long]),
+    "vad_decoder_grad_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p, c_float, c_float, c_double,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vad_decoder_grad_host": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p, c_float, c_float, c_double, c_void_p,
+                                      c_void_p, c_void_p, c_int]),
     "vad_iterator_feed":(c_long, [c_void_p, c_void_p, c_long, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_long]),
     "vad_stage_rows": (c_int, [POINTER(c_void_p), POINTER(c_long), c_long, c_long, c_size_t, c_void_p, c_int]),

@@ -18,6 +18,15 @@ __device__ __forceinline__ float tanh_f(float x) {
     return fmaf(2.0f, sigmoid_f(2.0f * x), -1.0f);
 }
 
+// The same two functions to an ulp or two, for the training kernels (kernel_train.hip).  The forms above are good to 1.1e-7 / 2.2e-7
+// ABSOLUTE, which is what a probability needs.  A gradient also needs the SIGN of h = o tanh(c): it decides whether the head's ReLU
+// hands anything back to the unit.  tanh_f returns 0 or the wrong sign for |c| below ~2e-7, and an absolute error of 1e-7 in a gate
+// moves a cell state that the sums have brought close to zero across it; of the half million live units of a 130 x 64 batch a few
+// are that close (smallest |c| measured: 3e-8), and each flipped unit changes that row's gradient by parts in a thousand, where
+// torch's ulp-accurate functions flip none (profiles/decoder_training.md).
+__device__ __forceinline__ float sigmoid_ulp_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float tanh_ulp_f(float x) { return tanhf(x); }
+
 // The head's ReLU.  torch.relu is clamp_min(0) and PROPAGATES NaN (v_max_f32 / fmaxf would return the other operand): a stream
 // whose carried (h, c) is NaN -- one NaN / Inf sample is enough, see fft_wave.hpp "non-finite input" -- must read NaN until it is
 // reset, exactly as the reference does (JIT!/torch/nn/modules/container/___torch_mangle_7.py:10-19; goldens: tests/golden/

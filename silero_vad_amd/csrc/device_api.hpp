@@ -295,4 +295,28 @@ hipError_t launch_foreign_spin(float *sink, int blocks, long iters, int kind, hi
 // gx (fragment order) -> row-major [B][T][512] for vad_debug_frontend
 hipError_t launch_unpack_gx(const float *gx, float *out, int B, long T, hipStream_t s);
 
+
+// Decoder training (kernel_train.hip; the rule and the workspace layout are trainer.hpp).  Every pointer is a device pointer; feat,
+// w_ih and w_hh are 16-byte aligned, the workspace 256-byte aligned and train_layout(B, T).total bytes long.  Six launches, no
+// synchronisation, no float atomics.
+struct TrainArgs {
+    const float *w_ih, *w_hh, *b_ih, *b_hh, *w_out, *b_out;    // the parameters of THIS call
+    const float *feat;                                         // [B][T][128]
+    int B;
+    long T;
+    const long *n_chunks;                                      // [B], clamped to [0, T]
+    const uint8_t *labels;                                     // [B][ldl]
+    long ldl;
+    const uint8_t *keep;                                       // [B][T][128] or nullptr
+    float keep_scale, noise_loss;
+    double denom;
+    float *g_wih, *g_whh, *g_bih, *g_bhh, *g_wout, *g_bout;
+    double *loss;
+    float *probs;                                              // [B][T] or nullptr
+    void *workspace;
+};
+hipError_t launch_decoder_grad(const TrainArgs &a, hipStream_t s);
+// vad_encode_audio: gate rows 0 .. 127 of a slab of gx (fragment order, nt steps) -> feat[B][T][128] at steps t0 .. t0 + nt
+hipError_t launch_unpack_feat(const float *gx, float *feat, int B, long T, long t0, long nt, hipStream_t s);
+
 }  // namespace vad

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cctype>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include "device_api.hpp"
 #include "host_threads.hpp"
 #include "layout.hpp"
+#include "trainer.hpp"
 #include "weights.hpp"
 
 #ifndef VAD_AB
@@ -43,6 +45,9 @@ struct vad_images {
     // the resampling tables in device memory, one per (src, dst) pair ever asked for (vad_resample_reserve / vad_resample_rows_device);
     // an engine and its clones -- the lanes of a corpus run, each on a thread or stream of its own -- share them
     std::mutex resample_mutex;
+    // vad_encode_audio: the images of the SAME container with W_ih = [I; 0; 0; 0] and b_ih = b_hh = 0, built on the first call
+    std::mutex enc_mutex;
+    std::shared_ptr<vad_images> enc;
     std::map<std::pair<int, int>, vad::ResampleDeviceTable> resample;
     ~vad_images() {
         if (device < 0) return;
@@ -243,7 +248,11 @@ int grow(vad_engine *e, void **buf, size_t *have, size_t need, hipStream_t strea
 // folded into the load; fp32 frontend).
 template <typename PcmT>
 int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm, long ld, float *ctx,
-                 float *state, float *probs, long ldp, hipStream_t stream, float *ctx_next = nullptr, const uint8_t *present = nullptr) {
+                 float *state, float *probs, long ldp, hipStream_t stream, float *ctx_next = nullptr, const uint8_t *present = nullptr,
+                 float *feat = nullptr) {
+    // feat: vad_encode_audio -- the frontend alone, on the image set whose "gate rows" 0 .. 127 are the encoder's output; no
+    // recurrence, and the context goes to scratch and stays there
+    const vad_images &im = feat ? *e->img->enc : *e->img;
     const int ni = net_index(sr);
     const int N = sr == 16000 ? 512 : 256, C = N / 8;
     const long Ld = (L + dec - 1) / dec;                 // samples per row at the net's rate
@@ -287,11 +296,11 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
         const long nt = std::min(slab, T - t0);
         vad::FrontArgs fa{};
 #if VAD_AB
-        fa.wfront = e->enc0 == 2 ? e->img->d_front4[ni] : e->enc0 == 1 ? e->img->d_front_wino[ni] : e->img->d_front[ni];
+        fa.wfront = e->enc0 == 2 ? im.d_front4[ni] : e->enc0 == 1 ? im.d_front_wino[ni] : im.d_front[ni];
 #else
-        fa.wfront = e->img->d_front4[ni];
+        fa.wfront = im.d_front4[ni];
 #endif
-        fa.tables = e->img->d_tables[ni];
+        fa.tables = im.d_tables[ni];
         fa.pcm = pcm;
         fa.tail = tail;
         fa.ld = ld; fa.L = Ld; fa.T = T; fa.t0 = t0; fa.nt = nt;
@@ -303,11 +312,11 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
         fa.trace = e->trace;
         // chunks with an exactly silent frame beside one that is not: double-precision gx (the product's fp32 frontend only)
         const bool exact = e->exact_transitions && e->enc0 == 2 && !e->front_b9;
-        fa.exact_net = exact ? e->img->d_ref + ni : nullptr;
-        fa.gx_silent = exact && e->exact_all_silent ? e->img->d_gx_silent + 512 * ni : nullptr;
+        fa.exact_net = exact ? im.d_ref + ni : nullptr;
+        fa.gx_silent = exact && e->exact_all_silent ? im.d_gx_silent + 512 * ni : nullptr;
         vad::RecArgs ra{};
-        ra.whh = e->rec_b9 ? reinterpret_cast<const float *>(e->img->d_whh_b9[ni]) : e->img->d_whh[ni];
-        ra.tables = e->img->d_tables[ni];
+        ra.whh = e->rec_b9 ? reinterpret_cast<const float *>(im.d_whh_b9[ni]) : im.d_whh[ni];
+        ra.tables = im.d_tables[ni];
         ra.gx = e->d_gx;
         ra.state = state;
         ra.probs = probs;
@@ -326,10 +335,10 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
         }
         const long tiles = (long)((B + 15) / 16) * nt;
         const bool one = T == 1 && dec == 1 && B <= e->one_max && !e->rec_b9 && !e->front_b9 && e->enc0 == 2;
-        if (T == 1 && e->fuse_step && !e->rec_b9 && !e->front_b9 && e->enc0 == 2 && (tiles <= e->lat_tiles || one)) {
+        if (T == 1 && !feat && e->fuse_step && !e->rec_b9 && !e->front_b9 && e->enc0 == 2 && (tiles <= e->lat_tiles || one)) {
             // one step, few tiles (a stream pool's tick, a B = 1 call): frontend, LSTM cell and head in ONE kernel, no gx round trip
             vad::CellArgs ca{};
-            ca.whh_lat = e->img->d_whh_lat[ni];
+            ca.whh_lat = im.d_whh_lat[ni];
             ca.state = state;
             ca.probs = probs;
             ca.ldp = ldp;
@@ -351,7 +360,7 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
         }
         bool front_stamped = false;
         if (e->front_b9) {
-            fa.wfront = reinterpret_cast<const float *>(e->img->d_front_b9[ni]);
+            fa.wfront = reinterpret_cast<const float *>(im.d_front_b9[ni]);
             HIP_TRY(e, vad::launch_front_b9<PcmT>(sr, fa, stream));
         } else
 #if VAD_AB
@@ -369,17 +378,23 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
             HIP_TRY(e, vad::launch_exact_fix<PcmT>(sr, fa, stream));     //  ... the fix-up pass is part of the path, not of that kernel)
         }
         if (prof && !front_stamped) HIP_TRY(e, hipEventRecord(ev[1], stream));
+        if (feat) {
+            HIP_TRY(e, vad::launch_unpack_feat(e->d_gx, feat, B, T, t0, nt, stream));
+            if (prof) HIP_TRY(e, hipEventRecord(ev[2], stream));
+            continue;
+        }
         if (e->rec_b9) HIP_TRY(e, vad::launch_rec_b9(sr, ra, stream));
         else if (e->rec_form != 1 && B <= vad::kRecSmallMaxB) {
             // a file at a time, a bucket of a few hundred: W_hh h as matrix-vector products on the VALU, 1-4 streams per CU -- the same bits
             // at 1.2-2.7 us per step instead of 4.3
-            ra.whh = e->img->d_whh_rows[ni];
+            ra.whh = im.d_whh_rows[ni];
             HIP_TRY(e, vad::launch_rec_small(sr, ra, stream));
         } else HIP_TRY(e, vad::launch_rec(sr, ra, stream));
         if (prof) HIP_TRY(e, hipEventRecord(ev[2], stream));
     }
     // rows without a chunk this tick: the step kernels left their (h, c) and probability alone; carry their context over and mark
     // their probability slot (kernel_present.hip)
+    if (feat) return VAD_OK;
     if (present) HIP_TRY(e, vad::launch_carry_absent(present, ctx, ctx_next ? ctx_next : ctx_in_place ? nullptr : e->d_ctx_new, C, probs, ldp, B, stream));
     if (!ctx_next && !ctx_in_place) HIP_TRY(e, hipMemcpyAsync(ctx, e->d_ctx_new, (size_t)B * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return VAD_OK;
@@ -387,10 +402,10 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
 
 template <typename PcmT>
 int forward_impl(vad_engine *e, int sr, int B, long L, const PcmT *pcm, long ld, float *ctx,
-                 float *state, float *probs, long ldp, void *stream_v) {
+                 float *state, float *probs, long ldp, void *stream_v, float *feat = nullptr) {
     if (!e) return VAD_ERR_ARG;
     if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
-    if (B < 0 || L < 0 || (B > 0 && L > 0 && (!pcm || !ctx || !state || !probs)) || ld < L)
+    if (B < 0 || L < 0 || (B > 0 && L > 0 && (!pcm || !ctx || (!feat && (!state || !probs)))) || ld < L)
         return fail(e, VAD_ERR_ARG, "bad argument");
     hipStream_t stream = (hipStream_t)stream_v;
     if (sr > 16000 && sr % 16000 == 0) {
@@ -402,31 +417,73 @@ int forward_impl(vad_engine *e, int sr, int B, long L, const PcmT *pcm, long ld,
         const int k = sr / 16000;
         HIP_TRY(e, hipSetDevice(e->device));
         if ((k == 2 || (k == 3 && e->enc0 == 2)) && !e->impl_reference && e->fused_decimation)
-            return forward_core<PcmT>(e, 16000, k, B, L, pcm, ld, ctx, state, probs, ldp, stream);
+            return forward_core<PcmT>(e, 16000, k, B, L, pcm, ld, ctx, state, probs, ldp, stream, nullptr, nullptr, feat);
         const long Ld = (L + k - 1) / k, ldd = (Ld + 15) / 16 * 16;
         int rc = grow(e, &e->d_decim, &e->decim_bytes, (size_t)B * ldd * sizeof(PcmT), stream, "decimation");
         if (rc) return rc;
         PcmT *dec = reinterpret_cast<PcmT *>(e->d_decim);
         HIP_TRY(e, vad::launch_decimate<PcmT>(pcm, ld, dec, ldd, B, Ld, k, stream));
-        return forward_impl<PcmT>(e, 16000, B, Ld, dec, ldd, ctx, state, probs, ldp, stream_v);
+        return forward_impl<PcmT>(e, 16000, B, Ld, dec, ldd, ctx, state, probs, ldp, stream_v, feat);
     }
     const int ni = net_index(sr);
     if (ni < 0) return fail(e, VAD_ERR_SAMPLE_RATE, "Supported sampling rates: [8000, 16000] (or multiply of 16000)");
     if (B == 0 || L == 0) return VAD_OK;
     HIP_TRY(e, hipSetDevice(e->device));
     if (e->impl_reference) {
+        if (feat) return fail(e, VAD_ERR_OPTION, "vad_encode_audio needs impl=mfma");
         const int N = sr == 16000 ? 512 : 256;
         if (ldp < (L + N - 1) / N) return fail(e, VAD_ERR_ARG, "ldp < T");
         HIP_TRY(e, vad::launch_ref_forward<PcmT>(e->img->ref[ni], sr, B, L, pcm, ld, ctx, state, probs, ldp, stream));
         return VAD_OK;
     }
-    return forward_core<PcmT>(e, sr, 1, B, L, pcm, ld, ctx, state, probs, ldp, stream);
+    return forward_core<PcmT>(e, sr, 1, B, L, pcm, ld, ctx, state, probs, ldp, stream, nullptr, nullptr, feat);
 }
 
 template <typename T>
 int upload(vad_engine *e, T **dst, const std::vector<T> &src) {
     HIP_TRY(e, hipMalloc((void **)dst, src.size() * sizeof(T)));
     HIP_TRY(e, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return VAD_OK;
+}
+
+// The device images of one parsed container (vad_create; vad_encode_audio for its second set)
+int build_images(vad_engine *e, const vad::Weights &w, vad_images &im) {
+    for (int ni = 0; ni < 2; ++ni) {
+        const vad::PackedNet &pk = w.packed[ni];
+        if (upload(e, &im.d_front4[ni], pk.front_wino4)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_whh[ni], pk.whh)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_whh_b9[ni], pk.whh_b9)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_front_b9[ni], pk.front_b9)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_whh_lat[ni], pk.whh_lat)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_whh_rows[ni], pk.whh_rows)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_tables[ni], pk.tables)) return VAD_ERR_HIP;
+#if VAD_AB
+        if (upload(e, &im.d_front[ni], pk.front)) return VAD_ERR_HIP;
+        if (upload(e, &im.d_front_wino[ni], pk.front_wino)) return VAD_ERR_HIP;
+#endif
+    }
+    // canonical tensors for impl=reference
+    const auto &blob = w.blob;
+    if (hipMalloc((void **)&im.d_blob, blob.size()) != hipSuccess) return VAD_ERR_ALLOC;
+    if (hipMemcpy(im.d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return VAD_ERR_HIP;
+    for (int ni = 0; ni < 2; ++ni) {
+        const vad::NetTensors &t = w.net[ni];
+        auto dev = [&](const float *p) {
+            return reinterpret_cast<const float *>(im.d_blob + ((const uint8_t *)p - blob.data()));
+        };
+        vad::RefNet &r = im.ref[ni];
+        r.basis = dev(t.basis);
+        for (int l = 0; l < 4; ++l) { r.ew[l] = dev(t.ew[l]); r.eb[l] = dev(t.eb[l]); }
+        r.w_ih = dev(t.w_ih); r.w_hh = dev(t.w_hh); r.b_ih = dev(t.b_ih); r.b_hh = dev(t.b_hh);
+        r.w_out = dev(t.w_out); r.b_out = dev(t.b_out);
+    }
+    if (hipMalloc((void **)&im.d_ref, sizeof(im.ref)) != hipSuccess) return VAD_ERR_ALLOC;
+    if (hipMemcpy(im.d_ref, im.ref, sizeof(im.ref), hipMemcpyHostToDevice) != hipSuccess) return VAD_ERR_HIP;
+    if (hipMalloc((void **)&im.d_gx_silent, 2 * 512 * sizeof(float)) != hipSuccess) return VAD_ERR_ALLOC;
+    for (int ni = 0; ni < 2; ++ni)
+        if (vad::launch_exact_silent(ni == 0 ? 16000 : 8000, im.d_ref + ni, im.d_gx_silent + 512 * ni, nullptr) != hipSuccess) return VAD_ERR_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return VAD_ERR_HIP;
     return VAD_OK;
 }
 
@@ -494,45 +551,13 @@ int vad_create(const void *weights, size_t nbytes, int device, vad_engine **out)
         return code;
     };
     if (hipSetDevice(device) != hipSuccess) return bail(VAD_ERR_HIP);
+    // an error some earlier call of the thread left pending (a refused call on a host-only engine sets hipErrorInvalidDevice) is not
+    // this engine's: the launches below report hipGetLastError()
+    (void)hipGetLastError();
     e->img = std::make_shared<vad_images>();
-    vad_images &im = *e->img;
-    im.device = device;
-    for (int ni = 0; ni < 2; ++ni) {
-        const vad::PackedNet &pk = e->weights->packed[ni];
-        if (upload(e, &im.d_front4[ni], pk.front_wino4)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_whh[ni], pk.whh)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_whh_b9[ni], pk.whh_b9)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_front_b9[ni], pk.front_b9)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_whh_lat[ni], pk.whh_lat)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_whh_rows[ni], pk.whh_rows)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_tables[ni], pk.tables)) return bail(VAD_ERR_HIP);
-#if VAD_AB
-        if (upload(e, &im.d_front[ni], pk.front)) return bail(VAD_ERR_HIP);
-        if (upload(e, &im.d_front_wino[ni], pk.front_wino)) return bail(VAD_ERR_HIP);
-#endif
-    }
-    // canonical tensors for impl=reference
-    const auto &blob = e->weights->blob;
-    if (hipMalloc((void **)&im.d_blob, blob.size()) != hipSuccess) return bail(VAD_ERR_ALLOC);
-    if (hipMemcpy(im.d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(VAD_ERR_HIP);
-    for (int ni = 0; ni < 2; ++ni) {
-        const vad::NetTensors &t = e->weights->net[ni];
-        auto dev = [&](const float *p) {
-            return reinterpret_cast<const float *>(im.d_blob + ((const uint8_t *)p - blob.data()));
-        };
-        vad::RefNet &r = im.ref[ni];
-        r.basis = dev(t.basis);
-        for (int l = 0; l < 4; ++l) { r.ew[l] = dev(t.ew[l]); r.eb[l] = dev(t.eb[l]); }
-        r.w_ih = dev(t.w_ih); r.w_hh = dev(t.w_hh); r.b_ih = dev(t.b_ih); r.b_hh = dev(t.b_hh);
-        r.w_out = dev(t.w_out); r.b_out = dev(t.b_out);
-    }
-    if (hipMalloc((void **)&im.d_ref, sizeof(im.ref)) != hipSuccess) return bail(VAD_ERR_ALLOC);
-    if (hipMemcpy(im.d_ref, im.ref, sizeof(im.ref), hipMemcpyHostToDevice) != hipSuccess) return bail(VAD_ERR_HIP);
-    if (hipMalloc((void **)&im.d_gx_silent, 2 * 512 * sizeof(float)) != hipSuccess) return bail(VAD_ERR_ALLOC);
-    for (int ni = 0; ni < 2; ++ni)
-        if (vad::launch_exact_silent(ni == 0 ? 16000 : 8000, im.d_ref + ni, im.d_gx_silent + 512 * ni, nullptr) != hipSuccess) return bail(VAD_ERR_HIP);
-    if (hipDeviceSynchronize() != hipSuccess) return bail(VAD_ERR_HIP);
+    e->img->device = device;
+    rc = build_images(e, *e->weights, *e->img);
+    if (rc) return bail(rc);
     *out = e;
     return VAD_OK;
 }
@@ -839,6 +864,85 @@ int vad_forward_audio(vad_engine *e, int sr, int B, long L, const float *pcm, lo
 int vad_forward_audio_i16(vad_engine *e, int sr, int B, long L, const int16_t *pcm, long ld,
                           float *ctx, float *state, float *probs, long ldp, void *stream) {
     return forward_impl<int16_t>(e, sr, B, L, pcm, ld, ctx, state, probs, ldp, stream);
+}
+
+// ---- decoder training: the encoder's features, and the loss and gradients of the decoder (trainer.hpp, kernel_train.hip) -------------
+namespace {
+// The second image set: the engine's own container with every decoder's W_ih = [I; 0; 0; 0] and b_ih = b_hh = 0, through the same
+// parser and packer.  A frontend run on it leaves the encoder's output in gate rows 0 .. 127.
+int ensure_encode_images(vad_engine *e) {
+    std::lock_guard<std::mutex> lk(e->img->enc_mutex);
+    if (e->img->enc) return VAD_OK;
+    const vad::Weights &w = *e->weights;
+    std::vector<uint8_t> blob = w.blob;
+    for (int ni = 0; ni < 2; ++ni) {
+        auto at = [&](const float *p) { return reinterpret_cast<float *>(blob.data() + ((const uint8_t *)p - w.blob.data())); };
+        float *w_ih = at(w.net[ni].w_ih), *b_ih = at(w.net[ni].b_ih), *b_hh = at(w.net[ni].b_hh);
+        std::fill(w_ih, w_ih + 512 * 128, 0.f);
+        for (int k = 0; k < 128; ++k) w_ih[k * 128 + k] = 1.f;
+        std::fill(b_ih, b_ih + 512, 0.f);
+        std::fill(b_hh, b_hh + 512, 0.f);
+    }
+    vad::Weights w2;
+    const std::string err = w2.load(blob.data(), blob.size());
+    if (!err.empty()) return fail(e, VAD_ERR_WEIGHTS, err);
+    auto im = std::make_shared<vad_images>();
+    im->device = e->device;
+    const int rc = build_images(e, w2, *im);
+    if (rc) return rc;
+    e->img->enc = im;
+    return VAD_OK;
+}
+}  // namespace
+
+int vad_encode_audio(vad_engine *e, int sr, int B, long L, const void *pcm, size_t elem_size, long ld, const float *ctx, float *feat,
+                     void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (B <= 0 || L <= 0 || !pcm || !ctx || !feat || ld < L || (elem_size != 2 && elem_size != 4) || ((size_t)feat & 15))
+        return fail(e, VAD_ERR_ARG, "vad_encode_audio: bad argument");
+    HIP_TRY(e, hipSetDevice(e->device));
+    const int rc = ensure_encode_images(e);
+    if (rc) return rc;
+    float *c = const_cast<float *>(ctx);                         // (read only: the next context goes to scratch)
+    if (elem_size == 2) return forward_impl<int16_t>(e, sr, B, L, static_cast<const int16_t *>(pcm), ld, c, nullptr, nullptr, LONG_MAX, stream, feat);
+    return forward_impl<float>(e, sr, B, L, static_cast<const float *>(pcm), ld, c, nullptr, nullptr, LONG_MAX, stream, feat);
+}
+
+size_t vad_decoder_grad_workspace_bytes(int B, long T) {
+    if (B <= 0 || T <= 0 || (double)B * (double)T > 1e9) return 0;
+    return vad::train_layout(B, T).total;
+}
+
+int vad_decoder_grad_device(vad_engine *e, const vad_decoder_params *p, const float *feat, int B, long T, const long *n_chunks,
+                            const uint8_t *labels, long ldl, const uint8_t *keep, float keep_scale, float noise_loss, double denom,
+                            vad_decoder_grads *g, double *loss, float *probs, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (!p || !g || !feat || !n_chunks || !labels || !loss || !workspace || B <= 0 || T <= 0 || ldl < T || !(denom > 0.0))
+        return fail(e, VAD_ERR_ARG, "vad_decoder_grad_device: bad argument");
+    if (!p->w_ih || !p->w_hh || !p->b_ih || !p->b_hh || !p->w_out || !p->b_out || !g->w_ih || !g->w_hh || !g->b_ih || !g->b_hh || !g->w_out ||
+        !g->b_out)
+        return fail(e, VAD_ERR_ARG, "vad_decoder_grad_device: null tensor");
+    const size_t need = vad_decoder_grad_workspace_bytes(B, T);
+    if (need == 0) return fail(e, VAD_ERR_ARG, "vad_decoder_grad_device: B T too large");
+    if (workspace_bytes < need) return fail(e, VAD_ERR_ARG, "vad_decoder_grad_device: workspace smaller than vad_decoder_grad_workspace_bytes(B, T)");
+    // 16-byte vector loads of the features and the two matrices; everything else is read and written as single words
+    if (((size_t)feat & 15) || ((size_t)p->w_ih & 15) || ((size_t)p->w_hh & 15) || ((size_t)workspace & 255) || ((size_t)loss & 7) ||
+        ((size_t)n_chunks & 7))
+        return fail(e, VAD_ERR_ARG, "vad_decoder_grad_device: misaligned pointer");
+    const void *words[] = {p->b_ih, p->b_hh, p->w_out, p->b_out, g->w_ih, g->w_hh, g->b_ih, g->b_hh, g->w_out, g->b_out, probs};
+    for (const void *q : words)
+        if ((size_t)q & 3) return fail(e, VAD_ERR_ARG, "vad_decoder_grad_device: misaligned pointer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    vad::TrainArgs a{};
+    a.w_ih = p->w_ih; a.w_hh = p->w_hh; a.b_ih = p->b_ih; a.b_hh = p->b_hh; a.w_out = p->w_out; a.b_out = p->b_out;
+    a.feat = feat; a.B = B; a.T = T; a.n_chunks = n_chunks; a.labels = labels; a.ldl = ldl;
+    a.keep = keep; a.keep_scale = keep ? keep_scale : 1.0f; a.noise_loss = noise_loss; a.denom = denom;
+    a.g_wih = g->w_ih; a.g_whh = g->w_hh; a.g_bih = g->b_ih; a.g_bhh = g->b_hh; a.g_wout = g->w_out; a.g_bout = g->b_out;
+    a.loss = loss; a.probs = probs; a.workspace = workspace;
+    HIP_TRY(e, vad::launch_decoder_grad(a, (hipStream_t)stream));
+    return VAD_OK;
 }
 
 int vad_segment_probs_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams,

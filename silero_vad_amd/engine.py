@@ -41,7 +41,8 @@ def _net_rate(sr: int):
 class Engine:
     """Thin RAII wrapper of a `vad_engine*` (one per GPU; `clone()` gives further handles that share the weights)."""
 
-    def __init__(self, device=0, weights_path=None, library=None, _handle=None):
+    def __init__(self, device=0, weights_path=None, library=None, _handle=None, weights=None):
+        """weights: the bytes of a container (e.g. `DecoderTrainer.weights()`) instead of a file at weights_path."""
         if not torch.cuda.is_available():
             raise RuntimeError("silero_vad_amd needs an MI355X (gfx950) GPU: torch.cuda.is_available() "
                                "is False and there is no CPU fallback")
@@ -52,7 +53,10 @@ class Engine:
         if _handle is not None:
             self._h = _handle
             return
-        blob = open(weights_path or _lib.WEIGHTS_PATH, "rb").read()
+        if weights is not None and weights_path is not None:
+            raise ValueError("give weights or weights_path, not both")
+        blob = bytes(weights) if weights is not None else open(weights_path or _lib.WEIGHTS_PATH, "rb").read()
+        self.weights = blob                          # the container this engine was made from (silero_vad_amd/tuning.py starts from it)
         self._h = ctypes.c_void_p()
         status = self._L.vad_create(blob, len(blob), self.device, ctypes.byref(self._h))
         if status != _lib.VAD_OK:
@@ -72,6 +76,7 @@ class Engine:
         self._check(self._L.vad_clone(self._h, ctypes.byref(h)))
         e = Engine(self.device, library=self._L, _handle=h)
         e.options = dict(self.options)
+        e.weights = getattr(self, "weights", None)
         return e
 
     def close(self):
@@ -232,6 +237,23 @@ class Engine:
         if rc < 0:
             self._check(-rc)
         return rc == 1
+
+    def encode_audio(self, pcm, sr, ctx, feat=None):
+        """vad_encode_audio: pcm [B, L] (float32 or int16, cuda) at `sr` as for forward_audio, ctx [B, C] (read only) -> the encoder's
+        output feat [B, T, 128] (cuda), what the reference's stft + encoder layers return chunk by chunk."""
+        assert pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1
+        if pcm.dtype not in (torch.float32, torch.int16):
+            raise TypeError(f"pcm dtype must be float32 or int16, got {pcm.dtype}")
+        B, L = pcm.shape
+        net, step = _net_rate(sr)
+        n = 512 if net == 16000 else 256
+        T = ((L + step - 1) // step + n - 1) // n
+        if feat is None:
+            feat = torch.empty((B, T, 128), dtype=torch.float32, device=pcm.device)
+        ld = pcm.stride(0) if B > 1 else L
+        self._check(self._retry_alloc(lambda: self._L.vad_encode_audio(self._h, sr, B, L, pcm.data_ptr(), pcm.element_size(), ld, ctx.data_ptr(),
+                                                                       feat.data_ptr(), self._stream())))
+        return feat
 
     def debug_frontend(self, pcm, sr, ctx):
         B, L = pcm.shape
@@ -426,6 +448,16 @@ class HipSileroVAD:
         return probs
 
 
+    def encode(self, x, sr: int):
+        """The frozen part of the reference's training loop (tuning/utils.py:227-234): feat [B, T, 128] on the device, the output of the
+        STFT and encoder layers for every chunk of every row, each row from a zero context.  x as for `audio_forward`.  The model's
+        streaming state is not touched."""
+        x, sr_raw, sr, _ = self._front_door(x, sr)
+        with self._device_ctx():
+            xd = self._to_device(x)
+            ctx = torch.zeros((xd.shape[0], 64 if sr == 16000 else 32), dtype=torch.float32, device=self.device)
+            return self.engine.encode_audio(xd, sr_raw, ctx)
+
     def audio_forward_slabs(self, x, sr: int, slab_chunks: int = 256):
         """`audio_forward_device` in time slabs of `slab_chunks` chunks with the state carried between them: yields
         (index of the slab's first chunk, probs[B, t] in HBM) slab by slab -- the same probabilities as one call (the engine slabs
@@ -444,8 +476,9 @@ class HipSileroVAD:
         self._last_batch_size = batch_size
 
 
-def load_silero_vad(onnx=False, opset_version=16, device=0, precision="fp32"):
+def load_silero_vad(onnx=False, opset_version=16, device=0, precision="fp32", weights=None):
     """Reference signature (src/silero_vad/model.py:6) plus `device`.
     `onnx`/`opset_version` are accepted for source compatibility and ignored: there is one backend,
-    the HIP engine, and one arithmetic, fp32."""
-    return HipSileroVAD(device=device, precision=precision)
+    the HIP engine, and one arithmetic, fp32.  weights: the bytes of a container other than the published one (a decoder
+    tuned by silero_vad_amd.tuning)."""
+    return HipSileroVAD(device=device, engine=None if weights is None else Engine(device, weights=weights), precision=precision)
