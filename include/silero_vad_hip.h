@@ -875,6 +875,61 @@ int vad_decoder_grad_host(const vad_decoder_params_f64 *p, const float *feat, in
                           long ldl, const uint8_t *keep, float keep_scale, float noise_loss, double denom, vad_decoder_grads_f64 *g,
                           double *loss, float *probs, int threads);
 
+/* ---- AUDIO AUGMENTATION of training batches (the rule: csrc/augment.hpp) ------------------------------------------------------------
+ * The reference trains on audiomentations' SomeOf((1, 3)) of fifteen transforms; the ten with arithmetic that can be stated are three
+ * op kinds here.  A row's recipe is an ordered list of 0 .. 3 ops, each applied to the float32 output of the one before:
+ *   VAD_AUGMENT_NOISE    y[n] = x[n] + float(a) g(seed, row_key, n), g standard normal from Philox4x32-10 (key = seed, counter =
+ *                        (n / 4, row_key)) through Box-Muller in double: a sample's noise depends on (seed, row_key, n) alone.
+ *   VAD_AUGMENT_BIQUADS  n_sections (1 .. 8) second-order sections coef[s] = b0 b1 b2 a1 a2 (a0 = 1), zero initial state, the
+ *                        recursion in DOUBLE on the device as in the twin, rounded to float32 once: scipy.signal.sosfilt's function.
+ *   VAD_AUGMENT_CLIP     lo, hi = the a- and b-quantile (0 <= a <= b <= 1) of the row's own len samples, numpy's default method in
+ *                        double (exact order statistics), rounded to float32; y = x < lo ? lo : x > hi ? hi : x.
+ * pcm [n][ld]: int16 (elem_size 2, taken as x / 32768) or float32 (elem_size 4).  out [n][ld_out] float32, 16-byte aligned, ld_out a
+ * multiple of 4, not overlapping pcm: row i is written over its whole ld_out, zero at and behind lens[i].  A row whose final result
+ * holds a non-finite value comes back as its input converted to float32, bit for bit; so does a row whose recipe is empty.
+ * Device call: every pointer but the engine is a device pointer; asynchronous on `stream`, allocates nothing, no float atomics: the
+ * same call gives the same bits and a row's output does not depend on its place in the batch.  lens[i] is clamped to
+ * [0, min(ld, ld_out)].  The recipes are device memory the call cannot read: a row whose recipe vad_augment_check_recipes would refuse
+ * comes back as its input.  Workspace: vad_augment_workspace_bytes(n, ld_out) bytes, 256-byte aligned (0 = out of range): 128 bytes
+ * per block of vad_augment_block() samples.  VAD_ERR_ARG with nothing queued: a NULL pointer, n <= 0, ld or ld_out <= 0, elem_size
+ * not 2 or 4, a misaligned pointer, ld_out not a multiple of 4, a workspace too small.  A host-only engine: VAD_ERR_NO_DEVICE.
+ * Host twin: host pointers, no alignment rule; the same function, not the same block structure; the result does not depend on
+ * `threads` (<= 0: vad_host_threads(), at most 64).  VAD_ERR_ARG: the above, a lens[i] outside [0, min(ld, ld_out)], and a recipe
+ * that vad_augment_check_recipes refuses.
+ * vad_augment_check_recipes (host memory): VAD_OK, or VAD_ERR_ARG with *why (may be NULL) set to a static sentence: n_ops outside
+ * 0 .. 3, n_sections outside 1 .. 8, a non-finite coefficient or amplitude, quantiles outside 0 <= a <= b <= 1, an unknown kind.
+ * vad_biquad_design (host, double): one Audio-EQ-cookbook (R. Bristow-Johnson) section normalised to a0 = 1.  12 dB/oct Butterworth
+ * low- and high-pass are one section at q = 1/sqrt(2); 24 dB/oct two sections at q = 1 / (2 cos(pi / 8)), 1 / (2 cos(3 pi / 8)) = 0.54119610, 1.30656296.  Band-pass has 0 dB
+ * peak gain; gain_db is read by peaking and the shelves only (q is the shelves' Q, not a slope).  VAD_ERR_ARG: an unknown kind,
+ * sr <= 0, f0 outside (0, sr / 2), q <= 0, a non-finite argument.                                                                   */
+#define VAD_AUGMENT_MAX_OPS 3
+#define VAD_AUGMENT_MAX_SECTIONS 8
+enum { VAD_AUGMENT_NOISE = 1, VAD_AUGMENT_BIQUADS = 2, VAD_AUGMENT_CLIP = 3 };
+enum { VAD_BIQUAD_LOWPASS = 0, VAD_BIQUAD_HIGHPASS = 1, VAD_BIQUAD_BANDPASS = 2, VAD_BIQUAD_NOTCH = 3, VAD_BIQUAD_PEAKING = 4,
+       VAD_BIQUAD_LOWSHELF = 5, VAD_BIQUAD_HIGHSHELF = 6 };
+typedef struct {
+    int32_t kind;                                   /* VAD_AUGMENT_*                                     */
+    int32_t n_sections;                             /* BIQUADS                                           */
+    double coef[VAD_AUGMENT_MAX_SECTIONS][5];       /* BIQUADS: b0 b1 b2 a1 a2                           */
+    double a, b;                                    /* NOISE: a = amplitude; CLIP: a = q_lo, b = q_hi    */
+    uint64_t seed;                                  /* NOISE                                             */
+} vad_augment_op;
+typedef struct {
+    int32_t n_ops;
+    int32_t reserved;
+    vad_augment_op ops[VAD_AUGMENT_MAX_OPS];
+    uint64_t row_key;
+} vad_augment_recipe;
+long vad_augment_block(void);
+size_t vad_augment_workspace_bytes(long n_rows, long width);
+int vad_augment_check_recipes(const vad_augment_recipe *recipes, long n, const char **why);
+int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                            const vad_augment_recipe *recipes, float *out, long ld_out, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int vad_augment_rows_host(const void *pcm, size_t elem_size, long ld, const long *lens, long n, const vad_augment_recipe *recipes,
+                          float *out, long ld_out, int threads);
+int vad_biquad_design(int kind, double sr, double f0, double q, double gain_db, double coef[5]);
+
 /* ---- test / bring-up hooks (not part of the drop-in surface) -------------------------------------
  * Host-only: size and contents of the packed weight images the kernels consume, so CPU tests can
  * check the fragment packing without a GPU.  which: 0 = frontend GEMM stream (enc0 "direct"), 1 = recurrent

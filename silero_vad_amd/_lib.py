@@ -147,6 +147,13 @@ SYMBOLS = {
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vad_decoder_grad_host": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p, c_float, c_float, c_double, c_void_p,
                                       c_void_p, c_void_p, c_int]),
+    "vad_augment_block": (c_long, []),
+    "vad_augment_workspace_bytes": (c_size_t, [c_long, c_long]),
+    "vad_augment_check_recipes": (c_int, [c_void_p, c_long, POINTER(c_char_p)]),
+    "vad_augment_rows_device": (c_int, [c_void_p, c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_size_t,
+                                        c_void_p]),
+    "vad_augment_rows_host": (c_int, [c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_int]),
+    "vad_biquad_design": (c_int, [c_int, c_double, c_double, c_double, c_double, POINTER(c_double)]),
     "vad_iterator_feed":(c_long, [c_void_p, c_void_p, c_long, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_long]),
     "vad_stage_rows": (c_int, [POINTER(c_void_p), POINTER(c_long), c_long, c_long, c_size_t, c_void_p, c_int]),

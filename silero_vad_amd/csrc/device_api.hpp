@@ -319,4 +319,21 @@ hipError_t launch_decoder_grad(const TrainArgs &a, hipStream_t s);
 // vad_encode_audio: gate rows 0 .. 127 of a slab of gx (fragment order, nt steps) -> feat[B][T][128] at steps t0 .. t0 + nt
 hipError_t launch_unpack_feat(const float *gx, float *feat, int B, long T, long t0, long nt, hipStream_t s);
 
+// Audio augmentation (kernel_augment.hip; the rule and the workspace layout are augment.hpp).  Every pointer is a device pointer; out
+// is 16-byte aligned and ld_out a multiple of 4, the workspace 256-byte aligned and aug_layout(n, ld_out).total bytes long, n at
+// most 65535.  One plan and one conversion launch, five launches per op position (a row without that op there leaves at once), one
+// restoring launch; no synchronisation, no float atomics.
+struct AugArgs {
+    const void *pcm;                                           // [n][ld] int16 or float32
+    int elem_size;
+    long ld;
+    const long *lens;                                          // [n]
+    long n;
+    const vad_augment_recipe *recipes;                         // [n]
+    float *out;                                                // [n][ld_out]
+    long ld_out;
+    void *workspace;
+};
+hipError_t launch_augment(const AugArgs &a, hipStream_t s);
+
 }  // namespace vad

@@ -945,6 +945,27 @@ int vad_decoder_grad_device(vad_engine *e, const vad_decoder_params *p, const fl
     return VAD_OK;
 }
 
+int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                            const vad_augment_recipe *recipes, float *out, long ld_out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (!pcm || !lens || !recipes || !out || !workspace || n <= 0 || n > 65535 || ld <= 0 || ld_out <= 0)
+        return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: bad argument");
+    if (elem_size != 2 && elem_size != 4) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: elem_size must be 2 (int16) or 4 (float32)");
+    if (ld_out & 3) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: ld_out must be a multiple of 4");
+    if (((size_t)out & 15) || ((size_t)pcm & (elem_size - 1)) || ((size_t)lens & 7) || ((size_t)recipes & 7) || ((size_t)workspace & 255))
+        return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: misaligned pointer");
+    const size_t need = vad_augment_workspace_bytes(n, ld_out);
+    if (need == 0) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: n ld_out too large");
+    if (workspace_bytes < need) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: workspace smaller than vad_augment_workspace_bytes(n, ld_out)");
+    HIP_TRY(e, hipSetDevice(e->device));
+    vad::AugArgs a{};
+    a.pcm = pcm; a.elem_size = (int)elem_size; a.ld = ld; a.lens = lens; a.n = n; a.recipes = recipes; a.out = out; a.ld_out = ld_out;
+    a.workspace = workspace;
+    HIP_TRY(e, vad::launch_augment(a, (hipStream_t)stream));
+    return VAD_OK;
+}
+
 int vad_segment_probs_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams,
                              const long *n_chunks,
                              long n_chunks_all, const long *audio_len, const vad_segment_params *p,

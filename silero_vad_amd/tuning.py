@@ -7,6 +7,7 @@ plumbing: device tensors, the optimizer, the dropout mask's generator.
 
     trainer = DecoderTrainer(model)                      # Adam(5e-4), dropout 0.1, noise loss 0.5, 8 s cuts: tuning/config.yml
     trainer.epoch(audios, labels)                        # labels: `chunk_labels` per recording
+    trainer.epoch(audios, labels, augment=Augmenter())   # the reference's augmentations, on the device (augment.py)
     tuned = trainer.model()                              # a HipSileroVAD on trainer.weights()
 """
 import ctypes
@@ -182,7 +183,9 @@ class DecoderTrainer:
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(int(seed))
         self._workspace = None
+        self._aug_workspace = None
         self.last_grads = None
+        self.last_augmented = None
 
     def _batch(self, audios, labels):
         n = self.chunk
@@ -202,12 +205,24 @@ class DecoderTrainer:
             lab[b, :nck[b]] = l
         return pcm, nck, lab, T
 
-    def step(self, audios: Sequence, labels: Sequence):
-        """One optimizer step on one batch; returns the batch's loss (a float: one host synchronisation)."""
+    def step(self, audios: Sequence, labels: Sequence, recipes=None):
+        """One optimizer step on one batch; returns the batch's loss (a float: one host synchronisation).  recipes: one augmentation
+        recipe per recording (augment.RECIPE_DTYPE, e.g. `Augmenter.draw`): the uploaded padded batch goes through `augment_device`
+        on the current stream before `encode` -- the recordings are cut to `max_train_length_sec` first, so the augmentation sees the
+        cut -- and the augmented batch stays in `last_augmented`.  None: no augmentation."""
         pcm, nck, lab, T = self._batch(audios, labels)
         B = len(nck)
         with torch.cuda.device(self.device):
             x = torch.from_numpy(pcm).to(self.device)
+            if recipes is not None:
+                from .augment import augment_device, augment_workspace_bytes
+                lens = [min(len(a), self.max_samples) for a in audios]
+                need = augment_workspace_bytes(B, x.shape[1])
+                if self._aug_workspace is None or self._aug_workspace.numel() < need:
+                    self._aug_workspace = None
+                    self._aug_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+                x = augment_device(self.base_model.engine, x, lens, recipes, workspace=self._aug_workspace)
+                self.last_augmented = x
             feat = self.base_model.encode(x, self.sampling_rate)
             keep = None
             if self.dropout > 0.0:
@@ -227,13 +242,21 @@ class DecoderTrainer:
             return float(loss.item())
 
     def epoch(self, audios: Sequence, labels: Sequence, batch_size: int = 128, shuffle: bool = True, augment=None):
-        """One pass over the corpus in batches; returns the reference's `losses.avg` (each batch weighted by its padded size)."""
+        """One pass over the corpus in batches; returns the reference's `losses.avg` (each batch weighted by its padded size).
+        augment: None, a callable `wav -> wav` run on the host per visited recording, or an `Augmenter`: one recipe is drawn per visited
+        recording, with the recording's index as row_key (its noise differs from its neighbours' and, the seeds being drawn anew,
+        between epochs), and applied on the device inside `step`."""
+        from .augment import Augmenter
+        on_device = isinstance(augment, Augmenter)
         order = torch.randperm(len(audios), generator=self._cpu_generator()).tolist() if shuffle else list(range(len(audios)))
         total, count = 0.0, 0
         for i in range(0, len(order), batch_size):
             idx = order[i:i + batch_size]
-            wavs = [audios[j] if augment is None else augment(audios[j]) for j in idx]
-            loss = self.step(wavs, [labels[j] for j in idx])
+            if on_device:
+                loss = self.step([audios[j] for j in idx], [labels[j] for j in idx], recipes=augment.draw(len(idx), row_keys=idx))
+            else:
+                wavs = [audios[j] if augment is None else augment(audios[j]) for j in idx]
+                loss = self.step(wavs, [labels[j] for j in idx])
             total += loss * self.last_numel
             count += self.last_numel
         return total / max(count, 1)
@@ -264,7 +287,7 @@ def _model_weights(model) -> bytes:
 def tune(train_audios, train_labels, val_audios, val_labels, model, num_epochs: int = 20, sampling_rate: int = 16000, batch_size: int = 128,
          noise_loss: float = 0.5, trainer: Optional[DecoderTrainer] = None, augment=None, **trainer_kw):
     """tune.py's loop: every epoch one `DecoderTrainer.epoch`, then `validate` on the tuned model; the weights of the best rounded ROC-AUC
-    are kept.  Returns (container bytes of the best epoch or None if no epoch beat 0, [(train loss, val loss, val ROC-AUC), ...])."""
+    are kept.  augment: as in `DecoderTrainer.epoch` (a callable or an `Augmenter`).  Returns (container bytes of the best epoch or None if no epoch beat 0, [(train loss, val loss, val ROC-AUC), ...])."""
     from .streams import validate
     trainer = trainer or DecoderTrainer(model, sampling_rate=sampling_rate, noise_loss=noise_loss, **trainer_kw)
     best_auc, best, history = 0.0, None, []
