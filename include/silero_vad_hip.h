@@ -930,6 +930,46 @@ int vad_augment_rows_host(const void *pcm, size_t elem_size, long ld, const long
                           float *out, long ld_out, int threads);
 int vad_biquad_design(int kind, double sr, double f0, double q, double gain_db, double coef[5]);
 
+/* ---- RESIDENT TRAINING: batches cut out of a corpus in HBM, Adam on the device (the rules: csrc/trainset.hpp) -----------------------
+ * A tuning corpus is small beside HBM and is visited once per epoch: it is uploaded once, as one arena of int16 or float32 samples
+ * (elem_size 2 or 4) with recording r at arena[offs[r] .. offs[r] + lens[r]) and its per-chunk labels at label_arena[label_offs[r] ..),
+ * and every batch is assembled where it lies.  Row b takes recording r = idx[b]:
+ *     len = min(lens[r], max_samples),  out_pcm[b][0 .. len) = the recording's first len samples in the arena's element type, exact
+ *     zeros from len to ld;  out_n_chunks[b] = ceil(len / chunk);  out_labels[b][t] = the recording's label for t < n_chunks,
+ *     VAD_LABEL_IGNORE from there to ldl;  out_lens[b] = len.
+ * Every output is written over its whole pitch, whatever it held.  offs, lens, label_offs, idx, out_lens and out_n_chunks are longs.
+ * Device call: every pointer but the engine is a device pointer; stateless, allocates nothing, asynchronous on `stream`, one launch,
+ * no atomics: a row's bytes depend on its recording alone, not on its place in the batch.  A recording may start at ANY
+ * element-aligned address (even for int16, 4-byte for float32): 16-byte vectors where source and destination allow, elements
+ * otherwise, the same bytes either way.  The call cannot read the tables: an idx[b] outside [0, n_recordings) gives an empty row (len
+ * 0, zeros, VAD_LABEL_IGNORE), and a cut longer than ld (or its chunks than ldl) is cut at the pitch, never written past it.
+ * VAD_ERR_ARG with nothing queued: a NULL pointer, elem_size not 2 or 4, n_recordings, B, chunk, ld or ldl <= 0, max_samples < 0, a
+ * sample pointer that is not element-aligned, a table that is not 8-byte aligned.  A host-only engine: VAD_ERR_NO_DEVICE.
+ * Host twin: host pointers, no engine; VAD_ERR_ARG besides: an idx[b] outside [0, n_recordings), a negative length, ld < a row's
+ * len, ldl < a row's n_chunks -- nothing is written then.
+ *
+ * vad_decoder_adam_device: torch.optim.Adam's default rule (no amsgrad, no weight decay, not maximize) over the six decoder tensors,
+ * 132 225 parameters, in one launch, in float32 in the order of torch's composed operations:
+ *     m = m + (g - m)(1 - beta1),  v = beta2 v + (1 - beta2) g g,  p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * params (written), m and v (state, written) are vad_decoder_grads-shaped, grads (read) vad_decoder_params-shaped, device pointers,
+ * 4-byte aligned.  The bias corrections are taken on the host in double from `step` and passed as kernel arguments: there is no
+ * counter on the device, the caller counts.  step == 1 starts the state: m and v are zeroed by a launch in front (they count as
+ * zero whatever they held); no later step touches them but through the rule.  A non-finite gradient propagates, as under torch.
+ * Stateless, allocates nothing, asynchronous on `stream`.  VAD_ERR_ARG with nothing queued: a NULL pointer, a misaligned tensor,
+ * step < 1, beta1 or beta2 outside [0, 1), lr or eps negative or NaN.
+ * Host twin: double parameters, gradients and state (as vad_decoder_grad_host takes double parameters), the same rule in double.      */
+int vad_trainset_batch_device(vad_engine *e, const void *arena, size_t elem_size, const long *offs, const long *lens,
+                              const uint8_t *label_arena, const long *label_offs, long n_recordings, const long *idx, long B,
+                              long max_samples, long chunk, void *out_pcm, long ld, uint8_t *out_labels, long ldl, long *out_lens,
+                              long *out_n_chunks, void *stream);
+int vad_trainset_batch_host(const void *arena, size_t elem_size, const long *offs, const long *lens, const uint8_t *label_arena,
+                            const long *label_offs, long n_recordings, const long *idx, long B, long max_samples, long chunk,
+                            void *out_pcm, long ld, uint8_t *out_labels, long ldl, long *out_lens, long *out_n_chunks);
+int vad_decoder_adam_device(vad_engine *e, const vad_decoder_grads *params, const vad_decoder_params *grads, const vad_decoder_grads *m,
+                            const vad_decoder_grads *v, long step, double lr, double beta1, double beta2, double eps, void *stream);
+int vad_decoder_adam_host(const vad_decoder_grads_f64 *params, const vad_decoder_params_f64 *grads, const vad_decoder_grads_f64 *m,
+                          const vad_decoder_grads_f64 *v, long step, double lr, double beta1, double beta2, double eps);
+
 /* ---- test / bring-up hooks (not part of the drop-in surface) -------------------------------------
  * Host-only: size and contents of the packed weight images the kernels consume, so CPU tests can
  * check the fragment packing without a GPU.  which: 0 = frontend GEMM stream (enc0 "direct"), 1 = recurrent

@@ -11,7 +11,7 @@ from .streams import (BatchVADIterator, PackedRecordings, RaggedPlan, RefillPlan
                       ThresholdCounts, ThresholdPairs, LABEL_IGNORE, threshold_pairs, chunk_labels, threshold_counts, threshold_counts_device, ragged_threshold_counts, search_thresholds,
                       ValidationScores, SCORE_KEY_NONE, chunk_scores, chunk_scores_device, ragged_validation, validate)
 from .tuning import (DecoderTrainer, decoder_grad, decoder_grad_host, decoder_grad_workspace_bytes, decoder_state_dict, replace_decoder, tune,  # noqa: F401
-                     DECODER_NAMES)
+                     DECODER_NAMES, FusedAdam, TrainingSet, decoder_adam, decoder_adam_host)
 from .augment import (Augmenter, RECIPE_DTYPE, augment_device, augment_host, augment_workspace_bytes, biquad_design, check_recipes,  # noqa: F401
                       make_recipes)
 from .sharding import shard_range, shard_by_duration, gather_to_rank0, batch_speech_timestamps  # noqa: F401

@@ -153,6 +153,12 @@ SYMBOLS = {
     "vad_augment_rows_device": (c_int, [c_void_p, c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_size_t,
                                         c_void_p]),
     "vad_augment_rows_host": (c_int, [c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_int]),
+    "vad_trainset_batch_device": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_long,
+                                          c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "vad_trainset_batch_host": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_void_p,
+                                        c_long, c_void_p, c_long, c_void_p, c_void_p]),
+    "vad_decoder_adam_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_double, c_double, c_double, c_double, c_void_p]),
+    "vad_decoder_adam_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_double, c_double, c_double, c_double]),
     "vad_biquad_design": (c_int, [c_int, c_double, c_double, c_double, c_double, POINTER(c_double)]),
     "vad_iterator_feed":(c_long, [c_void_p, c_void_p, c_long, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_long]),

@@ -336,4 +336,26 @@ struct AugArgs {
 };
 hipError_t launch_augment(const AugArgs &a, hipStream_t s);
 
+// Resident training (kernel_trainset.hip; the rules are trainset.hpp).  Every pointer is a device pointer, element-aligned; the
+// 16-byte path is chosen per vector from the addresses.  One launch, no synchronisation, no atomics.
+struct TrainsetArgs {
+    const void *arena;                                         // the corpus, int16 or float32
+    int elem_size;
+    const long *offs, *lens;                                   // [n_recordings], in elements
+    const uint8_t *label_arena;
+    const long *label_offs;                                    // [n_recordings]
+    long n_recordings;
+    const long *idx;                                           // [B]
+    long B, max_samples, chunk;
+    void *out_pcm;                                             // [B][ld] of the arena's type
+    long ld;
+    uint8_t *out_labels;                                       // [B][ldl]
+    long ldl;
+    long *out_lens, *out_n_chunks;                             // [B]
+};
+hipError_t launch_trainset_batch(const TrainsetArgs &a, hipStream_t s);
+// torch.optim.Adam's step over the six decoder tensors: one launch, in front of it the state's reset when step == 1
+hipError_t launch_decoder_adam(const vad_decoder_grads &p, const vad_decoder_params &g, const vad_decoder_grads &m, const vad_decoder_grads &v,
+                               long step, double lr, double beta1, double beta2, double eps, hipStream_t s);
+
 }  // namespace vad

@@ -966,6 +966,52 @@ int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, lo
     return VAD_OK;
 }
 
+int vad_trainset_batch_device(vad_engine *e, const void *arena, size_t elem_size, const long *offs, const long *lens,
+                              const uint8_t *label_arena, const long *label_offs, long n_recordings, const long *idx, long B, long max_samples,
+                              long chunk, void *out_pcm, long ld, uint8_t *out_labels, long ldl, long *out_lens, long *out_n_chunks,
+                              void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (!arena || !offs || !lens || !label_arena || !label_offs || !idx || !out_pcm || !out_labels || !out_lens || !out_n_chunks)
+        return fail(e, VAD_ERR_ARG, "vad_trainset_batch_device: null pointer");
+    if (elem_size != 2 && elem_size != 4) return fail(e, VAD_ERR_ARG, "vad_trainset_batch_device: elem_size must be 2 (int16) or 4 (float32)");
+    if (n_recordings <= 0 || B <= 0 || chunk <= 0 || ld <= 0 || ldl <= 0 || max_samples < 0)
+        return fail(e, VAD_ERR_ARG, "vad_trainset_batch_device: bad argument");
+    if (((size_t)arena & (elem_size - 1)) || ((size_t)out_pcm & (elem_size - 1)))
+        return fail(e, VAD_ERR_ARG, "vad_trainset_batch_device: sample pointer not element-aligned");
+    const void *tables[] = {offs, lens, label_offs, idx, out_lens, out_n_chunks};
+    for (const void *q : tables)
+        if ((size_t)q & 7) return fail(e, VAD_ERR_ARG, "vad_trainset_batch_device: table not 8-byte aligned");
+    // one workgroup per 4 KiB of a row
+    if ((double)B * (double)((ld * (long)elem_size + 4095) / 4096) >= 2147483647.0) return fail(e, VAD_ERR_ARG, "vad_trainset_batch_device: B ld too large");
+    HIP_TRY(e, hipSetDevice(e->device));
+    vad::TrainsetArgs a{};
+    a.arena = arena; a.elem_size = (int)elem_size; a.offs = offs; a.lens = lens; a.label_arena = label_arena; a.label_offs = label_offs;
+    a.n_recordings = n_recordings; a.idx = idx; a.B = B; a.max_samples = max_samples; a.chunk = chunk; a.out_pcm = out_pcm; a.ld = ld;
+    a.out_labels = out_labels; a.ldl = ldl; a.out_lens = out_lens; a.out_n_chunks = out_n_chunks;
+    HIP_TRY(e, vad::launch_trainset_batch(a, (hipStream_t)stream));
+    return VAD_OK;
+}
+
+int vad_decoder_adam_device(vad_engine *e, const vad_decoder_grads *params, const vad_decoder_params *grads, const vad_decoder_grads *m,
+                            const vad_decoder_grads *v, long step, double lr, double beta1, double beta2, double eps, void *stream) {
+    if (!e) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    if (!params || !grads || !m || !v) return fail(e, VAD_ERR_ARG, "vad_decoder_adam_device: null pointer");
+    if (step < 1) return fail(e, VAD_ERR_ARG, "vad_decoder_adam_device: step counts from 1");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(lr >= 0.0) || !(eps >= 0.0))
+        return fail(e, VAD_ERR_ARG, "vad_decoder_adam_device: lr, eps >= 0 and betas in [0, 1)");
+    const void *words[] = {params->w_ih, params->w_hh, params->b_ih, params->b_hh, params->w_out, params->b_out,
+                           grads->w_ih,  grads->w_hh,  grads->b_ih,  grads->b_hh,  grads->w_out,  grads->b_out,
+                           m->w_ih,      m->w_hh,      m->b_ih,      m->b_hh,      m->w_out,      m->b_out,
+                           v->w_ih,      v->w_hh,      v->b_ih,      v->b_hh,      v->w_out,      v->b_out};
+    for (const void *q : words)
+        if (!q || ((size_t)q & 3)) return fail(e, VAD_ERR_ARG, "vad_decoder_adam_device: null or misaligned tensor");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, vad::launch_decoder_adam(*params, *grads, *m, *v, step, lr, beta1, beta2, eps, (hipStream_t)stream));
+    return VAD_OK;
+}
+
 int vad_segment_probs_device(vad_engine *e, const float *probs, long ldp, const long *row_offsets, long n_streams,
                              const long *n_chunks,
                              long n_chunks_all, const long *audio_len, const vad_segment_params *p,

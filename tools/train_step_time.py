@@ -2,12 +2,16 @@
 """Times of one decoder training step on the GPU (silero_vad_amd/tuning.py), per part and whole, beside the same step written with
 torch.nn.LSTMCell and autograd on the same GPU -- what the reference's train() costs a user who sets device: 'cuda'.
 
-    python tools/train_step_time.py [--shapes 128x250,1024x250] [--reps 10] [--out profiles/decoder_training_times.json]
+    python tools/train_step_time.py [--shapes 128x250,1024x250] [--reps 10] [--resident] [--out profiles/decoder_training_times.json]
 
 Every figure is the median of `reps` runs behind warm-up runs.  `encode` and the gradient call (its six kernels together) are
 event-timed as calls; the whole `.step` (padding, upload, encode, mask, gradient call, Adam) and the torch step are wall-clock times
 around a synchronisation, host time included, as a user sees them.  The torch step starts from features already on the device: it is
 the decoder's share alone.
+
+--resident adds, in the same process: the one-time upload of a `TrainingSet` holding the batch's recordings, an epoch of `reps`
+`step_resident` calls (optimizer="fused_adam") with ONE synchronisation at its end -- the median per-step time of five such epochs --
+its ratio to `.step`, and batch assembly (vad_trainset_batch_device) and the fused Adam step event-timed on their own.
 """
 import argparse
 import json
@@ -71,9 +75,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="128x250,1024x250")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--resident", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    from silero_vad_amd import DecoderTrainer, decoder_grad, decoder_grad_workspace_bytes, load_silero_vad
+    from silero_vad_amd import DecoderTrainer, TrainingSet, decoder_grad, decoder_grad_workspace_bytes, load_silero_vad
     model = load_silero_vad(device=0)
     dev = model.device
     rng = np.random.default_rng(0)
@@ -105,6 +110,24 @@ def main():
             return loss
 
         r["torch_decoder_step_ms"] = wall_ms(torch_step, max(2, a.reps // 3), warm=1)
+        if a.resident:
+            del ref, opt, x, feat
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ts = TrainingSet(wavs, labels, model, max_train_length_sec=T * 512 / 16000)
+            r["trainset_upload_ms"], r["trainset_MB"] = (time.perf_counter() - t0) * 1e3, ts.nbytes / 1e6
+            fused = DecoderTrainer(model, max_train_length_sec=T * 512 / 16000, optimizer="fused_adam")
+            idx = list(range(B))
+
+            def resident_epoch():
+                for _ in range(a.reps):
+                    fused.step_resident(ts, idx)
+
+            r["resident_step_ms"] = wall_ms(resident_epoch, 5, warm=1) / a.reps
+            r["resident_over_host"] = r["resident_step_ms"] / r["step_ms"]
+            r["batch_ms"] = event_ms(lambda: ts.batch(idx), a.reps)
+            r["fused_adam_ms"] = event_ms(fused.optimizer.step, a.reps)
+            r["torch_adam_ms"] = event_ms(trainer.optimizer.step, a.reps)
         print(json.dumps(r), flush=True)
         rows.append(r)
     if a.out:
