@@ -102,6 +102,33 @@ __device__ __forceinline__ void nyq_update(f32x4 (&Y)[RB], float xn, const float
     }
 }
 
+// ---- the vector sections between the GEMMs, from registers ------------------------------------------------------------------------
+// nyq_update / add_bias above take their LDS round trips one at a time: two reads, a wait, 8 VALU instructions, 14 times per
+// encoder-0 row part, and fetch the same tap row up to four times.  A wave issues nothing while it waits, and every stall hands the
+// SIMD's one vector pipe to the partner wave for a switch each way -- what profiles/r07a_fft_pass_order.md cured in the FFT pass.
+// The pieces below split the section into its reads (each table vector ONCE, requested ahead of use -- the caller places them under
+// the MFMAs of the product in front) and its arithmetic, which then runs from registers without a wait.  The value and the order of
+// the operations of every accumulator are those of nyq_update / add_bias / relu.
+template <int M>
+__device__ __forceinline__ void tab_rows(f32x4 (&o)[M], const float *row_lds, const Lane &ln) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) o[m] = *reinterpret_cast<const f32x4 *>(row_lds + 16 * m + 4 * ln.g);
+}
+template <int M>
+__device__ __forceinline__ void rank1(f32x4 (&Y)[M], float xn, const f32x4 (&w)[M]) {
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Y[m][r] = fmaf(w[m][r], xn, Y[m][r]);
+}
+template <int M>
+__device__ __forceinline__ void add_rows(f32x4 (&acc)[M], const f32x4 (&b)[M]) {
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][r] += b[m][r];
+}
+
 // ---- encoder 1's program for one output row block: 40 blocks = 10 units x 4 k-groups, in the order the one-wave program
 // accumulates them (kernel_front_f43.hip, "encoder 1 fed part by part"; layout.hpp w4_e1) -------------------------------------
 struct E1Blk {

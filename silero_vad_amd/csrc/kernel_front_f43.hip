@@ -46,6 +46,9 @@ namespace {
 #ifndef VAD_BV_BATCH
 #define VAD_BV_BATCH 1           // 1: a step's four B operands are formed first, then its 8 MFMAs issue back to back (gemm_r)
 #endif
+#ifndef VAD_EPI_BATCH
+#define VAD_EPI_BATCH 1          // 1: the sections between the GEMMs read every table vector once, ahead of use, and run from registers
+#endif                           // (front_common.hpp tab_rows): 5.323 against 5.408 ms per C2 step (profiles/r08a_front_sections.md).  0: one LDS round trip at a time
 constexpr int kUnitBytes = (int)vadl::kWUnitFloats * 4;      // 16 blocks of 1 KiB
 // ---- the weight ring -------------------------------------------------------------------------------------------------
 struct Ring {
@@ -301,6 +304,19 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
             zero<RB>(Y1);
             zero<RB>(Y2);
             zero<RB>(Y3);
+            // the part epilogue's table vectors -- three Nyquist tap rows and the bias -- are read ONCE each: taps 1 and 2 are requested
+            // under the MFMAs of the part's last product, tap 0 and the bias right behind it, and y0, which needs taps 1 and 2 only, is
+            // updated while they travel.  (All eight under the product spill 67-72 registers at 16 kHz, taps 0 and 1 under it -- 56
+            // updates to run meanwhile -- 2-3; all eight behind the product, no spill, measure the same as this form.)
+            [[maybe_unused]] f32x4 wt0[RB], wt1[RB], wt2[RB], bia[RB];
+            auto epi_ahead = [&]() VAD_INLINE {
+                if constexpr (VAD_EPI_BATCH != 0) {
+                    lds_fence();
+                    tab_rows<RB>(wt1, wn + 128, ln);
+                    tab_rows<RB>(wt2, wn + 256, ln);
+                    lds_fence();
+                }
+            };
 #if VAD_F43_EF
             // (E = X3, F = X0, x1 = X1, x2 = X2 from here on)
             {   const Coef k = opaque_coef<kF4, kFm3>();
@@ -343,14 +359,38 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
 #if VAD_F43_EF
             {   const Coef k = opaque_coef<kFm4, kFm025>();
                 gemm_r<RB, KG0, 2>(Y0, [&](int s) VAD_INLINE { return fmaf(X1[s], k.a, X3[s]); }, ring);              // x3 - 5 x1 = E - 4 x1
+                epi_ahead();
                 gemm_r<RB, KG0, 2>(Y3, [&](int s) VAD_INLINE { return fmaf(X2[s], k.b, -X0[s]); }, ring);             // x0 - 1.25 x2 = -F - x2/4
             }
 #else
             {   const Coef k = opaque_coef<kFm5, kFm125>();
                 gemm_r<RB, KG0, 2>(Y0, [&](int s) VAD_INLINE { return fmaf(X1[s], k.a, X3[s]); }, ring);  // x3 - 5 x1
+                epi_ahead();
                 gemm_r<RB, KG0, 2>(Y3, [&](int s) VAD_INLINE { return fmaf(X2[s], k.b, X0[s]); }, ring);  // x0 - 1.25 x2
             }
 #endif
+#if VAD_EPI_BATCH
+            // (per accumulator the order of nyq_update / add_bias below: y0 taps 1, 2; y1 0, 1, 2; y2 0, 1, 2; y3 0, 1; then the bias)
+            lds_fence();
+            tab_rows<RB>(wt0, wn, ln);
+            tab_rows<RB>(bia, tab + tb.b_e0 + row0, ln);
+            lds_fence();
+            rank1<RB>(Y0, xn0, wt1);
+            rank1<RB>(Y0, xn1, wt2);
+            lds_fence();
+            rank1<RB>(Y1, xn0, wt0);
+            rank1<RB>(Y1, xn1, wt1);
+            rank1<RB>(Y1, xn2, wt2);
+            rank1<RB>(Y2, xn1, wt0);
+            rank1<RB>(Y2, xn2, wt1);
+            rank1<RB>(Y2, xn3, wt2);
+            rank1<RB>(Y3, xn2, wt0);
+            rank1<RB>(Y3, xn3, wt1);
+            add_rows<RB>(Y0, bia);
+            add_rows<RB>(Y1, bia);
+            add_rows<RB>(Y2, bia);
+            add_rows<RB>(Y3, bia);
+#else
             nyq_update<RB>(Y0, xn0, wn + 128, ln);
             nyq_update<RB>(Y0, xn1, wn + 256, ln);
             nyq_update<RB>(Y1, xn0, wn, ln);
@@ -365,6 +405,7 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
             add_bias<RB>(Y1, tab + tb.b_e0 + row0, ln);
             add_bias<RB>(Y2, tab + tb.b_e0 + row0, ln);
             add_bias<RB>(Y3, tab + tb.b_e0 + row0, ln);
+#endif
             relu<RB>(Y0);
             relu<RB>(Y1);
             relu<RB>(Y2);
@@ -392,24 +433,43 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
             }
         });
     }
+    f32x4 Vv[4], Fe[8];
+#if VAD_EPI_BATCH
+    {   // encoder 1's bias (read once for both outputs) and encoder 2's initial value: one batch, one wait
+        f32x4 b1[4];
+        lds_fence();
+        tab_rows<4>(b1, tab + tb.b_e1, ln);
+        init_bias<4>(Vv, tab + tb.b_e2, ln);
+        lds_fence();
+        add_rows<4>(Z0, b1);
+        add_rows<4>(Z1, b1);
+    }
+#else
     add_bias<4>(Z0, tab + tb.b_e1, ln);
     add_bias<4>(Z1, tab + tb.b_e1, ln);
+#endif
     relu<4>(Z0);
     relu<4>(Z1);
     VAD_WAVE_STAMP(ln, 10);
 
     // ---- enc2 (T 2 -> 1, stride 2: taps 1,2 see enc1 outputs 0,1), enc3 (T = 1: centre tap only), W_ih -----------------
-    f32x4 Vv[4];
     auto bZ0 = [&](int s) VAD_INLINE { return Z0[s >> 2][s & 3]; };
     auto bZ1 = [&](int s) VAD_INLINE { return Z1[s >> 2][s & 3]; };
     auto bV = [&](int s) VAD_INLINE { return Vv[s >> 2][s & 3]; };
+    auto bF = [&](int s) VAD_INLINE { return Fe[s >> 2][s & 3]; };
+#if VAD_EPI_BATCH
+    lds_fence();
+    init_bias<8>(Fe, tab + tb.b_e3, ln);                  // encoder 3's initial value travels under encoder 2's MFMAs
+    lds_fence();
+#else
     init_bias<4>(Vv, tab + tb.b_e2, ln);
+#endif
     gemm_r<4, 4, 2>(Vv, bZ0, ring);
     gemm_r<4, 4, 2>(Vv, bZ1, ring);
     relu<4>(Vv);
-    f32x4 Fe[8];
-    auto bF = [&](int s) VAD_INLINE { return Fe[s >> 2][s & 3]; };
+#if !VAD_EPI_BATCH
     init_bias<8>(Fe, tab + tb.b_e3, ln);
+#endif
     gemm_r<8, 4, 2>(Fe, bV, ring);
     relu<8>(Fe);
     poison_into(Fe[0], poison);

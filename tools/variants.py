@@ -30,6 +30,7 @@ VARIANTS = {
     "rec_skew_noprio": ["-DVAD_REC_SKEW=1", "-DVAD_REC_PRIO=0"],
     "nobvbatch": ["-DVAD_BV_BATCH=0"],                 # frontend: B-operand transforms interleaved with the MFMAs (round-2 form)
     "xbasis": ["-DVAD_F43_EF=0"],                       # F(4,3) input transform from x0..x3 instead of (E, F, x1, x2) (f43 form only)
+    "noepibatch": ["-DVAD_EPI_BATCH=0"],               # frontend: part epilogue and encoder 1-3 bias sections one LDS round trip at a time (the form before r08a)
     "trace": ["-DVAD_TRACE=1"],
     "fftprio0": ["-DVAD_F43_FFT_PRIO=0"], "fftprio1": ["-DVAD_F43_FFT_PRIO=1"], "fftprio3": ["-DVAD_F43_FFT_PRIO=3"],   # (default: 1)
     "trace_fftprio3": ["-DVAD_TRACE=1", "-DVAD_F43_FFT_PRIO=3"],
