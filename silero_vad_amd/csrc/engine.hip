@@ -243,6 +243,49 @@ int grow(vad_engine *e, void **buf, size_t *have, size_t need, hipStream_t strea
     return VAD_OK;
 }
 
+// The fields of `fa` that the engine's options decide -- weight image, tables, exact-transition arguments (chunks with an exactly
+// silent frame beside one that is not get double-precision gx: the product's fp32 frontend only); the caller has set its own.
+// Returns whether the exact-transition handling is on.
+bool front_images(const vad_engine *e, const vad_images &im, int ni, vad::FrontArgs &fa) {
+    fa.wfront = e->front_b9 ? reinterpret_cast<const float *>(im.d_front_b9[ni]) : im.d_front4[ni];
+    fa.tables = im.d_tables[ni];
+    const bool exact = e->exact_transitions && e->enc0 == 2 && !e->front_b9;
+    fa.exact_net = exact ? im.d_ref + ni : nullptr;
+    fa.gx_silent = exact && e->exact_all_silent ? im.d_gx_silent + 512 * ni : nullptr;
+    return exact;
+}
+
+// THE choice of the frontend kernel, for the product path (forward_core) and for the tests' view of the frontend alone
+// (vad_debug_frontend): completes `fa` (front_images) and launches.  one: the caller's test for the one-stream form; tiles: its count
+// of 16-chunk tiles.  stamp (profiling; may be null) is recorded where the frontend's own time ends: the throughput form's fix-up
+// pass is part of the path, not of that kernel.
+template <typename PcmT>
+int launch_frontend(vad_engine *e, const vad_images &im, int ni, int sr, vad::FrontArgs &fa, bool one, long tiles,
+                    hipStream_t stream, hipEvent_t stamp = nullptr) {
+    const bool exact = front_images(e, im, ni, fa);
+    bool fix = false;
+    if (e->front_b9) HIP_TRY(e, vad::launch_front_b9<PcmT>(sr, fa, stream));
+#if VAD_AB
+    else if (e->enc0 == 1) {
+        fa.wfront = im.d_front_wino[ni];
+        HIP_TRY(e, vad::launch_front_wino<PcmT>(sr, fa, stream));
+    } else if (e->enc0 == 0) {
+        fa.wfront = im.d_front[ni];
+        HIP_TRY(e, vad::launch_front<PcmT>(sr, fa, stream));
+    }
+#endif
+    else if (one) HIP_TRY(e, vad::launch_front_one<PcmT>(sr, fa, stream));       // (fuse_step=0: the one-stream frontend + a recurrence kernel)
+    else if (tiles <= e->lat_tiles) HIP_TRY(e, vad::launch_front_lat<PcmT>(sr, fa, stream));
+    else {
+        fa.exact_list = exact ? e->d_exact : nullptr;
+        HIP_TRY(e, vad::launch_front_f43<PcmT>(sr, fa, stream));
+        fix = true;
+    }
+    if (stamp) HIP_TRY(e, hipEventRecord(stamp, stream));
+    if (fix) HIP_TRY(e, vad::launch_exact_fix<PcmT>(sr, fa, stream));
+    return VAD_OK;
+}
+
 // L, ld: samples per row / row stride of `pcm` AS HANDED OVER (raw rate).  dec = 1: pcm is at the net's rate `sr`.
 // dec = 2, 3: pcm is at dec x 16 kHz and the frontend reads every dec-th sample itself (sample-rate front door
 // folded into the load; fp32 frontend).
@@ -295,12 +338,6 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
     for (long t0 = 0; t0 < T; t0 += slab) {
         const long nt = std::min(slab, T - t0);
         vad::FrontArgs fa{};
-#if VAD_AB
-        fa.wfront = e->enc0 == 2 ? im.d_front4[ni] : e->enc0 == 1 ? im.d_front_wino[ni] : im.d_front[ni];
-#else
-        fa.wfront = im.d_front4[ni];
-#endif
-        fa.tables = im.d_tables[ni];
         fa.pcm = pcm;
         fa.tail = tail;
         fa.ld = ld; fa.L = Ld; fa.T = T; fa.t0 = t0; fa.nt = nt;
@@ -310,10 +347,6 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
         fa.B = B;
         fa.dec = dec;
         fa.trace = e->trace;
-        // chunks with an exactly silent frame beside one that is not: double-precision gx (the product's fp32 frontend only)
-        const bool exact = e->exact_transitions && e->enc0 == 2 && !e->front_b9;
-        fa.exact_net = exact ? im.d_ref + ni : nullptr;
-        fa.gx_silent = exact && e->exact_all_silent ? im.d_gx_silent + 512 * ni : nullptr;
         vad::RecArgs ra{};
         ra.whh = e->rec_b9 ? reinterpret_cast<const float *>(im.d_whh_b9[ni]) : im.d_whh[ni];
         ra.tables = im.d_tables[ni];
@@ -337,6 +370,7 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
         const bool one = T == 1 && dec == 1 && B <= e->one_max && !e->rec_b9 && !e->front_b9 && e->enc0 == 2;
         if (T == 1 && !feat && e->fuse_step && !e->rec_b9 && !e->front_b9 && e->enc0 == 2 && (tiles <= e->lat_tiles || one)) {
             // one step, few tiles (a stream pool's tick, a B = 1 call): frontend, LSTM cell and head in ONE kernel, no gx round trip
+            front_images(e, im, ni, fa);
             vad::CellArgs ca{};
             ca.whh_lat = im.d_whh_lat[ni];
             ca.state = state;
@@ -358,26 +392,8 @@ int forward_core(vad_engine *e, int sr, int dec, int B, long L, const PcmT *pcm,
             }
             continue;
         }
-        bool front_stamped = false;
-        if (e->front_b9) {
-            fa.wfront = reinterpret_cast<const float *>(im.d_front_b9[ni]);
-            HIP_TRY(e, vad::launch_front_b9<PcmT>(sr, fa, stream));
-        } else
-#if VAD_AB
-        if (e->enc0 == 1) HIP_TRY(e, vad::launch_front_wino<PcmT>(sr, fa, stream));
-        else if (e->enc0 == 0) HIP_TRY(e, vad::launch_front<PcmT>(sr, fa, stream));
-        else
-#endif
-        if (one) HIP_TRY(e, vad::launch_front_one<PcmT>(sr, fa, stream));       // (fuse_step=0: the one-stream frontend + a recurrence kernel)
-        else if (tiles <= e->lat_tiles) HIP_TRY(e, vad::launch_front_lat<PcmT>(sr, fa, stream));
-        else {
-            fa.exact_list = exact ? e->d_exact : nullptr;
-            HIP_TRY(e, vad::launch_front_f43<PcmT>(sr, fa, stream));
-            if (prof) HIP_TRY(e, hipEventRecord(ev[1], stream));         // (the frontend's own time ends here ...
-            front_stamped = prof;
-            HIP_TRY(e, vad::launch_exact_fix<PcmT>(sr, fa, stream));     //  ... the fix-up pass is part of the path, not of that kernel)
-        }
-        if (prof && !front_stamped) HIP_TRY(e, hipEventRecord(ev[1], stream));
+        rc = launch_frontend<PcmT>(e, im, ni, sr, fa, one, tiles, stream, prof ? ev[1] : nullptr);
+        if (rc) return rc;
         if (feat) {
             HIP_TRY(e, vad::launch_unpack_feat(e->d_gx, feat, B, T, t0, nt, stream));
             if (prof) HIP_TRY(e, hipEventRecord(ev[2], stream));
@@ -1304,12 +1320,6 @@ int vad_debug_frontend(vad_engine *e, int sr, int B, long L, const float *pcm, l
     if (L % N || ((size_t)pcm & 15) || (ld * sizeof(float)) % 16 || ((size_t)ctx & 15))
         return fail(e, VAD_ERR_ARG, "debug frontend: whole chunks and 16-byte aligned rows only");
     vad::FrontArgs fa{};
-#if VAD_AB
-    fa.wfront = e->enc0 == 2 ? e->img->d_front4[ni] : e->enc0 == 1 ? e->img->d_front_wino[ni] : e->img->d_front[ni];
-#else
-    fa.wfront = e->img->d_front4[ni];
-#endif
-    fa.tables = e->img->d_tables[ni];
     fa.pcm = pcm;
     fa.ld = ld; fa.L = L; fa.T = T; fa.t0 = 0; fa.nt = T;
     fa.ctx_in = ctx;
@@ -1317,25 +1327,10 @@ int vad_debug_frontend(vad_engine *e, int sr, int B, long L, const float *pcm, l
     fa.gx = e->d_gx;
     fa.B = B;
     fa.trace = e->trace;
-    const bool exact = e->exact_transitions && e->enc0 == 2 && !e->front_b9;
-    fa.exact_net = exact ? e->img->d_ref + ni : nullptr;
-    fa.gx_silent = exact && e->exact_all_silent ? e->img->d_gx_silent + 512 * ni : nullptr;
-    if (e->front_b9) {
-        fa.wfront = reinterpret_cast<const float *>(e->img->d_front_b9[ni]);
-        HIP_TRY(e, vad::launch_front_b9<float>(sr, fa, stream));
-    } else
-#if VAD_AB
-    if (e->enc0 == 1) HIP_TRY(e, vad::launch_front_wino<float>(sr, fa, stream));
-    else if (e->enc0 == 0) HIP_TRY(e, vad::launch_front<float>(sr, fa, stream));
-    else
-#endif
-    if (T == 1 && B <= e->one_max && e->enc0 == 2) HIP_TRY(e, vad::launch_front_one<float>(sr, fa, stream));
-    else if ((long)((B + 15) / 16) * T <= e->lat_tiles) HIP_TRY(e, vad::launch_front_lat<float>(sr, fa, stream));
-    else {
-        fa.exact_list = exact ? e->d_exact : nullptr;
-        HIP_TRY(e, vad::launch_front_f43<float>(sr, fa, stream));
-        HIP_TRY(e, vad::launch_exact_fix<float>(sr, fa, stream));
-    }
+    const bool one = T == 1 && B <= e->one_max && e->enc0 == 2;
+    const long tiles = (long)((B + 15) / 16) * T;
+    rc = launch_frontend<float>(e, *e->img, ni, sr, fa, one, tiles, stream);
+    if (rc) return rc;
     HIP_TRY(e, vad::launch_unpack_gx(e->d_gx, gx, B, T, stream));
     return VAD_OK;
 }

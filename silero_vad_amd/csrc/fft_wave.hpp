@@ -13,10 +13,6 @@
 #include "device_api.hpp"
 #include "layout.hpp"
 
-#ifndef VAD_NT_PCM
-#define VAD_NT_PCM 0     // 1: PCM is loaded with the non-temporal hint (read once; keep the L2 for the weights)
-#endif
-
 namespace vad {
 namespace {
 
@@ -54,7 +50,8 @@ struct Lane {
     int b;                   // stream of this lane (clamped to B-1)
     bool tile_valid;         // wave-uniform
     bool from_tail;          // wave-uniform: this is the last, partial chunk -> read a.tail
-    float sgnA, sgnB;        // +-1 butterfly signs for the cross-lane radix-4
+    float sgnA, sgnB;        // +-1 butterfly signs of the retired shuffle form of the cross-lane radix-4: unread, but the frontends sit at
+                             // their register budget and compile to other code without the two fields, so they stay
 #if VAD_TRACE
     mutable unsigned long long ts[20] = {};    // bring-up: shader-clock timestamps of this WAVE, kept in SGPRs (wave-uniform) and written
                                                // out at the end of the kernel -- no vector register, no memory operation in flight
@@ -83,8 +80,7 @@ __device__ __forceinline__ void load_vec(const float *p, float (&s)[SL]) {
     if (DEC == 1) {
 #pragma unroll
         for (int k = 0; k < SL / 4; ++k) {
-            const f32x4 v = VAD_NT_PCM ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p) + k)
-                                       : reinterpret_cast<const f32x4 *>(p)[k];
+            const f32x4 v = reinterpret_cast<const f32x4 *>(p)[k];
 #pragma unroll
             for (int e = 0; e < 4; ++e) s[4 * k + e] = v[e];
         }
@@ -101,8 +97,7 @@ __device__ __forceinline__ void load_vec(const int16_t *p, float (&s)[SL]) {
     if (DEC == 1) {
 #pragma unroll
         for (int k = 0; k < SL / 8; ++k)
-            cvt8(VAD_NT_PCM ? __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p) + k)
-                            : reinterpret_cast<const u32x4 *>(p)[k], &s[8 * k]);
+            cvt8(reinterpret_cast<const u32x4 *>(p)[k], &s[8 * k]);
     } else {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {                          // two batches: half the raw values in flight at a time
@@ -210,9 +205,6 @@ __device__ __forceinline__ f32x2 cmul(f32x2 v, float c, float sn) {
     return __builtin_elementwise_fma(swap2(v), f32x2{-sn, sn}, v * f32x2{c, c});
 }
 
-#ifndef VAD_XLANE_SWAP
-#define VAD_XLANE_SWAP 1
-#endif
 // a of lanes 32..63 <-> b of lanes 0..31 (v_permlane32_swap_b32); a of odd 16-lane rows <-> b of even rows
 // (v_permlane16_swap_b32).  Both registers change in place.
 __device__ __forceinline__ void trade32(f32x2 &a, f32x2 &b) {
@@ -378,7 +370,6 @@ __device__ __forceinline__ void fft_math(float (&X)[Q + 1], const float (&s)[2 *
     // (v_permlane32_swap / v_permlane16_swap: VALU, no LDS round trip, no lane selects): the lower lane trades its
     // upper Q/2 values for the upper lane's lower Q/2, both lanes form sums and differences of what they now hold,
     // and a second trade leaves all sums in the lower lane and all differences (lower minus upper) in the upper one.
-#if VAD_XLANE_SWAP
     constexpr int H = Q / 2;
     // lane group 3 multiplies by -i between the two stages.  Its values are the stage-A differences formed in the odd lane
     // groups (1 keeps the lower half for 3, 3 its own upper half), so only those H differences are rotated, before they are
@@ -405,21 +396,6 @@ __device__ __forceinline__ void fft_math(float (&X)[Q + 1], const float (&s)[2 *
     }
 #pragma unroll
     for (int q = 0; q < H; ++q) trade16(z[q], z[q + H]);
-#else
-    const f32x2 sA{ln.sgnA, ln.sgnA}, sB{ln.sgnB, ln.sgnB};
-    // lane group 3 multiplies by -i between the two stages: x*rotA + swap(x)*rotB
-    const f32x2 rotA = ln.g == 3 ? f32x2{0.f, 0.f} : f32x2{1.f, 1.f};
-    const f32x2 rotB = ln.g == 3 ? f32x2{1.f, -1.f} : f32x2{0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        f32x2 x = z[q];
-        const f32x2 p{__shfl_xor(x.x, 32), __shfl_xor(x.y, 32)};
-        x = __builtin_elementwise_fma(sA, x, p);       // g<2: own + partner ; g>=2: partner - own
-        x = __builtin_elementwise_fma(swap2(x), rotB, x * rotA);
-        const f32x2 r{__shfl_xor(x.x, 16), __shfl_xor(x.y, 16)};
-        z[q] = __builtin_elementwise_fma(sB, x, r);    // g even: own + partner ; g odd: partner - own
-    }
-#endif
     // * W_4Q^(P[g] q), rows (-s, s, c, 0): a batch is multiplied while the next two travel
     lds_fence();
 #pragma unroll

@@ -11,9 +11,6 @@ namespace vad {
 namespace {
 
 #define VAD_INLINE __attribute__((always_inline))
-#ifndef VAD_F43_EF
-#define VAD_F43_EF 1             // the F(4,3) input transform reads the frames through E = x3 - x1, F = x2 - x0 (one fma for t0, t3, t4,
-#endif                           // t5); 0: straight from x0..x3 (three fma's each; the form rounds 1-2 used, A/B: tools/variants.py)
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F &&f) {
@@ -42,8 +39,8 @@ __device__ __forceinline__ Coef opaque_coef() {
                  : "=s"(k.p1), "=s"(k.m1), "=s"(k.a), "=s"(k.b) : "n"(A_BITS), "n"(B_BITS));
     return k;
 }
-[[maybe_unused]] constexpr unsigned kF2 = 0x40000000u, kFm2 = 0xC0000000u, kF4 = 0x40800000u, kFm4 = 0xC0800000u, kFm5 = 0xC0A00000u,
-                   kFm125 = 0xBFA00000u, kF3 = 0x40400000u, kFm3 = 0xC0400000u, kFm025 = 0xBE800000u;
+[[maybe_unused]] constexpr unsigned kF2 = 0x40000000u, kFm2 = 0xC0000000u, kF4 = 0x40800000u, kFm4 = 0xC0800000u,
+                   kF3 = 0x40400000u, kFm3 = 0xC0400000u, kFm025 = 0xBE800000u;
 
 template <int M>
 __device__ __forceinline__ void init_bias(f32x4 (&acc)[M], const float *bias_lds, const Lane &ln) {

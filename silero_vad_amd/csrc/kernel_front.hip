@@ -33,33 +33,17 @@
 namespace vad {
 namespace {
 
-// ---- build-time knobs (tools/variants.py builds A/B variants; the defaults are the product) -------
-#ifndef VAD_SLOT_BLOCKS
-#define VAD_SLOT_BLOCKS 16       // 1-KiB blocks per ring slot (one unit = up to this many blocks); 8 / 16 / 24 measured:
-                                 // 5.46 / 5.36 / 5.49 ms per C2 launch (profiles/r02a_fp32_ablations.md)
-#endif
-#ifndef VAD_NYQ_VALU
-#define VAD_NYQ_VALU 1           // 1: the Nyquist bin (enc0's 129th / 65th input channel, alone in a 9th / 5th k-group of the
-#endif                           // image) is applied as an exact fp32 rank-1 VALU update from Tab::w_nyq instead of an MFMA
-                                 // step whose other 3 lane groups multiply zeros: -80 MFMAs, -10 ring units per tile
-#ifndef VAD_STAGGER
-#define VAD_STAGGER 0            // x 8128 cycles of start delay for odd wave slots (first workgroups)
-#endif
-
-#ifndef VAD_RING_SLOTS
-#define VAD_RING_SLOTS 3         // 3 (product): "seamless" pipeline -- a static schedule of the whole weight stream (make_sched), the
-#endif                           //    workgroup barrier for unit u+1 in the MIDDLE of unit u, fragment reads carried across unit and
-                                 //    segment boundaries (gemm_seg).  Needs uniform 16-block units (VAD_SLOT_BLOCKS 16, VAD_NYQ_VALU 1).
-                                 // 2: round-1 form: a unit is requested when the previous one starts being consumed, awaited with
-                                 //    vmcnt(0) + barrier at the unit boundary (5.27 vs 5.17 ms per C2 launch)
-constexpr int kSlotBlocks = VAD_SLOT_BLOCKS;
+// The weight ring: 3 slots of one 16-block unit each, walked by a static schedule of the whole weight stream (make_sched); the
+// workgroup barrier for unit u+1 sits in the MIDDLE of unit u and fragment reads are carried across unit and segment boundaries
+// (gemm_seg).  Retired forms, with their measurements: 8 / 24 blocks per slot (5.46 / 5.49 against 5.36 ms per C2 launch,
+// profiles/r02a_fp32_ablations.md); a 2-slot ring awaited at the unit boundary (5.27 against 5.17 ms); the Nyquist bin as an MFMA
+// k-group of its own instead of nyq_update below (+80 MFMAs, +10 ring units per tile).
+constexpr int kSlotBlocks = 16;                      // 1-KiB blocks per ring slot = per unit
 constexpr int kRingSlotFloats = kSlotBlocks * 256;   // one unit: whole k-groups of one segment
-constexpr int kRingSlots = VAD_RING_SLOTS;
-static_assert(kRingSlots == 2 || (kRingSlots == 3 && kSlotBlocks == 16 && VAD_NYQ_VALU),
-              "the 3-slot ring assumes that every unit is exactly 16 blocks");
+constexpr int kRingSlots = 3;
 
 // Program order of the weight stream as ring units (float offsets into the packed image): the kernel walks its
-// segments in exactly this order; gemm_seg() cross-checks every unit it consumes against it (3-slot ring only).
+// segments in exactly this order; gemm_seg() cross-checks every unit it consumes against it.
 struct Sched {
     int n;
     int off[128];
@@ -90,187 +74,100 @@ struct Ring {
     float *slots;            // LDS, kRingSlots x kRingSlotFloats
     const float *wfront;     // global
     int unit;                // units consumed so far (wave-uniform)
-    const Sched *sched;      // 3-slot ring: the static unit schedule
-    int bad;                 // 3-slot ring: a consumed unit was not the scheduled one (programming error)
-    f32x4 c0, c1;            // 3-slot ring: A fragments of the next step, carried across unit and segment boundaries
+    const Sched *sched;      // the static unit schedule
+    int bad;                 // a consumed unit was not the scheduled one (programming error)
+    f32x4 c0, c1;            // A fragments of the next step, carried across unit and segment boundaries
 #if VAD_TRACE
     long long wait = 0, span = 0, last = 0;   // cycles at unit barriers / between them (bring-up trace)
 #endif
 };
 
-// k-groups per ring unit for a segment of M row blocks, and the size of a segment's first unit
+// k-groups per ring unit for a segment of M row blocks
 constexpr int unit_kgroups(int M) { return kSlotBlocks / M; }
-constexpr int first_unit_blocks(int M, int KS) {
-    const int kg = (KS + 3) / 4, ug = unit_kgroups(M);
-    return M * (kg < ug ? kg : ug);
-}
 
-template <int BLOCKS>
 __device__ __forceinline__ void ring_issue(const Ring &r, long goff, int slot, const Lane &ln) {
-    // BLOCKS blocks of 1 KiB.  LDS destination = M0 (wave-uniform base) + instruction offset + lane*16, the
+    // One unit = 16 blocks of 1 KiB.  LDS destination = M0 (wave-uniform base) + instruction offset + lane*16, the
     // layout global_load_lds requires.
     //
     // The LDS-DMA is issued from inline asm ON PURPOSE: while the compiler knows of a pending
     // global_load_lds it degrades every `s_waitcnt lgkmcnt(N)` to lgkmcnt(0), which serialises the
     // ds_read -> MFMA pipeline of gemm_seg (one exposed LDS latency per 8 MFMAs).  The ring's own
-    // protocol orders the DMA instead: ring_wait() = s_waitcnt vmcnt(0) before the unit's barrier.
-    static_assert(BLOCKS % 4 == 0 && BLOCKS <= kSlotBlocks, "unit must be whole 4-block groups");
+    // protocol orders the DMA instead: s_waitcnt vmcnt(0) before the unit's barrier.
+    static_assert(kSlotBlocks == 16, "a wave's share of a unit is one group of 4 blocks");
     if (VAD_ABLATE & 8) return;
-    // Wave w copies the CONTIGUOUS blocks [w n, (w+1) n), n = BLOCKS / 4: one M0 value and one source base
-    // per group of up to 4 blocks, the instruction's immediate offset (which advances the global and the
-    // LDS address alike, 13 bits) selects the block within the group.
-    constexpr int PW = BLOCKS / 4;
-    const float *gbase = r.wfront + goff + (long)ln.wave * PW * 256;      // wave-uniform
+    // Wave w copies the CONTIGUOUS blocks [4w, 4w + 4): one M0 value and one source base, the instruction's
+    // immediate offset (which advances the global and the LDS address alike, 13 bits) selects the block.
+    const float *src = r.wfront + goff + (long)ln.wave * 4 * 256;         // wave-uniform
     const unsigned voff = ln.lane * 16;                                    // bytes
-    const unsigned lbase = (unsigned)(size_t)((__attribute__((address_space(3))) float *)(r.slots + slot * kRingSlotFloats))
-                           + (unsigned)ln.wave * PW * 1024u;
-#pragma unroll
-    for (int grp = 0; grp < PW; grp += 4) {
-        const float *src = gbase + (long)grp * 256;
-        const unsigned dst = lbase + (unsigned)grp * 1024u;
-        const int n = PW - grp < 4 ? PW - grp : 4;
-        unsigned keep_m0;                      // M0 is restored: the compiler may keep its own value there
-        if (n == 4)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-                         "s_mov_b32 m0, %0"
-                         : "=&s"(keep_m0) : "v"(voff), "s"(src), "s"(dst) : "memory");
-        else if (n == 3)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep_m0) : "v"(voff), "s"(src), "s"(dst) : "memory");
-        else if (n == 2)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                         "s_mov_b32 m0, %0"
-                         : "=&s"(keep_m0) : "v"(voff), "s"(src), "s"(dst) : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep_m0) : "v"(voff), "s"(src), "s"(dst) : "memory");
-    }
+    const unsigned dst = (unsigned)(size_t)((__attribute__((address_space(3))) float *)(r.slots + slot * kRingSlotFloats))
+                         + (unsigned)ln.wave * 4 * 1024u;
+    unsigned keep_m0;                          // M0 is restored: the compiler may keep its own value there
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep_m0) : "v"(voff), "s"(src), "s"(dst) : "memory");
 }
-// All of this wave's ring DMA has landed in LDS (and everything else it had in flight on vmcnt).
-__device__ __forceinline__ void ring_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// One segment = KG k-groups of M row blocks, streamed as units of up to unit_kgroups(M) k-groups.
+// One segment = KG k-groups of M row blocks, streamed as units of unit_kgroups(M) k-groups.
 // acc[m] += A_seg[m][:, k] * B[k][:]  for all k-steps.  bfun(s) must return the B-operand register of
-// k-step s (compile-time s).  NEXT_BLOCKS / next_off describe the first unit of the segment that
-// follows in program order (prefetch; 0 = none).
+// k-step s (compile-time s).  next_off, the first unit of the segment that follows in program order, is not read (the retired
+// 2-slot ring prefetched it): it stays because the compiler orders the W_ih section differently once the call sites stop
+// evaluating it, and this kernel is the fixed form the parity tests compare the product with.
 //
-// 3-slot ring ("seamless" pipeline, VAD_RING_SLOTS == 3): every unit is 16 blocks = 8 steps.  The workgroup barrier that
+// Every unit is 16 blocks = 8 steps ("seamless" pipeline).  The workgroup barrier that
 // makes unit u+1 visible sits in the MIDDLE of unit u (its DMA was requested in the middle of unit u-1, a full unit
 // earlier), and the double-buffered fragment reads run across unit and segment boundaries: the last step of a unit
 // prefetches the first fragments of the next one (CARRY_OUT / CARRY_IN; dropped only around the FFT of frame 3 and at
-// the end).  No LDS latency and no DMA wait is exposed at a unit boundary any more; the slot that the barrier frees is
+// the end).  No LDS latency and no DMA wait is exposed at a unit boundary; the slot that the barrier frees is
 // the one of unit u-1, which every wave has left.
-template <int M, int KS, int NEXT_BLOCKS, bool CARRY_IN, bool CARRY_OUT, class BF>
+// The unit is consumed as "steps" of two row blocks x 4 k-steps (8 MFMAs).  The A fragments of step i+1 are read from LDS
+// BEFORE the MFMAs of step i are issued (explicit double buffer; the sched_barrier keeps the compiler from sinking the reads
+// back down): a lone wave then keeps the matrix pipe busy without exposing the LDS latency once per 8 MFMAs.
+template <int M, int KS, bool CARRY_IN, bool CARRY_OUT, class BF>
 __device__ __forceinline__ void gemm_seg(f32x4 (&acc)[M], BF bfun, Ring &ring, long seg_off,
                                          long next_off, const Lane &ln) {
-    constexpr int KG = (KS + 3) / 4, UG = unit_kgroups(M), NU = (KG + UG - 1) / UG;
-    static_assert(UG >= 1, "slot smaller than one k-group");
-    if constexpr (kRingSlots == 3) {
-        static_assert(UG * (M / 2) == 8 && KG % UG == 0, "uniform units of 8 steps");
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int unit = ring.unit, n_units = ring.sched->n;
-            if (ring.sched->off[unit] != (int)(seg_off + (long)u * UG * M * 256)) ring.bad = 1;
-            const f32x4 *A = reinterpret_cast<const f32x4 *>(ring.slots + (unit % 3) * kRingSlotFloats) + ln.lane;
-            const f32x4 *An = reinterpret_cast<const f32x4 *>(ring.slots + ((unit + 1) % 3) * kRingSlotFloats) + ln.lane;
-            if (!CARRY_IN && u == 0) {
-                ring.c0 = A[0];
-                ring.c1 = A[64];
-            }
-#pragma unroll
-            for (int st = 0; st < 8; ++st) {
-                if (st == 4 && unit + 1 < n_units) {
-                    // this wave's share of unit + 1 has landed; then everyone's, and everyone has left unit - 1.  A bare
-                    // s_barrier (no lgkmcnt(0) fence): the fragment reads in flight belong to the current slot
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (!(VAD_ABLATE & 1)) __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
-                    if (unit + 2 < n_units) ring_issue<kSlotBlocks>(ring, ring.sched->off[unit + 2], (unit + 2) % 3, ln);
-                }
-                f32x4 n0 = ring.c0, n1 = ring.c1;
-                if (st + 1 < 8) {
-                    n0 = A[(2 * (st + 1)) * 64];
-                    n1 = A[(2 * (st + 1) + 1) * 64];
-                } else if (u + 1 < NU || CARRY_OUT) {
-                    n0 = An[0];
-                    n1 = An[64];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const int kg = u * UG + st / (M / 2), mp = 2 * (st % (M / 2));
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const float bv = bfun(kg * 4 + ks);
-                    acc[mp + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring.c0[ks], bv, acc[mp + 0], 0, 0, 0);
-                    acc[mp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring.c1[ks], bv, acc[mp + 1], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                ring.c0 = n0;
-                ring.c1 = n1;
-            }
-            ring.unit++;
-        }
-        return;
-    }
+    constexpr int KG = KS / 4, UG = unit_kgroups(M), NU = KG / UG;
+    static_assert(KS % 4 == 0 && UG * (M / 2) == 8 && KG % UG == 0, "uniform units of 8 steps");
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
-#if VAD_TRACE
-        const long long ta = __builtin_readcyclecounter();
-        if (ring.last) ring.span += ta - ring.last;
-#endif
-        int slot;
-        {
-        ring_wait();
-        if (!(VAD_ABLATE & 1)) __syncthreads();   // unit `ring.unit` landed for every wave; other slot free
-#if VAD_TRACE
-        ring.last = __builtin_readcyclecounter();
-        ring.wait += ring.last - ta;
-#endif
-        slot = ring.unit & 1;
-        constexpr int TAIL = (KG % UG == 0) ? UG : KG % UG;     // k-groups in the segment's last unit
-        if (u + 1 < NU) {
-            const long off = seg_off + (long)(u + 1) * UG * M * 256;
-            if (u + 2 < NU) ring_issue<M * UG>(ring, off, slot ^ 1, ln);
-            else ring_issue<M * TAIL>(ring, off, slot ^ 1, ln);
-        } else if (NEXT_BLOCKS > 0) {
-            ring_issue<(NEXT_BLOCKS > 0 ? NEXT_BLOCKS : 4)>(ring, next_off, slot ^ 1, ln);
+        const int unit = ring.unit, n_units = ring.sched->n;
+        if (ring.sched->off[unit] != (int)(seg_off + (long)u * UG * M * 256)) ring.bad = 1;
+        const f32x4 *A = reinterpret_cast<const f32x4 *>(ring.slots + (unit % 3) * kRingSlotFloats) + ln.lane;
+        const f32x4 *An = reinterpret_cast<const f32x4 *>(ring.slots + ((unit + 1) % 3) * kRingSlotFloats) + ln.lane;
+        if (!CARRY_IN && u == 0) {
+            ring.c0 = A[0];
+            ring.c1 = A[64];
         }
-        }
-        // The unit is consumed as "steps" of two row blocks x 4 k-steps (8 MFMAs).  The A fragments of
-        // step i+1 are read from LDS BEFORE the MFMAs of step i are issued (explicit double buffer;
-        // the sched_barrier keeps the compiler from sinking the reads back down): a lone wave then
-        // keeps the matrix pipe busy without exposing the LDS latency once per 8 MFMAs.
-        const f32x4 *A = reinterpret_cast<const f32x4 *>(ring.slots + slot * kRingSlotFloats) + ln.lane;
-        const int nk = (KG - u * UG) < UG ? (KG - u * UG) : UG;        // k-groups in this unit
-        const int nsteps = nk * (M / 2);
-        f32x4 c0 = A[0], c1 = A[64];
 #pragma unroll
-        for (int st = 0; st < UG * (M / 2); ++st) {
-            if (st < nsteps) {
-                f32x4 n0 = c0, n1 = c1;
-                if (st + 1 < nsteps) {
-                    n0 = A[(2 * (st + 1)) * 64];
-                    n1 = A[(2 * (st + 1) + 1) * 64];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const int kg = u * UG + st / (M / 2), mp = 2 * (st % (M / 2));
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    if (kg * 4 + ks < KS) {
-                        const float bv = bfun(kg * 4 + ks);
-                        acc[mp + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(c0[ks], bv, acc[mp + 0], 0, 0, 0);
-                        acc[mp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(c1[ks], bv, acc[mp + 1], 0, 0, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                c0 = n0;
-                c1 = n1;
+        for (int st = 0; st < 8; ++st) {
+            if (st == 4 && unit + 1 < n_units) {
+                // this wave's share of unit + 1 has landed; then everyone's, and everyone has left unit - 1.  A bare
+                // s_barrier (no lgkmcnt(0) fence): the fragment reads in flight belong to the current slot
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (!(VAD_ABLATE & 1)) __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                if (unit + 2 < n_units) ring_issue(ring, ring.sched->off[unit + 2], (unit + 2) % 3, ln);
             }
+            f32x4 n0 = ring.c0, n1 = ring.c1;
+            if (st + 1 < 8) {
+                n0 = A[(2 * (st + 1)) * 64];
+                n1 = A[(2 * (st + 1) + 1) * 64];
+            } else if (u + 1 < NU || CARRY_OUT) {
+                n0 = An[0];
+                n1 = An[64];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const int kg = u * UG + st / (M / 2), mp = 2 * (st % (M / 2));
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const float bv = bfun(kg * 4 + ks);
+                acc[mp + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring.c0[ks], bv, acc[mp + 0], 0, 0, 0);
+                acc[mp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring.c1[ks], bv, acc[mp + 1], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            ring.c0 = n0;
+            ring.c1 = n1;
         }
         ring.unit++;
     }
@@ -316,11 +213,8 @@ __device__ __forceinline__ void nyq_update(f32x4 (&Y)[8], float xn, const float 
 #else
 #define TRACE(i) do {} while (0)
 #endif
-#ifndef VAD_WG_PER_CU_8K
-#define VAD_WG_PER_CU_8K 2       // (the 2-slot 8 kHz instantiation fits three workgroups per CU at 159 VGPRs; measured 224.3 vs
-#endif                           //  224.2 M chunks/s -- occupancy is not what limits the kernel)
 template <int Q, typename PcmT, int DEC>
-__global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_kernel(const FrontArgs a) {
+__global__ void __launch_bounds__(256, 2) front_kernel(const FrontArgs a) {
     using namespace vadl;
     constexpr Tab tb = make_tab(8 * Q, Q);
     constexpr int TABF = (tb.total + 3) / 4 * 4;
@@ -352,29 +246,13 @@ __global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_ker
         a.trace[(size_t)blockIdx.x * 16 + 11] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // XCC_ID
     }
 #endif
-    if (VAD_STAGGER > 0 && blockIdx.x < 512) {
-        // The two workgroups that share a CU start together and run the same program, so their VALU
-        // (FFT) and MFMA phases coincide for the whole launch (later workgroups inherit the phase of
-        // the one they replace).  Delay the one in the odd wave slot once, by about half a tile, so
-        // that one group's FFT overlaps the other's MFMAs.  HW_ID[3:0] = wave slot within the SIMD.
-        const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | 4) & 1u;
-        if (slot)
-            for (int i = 0; i < VAD_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-    }
     Ring ring{lds + TABF, a.wfront, 0, Q == 32 ? &kSched32 : &kSched16, 0, f32x4{}, f32x4{}};
     constexpr long o_e0t0 = seg_offset(E0T0, Q), o_e0t1 = seg_offset(E0T1, Q), o_e0t2 = seg_offset(E0T2, Q);
     constexpr long o_e1t0 = seg_offset(E1T0, Q), o_e1t1 = seg_offset(E1T1, Q), o_e1t2 = seg_offset(E1T2, Q);
     constexpr long o_e2t1 = seg_offset(E2T1, Q), o_e2t2 = seg_offset(E2T2, Q), o_e3t1 = seg_offset(E3T1, Q);
 
-    constexpr int FB_E0 = first_unit_blocks(8, VAD_NYQ_VALU ? Q : Q + 1), FB_E1 = first_unit_blocks(4, 32),
-                  FB_E2 = first_unit_blocks(4, 16), FB_E3 = first_unit_blocks(8, 16),
-                  FB_IH = first_unit_blocks(8, 32);
-    if (kRingSlots == 3) {                       // prime: units 0 and 1
-        ring_issue<kSlotBlocks>(ring, ring.sched->off[0], 0, ln);
-        ring_issue<kSlotBlocks>(ring, ring.sched->off[1], 1, ln);
-    } else {
-        ring_issue<FB_E0>(ring, o_e0t1, 0, ln);  // first unit of the program: head of E0T1
-    }
+    ring_issue(ring, ring.sched->off[0], 0, ln);             // prime: units 0 and 1
+    ring_issue(ring, ring.sched->off[1], 1, ln);
     {   // tables -> LDS: all loads of a thread are issued before the first is stored
         static_assert(tb.total % 4 == 0, "tables are copied as 16-byte vectors");
         constexpr int NV = tb.total / 4, PER = (NV + 255) / 256;
@@ -391,7 +269,7 @@ __global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_ker
             if (i < NV) reinterpret_cast<f32x4 *>(tab)[i] = v[k];
         }
     }
-    if (kRingSlots == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // units 0 and 1 (and the tables) have landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // units 0 and 1 (and the tables) have landed
     __syncthreads();
 
     float X0[Q + 1], X1[Q + 1], X2[Q + 1], X3[Q + 1];
@@ -421,36 +299,31 @@ __global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_ker
 
     f32x4 Y[8], Z0[4], Z1[4];
     auto bY = [&](int s) { return Y[s >> 2][s & 3]; };
-    constexpr int KS0 = VAD_NYQ_VALU ? Q : Q + 1;
     const float *wn = tab + tb.w_nyq;                  // [tap][row]
     // |Y_nyq| of chunk j lives in lane group 0 (X[Q]); every lane of the chunk needs it
     auto nyq = [&](const float (&X)[Q + 1]) { return __shfl(X[Q], ln.j); };
 
     // enc0 frame 0 (taps 1,2; tap 0 is the left zero pad)  -> enc1 out 0 tap 1
     init_bias<8>(Y, tab + tb.b_e0, ln);
-    gemm_seg<8, KS0, FB_E0, false, true>(Y, bX0, ring, o_e0t1, o_e0t2, ln);
-    gemm_seg<8, KS0, FB_E1, true, true>(Y, bX1, ring, o_e0t2, o_e1t1, ln);
-    if (VAD_NYQ_VALU) {
-        nyq_update(Y, nyq(X0), wn + 128, ln);
-        nyq_update(Y, nyq(X1), wn + 256, ln);
-    }
+    gemm_seg<8, Q, false, true>(Y, bX0, ring, o_e0t1, o_e0t2, ln);
+    gemm_seg<8, Q, true, true>(Y, bX1, ring, o_e0t2, o_e1t1, ln);
+    nyq_update(Y, nyq(X0), wn + 128, ln);
+    nyq_update(Y, nyq(X1), wn + 256, ln);
     relu<8>(Y);
     init_bias<4>(Z0, tab + tb.b_e1, ln);
-    gemm_seg<4, 32, FB_E0, true, true>(Z0, bY, ring, o_e1t1, o_e0t0, ln);
+    gemm_seg<4, 32, true, true>(Z0, bY, ring, o_e1t1, o_e0t0, ln);
     // enc0 frame 1 -> enc1 out 0 tap 2, out 1 tap 0
     init_bias<8>(Y, tab + tb.b_e0, ln);
-    gemm_seg<8, KS0, FB_E0, true, true>(Y, bX0, ring, o_e0t0, o_e0t1, ln);
-    gemm_seg<8, KS0, FB_E0, true, true>(Y, bX1, ring, o_e0t1, o_e0t2, ln);
-    gemm_seg<8, KS0, FB_E1, true, true>(Y, bX2, ring, o_e0t2, o_e1t2, ln);
-    if (VAD_NYQ_VALU) {
-        nyq_update(Y, nyq(X0), wn, ln);
-        nyq_update(Y, nyq(X1), wn + 128, ln);
-        nyq_update(Y, nyq(X2), wn + 256, ln);
-    }
+    gemm_seg<8, Q, true, true>(Y, bX0, ring, o_e0t0, o_e0t1, ln);
+    gemm_seg<8, Q, true, true>(Y, bX1, ring, o_e0t1, o_e0t2, ln);
+    gemm_seg<8, Q, true, true>(Y, bX2, ring, o_e0t2, o_e1t2, ln);
+    nyq_update(Y, nyq(X0), wn, ln);
+    nyq_update(Y, nyq(X1), wn + 128, ln);
+    nyq_update(Y, nyq(X2), wn + 256, ln);
     relu<8>(Y);
-    gemm_seg<4, 32, FB_E1, true, true>(Z0, bY, ring, o_e1t2, o_e1t0, ln);
+    gemm_seg<4, 32, true, true>(Z0, bY, ring, o_e1t2, o_e1t0, ln);
     init_bias<4>(Z1, tab + tb.b_e1, ln);
-    gemm_seg<4, 32, FB_E0, true, false>(Z1, bY, ring, o_e1t0, o_e0t0, ln);
+    gemm_seg<4, 32, true, false>(Z1, bY, ring, o_e1t0, o_e0t0, ln);
 
     TRACE(5);
 #if VAD_TRACE
@@ -463,26 +336,22 @@ __global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_ker
 
     // enc0 frame 2 -> enc1 out 1 tap 1
     init_bias<8>(Y, tab + tb.b_e0, ln);
-    gemm_seg<8, KS0, FB_E0, false, true>(Y, bX1, ring, o_e0t0, o_e0t1, ln);
-    gemm_seg<8, KS0, FB_E0, true, true>(Y, bX2, ring, o_e0t1, o_e0t2, ln);
-    gemm_seg<8, KS0, FB_E1, true, true>(Y, bX3, ring, o_e0t2, o_e1t1, ln);
-    if (VAD_NYQ_VALU) {
-        nyq_update(Y, nyq(X1), wn, ln);
-        nyq_update(Y, nyq(X2), wn + 128, ln);
-        nyq_update(Y, nyq(X3), wn + 256, ln);
-    }
+    gemm_seg<8, Q, false, true>(Y, bX1, ring, o_e0t0, o_e0t1, ln);
+    gemm_seg<8, Q, true, true>(Y, bX2, ring, o_e0t1, o_e0t2, ln);
+    gemm_seg<8, Q, true, true>(Y, bX3, ring, o_e0t2, o_e1t1, ln);
+    nyq_update(Y, nyq(X1), wn, ln);
+    nyq_update(Y, nyq(X2), wn + 128, ln);
+    nyq_update(Y, nyq(X3), wn + 256, ln);
     relu<8>(Y);
-    gemm_seg<4, 32, FB_E0, true, true>(Z1, bY, ring, o_e1t1, o_e0t0, ln);
+    gemm_seg<4, 32, true, true>(Z1, bY, ring, o_e1t1, o_e0t0, ln);
     // enc0 frame 3 (taps 0,1; tap 2 is the right zero pad) -> enc1 out 1 tap 2
     init_bias<8>(Y, tab + tb.b_e0, ln);
-    gemm_seg<8, KS0, FB_E0, true, true>(Y, bX2, ring, o_e0t0, o_e0t1, ln);
-    gemm_seg<8, KS0, FB_E1, true, true>(Y, bX3, ring, o_e0t1, o_e1t2, ln);
-    if (VAD_NYQ_VALU) {
-        nyq_update(Y, nyq(X2), wn, ln);
-        nyq_update(Y, nyq(X3), wn + 128, ln);
-    }
+    gemm_seg<8, Q, true, true>(Y, bX2, ring, o_e0t0, o_e0t1, ln);
+    gemm_seg<8, Q, true, true>(Y, bX3, ring, o_e0t1, o_e1t2, ln);
+    nyq_update(Y, nyq(X2), wn, ln);
+    nyq_update(Y, nyq(X3), wn + 128, ln);
     relu<8>(Y);
-    gemm_seg<4, 32, FB_E2, true, true>(Z1, bY, ring, o_e1t2, o_e2t1, ln);
+    gemm_seg<4, 32, true, true>(Z1, bY, ring, o_e1t2, o_e2t1, ln);
     relu<4>(Z0);
     relu<4>(Z1);
 
@@ -493,13 +362,13 @@ __global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_ker
     auto bV = [&](int s) { return Vv[s >> 2][s & 3]; };
     TRACE(7);
     init_bias<4>(Vv, tab + tb.b_e2, ln);
-    gemm_seg<4, 16, FB_E2, true, true>(Vv, bZ0, ring, o_e2t1, o_e2t2, ln);
-    gemm_seg<4, 16, FB_E3, true, true>(Vv, bZ1, ring, o_e2t2, o_e3t1, ln);
+    gemm_seg<4, 16, true, true>(Vv, bZ0, ring, o_e2t1, o_e2t2, ln);
+    gemm_seg<4, 16, true, true>(Vv, bZ1, ring, o_e2t2, o_e3t1, ln);
     relu<4>(Vv);
     f32x4 Fe[8];
     auto bF = [&](int s) { return Fe[s >> 2][s & 3]; };
     init_bias<8>(Fe, tab + tb.b_e3, ln);
-    gemm_seg<8, 16, FB_IH, true, true>(Fe, bV, ring, o_e3t1, seg_offset(IH0, Q), ln);
+    gemm_seg<8, 16, true, true>(Fe, bV, ring, o_e3t1, seg_offset(IH0, Q), ln);
     relu<8>(Fe);
     poison_into(Fe[0], pz_lds[threadIdx.x]);
     TRACE(8);
@@ -510,14 +379,14 @@ __global__ void __launch_bounds__(256, Q == 16 ? VAD_WG_PER_CU_8K : 2) front_ker
     for (int q = 0; q < 4; ++q) {
         f32x4 G[8];
         init_bias<8>(G, tab + tb.b_g + 128 * q, ln);
-        if (q < 3) gemm_seg<8, 32, FB_IH, true, true>(G, bF, ring, seg_offset(IH0 + q, Q), seg_offset(IH0 + q + 1, Q), ln);
-        else gemm_seg<8, 32, 0, true, false>(G, bF, ring, seg_offset(IH3, Q), 0, ln);
+        if (q < 3) gemm_seg<8, 32, true, true>(G, bF, ring, seg_offset(IH0 + q, Q), seg_offset(IH0 + q + 1, Q), ln);
+        else gemm_seg<8, 32, true, false>(G, bF, ring, seg_offset(IH3, Q), 0, ln);
         if (ln.tile_valid) {
             const float nanv = __builtin_nanf("");
 #pragma unroll
             for (int m = 0; m < 8; ++m)
                 *reinterpret_cast<f32x4 *>(gxt + (size_t)(8 * q + m) * 256) =
-                    (kRingSlots == 3 && ring.bad) ? f32x4{nanv, nanv, nanv, nanv} : G[m];
+                    ring.bad ? f32x4{nanv, nanv, nanv, nanv} : G[m];
         }
     }
     TRACE(9);

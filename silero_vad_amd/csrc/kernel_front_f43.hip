@@ -43,12 +43,6 @@
 namespace vad {
 namespace {
 
-#ifndef VAD_BV_BATCH
-#define VAD_BV_BATCH 1           // 1: a step's four B operands are formed first, then its 8 MFMAs issue back to back (gemm_r)
-#endif
-#ifndef VAD_EPI_BATCH
-#define VAD_EPI_BATCH 1          // 1: the sections between the GEMMs read every table vector once, ahead of use, and run from registers
-#endif                           // (front_common.hpp tab_rows): 5.323 against 5.408 ms per C2 step (profiles/r08a_front_sections.md).  0: one LDS round trip at a time
 constexpr int kUnitBytes = (int)vadl::kWUnitFloats * 4;      // 16 blocks of 1 KiB
 // ---- the weight ring -------------------------------------------------------------------------------------------------
 struct Ring {
@@ -110,7 +104,6 @@ __device__ __forceinline__ void gemm_r(f32x4 (&acc)[M], BF bfun, Ring &r) {
             }
             __builtin_amdgcn_sched_barrier(0);
             constexpr int i = u * 8 + st, kg = i / (M / 2), mp = 2 * (i % (M / 2));
-#if VAD_BV_BATCH
             // A VALU instruction between two fp32 MFMAs costs its issue plus a ~10-cycle switch (profiles/r03a_issue_pipes2.md):
             // form the step's four B operands first, then issue its 8 MFMAs back to back -- one switch per step instead of four
             float bv[4];
@@ -122,14 +115,6 @@ __device__ __forceinline__ void gemm_r(f32x4 (&acc)[M], BF bfun, Ring &r) {
                 acc[mp + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(r.c0[ks], bv[ks], acc[mp + 0], 0, 0, 0);
                 acc[mp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(r.c1[ks], bv[ks], acc[mp + 1], 0, 0, 0);
             }
-#else
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const float bv = bfun(kg * 4 + ks);
-                acc[mp + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(r.c0[ks], bv, acc[mp + 0], 0, 0, 0);
-                acc[mp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(r.c1[ks], bv, acc[mp + 1], 0, 0, 0);
-            }
-#endif
             __builtin_amdgcn_sched_barrier(0);
             r.c0 = n0;
             r.c1 = n1;
@@ -261,7 +246,6 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
         }
     }
 
-#if VAD_F43_EF
     // The input transform reads the frames through E = x3 - x1 and F = x2 - x0 (kept in place of x3 and x0): t3/t4 = E +- 2F,
     // t0 = E - 4 x1, t5 = -F - x2/4 are one fma each, t1 = (E + 4F) - 3(x1 + x2) and t2 = (E - 4F) + 3(x2 - x1) three.
 #pragma unroll
@@ -275,16 +259,6 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
         poison_acc<Q>(p0, p1, X0);
         poison = poison_nyq(p0, p1, xn0, xn1, xn2, xn3);
     }
-#else
-    float poison;
-    {   float p0 = 0.f, p1 = 0.f;
-        poison_acc<Q>(p0, p1, X0);
-        poison_acc<Q>(p0, p1, X1);
-        poison_acc<Q>(p0, p1, X2);
-        poison_acc<Q>(p0, p1, X3);
-        poison = poison_nyq(p0, p1, xn0, xn1, xn2, xn3);
-    }
-#endif
     ring.c0 = lds4(ring.a_cur);
     ring.c1 = lds4(ring.a_cur + 1024);
 
@@ -308,16 +282,13 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
             // under the MFMAs of the part's last product, tap 0 and the bias right behind it, and y0, which needs taps 1 and 2 only, is
             // updated while they travel.  (All eight under the product spill 67-72 registers at 16 kHz, taps 0 and 1 under it -- 56
             // updates to run meanwhile -- 2-3; all eight behind the product, no spill, measure the same as this form.)
-            [[maybe_unused]] f32x4 wt0[RB], wt1[RB], wt2[RB], bia[RB];
+            f32x4 wt0[RB], wt1[RB], wt2[RB], bia[RB];
             auto epi_ahead = [&]() VAD_INLINE {
-                if constexpr (VAD_EPI_BATCH != 0) {
-                    lds_fence();
-                    tab_rows<RB>(wt1, wn + 128, ln);
-                    tab_rows<RB>(wt2, wn + 256, ln);
-                    lds_fence();
-                }
+                lds_fence();
+                tab_rows<RB>(wt1, wn + 128, ln);
+                tab_rows<RB>(wt2, wn + 256, ln);
+                lds_fence();
             };
-#if VAD_F43_EF
             // (E = X3, F = X0, x1 = X1, x2 = X2 from here on)
             {   const Coef k = opaque_coef<kF4, kFm3>();
                 gemm_r<RB, KG0, 2>(Y0, [&](int s) VAD_INLINE {
@@ -330,21 +301,6 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
                 gemm_r<RB, KG0, 2>(Y2, [&](int s) VAD_INLINE { return fmaf(X0[s], k.a, X3[s]); }, ring);  // E + 2F
                 gemm_r<RB, KG0, 2>(Y3, [&](int s) VAD_INLINE { return fmaf(X0[s], k.b, X3[s]); }, ring);  // E - 2F
             }
-#else
-            {   const Coef k = opaque_coef<kFm4, kF4>();
-                gemm_r<RB, KG0, 2>(Y0, [&](int s) VAD_INLINE {
-                    return fmaf(fmaf(X1[s], k.p1, X0[s]), k.a, fmaf(X3[s], k.p1, X2[s])); }, ring);       // (x2+x3) - 4(x0+x1)
-                gemm_r<RB, KG0, 2>(Y1, [&](int s) VAD_INLINE {
-                    return fmaf(fmaf(X1[s], k.m1, X0[s]), k.b, fmaf(X2[s], k.m1, X3[s])); }, ring);       // (x3-x2) + 4(x0-x1)
-            }
-            {   const Coef k = opaque_coef<kF2, kFm2>();
-                gemm_r<RB, KG0, 2>(Y2, [&](int s) VAD_INLINE {
-                    return fmaf(fmaf(X0[s], k.m1, X2[s]), k.a, fmaf(X1[s], k.m1, X3[s])); }, ring);       // (x3-x1) + 2(x2-x0)
-                const Coef k2 = opaque_coef<kF2, kFm2>();
-                gemm_r<RB, KG0, 2>(Y3, [&](int s) VAD_INLINE {
-                    return fmaf(fmaf(X0[s], k2.m1, X2[s]), k2.b, fmaf(X1[s], k2.m1, X3[s])); }, ring);    // (x3-x1) - 2(x2-x0)
-            }
-#endif
 #pragma unroll
             for (int m = 0; m < RB; ++m)
 #pragma unroll
@@ -356,21 +312,13 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
                     Y2[m][r] = fmaf(4.f, s2, sm);
                     Y3[m][r] = fmaf(8.f, d2, df);
                 }
-#if VAD_F43_EF
             {   const Coef k = opaque_coef<kFm4, kFm025>();
                 gemm_r<RB, KG0, 2>(Y0, [&](int s) VAD_INLINE { return fmaf(X1[s], k.a, X3[s]); }, ring);              // x3 - 5 x1 = E - 4 x1
                 epi_ahead();
                 gemm_r<RB, KG0, 2>(Y3, [&](int s) VAD_INLINE { return fmaf(X2[s], k.b, -X0[s]); }, ring);             // x0 - 1.25 x2 = -F - x2/4
             }
-#else
-            {   const Coef k = opaque_coef<kFm5, kFm125>();
-                gemm_r<RB, KG0, 2>(Y0, [&](int s) VAD_INLINE { return fmaf(X1[s], k.a, X3[s]); }, ring);  // x3 - 5 x1
-                epi_ahead();
-                gemm_r<RB, KG0, 2>(Y3, [&](int s) VAD_INLINE { return fmaf(X2[s], k.b, X0[s]); }, ring);  // x0 - 1.25 x2
-            }
-#endif
-#if VAD_EPI_BATCH
-            // (per accumulator the order of nyq_update / add_bias below: y0 taps 1, 2; y1 0, 1, 2; y2 0, 1, 2; y3 0, 1; then the bias)
+            // (per accumulator the order the other frontends' nyq_update / add_bias calls have: y0 taps 1, 2; y1 0, 1, 2; y2 0, 1, 2; y3 0, 1;
+            //  then the bias.  Against one LDS round trip at a time: 5.323 instead of 5.408 ms per C2 step, profiles/r08a_front_sections.md)
             lds_fence();
             tab_rows<RB>(wt0, wn, ln);
             tab_rows<RB>(bia, tab + tb.b_e0 + row0, ln);
@@ -390,22 +338,6 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
             add_rows<RB>(Y1, bia);
             add_rows<RB>(Y2, bia);
             add_rows<RB>(Y3, bia);
-#else
-            nyq_update<RB>(Y0, xn0, wn + 128, ln);
-            nyq_update<RB>(Y0, xn1, wn + 256, ln);
-            nyq_update<RB>(Y1, xn0, wn, ln);
-            nyq_update<RB>(Y1, xn1, wn + 128, ln);
-            nyq_update<RB>(Y1, xn2, wn + 256, ln);
-            nyq_update<RB>(Y2, xn1, wn, ln);
-            nyq_update<RB>(Y2, xn2, wn + 128, ln);
-            nyq_update<RB>(Y2, xn3, wn + 256, ln);
-            nyq_update<RB>(Y3, xn2, wn, ln);
-            nyq_update<RB>(Y3, xn3, wn + 128, ln);
-            add_bias<RB>(Y0, tab + tb.b_e0 + row0, ln);
-            add_bias<RB>(Y1, tab + tb.b_e0 + row0, ln);
-            add_bias<RB>(Y2, tab + tb.b_e0 + row0, ln);
-            add_bias<RB>(Y3, tab + tb.b_e0 + row0, ln);
-#endif
             relu<RB>(Y0);
             relu<RB>(Y1);
             relu<RB>(Y2);
@@ -434,7 +366,6 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
         });
     }
     f32x4 Vv[4], Fe[8];
-#if VAD_EPI_BATCH
     {   // encoder 1's bias (read once for both outputs) and encoder 2's initial value: one batch, one wait
         f32x4 b1[4];
         lds_fence();
@@ -444,10 +375,6 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
         add_rows<4>(Z0, b1);
         add_rows<4>(Z1, b1);
     }
-#else
-    add_bias<4>(Z0, tab + tb.b_e1, ln);
-    add_bias<4>(Z1, tab + tb.b_e1, ln);
-#endif
     relu<4>(Z0);
     relu<4>(Z1);
     VAD_WAVE_STAMP(ln, 10);
@@ -457,19 +384,12 @@ __global__ void __launch_bounds__(256, 2) front_f43_kernel(const FrontArgs a) {
     auto bZ1 = [&](int s) VAD_INLINE { return Z1[s >> 2][s & 3]; };
     auto bV = [&](int s) VAD_INLINE { return Vv[s >> 2][s & 3]; };
     auto bF = [&](int s) VAD_INLINE { return Fe[s >> 2][s & 3]; };
-#if VAD_EPI_BATCH
     lds_fence();
     init_bias<8>(Fe, tab + tb.b_e3, ln);                  // encoder 3's initial value travels under encoder 2's MFMAs
     lds_fence();
-#else
-    init_bias<4>(Vv, tab + tb.b_e2, ln);
-#endif
     gemm_r<4, 4, 2>(Vv, bZ0, ring);
     gemm_r<4, 4, 2>(Vv, bZ1, ring);
     relu<4>(Vv);
-#if !VAD_EPI_BATCH
-    init_bias<8>(Fe, tab + tb.b_e3, ln);
-#endif
     gemm_r<8, 4, 2>(Fe, bV, ring);
     relu<8>(Fe);
     poison_into(Fe[0], poison);

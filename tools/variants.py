@@ -26,11 +26,6 @@ VARIANTS = {
     "lat_wg2": ["-DVAD_LAT_WG_PER_CU=2", "-DVAD_LAT_DEPTH=8"], "lat_wg2_d4": ["-DVAD_LAT_WG_PER_CU=2", "-DVAD_LAT_DEPTH=4"],
     "lat_d8": ["-DVAD_LAT_DEPTH=8"], "lat_d24": ["-DVAD_LAT_DEPTH=24"], "lat_d32": ["-DVAD_LAT_DEPTH=32"],
     "lat_noload": ["-DVAD_LAT_ABLATE=1"], "lat_nofft": ["-DVAD_LAT_ABLATE=2"], "lat_neither": ["-DVAD_LAT_ABLATE=3"],
-    "rec_skew": ["-DVAD_REC_SKEW=1"],                  # fp32 recurrence with the two waves of a SIMD half a step apart (slower: r03a)
-    "rec_skew_noprio": ["-DVAD_REC_SKEW=1", "-DVAD_REC_PRIO=0"],
-    "nobvbatch": ["-DVAD_BV_BATCH=0"],                 # frontend: B-operand transforms interleaved with the MFMAs (round-2 form)
-    "xbasis": ["-DVAD_F43_EF=0"],                       # F(4,3) input transform from x0..x3 instead of (E, F, x1, x2) (f43 form only)
-    "noepibatch": ["-DVAD_EPI_BATCH=0"],               # frontend: part epilogue and encoder 1-3 bias sections one LDS round trip at a time (the form before r08a)
     "trace": ["-DVAD_TRACE=1"],
     "fftprio0": ["-DVAD_F43_FFT_PRIO=0"], "fftprio1": ["-DVAD_F43_FFT_PRIO=1"], "fftprio3": ["-DVAD_F43_FFT_PRIO=3"],   # (default: 1)
     "trace_fftprio3": ["-DVAD_TRACE=1", "-DVAD_F43_FFT_PRIO=3"],
@@ -50,8 +45,8 @@ VARIANTS = {
     "nopk_all": [],                                     # every knob unit without packed fp32 (the bf16 x 9 recurrence beside plain VALU only)
     "b9_w4": ["-DVAD_B9_WAVES=4"],                     # bf16 x 9 frontend: two 4-wave workgroups per CU (default: one 8-wave workgroup)
     "pk_b9": [],
-    "noexact": ["-DVAD_NO_EXACT=1"],
-    "gather128": ["-DVAD_GATHER_WAVES=128"], "gather192": ["-DVAD_GATHER_WAVES=192"], "gather64": ["-DVAD_GATHER_WAVES=64"],   # ingest kernel's footprint                   # frontends without the silent-frame test (what does it cost at C2?  profiles/r06_exact.md)
+    "noexact": ["-DVAD_NO_EXACT=1"],                   # frontends without the silent-frame test (what does it cost at C2?  profiles/r06_exact.md)
+    "gather128": ["-DVAD_GATHER_WAVES=128"], "gather192": ["-DVAD_GATHER_WAVES=192"], "gather64": ["-DVAD_GATHER_WAVES=64"],   # ingest kernel's footprint
 }
 
 
