@@ -901,18 +901,47 @@ int vad_decoder_grad_host(const vad_decoder_params_f64 *p, const float *feat, in
  * vad_biquad_design (host, double): one Audio-EQ-cookbook (R. Bristow-Johnson) section normalised to a0 = 1.  12 dB/oct Butterworth
  * low- and high-pass are one section at q = 1/sqrt(2); 24 dB/oct two sections at q = 1 / (2 cos(pi / 8)), 1 / (2 cos(3 pi / 8)) = 0.54119610, 1.30656296.  Band-pass has 0 dB
  * peak gain; gain_db is read by peaking and the shelves only (q is the shelves' Q, not a slope).  VAD_ERR_ARG: an unknown kind,
- * sr <= 0, f0 outside (0, sr / 2), q <= 0, a non-finite argument.                                                                   */
+ * sr <= 0, f0 outside (0, sr / 2), q <= 0, a non-finite argument.
+ *
+ * Room reverb and aliasing (two more of the fifteen; AirAbsorption, Mp3Compression and PitchShift stay out), through the _x entry points:
+ *   VAD_AUGMENT_FIR      n_sections = K taps (1 .. VAD_AUGMENT_MAX_TAPS), seed = index of tap 0 in a float32 bank that travels beside
+ *                        the recipes: y[n] = sum over k = 0 .. min(n, K - 1) of h[k] x[n - k], causal from zero state, the output as
+ *                        long as the input (audiomentations' ApplyImpulseResponse / RoomSimulator with leave_length_unchanged).  Direct
+ *                        form: the twin sums exact products in double in ascending k and rounds once; the device runs a float32
+ *                        multiply-add chain in an order that depends on (K, n) alone, |device - twin| <= (K + 2) 2^-24 sum |h||x|; a
+ *                        zero tap adds exactly nothing and digital silence longer than K stays exactly zero.
+ *   VAD_AUGMENT_ALIAS    a = new sample rate, b = the row's, 0 < a <= b: audiomentations' Aliasing, two np.interp calls on
+ *                        linspace grids, numpy's statements in double (csrc/augment.hpp), rounded to float32 once; bit-equal on both
+ *                        sides.  len < 2 or round(len a / b) < 2 leaves the row as it is.
+ * vad_augment_extra is host memory read at the call; its pointers are device pointers for the device call: the bank (4-byte aligned,
+ * may be NULL with fir_bank_len 0) and the second row buffer both ops need (16-byte aligned, vad_augment_scratch_bytes(n, ld_out)
+ * bytes; 0 = out of range), separate from the workspace.  vad_augment_rows_device_x with extra == NULL is vad_augment_rows_device;
+ * the entry points without _x treat FIR and ALIAS as unknown kinds and queue none of their launches.  A FIR whose range
+ * [seed, seed + K) leaves the bank: the device returns the row as its input, the twin and the check refuse it.  Otherwise the _x
+ * calls keep the contract above; VAD_ERR_ARG with nothing queued also for a NULL or misaligned scratch, a scratch too small, a
+ * misaligned bank, fir_bank_len < 0 or a NULL bank with fir_bank_len > 0.
+ * vad_augment_check_recipes_bank: vad_augment_check_recipes that accepts the two kinds against a bank of bank_len taps; further
+ * sentences: taps outside 1 .. 8192, taps outside the bank, rates outside 0 < a <= b.
+ * vad_rir_shoebox (host, double): Allen and Berkley's image-source response of a box room, a STATED rule in the spirit of
+ * RoomSimulator, not pyroomacoustics' bits.  beta = sqrt(1 - absorption), c = 343 m/s, d0 = |src - mic|; for nx, ny, nz in
+ * [-max_order, max_order] and px, py, pz in {0, 1}, in that nesting order: image coordinate 2 n L + (1 - 2 p) src per axis,
+ * R = sum |n - p| + |n| (skipped if R > max_order), d its distance to the microphone, amplitude A = beta^R d0 / d (0^0 = 1), delay
+ * t = (d - d0) sr / c samples, j = floor(t), f = t - j: h[j] += A (1 - f), h[j + 1] += A f where the index is below n_taps; sums in
+ * double, written as float32.  The direct sound is tap 0 with gain 1: the flight time is taken out, so labels stay aligned.
+ * VAD_ERR_ARG: a NULL pointer, a non-finite argument, sr or a room size <= 0, a position not strictly inside the room, src == mic,
+ * absorption outside (0, 1], max_order < 0, n_taps outside 1 .. 8192.                                                                */
 #define VAD_AUGMENT_MAX_OPS 3
 #define VAD_AUGMENT_MAX_SECTIONS 8
-enum { VAD_AUGMENT_NOISE = 1, VAD_AUGMENT_BIQUADS = 2, VAD_AUGMENT_CLIP = 3 };
+#define VAD_AUGMENT_MAX_TAPS 8192
+enum { VAD_AUGMENT_NOISE = 1, VAD_AUGMENT_BIQUADS = 2, VAD_AUGMENT_CLIP = 3, VAD_AUGMENT_FIR = 4, VAD_AUGMENT_ALIAS = 5 };
 enum { VAD_BIQUAD_LOWPASS = 0, VAD_BIQUAD_HIGHPASS = 1, VAD_BIQUAD_BANDPASS = 2, VAD_BIQUAD_NOTCH = 3, VAD_BIQUAD_PEAKING = 4,
        VAD_BIQUAD_LOWSHELF = 5, VAD_BIQUAD_HIGHSHELF = 6 };
 typedef struct {
     int32_t kind;                                   /* VAD_AUGMENT_*                                     */
-    int32_t n_sections;                             /* BIQUADS                                           */
+    int32_t n_sections;                             /* BIQUADS; FIR: the number of taps                  */
     double coef[VAD_AUGMENT_MAX_SECTIONS][5];       /* BIQUADS: b0 b1 b2 a1 a2                           */
-    double a, b;                                    /* NOISE: a = amplitude; CLIP: a = q_lo, b = q_hi    */
-    uint64_t seed;                                  /* NOISE                                             */
+    double a, b;                                    /* NOISE: a = amplitude; CLIP: a = q_lo, b = q_hi; ALIAS: a = new rate, b = rate */
+    uint64_t seed;                                  /* NOISE; FIR: index of the first tap in the bank    */
 } vad_augment_op;
 typedef struct {
     int32_t n_ops;
@@ -929,6 +958,21 @@ int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, lo
 int vad_augment_rows_host(const void *pcm, size_t elem_size, long ld, const long *lens, long n, const vad_augment_recipe *recipes,
                           float *out, long ld_out, int threads);
 int vad_biquad_design(int kind, double sr, double f0, double q, double gain_db, double coef[5]);
+typedef struct {
+    const float *fir_bank;                          /* [fir_bank_len] taps, or NULL                      */
+    long fir_bank_len;
+    void *scratch;                                  /* vad_augment_scratch_bytes(n, ld_out) bytes        */
+    size_t scratch_bytes;
+} vad_augment_extra;
+size_t vad_augment_scratch_bytes(long n_rows, long width);
+int vad_augment_check_recipes_bank(const vad_augment_recipe *recipes, long n, long bank_len, const char **why);
+int vad_augment_rows_device_x(vad_engine *e, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                              const vad_augment_recipe *recipes, float *out, long ld_out, void *workspace, size_t workspace_bytes,
+                              const vad_augment_extra *extra, void *stream);
+int vad_augment_rows_host_x(const void *pcm, size_t elem_size, long ld, const long *lens, long n, const vad_augment_recipe *recipes,
+                            float *out, long ld_out, const float *fir_bank, long fir_bank_len, int threads);
+int vad_rir_shoebox(double sr, const double room[3], const double src[3], const double mic[3], double absorption, int max_order,
+                    float *h, long n_taps);
 
 /* ---- RESIDENT TRAINING: batches cut out of a corpus in HBM, Adam on the device (the rules: csrc/trainset.hpp) -----------------------
  * A tuning corpus is small beside HBM and is visited once per epoch: it is uploaded once, as one arena of int16 or float32 samples

@@ -13,7 +13,7 @@ from .streams import (BatchVADIterator, PackedRecordings, RaggedPlan, RefillPlan
 from .tuning import (DecoderTrainer, decoder_grad, decoder_grad_host, decoder_grad_workspace_bytes, decoder_state_dict, replace_decoder, tune,  # noqa: F401
                      DECODER_NAMES, FusedAdam, TrainingSet, decoder_adam, decoder_adam_host)
 from .augment import (Augmenter, RECIPE_DTYPE, augment_device, augment_host, augment_workspace_bytes, biquad_design, check_recipes,  # noqa: F401
-                      make_recipes)
+                      make_recipes, ALL_TRANSFORMS, augment_scratch_bytes, fir_bank, rir_shoebox)
 from .sharding import shard_range, shard_by_duration, gather_to_rank0, batch_speech_timestamps  # noqa: F401
 
 __version__ = "0.1.0"

@@ -153,6 +153,12 @@ SYMBOLS = {
     "vad_augment_rows_device": (c_int, [c_void_p, c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_size_t,
                                         c_void_p]),
     "vad_augment_rows_host": (c_int, [c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_int]),
+    "vad_augment_scratch_bytes": (c_size_t, [c_long, c_long]),
+    "vad_augment_check_recipes_bank": (c_int, [c_void_p, c_long, c_long, POINTER(c_char_p)]),
+    "vad_augment_rows_device_x": (c_int, [c_void_p, c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_size_t,
+                                          c_void_p, c_void_p]),
+    "vad_augment_rows_host_x": (c_int, [c_void_p, c_size_t, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int]),
+    "vad_rir_shoebox": (c_int, [c_double, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_double, c_int, c_void_p, c_long]),
     "vad_trainset_batch_device": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_long,
                                           c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "vad_trainset_batch_host": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_void_p,

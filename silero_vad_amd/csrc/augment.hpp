@@ -15,6 +15,16 @@
 //           virtual index v = len q + (1 - q) - 1, neighbours floor(v) and floor(v) + 1, numpy's _lerp, rounded to float32;
 //           y = x < lo ? lo : x > hi ? hi : x (a NaN sample stays).  Order is that of the order-preserving uint32 key below, so that
 //           NaNs and infinities have a place and twin and device agree on it.
+//   ALIAS   (a = new sample rate, b = the row's, 0 < a <= b)   audiomentations' Aliasing as two np.interp calls, n = len:
+//           x = linspace(0, n, n), m = rint(n a / b) (half to even), dx = linspace(0, n, m), y = float(interp(x, dx, interp(dx, x, s)));
+//           numpy's statements in double without contraction (aug_alias_sample below); n < 2 or m < 2 leaves the row as it is.
+//   FIR     (n_sections = K taps, 1 .. 8192, seed = index of tap 0 in the float32 bank beside the recipes)   causal from zero state,
+//           y[n] = sum over k = 0 .. min(n, K - 1) of h[k] x[n - k], the output as long as the input.  Twin: exact products summed in
+//           double in ascending k, rounded once.  Device: a float32 fmaf chain in ascending k (kernel_augment_x.hip), so that
+//           |device - twin| <= (K + 2) 2^-24 sum |h[k]| |x[n - k]|; K = 1 and a single tap of 1.0 are bit-equal.
+//   ALIAS and FIR exist for the _x entry points only (vad_augment_rows_device_x / _host_x, vad_augment_check_recipes_bank); the
+//   entry points without a bank keep refusing them as unknown kinds.  Neither runs in place: the device call takes a second row
+//   buffer (vad_augment_scratch_bytes).
 // A row whose final result holds a non-finite value comes back as its input converted to float32 (the reference's add_augs returns
 // the original wav on NaN); so does a row whose recipe is empty or invalid.
 //
@@ -42,6 +52,7 @@ namespace vad {
 constexpr int kAugMaxOps = VAD_AUGMENT_MAX_OPS;
 constexpr int kAugMaxSections = VAD_AUGMENT_MAX_SECTIONS;
 constexpr int kAugStates = 2 * kAugMaxSections;    // doubles of one cascade state
+constexpr int kAugMaxTaps = VAD_AUGMENT_MAX_TAPS;
 constexpr int kAugBlock = VAD_AUG_BLOCK;           // samples of one block of the three-pass cascade (profiles/augment.md)
 static_assert(kAugBlock % 32 == 0 && kAugBlock >= 32, "a block is a whole number of 32-sample tiles");
 
@@ -64,8 +75,9 @@ VAD_AUG_HD inline AugLayout aug_layout(long n, long width) {
 
 VAD_AUG_HD inline bool aug_finite(double v) { return v - v == 0.0; }
 
-// 0 = fine, else the index of the sentence in aug_why()
-VAD_AUG_HD inline int aug_check(const vad_augment_recipe &r) {
+// 0 = fine, else the index of the sentence in aug_why().  bank_len < 0: the entry points without a bank, to which FIR and ALIAS
+// are unknown kinds.
+VAD_AUG_HD inline int aug_check(const vad_augment_recipe &r, long bank_len = -1) {
     if (r.n_ops < 0 || r.n_ops > kAugMaxOps) return 1;
     for (int p = 0; p < r.n_ops; ++p) {
         const vad_augment_op &o = r.ops[p];
@@ -78,6 +90,11 @@ VAD_AUG_HD inline int aug_check(const vad_augment_recipe &r) {
                     if (!aug_finite(o.coef[s][c])) return 3;
         } else if (o.kind == VAD_AUGMENT_CLIP) {
             if (!(o.a >= 0.0 && o.b <= 1.0 && o.a <= o.b)) return 4;
+        } else if (o.kind == VAD_AUGMENT_FIR && bank_len >= 0) {
+            if (o.n_sections < 1 || o.n_sections > kAugMaxTaps) return 7;
+            if (o.seed > (uint64_t)bank_len || (uint64_t)o.n_sections > (uint64_t)bank_len - o.seed) return 8;
+        } else if (o.kind == VAD_AUGMENT_ALIAS && bank_len >= 0) {
+            if (!(aug_finite(o.a) && aug_finite(o.b) && o.a > 0.0 && o.a <= o.b)) return 9;
         } else {
             return 6;
         }
@@ -86,7 +103,8 @@ VAD_AUG_HD inline int aug_check(const vad_augment_recipe &r) {
 }
 inline const char *aug_why(int code) {
     static const char *const text[] = {"", "n_ops outside 0 .. 3", "n_sections outside 1 .. 8", "a non-finite filter coefficient",
-                                       "quantiles must satisfy 0 <= q_lo <= q_hi <= 1", "a non-finite noise amplitude", "unknown op kind"};
+                                       "quantiles must satisfy 0 <= q_lo <= q_hi <= 1", "a non-finite noise amplitude", "unknown op kind",
+                                       "fir taps outside 1 .. 8192", "fir taps outside the bank", "aliasing rates must satisfy 0 < new rate <= rate"};
     return text[code];
 }
 
@@ -161,5 +179,66 @@ VAD_AUG_HD inline float aug_lerp(float a, float b, double t) {
     return (float)r;
 }
 VAD_AUG_HD inline float aug_clip(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// ---- ALIAS -----------------------------------------------------------------------------------------------------------------------
+// numpy's linspace(0, n, num)[i] with step = n / (num - 1)
+VAD_AUG_HD inline double aug_grid(long i, long num, double step, double n) {
+#pragma clang fp contract(off)
+    return i == num - 1 ? n : (double)i * step;
+}
+// the j in [0, num - 2] with grid[j] <= q < grid[j + 1], for 0 <= q < grid[num - 1]: the quotient, corrected by at most one step
+VAD_AUG_HD inline long aug_grid_find(double q, long num, double step, double n) {
+#pragma clang fp contract(off)
+    long j = (long)floor(q / step);
+    if (j < 0) j = 0;
+    if (j > num - 2) j = num - 2;
+    if (j > 0 && aug_grid(j, num, step, n) > q) --j;
+    else if (j < num - 2 && aug_grid(j + 1, num, step, n) <= q) ++j;
+    return j;
+}
+// numpy's interp on a grid: the value at q of the line through (grid[j], f0) and (grid[j + 1], f1)
+VAD_AUG_HD inline double aug_interp_cell(double q, double x0, double x1, double f0, double f1) {
+#pragma clang fp contract(off)
+    if (q == x0) return f0;
+    return ((f1 - f0) / (x1 - x0)) * (q - x0) + f0;
+}
+// the new length of an ALIAS op: 0 when the op leaves the row as it is
+VAD_AUG_HD inline long aug_alias_m(long n, double a, double b) {
+#pragma clang fp contract(off)
+    if (n < 2) return 0;
+    const double m = rint((double)n * a / b);
+    return m < 2.0 ? 0 : (long)m;
+}
+struct AugAlias {
+    long n, m;
+    double dn, step_x, step_d;
+};
+VAD_AUG_HD inline AugAlias aug_alias_plan(long n, long m) {
+#pragma clang fp contract(off)
+    AugAlias p;
+    p.n = n; p.m = m; p.dn = (double)n;
+    p.step_x = p.dn / (double)(n - 1);
+    p.step_d = p.dn / (double)(m - 1);
+    return p;
+}
+// interp(dx[k], x, s) in double: the inner call, sample k of the row at the new rate
+VAD_AUG_HD inline double aug_alias_inner(const AugAlias &p, const float *s, long k) {
+#pragma clang fp contract(off)
+    const double q = aug_grid(k, p.m, p.step_d, p.dn);
+    if (q >= p.dn) return (double)s[p.n - 1];
+    const long j = aug_grid_find(q, p.n, p.step_x, p.dn);
+    return aug_interp_cell(q, aug_grid(j, p.n, p.step_x, p.dn), aug_grid(j + 1, p.n, p.step_x, p.dn), (double)s[j], (double)s[j + 1]);
+}
+// output sample i of the ALIAS op over the row s[0 .. n): four input samples, no intermediate array
+VAD_AUG_HD inline float aug_alias_sample(const AugAlias &p, const float *s, long i) {
+#pragma clang fp contract(off)
+    const double q = aug_grid(i, p.n, p.step_x, p.dn);
+    if (q >= p.dn) return (float)aug_alias_inner(p, s, p.m - 1);
+    const long k = aug_grid_find(q, p.m, p.step_d, p.dn);
+    const double x0 = aug_grid(k, p.m, p.step_d, p.dn);
+    const double f0 = aug_alias_inner(p, s, k);
+    if (q == x0) return (float)f0;
+    return (float)aug_interp_cell(q, x0, aug_grid(k + 1, p.m, p.step_d, p.dn), f0, aug_alias_inner(p, s, k + 1));
+}
 
 }  // namespace vad

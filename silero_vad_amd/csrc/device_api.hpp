@@ -333,8 +333,14 @@ struct AugArgs {
     float *out;                                                // [n][ld_out]
     long ld_out;
     void *workspace;
+    // vad_augment_rows_device_x (kernel_augment_x.hip): bank_len >= 0 admits FIR and ALIAS and queues three more launches per op
+    // position; scratch is then a second [n][ld_out] float32 buffer, 16-byte aligned.  bank_len < 0: neither is read.
+    const float *bank;                                         // [bank_len] or nullptr
+    long bank_len;
+    float *scratch;
 };
 hipError_t launch_augment(const AugArgs &a, hipStream_t s);
+hipError_t launch_augment_x(const AugArgs &a, int pos, hipStream_t s);     // ALIAS, FIR and the copy back at one op position
 
 // Resident training (kernel_trainset.hip; the rules are trainset.hpp).  Every pointer is a device pointer, element-aligned; the
 // 16-byte path is chosen per vector from the addresses.  One launch, no synchronisation, no atomics.

@@ -961,8 +961,9 @@ int vad_decoder_grad_device(vad_engine *e, const vad_decoder_params *p, const fl
     return VAD_OK;
 }
 
-int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
-                            const vad_augment_recipe *recipes, float *out, long ld_out, void *workspace, size_t workspace_bytes, void *stream) {
+int vad_augment_rows_device_x(vad_engine *e, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                              const vad_augment_recipe *recipes, float *out, long ld_out, void *workspace, size_t workspace_bytes,
+                              const vad_augment_extra *extra, void *stream) {
     if (!e) return VAD_ERR_ARG;
     if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
     if (!pcm || !lens || !recipes || !out || !workspace || n <= 0 || n > 65535 || ld <= 0 || ld_out <= 0)
@@ -974,12 +975,26 @@ int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, lo
     const size_t need = vad_augment_workspace_bytes(n, ld_out);
     if (need == 0) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: n ld_out too large");
     if (workspace_bytes < need) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device: workspace smaller than vad_augment_workspace_bytes(n, ld_out)");
-    HIP_TRY(e, hipSetDevice(e->device));
     vad::AugArgs a{};
+    a.bank_len = -1;
+    if (extra) {
+        if (extra->fir_bank_len < 0 || (!extra->fir_bank && extra->fir_bank_len > 0) || !extra->scratch)
+            return fail(e, VAD_ERR_ARG, "vad_augment_rows_device_x: null bank or scratch");
+        if (((size_t)extra->fir_bank & 3) || ((size_t)extra->scratch & 15)) return fail(e, VAD_ERR_ARG, "vad_augment_rows_device_x: misaligned pointer");
+        if (extra->scratch_bytes < vad_augment_scratch_bytes(n, ld_out))
+            return fail(e, VAD_ERR_ARG, "vad_augment_rows_device_x: scratch smaller than vad_augment_scratch_bytes(n, ld_out)");
+        a.bank = extra->fir_bank; a.bank_len = extra->fir_bank_len; a.scratch = static_cast<float *>(extra->scratch);
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
     a.pcm = pcm; a.elem_size = (int)elem_size; a.ld = ld; a.lens = lens; a.n = n; a.recipes = recipes; a.out = out; a.ld_out = ld_out;
     a.workspace = workspace;
     HIP_TRY(e, vad::launch_augment(a, (hipStream_t)stream));
     return VAD_OK;
+}
+
+int vad_augment_rows_device(vad_engine *e, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
+                            const vad_augment_recipe *recipes, float *out, long ld_out, void *workspace, size_t workspace_bytes, void *stream) {
+    return vad_augment_rows_device_x(e, pcm, elem_size, ld, lens, n, recipes, out, ld_out, workspace, workspace_bytes, nullptr, stream);
 }
 
 int vad_trainset_batch_device(vad_engine *e, const void *arena, size_t elem_size, const long *offs, const long *lens,

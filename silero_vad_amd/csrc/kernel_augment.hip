@@ -17,6 +17,7 @@
 // CLIP    one workgroup per row: a radix select over the order-preserving keys, four 8-bit digits from the top, for the (at most)
 //   four order statistics the two quantiles interpolate between -- targets that still share their leading digits share a histogram
 //   -- with integer LDS counters; then the clip over the row.
+// ALIAS, FIR (vad_augment_rows_device_x only): kernel_augment_x.hip, through a second row buffer.
 // No float atomics anywhere; every value is produced by one thread in a fixed order.
 #include <hip/hip_runtime.h>
 
@@ -46,12 +47,12 @@ inline AugWs aug_ws(void *workspace, long n, long width) {
 
 __device__ inline bool finite_f(float v) { return v - v == 0.0f; }
 
-__global__ void __launch_bounds__(256) aug_plan_kernel(const long *lens, const vad_augment_recipe *recipes, long n, long max_len, AugWs ws) {
+__global__ void __launch_bounds__(256) aug_plan_kernel(const long *lens, const vad_augment_recipe *recipes, long n, long max_len, long bank_len, AugWs ws) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const long l = lens[i];
     ws.len[i] = l < 0 ? 0 : (l > max_len ? max_len : l);
-    ws.n_ops[i] = aug_check(recipes[i]) == 0 ? recipes[i].n_ops : 0;
+    ws.n_ops[i] = aug_check(recipes[i], bank_len) == 0 ? recipes[i].n_ops : 0;
     ws.flag[i] = 0;
 }
 
@@ -388,7 +389,7 @@ void launch_convert(const AugArgs &a, const AugWs &ws, bool restore, hipStream_t
 hipError_t launch_augment(const AugArgs &a, hipStream_t s) {
     const AugWs ws = aug_ws(a.workspace, a.n, a.ld_out);
     const long max_len = a.ld < a.ld_out ? a.ld : a.ld_out;
-    hipLaunchKernelGGL(aug_plan_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a.lens, a.recipes, a.n, max_len, ws);
+    hipLaunchKernelGGL(aug_plan_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a.lens, a.recipes, a.n, max_len, a.bank_len, ws);
     if (a.elem_size == 2) launch_convert<int16_t>(a, ws, false, s);
     else launch_convert<float>(a, ws, false, s);
     const dim3 elementwise((unsigned)((a.ld_out + 1023) / 1024), (unsigned)a.n);
@@ -399,6 +400,7 @@ hipError_t launch_augment(const AugArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(biquad_scan_kernel, dim3((unsigned)a.n), dim3(kLanes), 0, s, a.recipes, pos, ws);
         hipLaunchKernelGGL(biquad_apply_kernel, groups, dim3(kLanes), 0, s, a.recipes, pos, a.out, a.ld_out, ws);
         hipLaunchKernelGGL(aug_clip_kernel, dim3((unsigned)a.n), dim3(kClipThreads), 0, s, a.recipes, pos, a.out, a.ld_out, ws);
+        if (a.bank_len >= 0) (void)launch_augment_x(a, pos, s);
     }
     if (a.elem_size == 2) launch_convert<int16_t>(a, ws, true, s);
     else launch_convert<float>(a, ws, true, s);

@@ -356,6 +356,7 @@ class DecoderTrainer:
         self.generator.manual_seed(int(seed))
         self._workspace = None
         self._aug_workspace = None
+        self._aug_scratch = None
         self.last_grads = None
         self.last_augmented = None
         self.last_features = None
@@ -379,23 +380,39 @@ class DecoderTrainer:
             lab[b, :nck[b]] = l
         return pcm, nck, lab, T
 
-    def step(self, audios: Sequence, labels: Sequence, recipes=None):
+    def _augment(self, x, lens, recipes, bank):
+        """`augment_device` with the trainer's workspace; with a bank (recipes that may hold "fir" and "alias" ops) the call with a
+        bank, and the trainer's second row buffer beside the workspace"""
+        from .augment import augment_device, augment_scratch_bytes, augment_workspace_bytes
+        B = int(x.shape[0])
+        need = augment_workspace_bytes(B, x.shape[1])
+        if self._aug_workspace is None or self._aug_workspace.numel() < need:
+            self._aug_workspace = None
+            self._aug_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if bank is None:
+            return augment_device(self.base_model.engine, x, lens, recipes, workspace=self._aug_workspace)
+        need = augment_scratch_bytes(B, (int(x.shape[1]) + 3) // 4 * 4)
+        if self._aug_scratch is None or self._aug_scratch.numel() < need:
+            self._aug_scratch = None
+            self._aug_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if not torch.is_tensor(bank):
+            bank = torch.from_numpy(np.ascontiguousarray(bank, dtype=np.float32)).to(self.device)
+        return augment_device(self.base_model.engine, x, lens, recipes, workspace=self._aug_workspace, bank=bank, scratch=self._aug_scratch)
+
+    def step(self, audios: Sequence, labels: Sequence, recipes=None, bank=None):
         """One optimizer step on one batch; returns the batch's loss (a float: one host synchronisation).  recipes: one augmentation
         recipe per recording (augment.RECIPE_DTYPE, e.g. `Augmenter.draw`): the uploaded padded batch goes through `augment_device`
         on the current stream before `encode` -- the recordings are cut to `max_train_length_sec` first, so the augmentation sees the
-        cut -- and the augmented batch stays in `last_augmented`.  None: no augmentation."""
+        cut -- and the augmented batch stays in `last_augmented`.  None: no augmentation.  bank: the taps the recipes' "fir" ops index
+        (a float32 array or cuda tensor, e.g. `Augmenter.bank`); with it "fir" and "alias" ops are admitted, without it the call is
+        the one it was."""
         pcm, nck, lab, T = self._batch(audios, labels)
         B = len(nck)
         with torch.cuda.device(self.device):
             x = torch.from_numpy(pcm).to(self.device)
             if recipes is not None:
-                from .augment import augment_device, augment_workspace_bytes
                 lens = [min(len(a), self.max_samples) for a in audios]
-                need = augment_workspace_bytes(B, x.shape[1])
-                if self._aug_workspace is None or self._aug_workspace.numel() < need:
-                    self._aug_workspace = None
-                    self._aug_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-                x = augment_device(self.base_model.engine, x, lens, recipes, workspace=self._aug_workspace)
+                x = self._augment(x, lens, recipes, bank)
                 self.last_augmented = x
             return float(self._train_on(x, nck, lab, B, T).item())
 
@@ -422,9 +439,9 @@ class DecoderTrainer:
             self.last_numel = B * T
             return loss
 
-    def step_resident(self, trainset: "TrainingSet", idx: Sequence, recipes=None):
+    def step_resident(self, trainset: "TrainingSet", idx: Sequence, recipes=None, bank=None):
         """`step` on a batch cut out of a resident `TrainingSet`: recordings `idx` (host integers, repeats allowed), the same padded
-        batch, augmentation, mask draw, gradients and optimizer step as `step([audios[i] ...], [labels[i] ...], recipes)` -- but the batch
+        batch, augmentation, mask draw, gradients and optimizer step as `step([audios[i] ...], [labels[i] ...], recipes, bank)` -- but the batch
         is assembled on the device and the loss comes back as the 0-dim float64 DEVICE tensor: nothing here synchronises, so the host
         runs ahead (drawing the next recipes) while the device works.
         tune_8k: a trainer at sampling_rate 8000 on a set at 16000 augments at 16 kHz, then resamples 16000 -> 8000 on the device
@@ -442,16 +459,12 @@ class DecoderTrainer:
             x, lens, nck, lab, T = trainset.batch(idx)
             B = int(x.shape[0])
             if recipes is not None:
-                from .augment import _recipes_array, augment_device, augment_workspace_bytes, check_recipes
+                from .augment import _recipes_array, check_recipes
                 if not torch.is_tensor(recipes):
                     r = _recipes_array(recipes, B)
-                    check_recipes(r)
+                    check_recipes(r, None if bank is None else int(bank.numel() if torch.is_tensor(bank) else np.size(bank)))
                     recipes = _pinned_upload(r.view(np.uint8).reshape(-1), self.device)
-                need = augment_workspace_bytes(B, x.shape[1])
-                if self._aug_workspace is None or self._aug_workspace.numel() < need:
-                    self._aug_workspace = None
-                    self._aug_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-                x = augment_device(self.base_model.engine, x, lens, recipes, workspace=self._aug_workspace)
+                x = self._augment(x, lens, recipes, bank)
                 self.last_augmented = x
             if down:
                 from .streams import resample_device
@@ -463,7 +476,8 @@ class DecoderTrainer:
         """One pass over the corpus in batches; returns the reference's `losses.avg` (each batch weighted by its padded size).
         augment: None, a callable `wav -> wav` run on the host per visited recording, or an `Augmenter`: one recipe is drawn per visited
         recording, with the recording's index as row_key (its noise differs from its neighbours' and, the seeds being drawn anew,
-        between epochs), and applied on the device inside `step`.
+        between epochs), and applied on the device inside `step`, with the augmenter's bank of impulse responses when it draws
+        "aliasing" or "room".
         audios may be a `TrainingSet` (labels omitted): every batch then goes through `step_resident`, the batches' losses x B T are
         summed on the device and ONE `.item()` at the end gives the average (augment: None or an `Augmenter`).
         sampling: "permutation" visits every recording once (shuffled or in order); "reference" draws len(corpus) indices WITH
@@ -471,6 +485,12 @@ class DecoderTrainer:
         loader's index is ignored (tuning/utils.py:88, 109-110).  The visited indices stay in `last_order`."""
         from .augment import Augmenter
         on_device = isinstance(augment, Augmenter)
+        # an augmenter that draws "aliasing" or "room" goes through the calls with a bank (its own, uploaded once; empty without "room")
+        bank = None
+        if on_device and augment.needs_bank:
+            bank = augment.bank_on(self.device)
+            if bank is None:
+                bank = torch.zeros(0, dtype=torch.float32, device=self.device)
         resident = isinstance(audios, TrainingSet)
         if resident and (labels is not None or not (augment is None or on_device)):
             raise ValueError("a TrainingSet carries its labels, and takes no host augmentation: augment is None or an Augmenter")
@@ -487,7 +507,7 @@ class DecoderTrainer:
             total, count = torch.zeros((), dtype=torch.float64, device=self.device), 0
             for i in range(0, len(order), batch_size):
                 idx = order[i:i + batch_size]
-                loss = self.step_resident(audios, idx, recipes=augment.draw(len(idx), row_keys=idx) if on_device else None)
+                loss = self.step_resident(audios, idx, recipes=augment.draw(len(idx), row_keys=idx) if on_device else None, bank=bank)
                 total = total + loss * self.last_numel
                 count += self.last_numel
             return float(total.item()) / max(count, 1)
@@ -495,7 +515,7 @@ class DecoderTrainer:
         for i in range(0, len(order), batch_size):
             idx = order[i:i + batch_size]
             if on_device:
-                loss = self.step([audios[j] for j in idx], [labels[j] for j in idx], recipes=augment.draw(len(idx), row_keys=idx))
+                loss = self.step([audios[j] for j in idx], [labels[j] for j in idx], recipes=augment.draw(len(idx), row_keys=idx), bank=bank)
             else:
                 wavs = [audios[j] if augment is None else augment(audios[j]) for j in idx]
                 loss = self.step(wavs, [labels[j] for j in idx])

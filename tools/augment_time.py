@@ -3,7 +3,13 @@
 the device call as a whole (recipes as `Augmenter(p=1)` draws them) and per op kind with one-kind recipes, the host twin on 16
 threads for the same batch, and the whole `DecoderTrainer.step` with and without recipes.
 
-    python tools/augment_time.py [--shape 128x250] [--reps 10] [--host-threads 16] [--no-step] [--out profiles/augment_times.json]
+    python tools/augment_time.py [--shape 128x250] [--reps 10] [--host-threads 16] [--no-step] [--no-host] [--room]
+                                 [--out profiles/augment_times.json]
+
+--room adds the two ops of the call with a bank (profiles/augment_room.md): ALIAS on every row, FIR on every row at 512, 2048 and
+8192 taps (with the fraction of the 157.3 TFLOP/s fp32 matrix peak the executed multiply-adds amount to), recipes as
+`Augmenter(p=1, transforms=ALL_TRANSFORMS)` draws them, the ten old transforms through the call with a bank, and `step_resident` with
+the ten and with the twelve transforms.
 
 Device calls are event-timed medians behind warm-up runs, with the recipes already on the device and the workspace and the output
 reused; `host` and the steps are wall-clock medians around a synchronisation.  SILERO_VAD_AMD_LIB selects another build of the library
@@ -22,12 +28,50 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from tools.train_step_time import event_ms, wall_ms  # noqa: E402
 
 
+def room_times(a, r, model, x, lens, out, ws, wavs, labels):
+    """the call with a bank: per new op, as drawn, and the resident step"""
+    from silero_vad_amd import ALL_TRANSFORMS, Augmenter, DecoderTrainer, TrainingSet, augment
+    dev, (B, W) = model.device, x.shape
+    rng = np.random.default_rng(1)
+    scratch = torch.empty(augment.augment_scratch_bytes(B, W), dtype=torch.uint8, device=dev)
+    all12 = Augmenter(p=1.0, seed=0, transforms=ALL_TRANSFORMS)
+    taps = (512, 2048, 8192)
+    bank, offs, _ = augment.fir_bank([(rng.standard_normal(K) * np.exp(-np.arange(K) / (K / 6.0)) / np.sqrt(K)).astype(np.float32) for K in taps])
+    cases = {"alias": (augment.make_recipes([[("alias", 11025, 16000)]] * B), bank),
+             "mixed12_p1": (all12.draw(B), all12.bank), "mixed10_p1_through_x": (Augmenter(p=1.0, seed=0).draw(B), bank)}
+    for K, o in zip(taps, offs):
+        cases[f"fir_{K}"] = (augment.make_recipes([[("fir", int(o), K)]] * B), bank)
+    r["scratch_MB"], r["device_x_ms"], r["fir_fraction_of_fp32_matrix_peak"] = scratch.numel() / 1e6, {}, {}
+    for name, (rec, bk) in cases.items():
+        rec_dev, bank_dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev), torch.from_numpy(bk).to(dev)
+        ms = event_ms(lambda: augment.augment_device(model.engine, x, lens, rec_dev, out=out, workspace=ws, bank=bank_dev, scratch=scratch), a.reps)
+        r["device_x_ms"][name] = ms
+    empty = r["device_x_ms"]["mixed10_p1_through_x"] - r["device_ms"]["mixed_p1"]      # (the nine launches that find nothing to do)
+    r["device_x_ms"]["nine_idle_launches"] = empty
+    for K in taps:
+        # executed per workgroup of 4096 outputs: ceil((K' + 15) / 16) groups, K' = min(K, the last output's index + 1), of sixteen
+        # instructions in every wave that has outputs (1024 each), 2 x 16 x 16 x 4 flop an instruction
+        mfma = sum(-(-(min(K, n0 + 4096, W) + 15) // 16) * 16 * min(4, -(-(W - n0) // 1024)) for n0 in range(0, W, 4096))
+        flop = B * mfma * 2048.0
+        r["fir_fraction_of_fp32_matrix_peak"][str(K)] = flop / ((r["device_x_ms"][f"fir_{K}"] - r["device_ms"]["empty"]) * 1e-3) / 157.3e12
+    if not a.no_step:
+        ts = TrainingSet(wavs, labels, model, max_train_length_sec=W / 16000)
+        idx = list(range(B))
+        for name, aug in (("ten", Augmenter(p=1.0, seed=0)), ("twelve", all12)):
+            trainer = DecoderTrainer(model, max_train_length_sec=W / 16000)
+            rec = aug.draw(B, row_keys=idx)
+            bk = aug.bank_on(dev) if aug.needs_bank else None
+            r[f"step_resident_{name}_ms"] = wall_ms(lambda: trainer.step_resident(ts, idx, recipes=rec, bank=bk).item(), a.reps)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="128x250")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--room", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     from silero_vad_amd import Augmenter, DecoderTrainer, augment, load_silero_vad
@@ -55,12 +99,16 @@ def main():
         rec_dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
         r["device_ms"][name] = event_ms(lambda: augment.augment_device(model.engine, x, lens, rec_dev, out=out, workspace=ws), a.reps)
     print(json.dumps(r), flush=True)
-    host = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        augment.augment_host(x_host, [W] * B, kinds["mixed_p1"], threads=a.host_threads)
-        host.append((time.perf_counter() - t0) * 1e3)
-    r["host_mixed_p1_ms"], r["host_threads"] = float(np.median(host)), a.host_threads
+    if a.room:
+        room_times(a, r, model, x, lens, out, ws, wavs, labels)
+        print(json.dumps(r), flush=True)
+    if not a.no_host:
+        host = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            augment.augment_host(x_host, [W] * B, kinds["mixed_p1"], threads=a.host_threads)
+            host.append((time.perf_counter() - t0) * 1e3)
+        r["host_mixed_p1_ms"], r["host_threads"] = float(np.median(host)), a.host_threads
     if not a.no_step:
         trainer = DecoderTrainer(model, max_train_length_sec=W / 16000)
         r["step_ms"] = wall_ms(lambda: trainer.step(wavs, labels), a.reps)
