@@ -577,6 +577,64 @@ uint8_t *vad_pump_wide_slot(vad_pump *p, int r);
 int  vad_pump_submit_wide_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
                                   const uint8_t *step_of_row, long n_rows);
 int  vad_pump_wide_phase(const vad_pump *p, int stream);
+/* RESAMPLED packet ticks -- speech-synthesis and realtime voice-agent APIs deliver 24 kHz PCM, desktop and browser capture and Bluetooth
+ * 44.1 / 22.05 kHz, some telephony 11.025 kHz, and a 48 kHz caller may want read_audio's low-pass instead of the wide route's comb.  A
+ * resampled tick's rows are int16 samples at one of the pump's enabled source rates, and the device runs the STREAMING form of the
+ * resampler ("resampling to the net's rate" below: vad_resample_stream_ready has the rule) on their way into the stream's chunk: no host
+ * pass, no filter state in the caller, int16 at the source rate on the link.
+ * vad_pump_set_resample(p, src_rates, n_rates): 1 ... VAD_PUMP_MAX_RATES distinct rates, each one vad_resample_geometry(rate, the pump's
+ * rate, ...) serves (VAD_ERR_SAMPLE_RATE otherwise; also for a pair whose chunk of input does not fit the assembly kernel's LDS -- none of
+ * the rates named here); on 8 kHz and 16 kHz pumps; only while no tick is in flight (VAD_ERR_ARG otherwise).  It allocates a third
+ * page-locked ring of ring_slots RESAMPLE slots and three device landing buffers, each [row table | flags | streams * A int16], A = the
+ * input samples of one chunk at the largest enabled rate, ceil(chunk O / N), rounded up to 8 (1 416 for 44.1 -> 16 kHz): every stream can
+ * deliver a full 32 ms in the same tick; ONE fp32 batch [streams][chunk], written and read on the compute stream only; an fp32 carry
+ * [streams][chunk]; an int16 history [streams][Hmax rounded up to 8], zeroed; and the pairs' tables through the engine's shared ones
+ * (vad_resample_reserve).  At 8 192 streams, 4 slots and 44.1 kHz: 94 MB page-locked, 70 MB + 34 MB + 0.7 MB on the device.  The same
+ * rates again are a no-op; another set reallocates, unbinds every stream and zeroes every history.  A pump on which it was never called
+ * allocates none of that and runs every other route through the code it always ran.  vad_pump_resample_slot(p, r): resample slot r's
+ * sample area, streams * A * 2 bytes; NULL when the route is not enabled or r is bad.  Ring slot r, wide slot r and resample slot r are
+ * the same tick slot: one tick at a time uses r, through any of them.
+ * vad_pump_submit_resampled_packets: row i of resample slot r's sample area holds len_of_row[i] int16 INPUT samples of stream
+ * stream_of_row[i], sampled at src_rates[rate_of_row[i]] Hz (rate_of_row == NULL: every row at src_rates[0]), starting at BYTE offset
+ * byte_off_of_row[i], a multiple of 16; one tick carries clients of every enabled rate side by side.  Rows are int16 only.  1 <= len <= A.
+ * Every stream carries, as host bookkeeping advanced at submit time like the pending count and the comb phase: the rate it is BOUND to,
+ * g = the input samples it has received and m = the outputs it has emitted -- both less the same whole periods (O inputs, N outputs), so
+ * neither grows with the stream's age --, and c = its fp32 outputs that wait for their chunk, 0 ... chunk - 1.  On the device it carries
+ * the last H input samples (vad_resample_stream_history) and those c outputs.  A row of len samples emits the outputs m ... ready(g + len)
+ * - 1 of the stream (possibly none: a first row shorter than the filter's latency; possibly two for one input sample when the pair
+ * upsamples); they are appended to the c pending ones, a stream whose pending outputs reach the chunk is stepped once on the first chunk
+ * of them, the rest stays pending, every other stream is absent.  A row with c + outputs >= 2 chunks is refused: a stream completes at
+ * most one chunk per tick (there are no resampled bursts).  One H2D copy per tick: row table, flags, rows.  The assembly kernel
+ * (kernel_present.hip assemble_resampled_packets) runs on the compute stream; the masked step behind it is that of every packet tick,
+ * reading the fp32 batch.
+ * RESULTS.  Every output carries the bits vad_resample_rows_device gives for the stream's concatenated rows (the same table, fp32 fmaf in
+ * tap order, a function of the output index alone), whatever the packetisation; probabilities, events, (h, c) and context are bit for bit
+ * those of vad_step_present over the chunks y[k chunk : (k + 1) chunk] of that signal, each at the tick its last sample became ready.
+ * Nothing is zero-extended on the right: an emitted output never changes, and the filter's tail (at most latency - 1 input samples'
+ * worth of outputs) stays unemitted when the stream is closed, like its pending samples on every route.  vad_iter_event.sample counts
+ * samples at the pump's rate, as on the wide route.
+ * BINDING.  A stream binds to a rate with its first resampled row after vad_pump_create / vad_pump_open.  While bound, a row at another
+ * rate is refused, and so is the stream on every other submit route (chunk, rows, packet, coded, burst and wide ticks), in the way the
+ * chunk routes refuse a stream with pending samples; a stream with int16 samples pending from those routes cannot take a resampled row.
+ * vad_pump_open unbinds the stream and zeroes its counters on the host and its history on the device, ordered behind the ticks in flight
+ * like the state reset; vad_pump_close unbinds in the same way and drops the pending outputs.  vad_pump_pending reports c for a bound
+ * stream.  vad_pump_resample_state: *src_rate = the rate the stream is bound to (0: none), *inputs_mod = g as defined above, i.e. the
+ * inputs received less O * (outputs emitted / N), *pending = c; any pointer may be NULL; VAD_ERR_ARG for a bad stream or a pump without
+ * the route.
+ * Invalid input is VAD_ERR_ARG, nothing is queued and no count is touched: the route not enabled, a rate index out of range, a stream out
+ * of range or listed twice, len < 1 or above A, a misaligned offset, a row that runs past the area, n_rows above `streams`, the binding
+ * rules and the two-chunk rule above.
+ * A row with byte_off_of_row[i] == VAD_ROW_SILENT is a silent row (see vad_pump_submit_packets) of 1 ... A INPUT samples at its rate:
+ * zeros enter the filter (the outputs are not zeros while the history rings out), no bytes of the slot, no offset checks; bit for bit
+ * a payload row of int16 zeros.
+ * SNAPSHOTS.  vad_pump_export_streams refuses (VAD_ERR_ARG, with a message) a stream that is bound to a rate: blob version 1 has no room
+ * for an fp32 carry and a history.  vad_pump_import_streams into a slot leaves it unbound.                                             */
+#define VAD_PUMP_MAX_RATES 4
+int  vad_pump_set_resample(vad_pump *p, const int *src_rates, int n_rates);
+uint8_t *vad_pump_resample_slot(vad_pump *p, int r);
+int  vad_pump_submit_resampled_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
+                                       const int32_t *len_of_row, const uint8_t *rate_of_row, long n_rows);
+int  vad_pump_resample_state(const vad_pump *p, int stream, int *src_rate, long *inputs_mod, long *pending);
 /* The host twin of the device's decimation, from the same definition: the samples of in[0 .. n) that the comb keeps -- in[k] with
  * (phase + k) % step == 0, i.e. in[(-phase) % step :: step] -- are written to out, and their number is returned.  phase = the number of
  * the stream's samples in front of in[0], modulo step; the next piece's phase is (phase + n) % step.  Host only, re-entrant.
@@ -778,7 +836,7 @@ int  vad_host_unregister(void *p);
  * (no low-pass); src = 48000 here is read_audio's low-pass resample.  Both exist in the reference.
  * Non-finite samples poison the outputs whose K stored taps cover them; a dense convolution would poison the whole 2 W + O window
  * (0 * NaN).  That is not emulated.
- * The first four need no engine and no GPU.                                                                                      */
+ * The first four and the three vad_resample_stream_* calls need no engine and no GPU.                                             */
 int  vad_resample_geometry(int src, int dst, int *O, int *N, int *W, int *K);      /* any pointer may be NULL */
 /* ceil(N n / O): the samples n input samples become; -VAD_ERR_SAMPLE_RATE, -VAD_ERR_ARG (n < 0) */
 long vad_resample_length(int src, int dst, long n);
@@ -787,6 +845,32 @@ int  vad_resample_table(int src, int dst, float *taps /* [N][K] */, int32_t *fir
 /* host twin, re-entrant: n samples of elem_size 2 (int16) or 4 (float32) at pcm -> out[0 .. vad_resample_length(src, dst, n)); the
  * same table, every sum accumulated in double over the K stored taps in order and rounded once to float32. */
 int  vad_resample_host(int src, int dst, const void *pcm, size_t elem_size, long n, float *out);
+/* THE STREAMING FORM of the same function, for a signal that arrives in pieces (the pump's resampled rows; host only, re-entrant).
+ * Output m = q N + j reads the K inputs p0 ... p0 + K - 1, p0 = q O + first[j] - W, inputs before 0 being zero.  A stream that has
+ * received g input samples has emitted exactly the outputs with p0 + K <= g: "ready(g)".  Nothing is zero-extended on the right, so an
+ * emitted output never changes and equals, for every cut of the signal into pieces, the output of the whole signal.  p0 + K does not
+ * fall from one output to the next (first[] is non-decreasing and first[N - 1] <= first[0] + O: checked when the table is made, and a
+ * pair that failed it would have no streaming form, -VAD_ERR_SAMPLE_RATE), so the emitted outputs are a prefix and ready(g) is a count;
+ * it is non-decreasing in g, at most ceil(N g / O), and ready(g + O) = ready(g) + N once g + O >= first[N - 1] - W + K.  The latency,
+ * the inputs behind an output's nominal position floor(m O / N) that must arrive before it is emitted, is at most max_j (first[j] -
+ * floor(j O / N)) - W + K: 19 input samples for 44.1 -> 16 kHz and 48 -> 16 kHz, 11 for 24 -> 16 kHz, 10 for 22.05 -> 16 kHz, 35 for
+ * 44.1 -> 8 kHz.
+ * vad_resample_stream_ready: ready(g); -VAD_ERR_SAMPLE_RATE for a pair that is not served, -VAD_ERR_ARG for g < 0.  Exact for g up to
+ * 2^40 and far beyond: whole periods (O inputs for N outputs) are taken out of g first, everything is 64-bit.
+ * vad_resample_stream_history: H, the input samples a stream must keep so that every output not yet emitted finds its K inputs in
+ * history ++ the next piece.  H = K - 1.  Derivation: an output m that is not emitted at g has p0(m) + K > g, i.e. p0(m) >= g - (K - 1),
+ * so no unemitted output reads further back than K - 1 samples; and the bound is met whenever a piece ends at g = p0(m) + K - 1 for a
+ * phase whose run has all K taps, so K - 2 samples are not enough (tests/test_pump_resample.py).  (K + (dhi - dlo) + ceil(O / N), with
+ * dlo / dhi the extremes of first[j] - floor(j O / N), also suffices, but it bounds the spread of the phases a second time: the rule
+ * above already says where every unemitted output starts.)  < 0: -VAD_ERR_SAMPLE_RATE.
+ * vad_resample_stream_host: the host twin of one piece.  g = the inputs the stream received before it, history[H] = the last H of them,
+ * oldest first, zeros where the stream has not lived that long; in[n] = the piece.  Writes the outputs ready(g) ... ready(g + n) - 1 to
+ * out (accumulated as vad_resample_host does: double, tap order, one rounding -- bit for bit its outputs of the whole signal) and, if
+ * history_out is not NULL, the next piece's history (history_out may be history).  Returns their number, ready(g + n) - ready(g), or
+ * -VAD_ERR_SAMPLE_RATE / -VAD_ERR_ARG (g < 0, n < 0, a NULL history, a NULL piece with n > 0, a NULL out with an output due).         */
+long vad_resample_stream_ready(int src, int dst, long g);
+int  vad_resample_stream_history(int src, int dst);
+long vad_resample_stream_host(int src, int dst, long g, const int16_t *history, const int16_t *in, long n, float *out, int16_t *history_out);
 /* The device route: pcm = DEVICE [n][ld] at rate src, elem_size 2 or 4; lens[r] = live samples of row r, a device-visible table
  * (device or page-locked memory, like vad_upload_rows' row table) that must stay valid until the stream has passed the call;
  * dst_buf = DEVICE float32 [n][ldd], ldd >= width_out.  Sample m of row r is the sum above for m < ceil(N lens[r] / O) and exactly

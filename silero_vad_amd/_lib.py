@@ -99,6 +99,10 @@ SYMBOLS = {
     "vad_pump_submit_wide_packets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
     "vad_pump_wide_phase": (c_int, [c_void_p, c_int]),
     "vad_decimate": (c_long, [c_int, c_int, c_void_p, c_long, c_void_p]),
+    "vad_pump_set_resample": (c_int, [c_void_p, POINTER(c_int), c_int]),
+    "vad_pump_resample_slot": (c_void_p, [c_void_p, c_int]),
+    "vad_pump_submit_resampled_packets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
+    "vad_pump_resample_state": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_long), POINTER(c_long)]),
     "vad_pump_play_compact": (c_long, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_long, c_int, c_int, c_void_p, c_long,
                                        POINTER(PumpStats)]),
     "vad_pump_poll": (c_long, [c_void_p, c_int, c_void_p, c_long, POINTER(c_int)]),
@@ -179,6 +183,9 @@ SYMBOLS = {
     "vad_resample_length": (c_long, [c_int, c_int, c_long]),
     "vad_resample_table": (c_int, [c_int, c_int, c_void_p, c_void_p]),
     "vad_resample_host": (c_int, [c_int, c_int, c_void_p, c_size_t, c_long, c_void_p]),
+    "vad_resample_stream_ready": (c_long, [c_int, c_int, c_long]),
+    "vad_resample_stream_history": (c_int, [c_int, c_int]),
+    "vad_resample_stream_host": (c_long, [c_int, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "vad_resample_reserve": (c_int, [c_void_p, c_int, c_int]),
     "vad_resample_rows_device": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_void_p]),
     "vad_refill_schedule": (c_int, [POINTER(c_long), c_long, c_long, POINTER(c_long), POINTER(c_long)]),

@@ -239,7 +239,14 @@ struct ResampleHostTable {                   // the one source of the table: tap
     ResampleGeom g;
     std::vector<float> taps;
     std::vector<int32_t> first;
+    // the STREAMING rule (vad_resample_stream_*): end[j] = first[j] - W + K, the inputs a stream must have received before output j of
+    // period 0 is emitted (output q N + j: q O + end[j]).  Filled only when the rule is a count -- end[] non-decreasing and end[N - 1] <=
+    // end[0] + O, so that the emitted outputs are always a prefix --; empty otherwise, and the pair then has no streaming form.
+    std::vector<int32_t> end;
+    int H = 0;                               // input samples of history a stream keeps: K - 1 (include/silero_vad_hip.h has the derivation)
 };
+// ready(g): the outputs a stream that has received g >= 0 inputs has emitted (t.end not empty).  64-bit throughout.
+long resample_stream_ready(const ResampleHostTable &t, long g);
 std::shared_ptr<const ResampleHostTable> resample_table(int src, int dst);      // null: the pair is not served; built once per process
 struct ResampleDeviceTable {
     ResampleGeom g;
@@ -250,6 +257,28 @@ struct ResampleDeviceTable {
 // (float32); lens: device-visible.  Input at and past lens[r] (clamped to ld) counts as zero whatever the batch holds.
 hipError_t launch_resample_rows(const ResampleDeviceTable &t, const void *pcm, int esz, long ld, const long *lens, long n, long width_out,
                                 float *dst, long ldd, hipStream_t s);
+// engine.hip: the pair's device table, made on first use and shared by the engine and its clones (what vad_resample_reserve puts there)
+int engine_resample_table(vad_engine *e, int src, int dst, ResampleDeviceTable *out);
+
+// A RESAMPLED packet tick of the pump (vad_pump_submit_resampled_packets; kernel_present.hip assemble_resampled_packets): int16 rows at
+// one of up to kMaxPumpRates source rates, brought to the net's rate by the streaming form of the filter above on their way into the
+// stream's fp32 carry / fp32 batch row.  The row table has kResampleRowWords int32 per row, every index computed and range-checked by
+// the host: {stream b, BYTE offset into `pkt` (a multiple of 16; VAD_ROW_SILENT: zeros), len | rate << kResampleRateShift, fp32 pending
+// c, base, j0, n_out, 0}.  The wave stages hist[b][0:H] ++ the row's len samples as floats in[0 : H + len); output i < n_out of the row
+// is phase j = (j0 + i) % N of period dq = (j0 + i) / N: sum_k taps[k][j] in[base + dq O + first[j] + k], fmaf in tap order from 0.0f --
+// the expression of resample_rows_kernel.  carry[b][0:c] ++ the outputs: c + n_out < 2 chunk; when they reach `chunk` the first `chunk`
+// become row b of `batch` and the rest the new carry.  hist[b] <- the last H staged samples.  hist: [streams][hist_ld] int16, carry and
+// batch: [streams][chunk] float.  max_len: the longest row the table may hold (sizes the LDS: (hist_ld + max_len + 2 chunk) floats).
+constexpr int kMaxPumpRates = 4;
+constexpr int kResampleRowWords = 8;
+constexpr int kResampleRateShift = 24;
+struct PumpRates {
+    const float *taps[kMaxPumpRates];        // TRANSPOSED, [K][N]
+    const int32_t *first[kMaxPumpRates];
+    int O[kMaxPumpRates], N[kMaxPumpRates], K[kMaxPumpRates], H[kMaxPumpRates];
+};
+hipError_t launch_assemble_resampled_packets(const int32_t *table, long n_rows, const uint8_t *pkt, const PumpRates &rates, int16_t *hist,
+                                             int hist_ld, int max_len, float *carry, float *batch, int chunk, hipStream_t s);
 
 // Segmenter on the device (kernel_scan.hip): lane i scans probs[i * ldp ...] (or probs[row_off[i] ...] if row_off is
 // not null), n_chunks[i] entries (or n_chunks_all if n_chunks is null), writes its segments to out[i * cap ...] and

@@ -1193,6 +1193,21 @@ int vad_resample_reserve(vad_engine *e, int src, int dst) {
     return resample_device_table(e, src, dst, &t);
 }
 
+extern "C++" {
+namespace vad {
+// (pump.hip: the pair's shared device table for the pump's resampled rows -- made on first use, owned by the engine's image)
+int engine_resample_table(vad_engine *e, int src, int dst, ResampleDeviceTable *out) {
+    if (!e || !out) return VAD_ERR_ARG;
+    if (e->host_only) return fail(e, VAD_ERR_NO_DEVICE, "host-only engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    const ResampleDeviceTable *t = nullptr;
+    if (int rc = resample_device_table(e, src, dst, &t)) return rc;
+    *out = *t;
+    return VAD_OK;
+}
+}  // namespace vad
+}
+
 int vad_resample_rows_device(vad_engine *e, int src, int dst, const void *pcm, size_t elem_size, long ld, const long *lens, long n,
                              long width_out, float *dst_buf, long ldd, void *stream) {
     if (!e) return VAD_ERR_ARG;

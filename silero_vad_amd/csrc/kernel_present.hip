@@ -31,7 +31,11 @@
 // Opus decoders) decimated to 16 kHz by the reference's rule x[::step] (utils_vad.py:39-42, :301-304) between their 16-byte loads and the
 // LDS row.  The comb's phase is carried per stream by the host and arrives in the row table.  Ticks of the other routes never take it.
 //
-// SILENT rows (VAD_ROW_SILENT, all four assembly kernels): a row that stands for `len` samples of digital silence and has no bytes in the
+// assemble_resampled_packets (resampled packet ticks, vad_pump_submit_resampled_packets): int16 rows at 44.1 / 24 / 22.05 kHz ... pass the
+// streaming form of kernel_resample.hip's polyphase filter on their way into the stream's fp32 chunk; the stream's last K - 1 input
+// samples and its fp32 pending outputs are carried on the device, every index comes from the host's row table.  Described at the kernel.
+//
+// SILENT rows (VAD_ROW_SILENT, every assembly kernel; the resampled one stages zeros in place of the row): a row that stands for `len` samples of digital silence and has no bytes in the
 // slot -- a lost packet, a DTX / comfort-noise period.  The table carries the marker where a payload row carries its offset: the offset
 // column (table[i].y) holds VAD_ROW_SILENT (-1), every payload offset is >= 0, and the length word keeps its fields (len, kCodecShift,
 // kCombShift) with the meanings they have; the host writes VAD_PCM_S16 into the codec field of a silent row, so a G.711 tick never
@@ -247,6 +251,75 @@ __global__ void __launch_bounds__(64) assemble_burst_kernel(const int4 *__restri
     if (at < fill) crow[lane] = *reinterpret_cast<const i16x8 *>(joined + at);
 }
 
+// assemble_resampled_packets (resampled packet ticks, vad_pump_submit_resampled_packets): int16 rows at 44.1 / 24 / 22.05 / ... kHz pass
+// the polyphase filter of kernel_resample.hip on their way into the stream's chunk -- the STREAMING form of that filter: a stream keeps
+// the last H = K - 1 input samples (hist, int16) and the outputs that do not fill a chunk yet (carry, fp32), and a row emits exactly the
+// outputs whose K inputs have all arrived.  One wave = one workgroup per row (the row's length, and with it the rounds of every loop,
+// differ from row to row; the barriers are the wave's own).  The host computed every index (device_api.hpp has the table): the wave
+//   1. stages hist[b] ++ row as floats in LDS (int16 / 32768 is exact; a silent row: zeros) and the fp32 carry behind them;
+//   2. makes the row's outputs, lane l the outputs l, l + 64, ...: acc = 0.0f; acc = fmaf(taps[k][j], in[k], acc), k = 0 ... K - 1 -- the
+//      expression and the tap order of resample_rows_kernel over the same transposed table, so every output carries the bits the batch
+//      kernel gives for the concatenated stream (consecutive lanes, consecutive phases: the tap loads are consecutive floats);
+//   3. writes the last H staged samples back as the new history (every lane read the old one in front of the first barrier);
+//   4. splices carry ++ outputs: if they reach `chunk` the first `chunk` go to the stream's fp32 batch row, the rest is the new carry.
+// All LDS is dynamic and moves as 32-bit words: in[hist_ld + max_len] ++ joined[2 chunk].  No atomics; nobody else touches the row's
+// history, carry or batch row (one row per stream and tick).
+constexpr int kResampleOutputsInFlight = 4;
+
+__global__ void __launch_bounds__(64) assemble_resampled_packets_kernel(const int4 *__restrict__ table, const uint8_t *__restrict__ pkt,
+                                                                        PumpRates R, int16_t *hist, int hist_ld, int max_len, float *carry,
+                                                                        float *__restrict__ batch, int chunk) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *in = lds, *joined = lds + hist_ld + max_len;
+    const int lane = threadIdx.x;
+    const int4 e0 = table[2 * (size_t)blockIdx.x], e1 = table[2 * (size_t)blockIdx.x + 1];
+    const int b = e0.x, off = e0.y, len = e0.z & ((1 << kResampleRateShift) - 1), r = e0.z >> kResampleRateShift, c = e0.w;
+    const int base = e1.x, j0 = e1.y, n_out = e1.z;
+    const int O = R.O[r], N = R.N[r], K = R.K[r], H = R.H[r];
+    const float *taps = R.taps[r];
+    const int32_t *first = R.first[r];
+    int16_t *hrow = hist + (size_t)b * hist_ld;
+    float *crow = carry + (size_t)b * chunk;
+    for (int s = lane; s < H; s += 64) in[s] = (float)hrow[s] * (1.0f / 32768.0f);
+    const i16x8 *src = reinterpret_cast<const i16x8 *>(pkt + off);              // (a silent row: never dereferenced)
+    for (int at = lane * 8; at < len; at += 64 * 8) {
+        i16x8 v = {};
+        if (off >= 0) v = __builtin_nontemporal_load(src + at / 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (at + j < len) in[H + at + j] = (float)v[j] * (1.0f / 32768.0f);
+    }
+    for (int s = lane; s < c; s += 64) joined[s] = crow[s];
+    __syncthreads();
+    // (kResampleOutputsInFlight outputs of a lane are made side by side -- each its own chain in tap order --: one wave is the whole
+    // workgroup, and the tap loads' latency is hidden by the lane's other chains, not by other waves; a slot behind the row's last output
+    // recomputes that output and is not stored)
+    for (int i0 = lane; i0 < n_out; i0 += 64 * kResampleOutputsInFlight) {
+        const float *x[kResampleOutputsInFlight], *h[kResampleOutputsInFlight];
+        float acc[kResampleOutputsInFlight];
+#pragma unroll
+        for (int u = 0; u < kResampleOutputsInFlight; ++u) {
+            const int t = j0 + min(i0 + 64 * u, n_out - 1), dq = t / N, j = t - dq * N;
+            x[u] = in + (base + dq * O + first[j]);
+            h[u] = taps + j;
+            acc[u] = 0.0f;
+        }
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int u = 0; u < kResampleOutputsInFlight; ++u) acc[u] = fmaf(h[u][(long)k * N], x[u][k], acc[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kResampleOutputsInFlight; ++u)
+            if (i0 + 64 * u < n_out) joined[c + i0 + 64 * u] = acc[u];
+    }
+    for (int s = lane; s < H; s += 64) hrow[s] = (int16_t)(in[len + s] * 32768.0f);     // (exact: the staged values are n / 32768)
+    __syncthreads();
+    const int total = c + n_out, done = total >= chunk ? chunk : 0;           // done == chunk: a chunk is complete, the rest is the new carry
+    if (done)
+        for (int s = lane; s < chunk; s += 64) batch[(size_t)b * chunk + s] = joined[s];
+    for (int s = (done ? 0 : c) + lane; s < total - done; s += 64) crow[s] = joined[done + s];
+}
+
 // one thread per (sub-step j >= 1, stream): flags[j - 1][b] = k[b] > j
 __global__ void __launch_bounds__(256) burst_flags_kernel(const uint8_t *__restrict__ k_of_stream, uint8_t *__restrict__ flags, long ld, int streams) {
     const int b = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y + 1;
@@ -299,6 +372,18 @@ hipError_t launch_assemble_wide_packets(const int32_t *table, long n_rows, const
     const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
     hipLaunchKernelGGL(assemble_wide_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
                        reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_resampled_packets(const int32_t *table, long n_rows, const uint8_t *pkt, const PumpRates &rates, int16_t *hist,
+                                             int hist_ld, int max_len, float *carry, float *batch, int chunk, hipStream_t s) {
+    if (n_rows <= 0) return hipSuccess;
+    const size_t lds = ((size_t)hist_ld + (size_t)max_len + 2 * (size_t)chunk) * sizeof(float);
+    if (!table || !pkt || !hist || !carry || !batch || chunk <= 0 || hist_ld <= 0 || hist_ld % 4 || max_len <= 0 || max_len % 8 || lds > 65536 ||
+        n_rows > 0x7fffffffL)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(assemble_resampled_packets_kernel, dim3((unsigned)n_rows), dim3(64), lds, s, reinterpret_cast<const int4 *>(table), pkt,
+                       rates, hist, hist_ld, max_len, carry, batch, chunk);
     return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 // poison the whole 2 W + O window through 0 * NaN.  That is not emulated.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <memory>
@@ -108,10 +109,34 @@ std::shared_ptr<const ResampleHostTable> build_table(int src, int dst) {
     const long span = (long)(kResampleTile - 1) * O / N + 1 + (dhi - dlo) + K;
     if (span * (long)sizeof(float) > 65536) return nullptr;
     t->g.span = (int)span;
+    // the streaming rule: output q N + j is emitted once q O + end[j] inputs have arrived.  It is a COUNT only if that figure never
+    // falls from one output to the next, inside a period and across its boundary; every pair within the caps passes (tests/test_pump_resample.py)
+    bool counts = true;
+    for (long j = 0; j < N; ++j) {
+        const long e = lo[(size_t)j] - W + K;
+        counts = counts && (j == 0 || e >= lo[(size_t)j - 1] - W + K);
+    }
+    counts = counts && lo[(size_t)N - 1] <= lo[0] + O;
+    if (counts) {
+        t->end.resize((size_t)N);
+        for (long j = 0; j < N; ++j) t->end[(size_t)j] = (int32_t)(lo[(size_t)j] - W + K);
+        t->H = (int)K - 1;
+    }
     return t;
 }
 
 }  // namespace
+
+// Periods q < full are complete at g (q O + end[N - 1] <= g); the few behind them (end[N - 1] - end[0] <= O: at most two) are counted
+// phase by phase.  q O never leaves 64 bits for g up to 2^62.
+long resample_stream_ready(const ResampleHostTable &t, long g) {
+    const long O = t.g.O, N = t.g.N, e_min = t.end.front(), e_max = t.end.back();
+    const long full = g >= e_max ? (g - e_max) / O + 1 : 0;
+    long n = full * N;
+    for (long q = full; q * O + e_min <= g; ++q)
+        n += std::upper_bound(t.end.begin(), t.end.end(), g - q * O) - t.end.begin();
+    return n;
+}
 
 std::shared_ptr<const ResampleHostTable> resample_table(int src, int dst) {
     std::lock_guard<std::mutex> g(g_table_mutex);
@@ -235,6 +260,52 @@ int vad_resample_host(int src, int dst, const void *pcm, size_t elem_size, long 
         out[m] = (float)acc;
     }
     return VAD_OK;
+}
+
+long vad_resample_stream_ready(int src, int dst, long g) {
+    auto t = vad::resample_table(src, dst);
+    if (!t || t->end.empty()) return -VAD_ERR_SAMPLE_RATE;
+    if (g < 0) return -VAD_ERR_ARG;
+    return vad::resample_stream_ready(*t, g);
+}
+
+int vad_resample_stream_history(int src, int dst) {
+    auto t = vad::resample_table(src, dst);
+    if (!t || t->end.empty()) return -VAD_ERR_SAMPLE_RATE;
+    return t->H;
+}
+
+long vad_resample_stream_host(int src, int dst, long g, const int16_t *history, const int16_t *in, long n, float *out, int16_t *history_out) {
+    auto t = vad::resample_table(src, dst);
+    if (!t || t->end.empty()) return -VAD_ERR_SAMPLE_RATE;
+    if (g < 0 || n < 0 || !history || (n > 0 && !in)) return -VAD_ERR_ARG;
+    const long O = t->g.O, N = t->g.N, W = t->g.W, K = t->g.K, H = t->H;
+    // whole periods that are complete at g leave both counters: the rule is periodic from there on (ready(g + O) = ready(g) + N once
+    // g + O >= end[N - 1]), and what is left of g stays below end[N - 1] + O
+    const long periods = g >= t->end.back() ? (g - t->end.back()) / O : 0;
+    const long g0 = g - periods * O;
+    const long m0 = vad::resample_stream_ready(*t, g0), m1 = vad::resample_stream_ready(*t, g0 + n);
+    if (m1 > m0 && !out) return -VAD_ERR_ARG;
+    for (long m = m0; m < m1; ++m) {
+        const long q = m / N, j = m - q * N;
+        const long p0 = q * O + t->first[(size_t)j] - W;             // >= g0 - H: the output was not ready at g0
+        const float *h = t->taps.data() + j * K;
+        double acc = 0.0;
+        for (long k = 0; k < K; ++k) {
+            const long p = p0 + k;
+            const int16_t x = p >= g0 ? in[p - g0] : history[H - (g0 - p)];
+            acc += (double)h[k] * ((double)x / 32768.0);
+        }
+        out[m - m0] = (float)acc;
+    }
+    if (history_out) {                                               // the last H samples of history ++ in (history_out may be history)
+        if (n >= H) std::copy(in + (n - H), in + n, history_out);
+        else {
+            std::copy(history + n, history + H, history_out);        // (forward, onto lower addresses: safe in place)
+            std::copy(in, in + n, history_out + (H - n));
+        }
+    }
+    return m1 - m0;
 }
 
 }  // extern "C"

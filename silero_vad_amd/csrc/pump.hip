@@ -63,6 +63,17 @@
 // the batch row.  The carry holds decimated int16: a stream may change route from tick to tick.  Still ONE copy per tick; everything
 // behind the assembly is the masked tick, bit for bit.
 //
+// RESAMPLED packet ticks (vad_pump_set_resample + vad_pump_submit_resampled_packets): voice-agent and speech-synthesis APIs deliver 24 kHz
+// PCM, desktop and browser capture 44.1 / 22.05 kHz.  A third page-locked ring of resample slots ([row table, 32 bytes a row | flags |
+// streams * A int16], A = a chunk's input samples at the largest enabled rate) and its device landing buffers take int16 rows at up to
+// four source rates; the host runs the streaming rule of the resampler per row (kernel_resample.hip resample_stream_ready: a stream that
+// has received g inputs has emitted the outputs whose K inputs have all arrived), keeps each stream's bound rate, its input and output
+// counters less whole periods and its fp32 pending count, and writes every index the kernel needs into the row table;
+// kernel_present.hip assemble_resampled_packets runs the filter over history ++ row, splices the outputs behind the stream's fp32 carry
+// and fills the ONE fp32 batch (compute stream only, like d_more), which the masked step then reads with elem_size 4.  A stream is
+// BOUND to its rate from its first resampled row to vad_pump_open / vad_pump_close, and while it is, every other route refuses it: the
+// int16 carry and the fp32 carry never hold samples of one stream at once.  Still ONE copy per tick.
+//
 // Waits block.  A source thread of a real server sleeps in its socket; the source threads of vad_pump_play, and its server loop, spin
 // for at most 20 us on the counter they wait for and then sleep on it (futex), whatever the CPU budget: one of eight ranks under a
 // 16-CPU quota has two CPUs for a server loop, a source thread and the HIP runtime's own threads, and a spinning (or yielding) thread
@@ -156,6 +167,26 @@ struct vad_pump {
     std::vector<uint8_t> w_step, w_phase;        // [streams] the step of the stream's last wide row (0: none yet) and its comb phase (host bookkeeping)
     struct Comb { int32_t stream, now; uint8_t step, phase; };
     std::vector<Comb> w_new;                     // what each listed stream has pending, and its step and phase, after the tick
+    // resampled packet ticks (vad_pump_set_resample; n_rates == 0: not enabled, none of this is allocated)
+    int n_rates = 0;
+    int rates[vad::kMaxPumpRates] = {0, 0, 0, 0};                               // the enabled source rates, by rate index
+    std::shared_ptr<const vad::ResampleHostTable> r_tab[vad::kMaxPumpRates];    // their tables and streaming rules (host)
+    vad::PumpRates r_dev{};                      // ... and the engine's shared device images, as the kernel takes them
+    int r_A = 0, r_hld = 0;                      // input samples a row holds at most (one chunk at the largest rate, rounded up to 8); pitch of d_hist
+    // a resample slot / landing buffer: [rtab bytes: the row table, 32 bytes a row, ending where the flags start][hdr bytes: present[streams]]
+    // [streams][r_A] int16
+    size_t rtab = 0, res_bytes = 0;
+    uint8_t *h_res = nullptr;                    // [R] resample slots, page-locked
+    uint8_t *d_res = nullptr;                    // [NB] where a resampled tick's copy lands
+    float *d_fbatch = nullptr;                   // [streams][N] fp32: the chunks a resampled tick steps (compute stream only: one buffer)
+    float *d_fcarry = nullptr;                   // [streams][N] fp32: the outputs that wait for their chunk (in place)
+    int16_t *d_hist = nullptr;                   // [streams][r_hld] the last H input samples of every bound stream, zero before its first
+    std::vector<int8_t> r_rate;                  // [streams] the rate index a stream is bound to, -1: none (host bookkeeping, like held)
+    std::vector<long> r_g, r_m;                  // [streams] inputs received / outputs emitted, both less the same whole periods
+    std::vector<int32_t> r_pend;                 // [streams] fp32 outputs pending, 0 ... N - 1
+    long n_bound = 0;                            // streams with r_rate[b] >= 0: the other routes look for them only while this is not 0
+    struct Res { int32_t stream, pend; int8_t rate; long g, m; };
+    std::vector<Res> r_new;                      // what each listed stream carries after the tick
     // snapshot / restore (vad_pump_export_streams / vad_pump_import_streams; allocated by the first of them, none of it touched by a tick)
     int32_t *h_snap_tab = nullptr;               // [streams] x {slot, part, pending, record}: page-locked, mapped -- the kernels read it in place
     int32_t *d_snap_tab = nullptr;               // device alias of h_snap_tab
@@ -172,9 +203,18 @@ struct vad_pump {
     float *step_probs(int r, int j) const {      // host side; the device aliases have the same layout
         return j == 0 ? h_prob + (size_t)r * streams : h_prob_more + ((size_t)r * (max_burst - 1) + (j - 1)) * streams;
     }
+    uint8_t *res_present(int r) const { return h_res + (size_t)r * res_bytes + rtab; }
     void drop_held(int b) {
         n_held -= held[b] > 0;
         held[b] = 0;
+    }
+    bool bound(int b) const { return n_bound > 0 && r_rate[b] >= 0; }
+    void unbind(int b) {                         // (host side; the device history is zeroed by the caller, in compute-stream order)
+        if (!n_rates) return;
+        n_bound -= r_rate[b] >= 0;
+        r_rate[b] = -1;
+        r_g[b] = r_m[b] = 0;
+        r_pend[b] = 0;
     }
 };
 
@@ -340,6 +380,11 @@ void vad_pump_destroy(vad_pump *p) {
     if (p->h_prob_more) (void)hipHostFree(p->h_prob_more);
     if (p->d_wide) (void)hipFree(p->d_wide);
     if (p->h_wide) (void)hipHostFree(p->h_wide);
+    if (p->d_res) (void)hipFree(p->d_res);
+    if (p->h_res) (void)hipHostFree(p->h_res);
+    if (p->d_fbatch) (void)hipFree(p->d_fbatch);
+    if (p->d_fcarry) (void)hipFree(p->d_fcarry);
+    if (p->d_hist) (void)hipFree(p->d_hist);
     if (p->d_snap) (void)hipFree(p->d_snap);
     if (p->d_snap_parts) (void)hipFree(p->d_snap_parts);
     if (p->h_snap_tab) (void)hipHostFree(p->h_snap_tab);
@@ -485,7 +530,10 @@ struct Packets {
     bool burst = false;                          // vad_pump_submit_burst: a stream may have several rows, a row may be longer than N
     bool wide = false;                           // vad_pump_submit_wide_packets: int16 rows of the WIDE slot, sampled at step x 16 kHz
     const uint8_t *step = nullptr;               // ... the step per row, or null (every row at max_step)
+    bool res = false;                            // vad_pump_submit_resampled_packets: int16 rows of the RESAMPLE slot, at rates[rate of row]
+    const uint8_t *rate = nullptr;               // ... the rate index per row, or null (every row at rate 0)
 };
+const char *const kBoundWhy = "a stream that is bound to a resampled rate (vad_pump_submit_resampled_packets) until vad_pump_open / vad_pump_close";
 
 // Validate a packet tick's rows and write its row table (ending where slot r's flags start) and its flags (the streams that complete
 // a chunk).  -> the bytes of the slot's sample area the copy has to carry, or < 0 (VAD_ERR_ARG, p->err says why; nothing queued).
@@ -518,6 +566,7 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
         const int codec = pk.codec && !silent ? pk.codec[i] : VAD_PCM_S16;
         const long at = pk.coded ? off : 2L * off, bytes = codec == VAD_PCM_S16 ? 2L * len : len;      // the row, in bytes
         if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
+        else if (p->bound(b)) why = kBoundWhy;
         else if (len < 1 || len > N) why = "a packet length out of 1 ... N (a longer packet goes in over two ticks)";
         else if (!silent && (at < 0 || at % 16 || at + bytes > S * N * 2))
             why = pk.coded ? "a packet byte offset that is not a multiple of 16, or a row that runs past the slot"
@@ -564,6 +613,7 @@ long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps)
         const long at = pk.off[i], len = pk.len[i], bytes = (pk.codec ? pk.codec[i] : VAD_PCM_S16) == VAD_PCM_S16 ? 2 * len : len;
         const bool silent = at == VAD_ROW_SILENT;
         if (b < 0 || b >= S) why = "a stream out of range";
+        else if (p->bound(b)) why = kBoundWhy;
         else if (len < 1) why = "a row length below 1";
         else if (!silent && (at < 0 || at % 16 || at + bytes > S * N * 2)) why = "a row byte offset that is not a multiple of 16, or a row that runs past the slot";
         else {
@@ -628,6 +678,7 @@ long build_wide(vad_pump *p, int r, const Packets &pk, long n_rows) {
         const bool silent = at == VAD_ROW_SILENT;
         if (step < 1 || step > M) why = "a step out of 1 ... max_step";
         else if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
+        else if (p->bound(b)) why = kBoundWhy;
         else if (len < 1 || len > step * N) why = "a row length out of 1 ... step * N (a longer row goes in over two ticks)";
         else if (!silent && (at < 0 || at % 16 || at + 2 * len > area)) why = "a row byte offset that is not a multiple of 16, or a row that runs past the wide slot";
         else {
@@ -641,6 +692,65 @@ long build_wide(vad_pump *p, int r, const Packets &pk, long n_rows) {
         }
     }
     for (long k = 0; k < i; ++k)                 // (only valid streams were marked)
+        if (pk.stream[k] >= 0 && pk.stream[k] < S) p->seen[pk.stream[k]] = 0;
+    if (why) {
+        std::memset(fl, 0, (size_t)S);
+        return pfail(p, VAD_ERR_ARG, fn + why), -1;
+    }
+    return end;
+}
+
+// The same for a resampled tick (vad_pump_submit_resampled_packets): the table (kResampleRowWords int32 a row, device_api.hpp) and the
+// flags go into RESAMPLE slot r.  Per row the host runs the streaming rule: with g inputs received and m outputs emitted (both less the
+// same whole periods) a row of len samples emits outputs m ... ready(g + len) - 1; the first of them is phase j0 = m % N of period
+// q0 = m / N, and input position p of the stream lies at p - (g - H) of the wave's staged history ++ row, so output i reads from
+// base + dq O + first[j], base = q0 O - W - g + H.  A stream completes a chunk when its fp32 pending outputs plus the row's reach the
+// chunk.  Nothing of the bookkeeping is touched: p->r_new holds it for the caller to apply once the tick is queued.  A SILENT row
+// stands for len input samples of silence: zeros enter the filter; no offset checks, no bytes of the copy.
+long build_resampled(vad_pump *p, int r, const Packets &pk, long n_rows) {
+    const long S = p->streams, N = p->N, A = p->r_A;
+    const std::string fn = "vad_pump_submit_resampled_packets: ";
+    if (!p->n_rates) return pfail(p, VAD_ERR_ARG, fn + "resampled rows are not enabled on this pump (vad_pump_set_resample)"), -1;
+    if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
+        return pfail(p, VAD_ERR_ARG, fn + "bad row list (a tick holds at most `streams` rows)"), -1;
+    uint8_t *fl = p->res_present(r);
+    int32_t *tab = reinterpret_cast<int32_t *>(fl) - vad::kResampleRowWords * n_rows;
+    std::memset(fl, 0, (size_t)S);
+    p->r_new.clear();
+    const long area = S * A * 2;                 // bytes of the resample slot's sample area
+    long end = 0, i = 0;
+    const char *why = nullptr;
+    for (; i < n_rows && !why; ++i) {
+        const int32_t b = pk.stream[i];
+        const long at = pk.off[i], len = pk.len[i], k = pk.rate ? pk.rate[i] : 0;
+        const bool silent = at == VAD_ROW_SILENT;
+        if (k >= p->n_rates) why = "a rate index out of 0 ... n_rates - 1";
+        else if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
+        else if (p->r_rate[b] >= 0 && p->r_rate[b] != k) why = "a row at another rate than the one the stream is bound to (vad_pump_open unbinds)";
+        else if (p->held[b] > 0) why = "a stream with int16 samples pending from another packet route";
+        else if (len < 1 || len > A) why = "a row length out of 1 ... the slot's samples per stream (a longer row goes in over two ticks)";
+        else if (!silent && (at < 0 || at % 16 || at + 2 * len > area)) why = "a row byte offset that is not a multiple of 16, or a row that runs past the resample slot";
+        else {
+            const vad::ResampleHostTable &t = *p->r_tab[k];
+            const bool is_bound = p->r_rate[b] >= 0;
+            const long g = is_bound ? p->r_g[b] : 0, m = is_bound ? p->r_m[b] : 0, c = is_bound ? p->r_pend[b] : 0;
+            const long m1 = vad::resample_stream_ready(t, g + len), n_out = m1 - m, total = c + n_out;
+            if (total >= 2 * N) {
+                why = "a row that would complete more than one chunk of its stream (submit it over two ticks)";
+                break;
+            }
+            p->seen[b] = 1;
+            const long O = t.g.O, Nr = t.g.N, q0 = m / Nr, j0 = m - q0 * Nr;
+            int32_t *e = tab + vad::kResampleRowWords * i;
+            e[0] = b, e[1] = (int32_t)at, e[2] = (int32_t)(len | k << vad::kResampleRateShift), e[3] = (int32_t)c;
+            e[4] = (int32_t)(q0 * O - t.g.W - g + t.H), e[5] = (int32_t)j0, e[6] = (int32_t)n_out, e[7] = 0;
+            fl[b] = total >= N;
+            const long periods = m1 / Nr;       // complete at g + len: they leave both counters (the rule is periodic behind them)
+            p->r_new.push_back(vad_pump::Res{b, (int32_t)(total >= N ? total - N : total), (int8_t)k, g + len - periods * O, m1 - periods * Nr});
+            if (!silent) end = std::max(end, (at + 2 * len + 15) / 16 * 16);
+        }
+    }
+    for (long k = 0; k < i && k < n_rows; ++k)   // (only valid streams were marked)
         if (pk.stream[k] >= 0 && pk.stream[k] < S) p->seen[pk.stream[k]] = 0;
     if (why) {
         std::memset(fl, 0, (size_t)S);
@@ -665,11 +775,12 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     bool g711 = false;                           // ... and it has a mu-law / A-law row
     int steps = 1;                               // a burst tick: the masked steps it runs
     if (pk) {
-        if ((pk_bytes = pk->wide    ? build_wide(p, r, *pk, n_rows)
+        if ((pk_bytes = pk->res     ? build_resampled(p, r, *pk, n_rows)
+                        : pk->wide  ? build_wide(p, r, *pk, n_rows)
                         : pk->burst ? build_burst(p, r, *pk, n_rows, &steps)
                                     : build_packets(p, r, *pk, n_rows, &g711)) < 0)
             return VAD_ERR_ARG;
-        present = pk->wide ? p->wide_present(r) : p->slot_present(r);      // (a wide tick's flags: copied to the slot's own row for vad_pump_poll)
+        present = pk->res ? p->res_present(r) : pk->wide ? p->wide_present(r) : p->slot_present(r);      // (a wide / resampled tick's flags: copied to the slot's own row for vad_pump_poll)
     } else if (rows != nullptr || n_rows != 0) {
         if (!rows || n_rows < 0 || n_rows > (long)S) return pfail(p, VAD_ERR_ARG, "vad_pump_submit_rows: bad row list");
         uint8_t *fl = p->slot_present(r);
@@ -694,6 +805,12 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
                 return pfail(p, VAD_ERR_ARG, "vad_pump_submit: stream " + std::to_string(b) +
                                                  " has samples pending from packets; its next chunk must arrive as packets");
     }
+    if (!pk && p->n_bound > 0) {                 // ... nor may a chunk enter a stream whose samples pass the resampler
+        for (size_t b = 0; b < S; ++b)
+            if (p->r_rate[b] >= 0 && (!masked || present[b]))
+                return pfail(p, VAD_ERR_ARG, "vad_pump_submit: stream " + std::to_string(b) + 
+                                                 " is bound to a resampled rate; until vad_pump_open / vad_pump_close its samples arrive as resampled rows");
+    }
     if (masked && present != p->slot_present(r)) std::memcpy(p->slot_present(r), present, S);
     uint8_t *dbuf = p->d_batch + (size_t)buf * p->slot_bytes + p->htab;
     int16_t *batch = reinterpret_cast<int16_t *>(dbuf + p->hpos + p->hdr);
@@ -706,7 +823,9 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
         // the position table: row of the slot that holds stream b's chunk (the i-th delivering stream's chunk is row i)
         const uint8_t *fl = p->slot_present(r);
         int32_t *pos = p->slot_pos(r);
-        if (pk && pk->wide) {
+        if (pk && pk->res) {
+            d_present = p->d_res + (size_t)buf * p->res_bytes + p->rtab;        // (its copy lands in the resample buffer, flags included)
+        } else if (pk && pk->wide) {
             d_present = p->d_wide + (size_t)buf * p->wide_bytes + p->wtab;      // (its copy lands in the wide buffer, flags included)
         } else if (pk) {
             // (no position table: the row table written with the flags lies over it)
@@ -737,14 +856,19 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     if (pk) {
         // ONE copy: row table + flags + the packets; the assembly pass on the compute stream splices the completing streams' rows out
         // of their carries and their packets (the carry's previous users and the batch buffer's previous readers are earlier there)
-        const size_t tab_bytes = (size_t)n_rows * 4 * sizeof(int32_t);
-        const uint8_t *h_fl = pk->wide ? p->wide_present(r) : p->slot_present(r);                  // the flags of the slot the rows lie in
-        uint8_t *d_fl = pk->wide ? p->d_wide + (size_t)buf * p->wide_bytes + p->wtab : cbuf + p->hpos;     // ... and of the buffer they land in
+        const size_t tab_bytes = (size_t)n_rows * (pk->res ? vad::kResampleRowWords : 4) * sizeof(int32_t);
+        const uint8_t *h_fl = pk->res ? p->res_present(r) : pk->wide ? p->wide_present(r) : p->slot_present(r);      // the flags of the slot the rows lie in
+        uint8_t *d_fl = pk->res    ? p->d_res + (size_t)buf * p->res_bytes + p->rtab                        // ... and of the buffer they land in
+                        : pk->wide ? p->d_wide + (size_t)buf * p->wide_bytes + p->wtab
+                                   : cbuf + p->hpos;
         TICK_TRY(hipMemcpyAsync(d_fl - tab_bytes, h_fl - tab_bytes, tab_bytes + p->hdr + pk_bytes, hipMemcpyHostToDevice, copy));
         TICK_TRY(hipEventRecord(p->h2d_done[buf][0], copy));
         TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));
         const int32_t *table = reinterpret_cast<const int32_t *>(d_fl - tab_bytes);
-        if (pk->wide) {                          // (the rows are decimated on the way; the carry holds 16 kHz samples)
+        if (pk->res) {                           // (the rows pass the filter on the way; the chunks are fp32, in the one fp32 batch)
+            TICK_TRY(vad::launch_assemble_resampled_packets(table, n_rows, d_fl + p->hdr, p->r_dev, p->d_hist, p->r_hld, p->r_A, p->d_fcarry,
+                                                            p->d_fbatch, p->N, p->compute));
+        } else if (pk->wide) {                   // (the rows are decimated on the way; the carry holds 16 kHz samples)
             TICK_TRY(vad::launch_assemble_wide_packets(table, n_rows, d_fl + p->hdr, p->d_carry, batch, p->N, p->compute));
         } else if (pk->burst) {                  // (chunk 0 of every stream into `batch`, chunks 1 ... into d_more; flags_j = k > j)
             TICK_TRY(vad::launch_assemble_burst(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->d_more, p->max_burst, p->streams, p->N,
@@ -783,7 +907,9 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
             const int n = p->hi[k] - p->lo[k];
             if (!compact) TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][k], 0));
             if (k > 0 && masked && !compact) TICK_TRY(hipStreamWaitEvent(p->compute, p->h2d_done[buf][0], 0));     // (the flags came with part 0)
-            const int rc = vad_step_present(p->eng, p->sr, n, rows_j + a * N, sizeof(int16_t), (long)N, ctx_in + a * C, ctx_out + a * C, p->d_state[k],
+            const bool f32 = pk && pk->res;      // (a resampled tick steps the fp32 batch; everything else about the step is the same)
+            const int rc = vad_step_present(p->eng, p->sr, n, f32 ? (const void *)(p->d_fbatch + a * N) : (const void *)(rows_j + a * N),
+                                            f32 ? sizeof(float) : sizeof(int16_t), (long)N, ctx_in + a * C, ctx_out + a * C, p->d_state[k],
                                             probs_j + a, masked ? flags_j + a : nullptr, p->compute);
             if (rc != VAD_OK) return broken(rc, std::string("vad_step_present: ") + vad_last_error(p->eng));
         }
@@ -791,7 +917,13 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     TICK_TRY(hipEventRecord(p->batch_free[buf], p->compute));
     TICK_TRY(hipEventRecord(p->tick_done[r], p->compute));
 #undef TICK_TRY
-    if (pk && pk->wide)                          // the pending counts and comb phases after this tick
+    if (pk && pk->res)                           // what every listed stream carries after this tick; its first row binds it to its rate
+        for (const vad_pump::Res &w : p->r_new) {
+            p->n_bound += p->r_rate[w.stream] < 0;
+            p->r_rate[w.stream] = w.rate;
+            p->r_g[w.stream] = w.g, p->r_m[w.stream] = w.m, p->r_pend[w.stream] = w.pend;
+        }
+    else if (pk && pk->wide)                     // the pending counts and comb phases after this tick
         for (const vad_pump::Comb &w : p->w_new) {
             p->n_held += (w.now > 0) - (p->held[w.stream] > 0);
             p->held[w.stream] = w.now;
@@ -953,6 +1085,100 @@ int vad_pump_wide_phase(const vad_pump *p, int stream) {
     return p->w_phase[stream];
 }
 
+int vad_pump_submit_resampled_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
+                                      const int32_t *len_of_row, const uint8_t *rate_of_row, long n_rows) {
+    Packets pk{stream_of_row, byte_off_of_row, len_of_row, true};
+    pk.res = true;
+    pk.rate = rate_of_row;
+    return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_pump_set_resample(vad_pump *p, const int *src_rates, int n_rates) {
+    if (!p) return VAD_ERR_ARG;
+    const std::string fn = "vad_pump_set_resample: ";
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (!src_rates || n_rates < 1 || n_rates > VAD_PUMP_MAX_RATES) return pfail(p, VAD_ERR_ARG, fn + "1 ... VAD_PUMP_MAX_RATES source rates");
+    if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, fn + "ticks in flight (retire them with vad_pump_poll first)");
+    std::shared_ptr<const vad::ResampleHostTable> tabs[vad::kMaxPumpRates];
+    long A = 0, hmax = 0;
+    for (int k = 0; k < n_rates; ++k) {
+        tabs[k] = vad::resample_table(src_rates[k], p->sr);
+        if (!tabs[k] || tabs[k]->end.empty())
+            return pfail(p, VAD_ERR_SAMPLE_RATE, fn + std::to_string(src_rates[k]) + " -> " + std::to_string(p->sr) + " Hz is not served (vad_resample_geometry)");
+        for (int q = 0; q < k; ++q)
+            if (src_rates[q] == src_rates[k]) return pfail(p, VAD_ERR_ARG, fn + "a rate listed twice");
+        A = std::max(A, ((long)p->N * tabs[k]->g.O + tabs[k]->g.N - 1) / tabs[k]->g.N);      // the input samples of one chunk
+        hmax = std::max(hmax, (long)tabs[k]->H);
+    }
+    A = (A + 7) / 8 * 8;
+    const long hld = (hmax + 7) / 8 * 8;
+    if ((size_t)(hld + A + 2 * p->N) * sizeof(float) > 65536)
+        return pfail(p, VAD_ERR_SAMPLE_RATE, fn + "a chunk of the largest rate and its history do not fit the assembly kernel's 64 KiB of LDS");
+    if (p->n_rates == n_rates && std::equal(src_rates, src_rates + n_rates, p->rates)) return VAD_OK;
+    PUMP_TRY(p, hipSetDevice(p->device));
+    PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    vad::PumpRates dev{};
+    for (int k = 0; k < n_rates; ++k) {          // the engine's shared tables (vad_resample_reserve): made once per pair and engine image
+        vad::ResampleDeviceTable t{};
+        if (const int rc = vad::engine_resample_table(p->eng, src_rates[k], p->sr, &t)) return pfail(p, rc, fn + vad_last_error(p->eng));
+        dev.taps[k] = t.taps, dev.first[k] = t.first;
+        dev.O[k] = t.g.O, dev.N[k] = t.g.N, dev.K[k] = t.g.K, dev.H[k] = tabs[k]->H;
+    }
+    auto drop = [&] {
+        if (p->d_res) (void)hipFree(p->d_res);
+        if (p->h_res) (void)hipHostFree(p->h_res);
+        if (p->d_fbatch) (void)hipFree(p->d_fbatch);
+        if (p->d_fcarry) (void)hipFree(p->d_fcarry);
+        if (p->d_hist) (void)hipFree(p->d_hist);
+        p->d_res = p->h_res = nullptr, p->d_fbatch = p->d_fcarry = nullptr, p->d_hist = nullptr;
+        p->n_rates = 0, p->n_bound = 0;
+    };
+    drop();                                      // (another set of rates: everything is made anew and every stream is unbound)
+    const size_t S = (size_t)p->streams, N = (size_t)p->N;
+    p->rtab = (S * vad::kResampleRowWords * sizeof(int32_t) + 4095) / 4096 * 4096;
+    p->res_bytes = p->rtab + p->hdr + S * (size_t)A * sizeof(int16_t);
+    // (a step computes every row, also the rows of streams that no resampled tick has filled yet: they hold a small constant, not digital
+    // silence -- see vad_pump_set_burst)
+    std::vector<float> quiet(S * N, 256.0f / 32768.0f);
+    const bool ok = hipHostMalloc((void **)&p->h_res, (size_t)p->R * p->res_bytes, hipHostMallocDefault) == hipSuccess &&
+                    hipMalloc((void **)&p->d_res, vad_pump::NB * p->res_bytes) == hipSuccess &&
+                    hipMalloc((void **)&p->d_fbatch, S * N * sizeof(float)) == hipSuccess &&
+                    hipMalloc((void **)&p->d_fcarry, S * N * sizeof(float)) == hipSuccess &&
+                    hipMalloc((void **)&p->d_hist, S * (size_t)hld * sizeof(int16_t)) == hipSuccess &&
+                    hipMemcpy(p->d_fbatch, quiet.data(), S * N * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemset(p->d_fcarry, 0, S * N * sizeof(float)) == hipSuccess &&
+                    hipMemset(p->d_hist, 0, S * (size_t)hld * sizeof(int16_t)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        drop();
+        (void)hipGetLastError();
+        return pfail(p, VAD_ERR_ALLOC, fn + "no memory for the resample slots");
+    }
+    std::memset(p->h_res, 0, (size_t)p->R * p->res_bytes);
+    for (int k = 0; k < n_rates; ++k) p->rates[k] = src_rates[k], p->r_tab[k] = tabs[k];
+    p->r_dev = dev;
+    p->r_A = (int)A, p->r_hld = (int)hld;
+    p->r_rate.assign(S, -1);
+    p->r_g.assign(S, 0);
+    p->r_m.assign(S, 0);
+    p->r_pend.assign(S, 0);
+    p->r_new.reserve(S);
+    p->n_rates = n_rates;
+    return VAD_OK;
+}
+
+uint8_t *vad_pump_resample_slot(vad_pump *p, int r) {
+    return (p && p->n_rates && r >= 0 && r < p->R) ? p->res_present(r) + p->hdr : nullptr;
+}
+
+int vad_pump_resample_state(const vad_pump *p, int stream, int *src_rate, long *inputs_mod, long *pending) {
+    if (!p || !p->n_rates || stream < 0 || stream >= p->streams) return VAD_ERR_ARG;
+    const int k = p->r_rate[stream];
+    if (src_rate) *src_rate = k < 0 ? 0 : p->rates[k];
+    if (inputs_mod) *inputs_mod = k < 0 ? 0 : p->r_g[stream];
+    if (pending) *pending = k < 0 ? 0 : p->r_pend[stream];
+    return VAD_OK;
+}
+
 long vad_decimate(int step, int phase, const int16_t *in, long n, int16_t *out) {
     if (step < 1 || phase < 0 || phase >= step || n < 0 || (n > 0 && (!in || !out))) return -VAD_ERR_ARG;
     long m = 0;
@@ -986,7 +1212,7 @@ long vad_deinterleave(int codec, int channels, int channel, const void *in, long
 
 long vad_pump_pending(const vad_pump *p, int stream) {
     if (!p || stream < 0 || stream >= p->streams) return -1;
-    return p->held[stream];
+    return p->bound(stream) ? p->r_pend[stream] : p->held[stream];      // (a bound stream's pending samples are its fp32 outputs)
 }
 
 long vad_pump_poll(vad_pump *p, int block, vad_iter_event *out, long cap, int *slot) {
@@ -1044,6 +1270,10 @@ int vad_pump_open(vad_pump *p, int stream) {
     PUMP_TRY(p, hipMemsetAsync(p->d_ctx[p->flips & 1] + (size_t)stream * p->C, 0, (size_t)p->C * sizeof(float), p->compute));
     p->drop_held(stream);                        // (the device carry needs nothing: the next packet tick's table says 0 samples pending)
     if (p->max_step) p->w_step[stream] = p->w_phase[stream] = 0;                // ... and the new stream's comb starts at its first sample
+    if (p->n_rates) {                            // ... it is bound to no rate, and its filter history is zeros: "inputs before 0 are zero"
+        PUMP_TRY(p, hipMemsetAsync(p->d_hist + (size_t)stream * p->r_hld, 0, (size_t)p->r_hld * sizeof(int16_t), p->compute));
+        p->unbind(stream);
+    }
     // ... and the host side (iterator state, active flag) when those ticks have been retired: their probabilities belong to the slot's
     // previous occupant and must neither advance the new stream's sample counter nor open a segment for it
     p->pending.push_back(vad_pump::Op{p->ticks, stream, true});
@@ -1060,6 +1290,11 @@ int vad_pump_close(vad_pump *p, int stream) {
     // the slot is still computed (lock-step batch) but emits no events -- from the next tick submitted on: the ticks in flight carry
     // chunks the stream did deliver, their events are still its own; samples it has pending are dropped
     p->drop_held(stream);
+    if (p->bound(stream)) {                      // (a resampled stream: unbound, its pending outputs dropped, its history zero for the slot's next user)
+        PUMP_TRY(p, hipSetDevice(p->device));
+        PUMP_TRY(p, hipMemsetAsync(p->d_hist + (size_t)stream * p->r_hld, 0, (size_t)p->r_hld * sizeof(int16_t), p->compute));
+        p->unbind(stream);
+    }
     p->pending.push_back(vad_pump::Op{p->ticks, stream, false});
     if (p->inflight.empty()) {
         p->retired = p->ticks;
@@ -1219,6 +1454,10 @@ int vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *b
     for (long k = 0; streams && k < i; ++k)      // (only valid slots were marked)
         if (streams[k] >= 0 && streams[k] < S) p->seen[streams[k]] = 0;
     if (bad) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
+    for (long k = 0; k < n && p->n_bound > 0; ++k)
+        if (p->r_rate[streams ? streams[k] : k] >= 0)
+            return pfail(p, VAD_ERR_ARG, fn + "stream " + std::to_string(streams ? streams[k] : k) + " is bound to a resampled rate: blob version 1 has no room for "
+                                                  "its fp32 pending outputs and filter history");
     uint8_t *rec = static_cast<uint8_t *>(blob) + sizeof(SnapHeader);
     if (n > 0) {
         if (const int rc = snap_reserve(p, (size_t)n * stride)) return rc;
@@ -1308,6 +1547,10 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         p->n_held += (f.pending > 0) - (p->held[b] > 0);
         p->held[b] = f.pending;
         if (p->max_step) p->w_step[b] = f.wide_step, p->w_phase[b] = f.wide_phase;
+        if (p->bound(b)) {                       // (the slot's previous stream was a resampled one: the imported stream is bound to no rate)
+            (void)hipMemsetAsync(p->d_hist + (size_t)b * p->r_hld, 0, (size_t)p->r_hld * sizeof(int16_t), p->compute);
+            p->unbind(b);
+        }
         p->src_pos[b] = 0;
     }
     return VAD_OK;

@@ -3108,6 +3108,51 @@ def resample(x, orig_freq: int, new_freq: int) -> np.ndarray:
     return out
 
 
+def resample_stream_ready(orig_freq: int, new_freq: int, n_in: int) -> int:
+    """ready(n_in) of the streaming resampler (vad_resample_stream_ready): the outputs a stream that has received n_in input samples has
+    emitted -- those whose K inputs have all arrived; nothing is zero-extended on the right, so `resample(x)[:ready(len(x))]` is what any
+    cut of x into pieces yields.  Exact for any n_in below 2^62."""
+    resample_geometry(orig_freq, new_freq)
+    if isinstance(n_in, (bool, np.bool_)) or not isinstance(n_in, (int, np.integer)) or not 0 <= n_in < 2 ** 62:
+        raise ValueError(f"n_in must be an integer in 0 ... 2^62 - 1, got {n_in!r}")
+    m = lib().vad_resample_stream_ready(int(orig_freq), int(new_freq), int(n_in))
+    if m < 0:
+        raise _lib.VadError(-m, "vad_resample_stream_ready")
+    return int(m)
+
+
+def resample_stream_history(orig_freq: int, new_freq: int) -> int:
+    """H of the pair (vad_resample_stream_history): the input samples a stream keeps between pieces, K - 1."""
+    resample_geometry(orig_freq, new_freq)
+    h = lib().vad_resample_stream_history(int(orig_freq), int(new_freq))
+    if h < 0:
+        raise _lib.VadError(-h, "vad_resample_stream_history")
+    return int(h)
+
+
+def resample_stream(x_new, orig_freq: int, new_freq: int, n_before: int, history):
+    """One piece of a stream through the streaming resampler on the host (vad_resample_stream_host, the CPU twin of the pump's resampled
+    rows): x_new = the piece, 1-D int16; n_before = the input samples the stream received before it; history = the last
+    `resample_stream_history` of them, oldest first, zeros where the stream has not lived that long (all zeros in front of the first
+    piece).  -> (outputs float32, the next piece's history int16): the outputs ready(n_before) ... ready(n_before + len(x_new)) - 1,
+    bit for bit those `resample` gives for the whole signal."""
+    H = resample_stream_history(orig_freq, new_freq)
+    x = np.ascontiguousarray(x_new)
+    hist = np.ascontiguousarray(history)
+    if x.dtype != np.int16 or x.ndim != 1:
+        raise ValueError(f"x_new must be a 1-D int16 array, got {x.dtype} of shape {x.shape}")
+    if hist.dtype != np.int16 or hist.shape != (H,):
+        raise ValueError(f"history must be an int16 array of {H} samples (resample_stream_history), got {hist.dtype} of shape {hist.shape}")
+    n0 = resample_stream_ready(orig_freq, new_freq, n_before)
+    out = np.empty(resample_stream_ready(orig_freq, new_freq, int(n_before) + x.size) - n0, np.float32)
+    nxt = np.empty(H, np.int16)
+    m = lib().vad_resample_stream_host(int(orig_freq), int(new_freq), int(n_before), hist.ctypes.data, x.ctypes.data if x.size else None, x.size,
+                                       out.ctypes.data if out.size else None, nxt.ctypes.data)
+    if m != out.size:
+        raise _lib.VadError(-m if m < 0 else 0, "vad_resample_stream_host")
+    return out, nxt
+
+
 def resample_device(engine, x_dev: torch.Tensor, lens, orig_freq: int, new_freq: int, out: torch.Tensor = None) -> torch.Tensor:
     """`resample` on the device, for a padded batch: x_dev [rows, L] (or 1-D: one row, and a 1-D result) int16 or float32 on the
     engine's GPU at orig_freq; lens: the live samples of each row (a sequence, or an int64 tensor -- on the device or pinned --; None:
@@ -3226,6 +3271,12 @@ class StreamPump:
     `submit_wide_packets(r, streams, lengths, steps)` are int16 samples at steps[i] x 16 kHz, and the device keeps every steps[i]-th one
     (the reference's `x[::step]`); the pump carries each stream's comb phase (`wide_phase(stream)`), events count 16 kHz samples.
 
+    44.1 / 24 / 22.05 / 11.025 kHz clients (voice-agent and speech-synthesis APIs, desktop and browser capture), or 48 kHz with
+    `read_audio`'s low-pass: after `pump.set_resample((44100, 24000))` the rows of `resample_slot(r)` + `submit_resampled_packets(r,
+    streams, lengths, rates)` (or `write_resampled_packets(r, [(stream, int16 samples, 44100), ...])`) are int16 samples at those rates
+    and the device resamples them per stream -- `resample_device`'s bits for the concatenated rows, whatever the packetisation; the pump
+    carries each stream's filter history and fp32 pending outputs (`resample_state(stream)`, `pending(stream)`).
+
     Moving live streams (a drain, a rebalancing between per-GPU ranks, a restart): with no tick in flight `blob = pump.export_streams([3, 7])`
     packs everything those streams carry into one uint8 array, `other.import_streams(blob, [0, 5])` puts the records into slots of any
     pump of the same sample rate (another GPU, another process), and `snapshot_info(blob)` reads a blob without a pump; the streams go
@@ -3276,7 +3327,7 @@ class StreamPump:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._slots = self._probs = self._present = self._probs_more = self._wide = None
+            self._slots = self._probs = self._present = self._probs_more = self._wide = self._res = None
             self._L.vad_pump_destroy(self._h)
             self._h = None
 
@@ -3552,6 +3603,102 @@ class StreamPump:
         if v < 0:
             raise ValueError(f"no such stream, or wideband is not enabled: {stream}")
         return int(v)
+
+    def set_resample(self, rates):
+        """Enable RESAMPLED packet ticks (vad_pump_set_resample): rows sampled at one of `rates` -- 1 ... 4 distinct source rates that
+        `resample_geometry(rate, the pump's rate)` serves, e.g. (44100, 24000, 22050) -- on a pump with no tick in flight.  Allocates the
+        resample slots ([streams * A] int16 each, A = the input samples of one chunk at the largest rate, rounded up to 8), their device
+        buffers, the fp32 batch and carry and every stream's filter history."""
+        rt = [r for r in rates]
+        if not 1 <= len(rt) <= 4 or not all(isinstance(r, (int, np.integer)) and not isinstance(r, (bool, np.bool_)) and 0 < r < 2 ** 31 for r in rt):
+            raise ValueError(f"rates must be 1 ... 4 (VAD_PUMP_MAX_RATES) positive integers, got {rates!r}")
+        arr = (ctypes.c_int * len(rt))(*[int(r) for r in rt])
+        self._check(self._L.vad_pump_set_resample(self._h, arr, len(rt)))
+        self.resample_rates = tuple(int(r) for r in rt)
+        self.resample_row = max(-(-self.n * resample_geometry(r, self.sr)[0] // resample_geometry(r, self.sr)[1]) for r in rt)
+        self.resample_row = (self.resample_row + 7) // 8 * 8
+        nbytes = self.streams * self.resample_row * 2
+        self._res = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_resample_slot(self._h, r), ctypes.POINTER(ctypes.c_uint8)),
+                                           shape=(nbytes,)) for r in range(self.ring_slots)]
+
+    def resample_slot(self, r: int) -> np.ndarray:
+        """Resample slot r's sample area as one flat uint8 array of streams * resample_row * 2 bytes (page-locked): where a resampled
+        tick's rows go."""
+        if getattr(self, "_res", None) is None:
+            raise ValueError("resampled rows are not enabled on this pump (set_resample)")
+        return self._res[r]
+
+    def submit_resampled_packets(self, r: int, streams, lengths, rates=None, byte_offsets=None):
+        """A RESAMPLED packet tick (vad_pump_submit_resampled_packets; needs `set_resample`): row i of `resample_slot(r)` holds lengths[i]
+        int16 INPUT samples (1 ... resample_row) of stream streams[i], sampled at resample_rates[rates[i]] Hz (rate INDICES; None = every
+        row at resample_rates[0]), at byte offset byte_offsets[i] (a multiple of 16; None = the rows back to back, each rounded up to 16
+        bytes).  The device runs the streaming resampler (`resample_stream`'s rule, `resample_device`'s bits) and appends the outputs
+        that are ready to what the stream has pending; a stream whose pending outputs reach N is stepped on the first N of them.  A
+        stream binds to the rate of its first row until `open_stream` / `close_stream`; while bound, every other submit route refuses
+        it.  A bad rate index, stream, length or offset, a row at another rate than the stream's, a stream with int16 samples pending,
+        or a row that would complete two chunks raises and queues nothing.
+        byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] input samples of silence (see `submit_packets`): zeros enter the
+        filter.  With byte_offsets=None every row has a payload."""
+        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
+        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
+        rt = None
+        if rates is not None:
+            rt = np.asarray(rates)
+            if rt.ndim != 1 or (rt.size and (not np.issubdtype(rt.dtype, np.integer) or rt.min() < 0 or rt.max() > 255)):
+                raise ValueError(f"rates must be a 1-D sequence of rate indices (uint8 values), got {rt.dtype} of shape {rt.shape}")
+            rt = np.ascontiguousarray(rt, dtype=np.uint8)
+        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (rt is not None and len(rt) != len(st)):
+            raise ValueError(f"streams, lengths, rates and byte_offsets must have one entry per row, got {len(st)}, {len(ln)}, "
+                             f"{len(st) if rt is None else len(rt)}, {len(st) if off is None else len(off)}")
+        if off is None:
+            off = np.zeros(len(st), np.int32)
+            if len(st):
+                off[1:] = np.cumsum((ln[:-1].astype(np.int64) * 2 + 15) // 16 * 16)
+        n = len(st)
+        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [rt.ctypes.data if n and rt is not None else None]
+        self._check(self._L.vad_pump_submit_resampled_packets(self._h, int(r), *ptrs, n))
+
+    def write_resampled_packets(self, r: int, packets):
+        """Pack [(stream, int16 samples, rate) | (stream, int16 samples), ...] back to back (each rounded up to 16 bytes) into
+        `resample_slot(r)` and submit the resampled tick, mirroring `write_packets`: `rate` is one of `resample_rates` in Hz (left out:
+        resample_rates[0]).  An int in place of the samples, `(stream, 441, 44100)`, is a silent row of that many input samples."""
+        area = self.resample_slot(r)
+        packets = [pk if len(pk) == 3 else (pk[0], pk[1], self.resample_rates[0]) for pk in packets]
+        for _, x, rate in packets:                               # (the rates and the silent rows first: nothing is written when one is bad)
+            if rate not in self.resample_rates:
+                raise ValueError(f"rate {rate!r} is none of the pump's resample_rates {self.resample_rates}")
+            n = _silent_len(x)
+            if n is not None and n > self.resample_row:
+                raise ValueError(f"a row holds 1 ... {self.resample_row} samples, got {n} (submit a longer one over two ticks)")
+        streams, lengths, rates, offsets, at = [], [], [], [], 0
+        for s, x, rate in packets:
+            rates.append(self.resample_rates.index(rate))
+            if _silent_len(x) is not None:
+                streams.append(s)
+                lengths.append(int(x))
+                offsets.append(ROW_SILENT)
+                continue
+            x = np.asarray(x)
+            if x.dtype != np.int16 or x.ndim != 1:
+                raise ValueError("a row must be a 1-D int16 array")
+            if not 1 <= len(x) <= self.resample_row:
+                raise ValueError(f"a row holds 1 ... {self.resample_row} samples, got {len(x)} (submit a longer one over two ticks)")
+            if at + x.nbytes > len(area):
+                raise ValueError("the rows do not fit into the slot")
+            area[at:at + x.nbytes] = x.view(np.uint8)
+            streams.append(s)
+            lengths.append(len(x))
+            offsets.append(at)
+            at += (x.nbytes + 15) // 16 * 16
+        self.submit_resampled_packets(r, streams, lengths, np.array(rates, np.uint8), offsets)
+
+    def resample_state(self, stream: int):
+        """(rate the stream is bound to in Hz or 0, its input samples received less O * (outputs emitted // N), its fp32 outputs pending)
+        of `stream` (vad_pump_resample_state; host bookkeeping, no synchronisation)."""
+        rate, g, c = ctypes.c_int(), ctypes.c_long(), ctypes.c_long()
+        if self._L.vad_pump_resample_state(self._h, int(stream), ctypes.byref(rate), ctypes.byref(g), ctypes.byref(c)):
+            raise ValueError(f"no such stream, or resampled rows are not enabled: {stream}")
+        return rate.value, g.value, c.value
 
     def burst_steps(self, r: int) -> int:
         """The sub-steps slot r's last tick ran: max(1, the most chunks a stream completed) for a burst tick, 1 for any other."""
