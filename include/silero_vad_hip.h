@@ -628,7 +628,8 @@ int  vad_pump_wide_phase(const vad_pump *p, int stream);
  * zeros enter the filter (the outputs are not zeros while the history rings out), no bytes of the slot, no offset checks; bit for bit
  * a payload row of int16 zeros.
  * SNAPSHOTS.  vad_pump_export_streams refuses (VAD_ERR_ARG, with a message) a stream that is bound to a rate: blob version 1 has no room
- * for an fp32 carry and a history.  vad_pump_import_streams into a slot leaves it unbound.                                             */
+ * for an fp32 carry and a history.  vad_pump_export_streams_v2 writes blob version 2, which carries them with the rate and the counters,
+ * and vad_pump_import_streams binds the slot a bound record enters; a version 1 record, or an unbound one, leaves its slot unbound.     */
 #define VAD_PUMP_MAX_RATES 4
 int  vad_pump_set_resample(vad_pump *p, const int *src_rates, int n_rates);
 uint8_t *vad_pump_resample_slot(vad_pump *p, int r);
@@ -692,9 +693,42 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * A record does not name the slot it came from.  Reserved bytes are written as zero and a reader refuses a record in which they are not;
  * samples behind `pending` are written as zero and ignored when read.  Two exports with no tick between them are byte for byte the same.
  * NOT carried: ticks in flight (there are none: see below), the position counter of the vad_pump_play* helpers (it restarts as after
- * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), and the model weights.                   */
+ * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), and the model weights.
+ *
+ * THE BLOB (version 2) carries, in addition, what a stream that is BOUND to a resampled rate holds (vad_pump_submit_resampled_packets):
+ * its rate, its two counters, its fp32 pending outputs and its filter history.  vad_pump_export_streams_v2 writes it, for bound and
+ * unbound streams alike; vad_pump_export_streams goes on writing version 1.
+ *   header, VAD_SNAPSHOT_HEADER_BYTES_V2 = 96:
+ *      0  the 64 bytes of the version 1 header, with version = VAD_SNAPSHOT_VERSION_2, header_bytes = 96 and
+ *         stride = the version 1 stride + 32 + 4 * N + 2 * 160 = 3072 / 4736, a multiple of 16
+ *     64  uint8   reserved[32]   zero
+ *   then n_records records of `stride` bytes, each:
+ *      0  the version 1 record, unchanged (S1 = the version 1 stride, 1696 / 2336 bytes)
+ *     S1  vad_resample_info (32 bytes, below)
+ *     S1 + 32        float32 carry[N]       the outputs that wait for their chunk, carry[0 : pending_out]; everything behind them is +0.0f
+ *     S1 + 32 + 4 N  int16   history[160]   the last H = vad_resample_stream_history(src_rate, sr) INPUT samples at src_rate, oldest
+ *                                           first, zeros where the stream has not lived that long: history[0 : H]; everything behind
+ *                                           them is ZERO.  VAD_SNAPSHOT_HISTORY = 160 holds every served pair's H (K <= 160 in
+ *                                           vad_resample_geometry, H = K - 1) and does not depend on the rates either pump enabled.
+ * src_rate is in Hz, never a rate index: the destination may have enabled its rates in another order.  A record of a stream that is
+ * bound to no rate has src_rate = 0 and an all-zero tail behind its version 1 part, and that part is byte for byte the version 1 record.
+ * The fields of a record with src_rate != 0, as the submit path produces them and as every reader demands them (O, N_r = the pair's O and
+ * N of vad_resample_geometry(src_rate, sr), ready = vad_resample_stream_ready(src_rate, sr, .)):
+ *   src_rate     a pair (src_rate, sr) with a streaming form: vad_resample_stream_history(src_rate, sr) >= 0
+ *   pending_out  0 ... N - 1 (N = the chunk)
+ *   outputs_mod  0 ... N_r - 1: the outputs emitted, less whole periods
+ *   inputs_mod   >= 0 with ready(inputs_mod) == outputs_mod -- the inputs received less O per dropped period; since ready(g) >= N_r from
+ *                the g on at which period 0 is complete, this also bounds it: inputs_mod < the smallest g with ready(g) == N_r (<= the
+ *                latency + O)
+ *   vad_stream_info.pending == 0: a bound stream has no int16 samples pending (BINDING above)
+ *   reserved bytes zero; carry[pending_out : N] all bits zero; history[H : 160] zero
+ * and with src_rate == 0 every other byte of the tail is zero.  A version 1 layout that merely says version 2 is refused: header_bytes
+ * and stride differ.                                                                                                                */
 #define VAD_SNAPSHOT_VERSION 1
 #define VAD_SNAPSHOT_HEADER_BYTES 64
+#define VAD_SNAPSHOT_VERSION_2 2
+#define VAD_SNAPSHOT_HEADER_BYTES_V2 96
+#define VAD_SNAPSHOT_HISTORY 160
 typedef struct vad_stream_info {
     int64_t current_sample;      /* VADIterator.current_sample: samples stepped since vad_pump_open; >= 0                            */
     int64_t temp_end;            /* VADIterator.temp_end: 0 ... current_sample                                                       */
@@ -705,8 +739,17 @@ typedef struct vad_stream_info {
     uint8_t wide_phase;          /* its comb phase (vad_pump_wide_phase), 0 ... max(1, wide_step) - 1                                */
     uint8_t reserved[8];         /* zero                                                                                             */
 } vad_stream_info;
-/* Bytes of a blob of n records at sample rate sr: 64 + n * stride.  0 for a bad sr or n < 0.  Host only.                            */
+typedef struct vad_resample_info {   /* the host's part of a version 2 record's tail; the ranges are stated above                        */
+    int32_t src_rate;            /* the rate the stream is bound to, in Hz; 0: none, and everything below is zero                    */
+    int32_t pending_out;         /* c: fp32 outputs that wait for their chunk (vad_pump_pending of a bound stream)                   */
+    int64_t inputs_mod;          /* g: input samples received, less whole periods (vad_pump_resample_state)                          */
+    int64_t outputs_mod;         /* m: outputs emitted, less the same whole periods                                                  */
+    uint8_t reserved[8];         /* zero                                                                                             */
+} vad_resample_info;
+/* Bytes of a blob of n records at sample rate sr: 64 + n * stride.  0 for a bad sr or n < 0.  Host only.  _v2: 96 + n * the version 2
+ * stride.                                                                                                                           */
 size_t vad_pump_snapshot_bytes(int sr, long n);
+size_t vad_pump_snapshot_bytes_v2(int sr, long n);
 /* EXPORT: the records of streams[0 ... n - 1] (distinct slots; NULL = every slot in ascending order, and n must be the pump's stream
  * count) into blob[0 : vad_pump_snapshot_bytes(sr, n)], ordinary host memory of `cap` bytes.  Read-only: the pump and the exported
  * streams go on exactly as if the call had not happened; the caller closes them when it wants to.  Synchronous: the blob is complete on
@@ -726,14 +769,28 @@ size_t vad_pump_snapshot_bytes(int sr, long n);
  * the host before a value from it can steer a device address or a loop bound); a sample rate other than the pump's
  * (VAD_ERR_SAMPLE_RATE); a record index out of range, a slot out of range or listed twice, a record with wide_step >= 2 for a pump
  * whose wideband max_step is smaller (a pump without wideband included) (VAD_ERR_ARG).  A record with wide_step 1 enters a pump
- * without wideband as a stream that never had a wide row: a step-1 comb has no phase to lose.                                       */
+ * without wideband as a stream that never had a wide row: a step-1 comb has no phase to lose.
+ * RESAMPLED STREAMS.  vad_pump_export_streams writes version 1 and refuses a stream that is bound to a rate (VAD_ERR_ARG).
+ * vad_pump_export_streams_v2: the same call with the same rules -- idle pump, read-only, synchronous, one gather kernel, one copy -- into
+ * blob[0 : vad_pump_snapshot_bytes_v2(sr, n)], version 2, bound and unbound streams alike, on a pump with or without the resampled route.
+ * vad_pump_import_streams takes both versions.  A version 1 record, and a version 2 record with src_rate == 0, leave the slot bound to
+ * no rate (a slot that was bound is unbound and its history zeroed, as by vad_pump_open).  A version 2 record with src_rate != 0
+ * replaces, besides everything above, the slot's whole resampled state: the binding (to the index src_rate has among the DESTINATION's
+ * rates) and the counters g, m, c on the host; the whole fp32 carry row and the whole history row, at the destination's own pitch, on the
+ * device -- zeros behind c and behind H whatever the blob and the slot held before.  Refused in addition, with nothing queued and
+ * nothing changed (VAD_ERR_ARG): a record whose src_rate is not among the destination's enabled rates (a pump without the route
+ * included), and -- already by vad_snapshot_inspect -- any field outside the ranges stated with the layout.                          */
 int  vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap);
+int  vad_pump_export_streams_v2(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap);
 int  vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const int32_t *records, const int32_t *streams, long n);
-/* Readers of a blob; host only, no pump and no device needed.  vad_snapshot_inspect: validate ALL of blob[0 : nbytes] (header and every
- * record's fields) -> VAD_OK and *n_records, *sr (either may be NULL), or VAD_ERR_ARG.  vad_snapshot_stream: record i of a valid blob
- * -> *info, h[128], c[128], ctx[C], pending[N] (any may be NULL); VAD_ERR_ARG for an invalid blob or i out of range.                */
+/* Readers of a blob of either version; host only, no pump and no device needed.  vad_snapshot_inspect: validate ALL of blob[0 : nbytes]
+ * (header and every record's fields; version 2: also every byte that has to be zero) -> VAD_OK and *n_records, *sr (either may be
+ * NULL), or VAD_ERR_ARG.  vad_snapshot_stream: the version 1 part of record i of a valid blob -> *info, h[128], c[128], ctx[C],
+ * pending[N] (any may be NULL); VAD_ERR_ARG for an invalid blob or i out of range.  vad_snapshot_resample: the tail of record i ->
+ * *info, carry[N], history[VAD_SNAPSHOT_HISTORY] (any may be NULL); a version 1 blob has no tail: all three come back zero.          */
 int  vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr);
 int  vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info *info, float *h, float *c, float *ctx, int16_t *pending);
+int  vad_snapshot_resample(const void *blob, size_t nbytes, long i, vad_resample_info *info, float *carry, int16_t *history);
 
 /* The whole loop in one native call -- for tests, benchmarks and file-fed servers: stream b plays rows[b * ld ...] circularly with
  * period `period` samples (a multiple of N): at tick t its chunk is rows[b * ld + (t * N) % period ...].  `fill_threads` SOURCE

@@ -55,6 +55,12 @@ class StreamInfo(Structure):
                 ("triggered", ctypes.c_uint8), ("wide_step", ctypes.c_uint8), ("wide_phase", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 8)]
 
 
+class ResampleInfo(Structure):
+    """vad_resample_info: the host's part of a version 2 snapshot record's tail (a stream bound to a resampled rate)."""
+    _fields_ = [("src_rate", ctypes.c_int32), ("pending_out", ctypes.c_int32), ("inputs_mod", c_int64), ("outputs_mod", c_int64),
+                ("reserved", ctypes.c_uint8 * 8)]
+
+
 # every symbol include/silero_vad_hip.h declares: name -> (restype, argtypes)
 f32p, i16p = POINTER(c_float), POINTER(c_int16)
 SYMBOLS = {
@@ -115,6 +121,9 @@ SYMBOLS = {
     "vad_pump_import_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_long]),
     "vad_snapshot_inspect": (c_int, [c_void_p, c_size_t, POINTER(c_long), POINTER(c_int)]),
     "vad_snapshot_stream": (c_int, [c_void_p, c_size_t, c_long, POINTER(StreamInfo), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vad_pump_snapshot_bytes_v2": (c_size_t, [c_int, c_long]),
+    "vad_pump_export_streams_v2": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_size_t]),
+    "vad_snapshot_resample": (c_int, [c_void_p, c_size_t, c_long, POINTER(ResampleInfo), c_void_p, c_void_p]),
     "vad_pump_play": (c_long, [c_void_p, c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_void_p, c_long, POINTER(PumpStats)]),
     "vad_forward_audio": (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_long, c_void_p, c_void_p,
                                   c_void_p, c_long, c_void_p]),

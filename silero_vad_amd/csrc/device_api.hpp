@@ -164,6 +164,19 @@ hipError_t launch_snapshot_gather(const int32_t *table, long n, const SnapPart *
                                   uint8_t *records, hipStream_t s);
 hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, int N, int C,
                                    const uint8_t *records, hipStream_t s);
+// Blob version 2 (vad_pump_export_streams_v2): the same records followed by the tail of a stream that is bound to a resampled rate --
+// 32 bytes of vad_resample_info (the host's), float carry[N], int16 history[kSnapHistory]; 32 + 4 * (256 + C) + 2 * N + 32 + 4 * N + 2 *
+// kSnapHistory bytes each.  The table has TWO int4 per record: the entry above and {fp32 pending c (0 ... N - 1), H (0 ... hist_ld and
+// kSnapHistory), bound 0 / 1, 0}.  gather2: a bound stream's tail <- zeros, fcarry[b][0:c] ++ zeros, hist[b][0:H] ++ zeros; an unbound
+// stream's tail <- zeros.  scatter2: a bound record writes fcarry[b][0:N] = the record's first c floats ++ zeros and hist[b][0:hist_ld] =
+// its first H samples ++ zeros; an unbound record leaves both rows alone.  fcarry: [streams][N] float, hist: [streams][hist_ld] int16,
+// hist_ld a multiple of 8 (the pump's own pitch: the record's is always kSnapHistory); both null on a pump without the resampled route,
+// whose table may hold no bound entry.
+constexpr int kSnapHistory = 160;            // == kResampleMaxTaps: H = K - 1 of every served pair fits
+hipError_t launch_snapshot_gather2(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, const float *fcarry,
+                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s);
+hipError_t launch_snapshot_scatter2(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, float *fcarry, int16_t *hist,
+                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s);
 
 // The comb of the reference's decimation x[::step] (src/silero_vad/utils_vad.py:39-42) over a stream that arrives in pieces: input sample g
 // of the stream is kept iff g % step == 0; `phase` = (samples that came before the piece) % step.  The one definition the pump's

@@ -52,7 +52,7 @@ long gcd_l(long a, long b) {
 }
 
 std::mutex g_table_mutex;
-std::map<std::pair<int, int>, std::shared_ptr<const ResampleHostTable>> g_tables;     // (src, dst) -> table; null: pair not served
+std::map<std::pair<int, int>, std::shared_ptr<const ResampleHostTable>> g_tables;     // (src, dst) -> table, served pairs only
 
 std::shared_ptr<const ResampleHostTable> build_table(int src, int dst) {
     if ((dst != 8000 && dst != 16000) || src <= 0 || src == dst) return nullptr;
@@ -143,7 +143,9 @@ std::shared_ptr<const ResampleHostTable> resample_table(int src, int dst) {
     auto it = g_tables.find({src, dst});
     if (it != g_tables.end()) return it->second;
     auto t = build_table(src, dst);
-    g_tables[{src, dst}] = t;
+    // (a pair that is not served is not remembered: rates arrive from outside -- a snapshot blob names one per record -- and the pairs that
+    // ARE served are a bounded set, O and N at most kResampleMaxRatio against two net rates)
+    if (t) g_tables[{src, dst}] = t;
     return t;
 }
 

@@ -14,6 +14,16 @@
 // The work list is a table of int4 {slot, part, pending, record} the host writes into page-locked mapped memory (16 bytes a record,
 // read in place like the probabilities are written in place); every field of it was range-checked on the host.  HBM-bound byte movers
 // like expand_rows_kernel: ~19 MB for 8 192 streams at 16 kHz, a few microseconds.
+//
+// Blob version 2 (vad_pump_export_streams_v2) carries a stream that is BOUND to a resampled rate as well.  Its record is the version 1
+// record followed by a tail, and the gather2 / scatter2 kernels are the same wave walking further vectors of a longer record:
+//   [T, T + 2)  vad_resample_info: host bookkeeping like the info block   (T = the vectors of a version 1 record)
+//   [T + 2, T + 2 + N / 4)  the stream's row of the fp32 carry, [0:c] live   [.., .. + 20)  its filter history, int16[160], [0:H] live
+// The work list has TWO int4 per record there: the entry above and {c, H, bound, 0}.  An unbound stream's tail is zeros in a record and
+// its scatter leaves the fp32 carry and the history alone (vad_pump_open / close zeroed them); a bound stream's scatter writes the WHOLE
+// carry row and the WHOLE history row -- zeros behind c and behind H whatever the record and the slot held -- at the destination's own
+// history pitch, which need not be the source's.  The history lies at the start of its row, oldest sample first, where
+// assemble_resampled_packets (kernel_present.hip) reads and writes it.
 #include <hip/hip_runtime.h>
 
 #include "device_api.hpp"
@@ -37,6 +47,20 @@ __device__ inline i16x8 pending_vec(const i16x8 *__restrict__ row, int j, int pe
     }
     return s;
 }
+
+// the same for fp32 outputs: floats [4 j, 4 j + 4) of a row, +0.0f from float `live` on
+__device__ inline f32x4 live_vec(const f32x4 *__restrict__ row, int j, int live) {
+    f32x4 s = {};
+    if (4 * j < live) {
+        s = row[j];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * j + k >= live) s[k] = 0.0f;
+    }
+    return s;
+}
+
+constexpr int kTailInfoVec = 2, kTailHistVec = kSnapHistory / 8;     // 16-byte vectors of vad_resample_info and of history[160]
 
 __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_gather_kernel(const int4 *__restrict__ table, long n, const SnapPart *__restrict__ parts,
                                                                           const f32x4 *__restrict__ ctx, const i16x8 *__restrict__ carry, int cv, int nv,
@@ -85,9 +109,77 @@ __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_scatter_kernel(const
     }
 }
 
+// Version 2: the version 1 vectors exactly as above, then the tail.  t = {c, H, bound, 0} of the record's second table entry.
+__global__ void __launch_bounds__(64 * kSnapWaves) snapshot_gather2_kernel(const int4 *__restrict__ table, long n, const SnapPart *__restrict__ parts,
+                                                                           const f32x4 *__restrict__ ctx, const i16x8 *__restrict__ carry,
+                                                                           const f32x4 *__restrict__ fcarry, const i16x8 *__restrict__ hist, int cv, int nv,
+                                                                           int fv, int hv, f32x4 *__restrict__ rec) {
+    const long i = (long)blockIdx.x * kSnapWaves + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= n) return;
+    const int4 e = table[2 * i], t = table[2 * i + 1];
+    const SnapPart pt = parts[e.y];
+    const size_t row = (size_t)(e.x - pt.lo);
+    const f32x4 *h = reinterpret_cast<const f32x4 *>(pt.state + row * 128), *c = reinterpret_cast<const f32x4 *>(pt.state + ((size_t)pt.n + row) * 128);
+    const int v1 = kInfoVec + 2 * kStateVec + cv + nv, total = v1 + kTailInfoVec + fv + kTailHistVec;
+    const int live = t.z ? t.x : 0, H = t.z ? t.y : 0;         // (an unbound stream: fcarry / hist may be null, and are not read)
+    f32x4 *out = rec + (size_t)e.w * total;
+    for (int v = lane; v < total; v += 64) {
+        if (v >= v1) {                           // the tail: zeros for the host's block, the live carry, the live history
+            const int w = v - v1 - kTailInfoVec;
+            if (w >= fv) reinterpret_cast<i16x8 *>(out)[v] = pending_vec(hist + (size_t)e.x * hv, w - fv, H);
+            else out[v] = w >= 0 ? live_vec(fcarry + (size_t)e.x * fv, w, live) : f32x4{};
+            continue;
+        }
+        const int u = v - kInfoVec - 2 * kStateVec;
+        if (u >= cv) {
+            reinterpret_cast<i16x8 *>(out)[v] = pending_vec(carry + (size_t)e.x * nv, u - cv, e.z);
+            continue;
+        }
+        f32x4 x = {};
+        if (u >= 0) x = ctx[(size_t)e.x * cv + u];
+        else if (v >= kInfoVec + kStateVec) x = c[v - kInfoVec - kStateVec];
+        else if (v >= kInfoVec) x = h[v - kInfoVec];
+        out[v] = x;
+    }
+}
+
+// hv: the DESTINATION's history pitch in vectors.  A bound record writes carry vectors [0, fv) and history vectors [0, hv) of the slot.
+__global__ void __launch_bounds__(64 * kSnapWaves) snapshot_scatter2_kernel(const int4 *__restrict__ table, long n, const SnapPart *__restrict__ parts,
+                                                                            f32x4 *__restrict__ ctx, i16x8 *__restrict__ carry, f32x4 *__restrict__ fcarry,
+                                                                            i16x8 *__restrict__ hist, int cv, int nv, int fv, int hv,
+                                                                            const f32x4 *__restrict__ rec) {
+    const long i = (long)blockIdx.x * kSnapWaves + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= n) return;
+    const int4 e = table[2 * i], t = table[2 * i + 1];
+    const SnapPart pt = parts[e.y];
+    const size_t row = (size_t)(e.x - pt.lo);
+    f32x4 *h = reinterpret_cast<f32x4 *>(pt.state + row * 128), *c = reinterpret_cast<f32x4 *>(pt.state + ((size_t)pt.n + row) * 128);
+    const int v1 = kInfoVec + 2 * kStateVec + cv + nv, stride = v1 + kTailInfoVec + fv + kTailHistVec;
+    const f32x4 *in = rec + (size_t)e.w * stride;
+    for (int v = kInfoVec + lane; v < v1; v += 64) {
+        const int u = v - kInfoVec - 2 * kStateVec;
+        if (u >= cv) carry[(size_t)e.x * nv + (u - cv)] = pending_vec(reinterpret_cast<const i16x8 *>(in) + (kInfoVec + 2 * kStateVec + cv), u - cv, e.z);
+        else if (u >= 0) ctx[(size_t)e.x * cv + u] = in[v];
+        else if (v >= kInfoVec + kStateVec) c[v - kInfoVec - kStateVec] = in[v];
+        else h[v - kInfoVec] = in[v];
+    }
+    if (!t.z) return;                            // an unbound record: the slot's fp32 carry and history stay as they are
+    const f32x4 *in_carry = in + v1 + kTailInfoVec;
+    const i16x8 *in_hist = reinterpret_cast<const i16x8 *>(in_carry + fv);
+    for (int w = lane; w < fv + hv; w += 64) {
+        if (w < fv) fcarry[(size_t)e.x * fv + w] = live_vec(in_carry, w, t.x);
+        else hist[(size_t)e.x * hv + (w - fv)] = pending_vec(in_hist, w - fv, w - fv < kTailHistVec ? t.y : 0);
+    }
+}
+
 bool snap_args_ok(const int32_t *table, const SnapPart *parts, const void *ctx, const void *carry, int N, int C, const void *records) {
     return table && parts && ctx && carry && records && N > 0 && N % 8 == 0 && C > 0 && C % 4 == 0;
 }
+
+// (a pump without the resampled route has neither buffer: its table then holds no bound entry, and the kernels touch neither)
+bool snap_tail_ok(const void *fcarry, const void *hist, int hist_ld) { return (fcarry && hist && hist_ld > 0 && hist_ld % 8 == 0) || (!fcarry && !hist); }
 
 }  // namespace
 
@@ -107,6 +199,28 @@ hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart 
     if (!snap_args_ok(table, parts, ctx, carry, N, C, records)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(snapshot_scatter_kernel, dim3((unsigned)((n + kSnapWaves - 1) / kSnapWaves)), dim3(64 * kSnapWaves), 0, s,
                        reinterpret_cast<const int4 *>(table), n, parts, reinterpret_cast<f32x4 *>(ctx), reinterpret_cast<i16x8 *>(carry), C / 4, N / 8,
+                       reinterpret_cast<const f32x4 *>(records));
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_gather2(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, const float *fcarry,
+                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!snap_args_ok(table, parts, ctx, carry, N, C, records) || !snap_tail_ok(fcarry, hist, hist_ld)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(snapshot_gather2_kernel, dim3((unsigned)((n + kSnapWaves - 1) / kSnapWaves)), dim3(64 * kSnapWaves), 0, s,
+                       reinterpret_cast<const int4 *>(table), n, parts, reinterpret_cast<const f32x4 *>(ctx), reinterpret_cast<const i16x8 *>(carry),
+                       reinterpret_cast<const f32x4 *>(fcarry), reinterpret_cast<const i16x8 *>(hist), C / 4, N / 8, N / 4, hist ? hist_ld / 8 : 0,
+                       reinterpret_cast<f32x4 *>(records));
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_scatter2(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, float *fcarry, int16_t *hist,
+                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!snap_args_ok(table, parts, ctx, carry, N, C, records) || !snap_tail_ok(fcarry, hist, hist_ld)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(snapshot_scatter2_kernel, dim3((unsigned)((n + kSnapWaves - 1) / kSnapWaves)), dim3(64 * kSnapWaves), 0, s,
+                       reinterpret_cast<const int4 *>(table), n, parts, reinterpret_cast<f32x4 *>(ctx), reinterpret_cast<i16x8 *>(carry),
+                       reinterpret_cast<f32x4 *>(fcarry), reinterpret_cast<i16x8 *>(hist), C / 4, N / 8, N / 4, hist ? hist_ld / 8 : 0,
                        reinterpret_cast<const f32x4 *>(records));
     return hipGetLastError();
 }

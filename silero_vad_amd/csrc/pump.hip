@@ -189,6 +189,7 @@ struct vad_pump {
     std::vector<Res> r_new;                      // what each listed stream carries after the tick
     // snapshot / restore (vad_pump_export_streams / vad_pump_import_streams; allocated by the first of them, none of it touched by a tick)
     int32_t *h_snap_tab = nullptr;               // [streams] x {slot, part, pending, record}: page-locked, mapped -- the kernels read it in place
+                                                 // (room for 2 x 4 words a stream: a version 2 entry goes on with {fp32 pending, H, bound, 0})
     int32_t *d_snap_tab = nullptr;               // device alias of h_snap_tab
     vad::SnapPart *d_snap_parts = nullptr;       // [parts] each part's state block and first slot
     uint8_t *d_snap = nullptr;                   // the packed records on the device: what the one copy of a call carries
@@ -1334,9 +1335,53 @@ struct SnapHeader {
     double threshold, min_silence, pad;
 };
 static_assert(sizeof(SnapHeader) == VAD_SNAPSHOT_HEADER_BYTES && sizeof(vad_stream_info) == 32, "the blob layout is the documented one");
+static_assert(sizeof(vad_resample_info) == 32 && VAD_SNAPSHOT_HEADER_BYTES_V2 % 16 == 0 && vad::kSnapHistory == VAD_SNAPSHOT_HISTORY &&
+                  vad::kResampleMaxTaps <= VAD_SNAPSHOT_HISTORY,
+              "the version 2 tail is the documented one, and holds the history of every served pair");
 const char kSnapMagic[8] = {'S', 'V', 'A', 'D', 'S', 'N', 'A', 'P'};
 
 size_t snap_stride(int N, int C) { return sizeof(vad_stream_info) + (size_t)(2 * 128 + C) * sizeof(float) + (size_t)N * sizeof(int16_t); }
+// version 2: the version 1 record, then vad_resample_info, float carry[N], int16 history[VAD_SNAPSHOT_HISTORY]
+size_t snap_stride2(int N, int C) { return snap_stride(N, C) + sizeof(vad_resample_info) + (size_t)N * sizeof(float) + VAD_SNAPSHOT_HISTORY * sizeof(int16_t); }
+
+bool any_byte_set(const uint8_t *at, size_t n) {
+    uint8_t acc = 0;
+    for (size_t i = 0; i < n; ++i) acc |= at[i];
+    return acc != 0;
+}
+
+// The tail of a version 2 record whose version 1 part is `f` (all of it, like everything of a blob, is read through memcpy).  *last: the
+// pair looked up last, so that a blob of 8 192 records of a few rates takes the table's lock a few times.  *H: the pair's history.
+struct SnapPair {
+    int rate = 0;
+    std::shared_ptr<const vad::ResampleHostTable> tab;
+};
+const char *snap_tail_fault(const uint8_t *tail, const vad_stream_info &f, int sr, int N, SnapPair *last, vad_resample_info *out, int *H) {
+    vad_resample_info q;
+    std::memcpy(&q, tail, sizeof(q));
+    for (const uint8_t z : q.reserved)
+        if (z) return "reserved bytes that are not zero";
+    long c = 0;
+    *H = 0;
+    if (q.src_rate == 0) {
+        if (q.pending_out || q.inputs_mod || q.outputs_mod) return "resample counters of a stream that is bound to no rate";
+    } else {
+        if (q.src_rate != last->rate) last->rate = q.src_rate, last->tab = q.src_rate > 0 ? vad::resample_table(q.src_rate, sr) : nullptr;
+        if (!last->tab || last->tab->end.empty()) return "a src_rate that is not served for the blob's sample rate";
+        const vad::ResampleHostTable &t = *last->tab;
+        if (q.pending_out < 0 || q.pending_out >= N) return "pending_out out of 0 ... N - 1";
+        if (q.outputs_mod < 0 || q.outputs_mod >= t.g.N) return "outputs_mod out of 0 ... the pair's N - 1";
+        if (q.inputs_mod < 0 || q.inputs_mod >= t.end.back()) return "inputs_mod below 0, or so large that a whole period would be ready";
+        if (vad::resample_stream_ready(t, q.inputs_mod) != q.outputs_mod) return "outputs_mod is not what a stream of inputs_mod inputs has emitted";
+        if (f.pending != 0) return "a stream that is bound to a rate with int16 samples pending";
+        c = q.pending_out, *H = t.H;
+    }
+    const uint8_t *carry = tail + sizeof(q), *hist = carry + (size_t)N * sizeof(float);
+    if (any_byte_set(carry + (size_t)c * sizeof(float), (size_t)(N - c) * sizeof(float))) return "a float behind pending_out that is not +0.0f";
+    if (any_byte_set(hist + (size_t)*H * sizeof(int16_t), (size_t)(VAD_SNAPSHOT_HISTORY - *H) * sizeof(int16_t))) return "a history sample behind H that is not zero";
+    if (out) *out = q;
+    return nullptr;
+}
 
 const char *snap_info_fault(const vad_stream_info &f, int N) {
     if (f.pending < 0 || f.pending >= N) return "pending out of 0 ... N - 1";
@@ -1355,15 +1400,25 @@ const char *snap_check(const void *blob, size_t nbytes, SnapHeader *hd) {
     if (!blob || nbytes < sizeof(SnapHeader)) return "shorter than a header";
     std::memcpy(hd, blob, sizeof(SnapHeader));
     if (std::memcmp(hd->magic, kSnapMagic, sizeof(kSnapMagic)) != 0) return "not a snapshot (magic)";
-    if (hd->version != VAD_SNAPSHOT_VERSION || hd->header_bytes != sizeof(SnapHeader)) return "a version this library does not read";
+    const bool v2 = hd->version == VAD_SNAPSHOT_VERSION_2;
+    if ((hd->version != VAD_SNAPSHOT_VERSION && !v2) || hd->header_bytes != (v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader)))
+        return "a version this library does not read";
+    if (nbytes < hd->header_bytes) return "shorter than a header";
+    if (v2 && any_byte_set(static_cast<const uint8_t *>(blob) + sizeof(SnapHeader), VAD_SNAPSHOT_HEADER_BYTES_V2 - sizeof(SnapHeader)))
+        return "reserved bytes that are not zero";
     int N = 0, C = 0;
-    if (vad_geometry(hd->sr, &N, &C) != VAD_OK || hd->N != N || hd->C != C || hd->stride != snap_stride(N, C)) return "a sample rate / geometry that does not exist";
-    if (hd->n_records < 0 || (uint64_t)hd->n_records > (nbytes - sizeof(SnapHeader)) / hd->stride) return "shorter than its header claims";
-    const uint8_t *rec = static_cast<const uint8_t *>(blob) + sizeof(SnapHeader);
+    if (vad_geometry(hd->sr, &N, &C) != VAD_OK || hd->N != N || hd->C != C || hd->stride != (v2 ? snap_stride2(N, C) : snap_stride(N, C)))
+        return "a sample rate / geometry that does not exist";
+    if (hd->n_records < 0 || (uint64_t)hd->n_records > (nbytes - hd->header_bytes) / hd->stride) return "shorter than its header claims";
+    const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd->header_bytes;
+    SnapPair last;
     for (int64_t i = 0; i < hd->n_records; ++i) {
         vad_stream_info f;
         std::memcpy(&f, rec + (size_t)i * hd->stride, sizeof(f));
         if (const char *why = snap_info_fault(f, N)) return why;
+        int H = 0;
+        if (v2)
+            if (const char *why = snap_tail_fault(rec + (size_t)i * hd->stride + snap_stride(N, C), f, hd->sr, N, &last, nullptr, &H)) return why;
     }
     return nullptr;
 }
@@ -1379,7 +1434,7 @@ int snap_reserve(vad_pump *p, size_t bytes) {
         vad::SnapPart *dp = nullptr;
         std::vector<vad::SnapPart> parts;
         for (int k = 0; k < p->parts; ++k) parts.push_back(vad::SnapPart{p->d_state[k], p->lo[k], p->hi[k] - p->lo[k]});
-        const bool ok = hipHostMalloc((void **)&tab, (size_t)p->streams * 4 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess &&
+        const bool ok = hipHostMalloc((void **)&tab, (size_t)p->streams * 8 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess &&
                         hipHostGetDevicePointer(&dv, tab, 0) == hipSuccess && dv &&
                         hipMalloc((void **)&dp, parts.size() * sizeof(vad::SnapPart)) == hipSuccess &&
                         hipMemcpy(dp, parts.data(), parts.size() * sizeof(vad::SnapPart), hipMemcpyHostToDevice) == hipSuccess;
@@ -1406,6 +1461,73 @@ int snap_idle(vad_pump *p, const std::string &fn) {
     return VAD_OK;
 }
 
+// vad_pump_export_streams (v2 == false: blob version 1, the launch and the bytes it always had) and vad_pump_export_streams_v2
+int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap, bool v2) {
+    if (!p) return VAD_ERR_ARG;
+    const std::string fn = v2 ? "vad_pump_export_streams_v2: " : "vad_pump_export_streams: ";
+    if (const int rc = snap_idle(p, fn)) return rc;
+    const long S = p->streams;
+    if (n < 0 || n > S || (!streams && n != S && n != 0) || !blob) return pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count) or no blob");
+    const size_t head = v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader), tail = snap_stride(p->N, p->C);       // tail: where a version 2 record's begins
+    const size_t stride = v2 ? snap_stride2(p->N, p->C) : tail, need = head + (size_t)n * stride;
+    if (cap < need) return pfail(p, VAD_ERR_ARG, fn + "the blob needs vad_pump_snapshot_bytes" + (v2 ? "_v2" : "") + "(sr, n) bytes");
+    bool bad = false;
+    long i = 0;
+    for (; streams && i < n && !bad; ++i) {
+        const int32_t b = streams[i];
+        if (!(bad = b < 0 || b >= S || p->seen[b])) p->seen[b] = 1;
+    }
+    for (long k = 0; streams && k < i; ++k)      // (only valid slots were marked)
+        if (streams[k] >= 0 && streams[k] < S) p->seen[streams[k]] = 0;
+    if (bad) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
+    for (long k = 0; !v2 && k < n && p->n_bound > 0; ++k)
+        if (p->r_rate[streams ? streams[k] : k] >= 0)
+            return pfail(p, VAD_ERR_ARG, fn + "stream " + std::to_string(streams ? streams[k] : k) + " is bound to a resampled rate: blob version 1 has no room for "
+                                                  "its fp32 pending outputs and filter history (vad_pump_export_streams_v2 writes version 2)");
+    uint8_t *rec = static_cast<uint8_t *>(blob) + head;
+    if (n > 0) {
+        if (const int rc = snap_reserve(p, (size_t)n * stride)) return rc;
+        for (long k = 0; k < n; ++k) {
+            const int32_t b = streams ? streams[k] : (int32_t)k;
+            int32_t *e = p->h_snap_tab + (v2 ? 8 : 4) * k;
+            e[0] = b, e[1] = part_of(p, b), e[2] = p->held[b], e[3] = (int32_t)k;
+            if (v2) {
+                const bool is_bound = p->bound(b);
+                e[4] = is_bound ? p->r_pend[b] : 0, e[5] = is_bound ? p->r_tab[p->r_rate[b]]->H : 0, e[6] = is_bound, e[7] = 0;
+            }
+        }
+        // (read-only, behind everything the compute stream has run: a failure leaves the pump as it was)
+        if (v2)
+            PUMP_TRY(p, vad::launch_snapshot_gather2(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->d_fcarry, p->d_hist, p->r_hld,
+                                                     p->N, p->C, p->d_snap, p->compute));
+        else
+            PUMP_TRY(p, vad::launch_snapshot_gather(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute));
+        PUMP_TRY(p, hipMemcpyAsync(rec, p->d_snap, (size_t)n * stride, hipMemcpyDeviceToHost, p->compute));
+        PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    }
+    SnapHeader hd;
+    std::memcpy(hd.magic, kSnapMagic, sizeof(kSnapMagic));
+    hd.version = v2 ? VAD_SNAPSHOT_VERSION_2 : VAD_SNAPSHOT_VERSION, hd.header_bytes = (uint32_t)head;
+    hd.sr = p->sr, hd.N = p->N, hd.C = p->C, hd.stride = (uint32_t)stride, hd.n_records = n;
+    hd.threshold = p->threshold, hd.min_silence = p->min_silence, hd.pad = p->pad;
+    std::memcpy(blob, &hd, sizeof(hd));
+    std::memset(static_cast<uint8_t *>(blob) + sizeof(hd), 0, head - sizeof(hd));
+    for (long k = 0; k < n; ++k) {               // the host's part of a record (the gather left it zero)
+        const int32_t b = streams ? streams[k] : (int32_t)k;
+        vad_stream_info f{};
+        f.current_sample = p->current[b], f.temp_end = p->temp_end[b], f.pending = p->held[b];
+        f.active = p->active[b], f.triggered = p->triggered[b];
+        if (p->max_step) f.wide_step = p->w_step[b], f.wide_phase = p->w_phase[b];
+        std::memcpy(rec + (size_t)k * stride, &f, sizeof(f));
+        if (v2 && p->bound(b)) {
+            vad_resample_info q{};
+            q.src_rate = p->rates[p->r_rate[b]], q.pending_out = p->r_pend[b], q.inputs_mod = p->r_g[b], q.outputs_mod = p->r_m[b];
+            std::memcpy(rec + (size_t)k * stride + tail, &q, sizeof(q));
+        }
+    }
+    return VAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1414,6 +1536,12 @@ size_t vad_pump_snapshot_bytes(int sr, long n) {
     int N = 0, C = 0;
     if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
     return sizeof(SnapHeader) + (size_t)n * snap_stride(N, C);
+}
+
+size_t vad_pump_snapshot_bytes_v2(int sr, long n) {
+    int N = 0, C = 0;
+    if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
+    return VAD_SNAPSHOT_HEADER_BYTES_V2 + (size_t)n * snap_stride2(N, C);
 }
 
 int vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr) {
@@ -1427,7 +1555,7 @@ int vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *
 int vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info *info, float *h, float *c, float *ctx, int16_t *pending) {
     SnapHeader hd;
     if (snap_check(blob, nbytes, &hd) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
-    const uint8_t *rec = static_cast<const uint8_t *>(blob) + sizeof(SnapHeader) + (size_t)i * hd.stride;
+    const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)i * hd.stride;
     const size_t st = 128 * sizeof(float), cx = (size_t)hd.C * sizeof(float);
     if (info) std::memcpy(info, rec, sizeof(*info));
     if (h) std::memcpy(h, rec + sizeof(vad_stream_info), st);
@@ -1437,56 +1565,26 @@ int vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info
     return VAD_OK;
 }
 
-int vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) {
-    if (!p) return VAD_ERR_ARG;
-    const std::string fn = "vad_pump_export_streams: ";
-    if (const int rc = snap_idle(p, fn)) return rc;
-    const long S = p->streams;
-    if (n < 0 || n > S || (!streams && n != S && n != 0) || !blob) return pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count) or no blob");
-    const size_t stride = snap_stride(p->N, p->C), need = sizeof(SnapHeader) + (size_t)n * stride;
-    if (cap < need) return pfail(p, VAD_ERR_ARG, fn + "the blob needs vad_pump_snapshot_bytes(sr, n) bytes");
-    bool bad = false;
-    long i = 0;
-    for (; streams && i < n && !bad; ++i) {
-        const int32_t b = streams[i];
-        if (!(bad = b < 0 || b >= S || p->seen[b])) p->seen[b] = 1;
-    }
-    for (long k = 0; streams && k < i; ++k)      // (only valid slots were marked)
-        if (streams[k] >= 0 && streams[k] < S) p->seen[streams[k]] = 0;
-    if (bad) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
-    for (long k = 0; k < n && p->n_bound > 0; ++k)
-        if (p->r_rate[streams ? streams[k] : k] >= 0)
-            return pfail(p, VAD_ERR_ARG, fn + "stream " + std::to_string(streams ? streams[k] : k) + " is bound to a resampled rate: blob version 1 has no room for "
-                                                  "its fp32 pending outputs and filter history");
-    uint8_t *rec = static_cast<uint8_t *>(blob) + sizeof(SnapHeader);
-    if (n > 0) {
-        if (const int rc = snap_reserve(p, (size_t)n * stride)) return rc;
-        for (long k = 0; k < n; ++k) {
-            const int32_t b = streams ? streams[k] : (int32_t)k;
-            int32_t *e = p->h_snap_tab + 4 * k;
-            e[0] = b, e[1] = part_of(p, b), e[2] = p->held[b], e[3] = (int32_t)k;
-        }
-        // (read-only, behind everything the compute stream has run: a failure leaves the pump as it was)
-        PUMP_TRY(p, vad::launch_snapshot_gather(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute));
-        PUMP_TRY(p, hipMemcpyAsync(rec, p->d_snap, (size_t)n * stride, hipMemcpyDeviceToHost, p->compute));
-        PUMP_TRY(p, hipStreamSynchronize(p->compute));
-    }
+int vad_snapshot_resample(const void *blob, size_t nbytes, long i, vad_resample_info *info, float *carry, int16_t *history) {
     SnapHeader hd;
-    std::memcpy(hd.magic, kSnapMagic, sizeof(kSnapMagic));
-    hd.version = VAD_SNAPSHOT_VERSION, hd.header_bytes = sizeof(SnapHeader);
-    hd.sr = p->sr, hd.N = p->N, hd.C = p->C, hd.stride = (uint32_t)stride, hd.n_records = n;
-    hd.threshold = p->threshold, hd.min_silence = p->min_silence, hd.pad = p->pad;
-    std::memcpy(blob, &hd, sizeof(hd));
-    for (long k = 0; k < n; ++k) {               // the host's part of a record (the gather left it zero)
-        const int32_t b = streams ? streams[k] : (int32_t)k;
-        vad_stream_info f{};
-        f.current_sample = p->current[b], f.temp_end = p->temp_end[b], f.pending = p->held[b];
-        f.active = p->active[b], f.triggered = p->triggered[b];
-        if (p->max_step) f.wide_step = p->w_step[b], f.wide_phase = p->w_phase[b];
-        std::memcpy(rec + (size_t)k * stride, &f, sizeof(f));
+    if (snap_check(blob, nbytes, &hd) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
+    const size_t cb = (size_t)hd.N * sizeof(float), hb = VAD_SNAPSHOT_HISTORY * sizeof(int16_t);
+    if (hd.version != VAD_SNAPSHOT_VERSION_2) {  // (a version 1 record has no tail: the stream is bound to no rate)
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (carry) std::memset(carry, 0, cb);
+        if (history) std::memset(history, 0, hb);
+        return VAD_OK;
     }
+    const uint8_t *tail = static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)i * hd.stride + snap_stride(hd.N, hd.C);
+    if (info) std::memcpy(info, tail, sizeof(*info));
+    if (carry) std::memcpy(carry, tail + sizeof(vad_resample_info), cb);
+    if (history) std::memcpy(history, tail + sizeof(vad_resample_info) + cb, hb);
     return VAD_OK;
 }
+
+int vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) { return snap_export(p, streams, n, blob, cap, false); }
+
+int vad_pump_export_streams_v2(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) { return snap_export(p, streams, n, blob, cap, true); }
 
 int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const int32_t *records, const int32_t *streams, long n) {
     if (!p) return VAD_ERR_ARG;
@@ -1497,12 +1595,23 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
     if (hd.sr != p->sr) return pfail(p, VAD_ERR_SAMPLE_RATE, fn + "the blob's sample rate is not the pump's");
     const long S = p->streams;
     if (n < 0 || n > S || (n > 0 && !streams)) return pfail(p, VAD_ERR_ARG, fn + "bad slot list");
-    const uint8_t *rec = static_cast<const uint8_t *>(blob) + sizeof(SnapHeader);
+    const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd.header_bytes;
     const size_t stride = hd.stride;
+    const bool v2 = hd.version == VAD_SNAPSHOT_VERSION_2;
     auto info_of = [&](long r) {
         vad_stream_info f;
         std::memcpy(&f, rec + (size_t)r * stride, sizeof(f));
         return f;
+    };
+    auto tail_of = [&](long r) {                 // (version 1: no tail, bound to no rate)
+        vad_resample_info q{};
+        if (v2) std::memcpy(&q, rec + (size_t)r * stride + snap_stride(p->N, p->C), sizeof(q));
+        return q;
+    };
+    auto rate_index = [&](int src_rate) {        // among THIS pump's rates; -1: not enabled here
+        for (int k = 0; k < p->n_rates; ++k)
+            if (p->rates[k] == src_rate) return k;
+        return -1;
     };
     // everything is decided here, on the host, from values snap_check has range-checked: nothing is queued before the last check
     const char *why = nullptr;
@@ -1513,6 +1622,7 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         if (r < 0 || r >= hd.n_records) why = "a record index out of range";
         else if (b < 0 || b >= S || p->seen[b]) why = "a slot out of range, or listed twice";
         else if (info_of(r).wide_step >= 2 && info_of(r).wide_step > p->max_step) why = "a record of a 32 / 48 kHz stream, and the pump's wideband max_step is smaller (vad_pump_set_wideband)";
+        else if (tail_of(r).src_rate && rate_index(tail_of(r).src_rate) < 0) why = "a record of a stream that is bound to a rate this pump has not enabled (vad_pump_set_resample)";
         else {
             p->seen[b] = 1;
             first = std::min(first, r), last = std::max(last, r);
@@ -1526,14 +1636,21 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
     if (const int rc = snap_reserve(p, bytes)) return rc;
     for (long k = 0; k < n; ++k) {
         const long r = records ? records[k] : k;
-        int32_t *e = p->h_snap_tab + 4 * k;
+        int32_t *e = p->h_snap_tab + (v2 ? 8 : 4) * k;
         e[0] = streams[k], e[1] = part_of(p, streams[k]), e[2] = info_of(r).pending, e[3] = (int32_t)(r - first);
+        if (v2) {                                // (snap_check has held c and the pair against their ranges; H <= this pump's pitch: the rate is enabled here)
+            const vad_resample_info q = tail_of(r);
+            e[4] = q.pending_out, e[5] = q.src_rate ? p->r_tab[rate_index(q.src_rate)]->H : 0, e[6] = q.src_rate != 0, e[7] = 0;
+        }
     }
     // ONE copy: the records first ... last; the scatter behind it on the compute stream.  From the copy on a failure leaves slots
     // half-replaced: the pump says so from then on.
     const hipError_t rc = [&] {
         hipError_t e = hipMemcpyAsync(p->d_snap, rec + (size_t)first * stride, bytes, hipMemcpyHostToDevice, p->compute);
-        if (e == hipSuccess) e = vad::launch_snapshot_scatter(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute);
+        if (e == hipSuccess)
+            e = v2 ? vad::launch_snapshot_scatter2(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->d_fcarry, p->d_hist, p->r_hld, p->N,
+                                                   p->C, p->d_snap, p->compute)
+                   : vad::launch_snapshot_scatter(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute);
         return e == hipSuccess ? hipStreamSynchronize(p->compute) : e;
     }();
     if (rc != hipSuccess) {
@@ -1547,7 +1664,12 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         p->n_held += (f.pending > 0) - (p->held[b] > 0);
         p->held[b] = f.pending;
         if (p->max_step) p->w_step[b] = f.wide_step, p->w_phase[b] = f.wide_phase;
-        if (p->bound(b)) {                       // (the slot's previous stream was a resampled one: the imported stream is bound to no rate)
+        const vad_resample_info q = tail_of(records ? records[k] : k);
+        if (q.src_rate) {                        // a bound record: the scatter wrote the slot's whole carry and history rows
+            p->n_bound += p->r_rate[b] < 0;
+            p->r_rate[b] = (int8_t)rate_index(q.src_rate);
+            p->r_g[b] = (long)q.inputs_mod, p->r_m[b] = (long)q.outputs_mod, p->r_pend[b] = q.pending_out;
+        } else if (p->bound(b)) {                // (the slot's previous stream was a resampled one: the imported stream is bound to no rate)
             (void)hipMemsetAsync(p->d_hist + (size_t)b * p->r_hld, 0, (size_t)p->r_hld * sizeof(int16_t), p->compute);
             p->unbind(b);
         }

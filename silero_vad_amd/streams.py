@@ -3221,26 +3221,42 @@ def _distinct_slots(x, name) -> np.ndarray:
 
 
 def snapshot_info(blob) -> list:
-    """The records of a snapshot blob (`StreamPump.export_streams`), host only (vad_snapshot_inspect / vad_snapshot_stream): per record a
+    """The records of a snapshot blob (`StreamPump.export_streams`), host only (vad_snapshot_inspect validates it, once): per record a
     dict of the vad_stream_info fields (`active`, `triggered`, `temp_end`, `current_sample`, `pending`, `wide_step`, `wide_phase`) plus
-    `h` [128], `c` [128], `ctx` [C] float32 and `pending_samples` [N] int16 (zeros behind `pending`).  A blob the library refuses --
-    bad magic or version, truncated, a field out of range -- raises."""
+    `h` [128], `c` [128], `ctx` [C] float32 and `pending_samples` [N] int16 (zeros behind `pending`).  A record of a version 2 blob
+    (`export_streams(version=2)`) has a `resample` entry besides (what vad_snapshot_resample reads): a dict of `src_rate` (Hz; 0 = bound to no
+    rate), `pending_out`, `inputs_mod`, `outputs_mod`, `carry` (the pending_out fp32 outputs that wait for their chunk) and `history`
+    (the last H int16 inputs at src_rate, oldest first).  A blob the library refuses -- bad magic or version, truncated, a field out of
+    range -- raises."""
     a = _blob_bytes(blob)
     L = lib()
     n, sr = ctypes.c_long(), ctypes.c_int()
     rc = L.vad_snapshot_inspect(a.ctypes.data if a.size else None, a.size, ctypes.byref(n), ctypes.byref(sr))
     if rc:
         raise _lib.VadError(rc, "vad_snapshot_inspect: not a valid snapshot blob")
+    # The library has validated the WHOLE blob, once; the records are then read here from the documented layout.  (vad_snapshot_stream /
+    # vad_snapshot_resample validate the whole blob again on every call, as a C caller that reads one record wants: a loop over them
+    # would be quadratic in the blob, and a whole pump's version 2 blob is 39 MB.)
     N = chunk_size(sr.value)
+    C = N // 8
+    version, head = (int(v) for v in a[8:16].view("<u4"))
+    stride = int(a[28:32].view("<u4")[0])
+    s1 = 32 + 4 * (256 + C) + 2 * N                                # the version 1 part of a record
+    H_of = {0: 0}
     out = []
     for i in range(n.value):
-        f = _lib.StreamInfo()
-        h, c, x, pend = np.empty(128, np.float32), np.empty(128, np.float32), np.empty(N // 8, np.float32), np.empty(N, np.int16)
-        rc = L.vad_snapshot_stream(a.ctypes.data, a.size, i, ctypes.byref(f), h.ctypes.data, c.ctypes.data, x.ctypes.data, pend.ctypes.data)
-        if rc:
-            raise _lib.VadError(rc, "vad_snapshot_stream")
+        rec = a[head + i * stride:head + (i + 1) * stride]
+        f = _lib.StreamInfo.from_buffer_copy(rec[:32].tobytes())
         d = {k: int(getattr(f, k)) for k in ("active", "triggered", "temp_end", "current_sample", "pending", "wide_step", "wide_phase")}
-        d.update(h=h, c=c, ctx=x, pending_samples=pend)
+        d.update(h=rec[32:544].view("<f4").copy(), c=rec[544:1056].view("<f4").copy(), ctx=rec[1056:1056 + 4 * C].view("<f4").copy(),
+                 pending_samples=rec[1056 + 4 * C:s1].view("<i2").copy())
+        if version == 2:
+            q = _lib.ResampleInfo.from_buffer_copy(rec[s1:s1 + 32].tobytes())
+            if q.src_rate not in H_of:
+                H_of[q.src_rate] = L.vad_resample_stream_history(q.src_rate, sr.value)
+            carry, hist = rec[s1 + 32:s1 + 32 + 4 * N].view("<f4"), rec[s1 + 32 + 4 * N:stride].view("<i2")
+            d["resample"] = dict(src_rate=int(q.src_rate), pending_out=int(q.pending_out), inputs_mod=int(q.inputs_mod),
+                                 outputs_mod=int(q.outputs_mod), carry=carry[:q.pending_out].copy(), history=hist[:H_of[q.src_rate]].copy())
         out.append(d)
     return out
 
@@ -3280,7 +3296,7 @@ class StreamPump:
     Moving live streams (a drain, a rebalancing between per-GPU ranks, a restart): with no tick in flight `blob = pump.export_streams([3, 7])`
     packs everything those streams carry into one uint8 array, `other.import_streams(blob, [0, 5])` puts the records into slots of any
     pump of the same sample rate (another GPU, another process), and `snapshot_info(blob)` reads a blob without a pump; the streams go
-    on bit for bit.
+    on bit for bit.  `export_streams(..., version=2)` also moves streams that are bound to a resampled rate.
 
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
@@ -3741,22 +3757,30 @@ class StreamPump:
         self._check(self._L.vad_pump_state(self._h, int(stream), h.ctypes.data, c.ctypes.data, x.ctypes.data))
         return h, c, x
 
-    def export_streams(self, streams=None) -> np.ndarray:
+    def export_streams(self, streams=None, version: int = 1) -> np.ndarray:
         """Everything `streams` (distinct slots; None = every slot, ascending) carry, as one self-describing uint8 blob
         (vad_pump_export_streams; layout: include/silero_vad_hip.h): (h, c), the context the next tick reads, the pending samples, the
         comb step and phase, the iterator state and the open / closed flag.  Only with no tick in flight (poll them first).  Read-only:
-        the pump and the streams go on as if nothing had happened."""
+        the pump and the streams go on as if nothing had happened.
+        version=1 refuses a stream that is bound to a resampled rate; version=2 (vad_pump_export_streams_v2) writes the longer record
+        that also carries the rate, the resampler's counters, the fp32 pending outputs and the filter history, for bound and unbound
+        streams alike.  `import_streams` takes both."""
+        if isinstance(version, (bool, np.bool_)) or not isinstance(version, (int, np.integer)) or version not in (1, 2):
+            raise ValueError(f"version must be 1 or 2, got {version!r}")
         st = None if streams is None else _distinct_slots(streams, "streams")
         n = self.streams if st is None else len(st)
-        blob = np.zeros(int(self._L.vad_pump_snapshot_bytes(self.sr, n)), np.uint8)
-        self._check(self._L.vad_pump_export_streams(self._h, st.ctypes.data if st is not None and n else None, n, blob.ctypes.data, blob.size))
+        size, export = ((self._L.vad_pump_snapshot_bytes, self._L.vad_pump_export_streams) if version == 1 else
+                        (self._L.vad_pump_snapshot_bytes_v2, self._L.vad_pump_export_streams_v2))
+        blob = np.zeros(int(size(self.sr, n)), np.uint8)
+        self._check(export(self._h, st.ctypes.data if st is not None and n else None, n, blob.ctypes.data, blob.size))
         return blob
 
     def import_streams(self, blob, slots, records=None):
         """Record records[i] of `blob` (None = record i) replaces the whole carried state of slot slots[i] (vad_pump_import_streams); the
         stream continues bit for bit if this pump has the iterator parameters of the pump that wrote the blob.  Only with no tick in
-        flight.  A blob of another sample rate, a malformed blob, a bad record index or slot, or a 32 / 48 kHz stream for a pump without
-        that wideband step raises, and nothing has changed."""
+        flight.  A blob of another sample rate, a malformed blob, a bad record index or slot, a 32 / 48 kHz stream for a pump without
+        that wideband step, or (version 2) a stream bound to a rate that is none of this pump's `resample_rates` raises, and nothing
+        has changed.  A bound record binds its slot; every other record leaves its slot bound to no rate."""
         a = _blob_bytes(blob)
         sl = _distinct_slots(slots, "slots")
         rc = None if records is None else _int32_rows(records, "records")
