@@ -663,6 +663,62 @@ int  vad_pump_close(vad_pump *p, int stream);
 /* Test / migration hook: copy stream's carried h[128], c[128], ctx[C] to the host (any may be NULL).  Synchronises.        */
 int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
 
+/* THE TAPE: every stream's recent audio kept on the device, fetched by sample range.  The consumer of a VAD front end (an ASR or a
+ * diarisation model) wants the utterance behind an END event, at the rate and in the form the net heard it -- the reference's own flow is
+ * VADIterator events, then the slice audio[start:end].  On the packet routes the host never has that audio: G.711 rows are expanded on
+ * the device, 32 / 48 kHz rows are combed there at a phase only the pump knows, silent rows exist only as zeros spliced in there.  With a
+ * tape the pump keeps, per stream, a ring of the last `chunks` chunks it stepped the stream on -- written on the device as a side effect
+ * of every step of every route (full, masked, compact, rows, packets, coded, burst, wide), from the very rows the step kernels read --
+ * and copies any still-held sample range of any set of streams out, packed.
+ *
+ * THE CLOCK.  Two int64 counters per stream live on the device: `count`, the chunks stepped since the stream's clock started, and
+ * `floor`, the first chunk the tape can hold.  A stream that is stepped (its flag is set, or the tick has no flags) has its chunk taped
+ * into ring slot count % chunks and its count incremented; a stream that is absent from a step is untouched.  vad_pump_open zeroes both
+ * counters in compute-stream order, behind the ticks in flight, exactly as it zeroes (h, c): so for every open stream count * N is
+ * the iterator's current_sample at every tick boundary, and the sample numbers of the events ARE tape positions.  vad_pump_close
+ * changes nothing (a closed stream that a full tick still steps is taped; the next open restarts its clock).  vad_pump_import_streams
+ * into a pump with a tape sets count = floor = current_sample / N of the record: the clock continues, nothing before the import is held.
+ * Snapshot blobs do not carry the tape: versions 1 and 2 are unchanged, and a pump with a tape exports the bytes one without it does.
+ *
+ * THE WINDOW.  With held_lo = max(floor, count - chunks) * N and held_hi = count * N the tape holds the samples [held_lo, held_hi) of
+ * the stream's clock.  A request [start, end), start <= end, of ANY int64 values is confined to it:
+ *     first = min(max(start, held_lo), held_hi),  last = min(max(end, first), held_hi),  n = last - first
+ * (csrc/tape.hpp, the one source of the rule).  first > start: the head of the range is no longer held (or lies before the clock).
+ * vad_tape_window: the rule for given counters -> *first, *n.  Host only, re-entrant, no GPU.  VAD_ERR_ARG: start > end, chunks < 2,
+ * N < 1, count < 0, or counters whose product with N is no int64.
+ *
+ * vad_pump_set_tape: once, before the pump's first tick, chunks >= 2 (any value, not only powers of two).  Allocates
+ * [streams][chunks][N] int16 and the counters, all zero.  VAD_ERR_ARG with nothing changed: after a tick was submitted, a second call,
+ * chunks < 2, a pump with vad_pump_set_resample enabled -- and vad_pump_set_resample on a pump with a tape: that route steps an fp32
+ * batch, an int16 tape of it would not be what the net saw.  VAD_ERR_ALLOC: no device memory; the pump stays usable without a tape.  A
+ * pump that never calls it allocates nothing and launches nothing for it.
+ * SIZING.  streams x chunks x N x 2 bytes: 8192 streams x 512 chunks (16.4 s) = 4.3 GB.  A sample stays fetchable for `chunks` chunks of
+ * ITS stream, counted from when it is stepped -- ticks in flight count: up to ring_slots x max_chunks chunks.  Size chunks as the
+ * longest utterance + speech_pad + that slack.
+ *
+ * FETCHING, both from the thread that drives the pump.
+ * vad_pump_tape_window: synchronises the compute stream -- so it sees every tick submitted so far, retired or in flight -- reads the
+ * counters and applies the rule to request i = (stream[i], [start[i], end[i])) -> first[i], count[i]; returns the total number of
+ * samples (>= 0).  A stream may appear in any number of requests; n == 0 is fine.  -VAD_ERR_ARG with nothing written: a pump without a
+ * tape, a stream out of range, start > end.
+ * vad_pump_fetch_audio: request i's count[i] samples from sample first[i] of stream[i]'s clock go to out + out_offset[i] (in samples).
+ * An exclusive sum of the counts, each rounded up to 8, keeps every start 16-byte aligned (the gather kernel's fast path); any other
+ * offset is honoured element by element.  EXACTLY count[i] samples are written per request: what lies between the requests and behind
+ * the last one is not touched.  out_on_device == 0: `out` is host memory -- the samples are packed in a device buffer that grows on
+ * demand, cross the link in ONE copy and are dealt out on the host; out_on_device == 1: `out` is device memory of the pump's GPU, for a
+ * consumer there, and the kernel writes it directly.  Synchronous: the samples are in `out` on return.  The call synchronises first and
+ * checks every range again, by the same rule, against the counters as they are then: a range with count[i] > 0 that is not wholly
+ * inside its stream's window is VAD_ERR_ARG, "no longer held", and nothing is written (a tick submitted between the two calls taped
+ * over it).  Also VAD_ERR_ARG: a pump without a tape, a stream out of range, a negative count or offset.  It touches none of the
+ * pump's carried state and works with ticks in flight.
+ * vad_pump_tape_state: test hook -> *count, *floor of one stream (either may be NULL).  Synchronises.                                  */
+int  vad_tape_window(int64_t count, int64_t floor, int chunks, int N, int64_t start, int64_t end, int64_t *first, int64_t *n);
+int  vad_pump_set_tape(vad_pump *p, int chunks);
+long vad_pump_tape_window(vad_pump *p, const int32_t *stream, const int64_t *start, const int64_t *end, long n, int64_t *first, int64_t *count);
+int  vad_pump_fetch_audio(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
+                          int16_t *out, int out_on_device);
+int  vad_pump_tape_state(vad_pump *p, int stream, int64_t *count, int64_t *floor);
+
 /* SNAPSHOT AND RESTORE of live streams: everything a stream carries from one tick to the next leaves a pump as plain bytes and enters
  * any slot of any pump of the same sample rate -- another GPU, another process, another machine -- for a drain, a rebalancing of
  * streams between per-GPU ranks, a rolling restart or a failover.  The reference treats this state as the resumable unit of the model
@@ -693,7 +749,8 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * A record does not name the slot it came from.  Reserved bytes are written as zero and a reader refuses a record in which they are not;
  * samples behind `pending` are written as zero and ignored when read.  Two exports with no tick between them are byte for byte the same.
  * NOT carried: ticks in flight (there are none: see below), the position counter of the vad_pump_play* helpers (it restarts as after
- * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), and the model weights.
+ * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), the tape (THE TAPE above: a pump with a tape
+ * writes the same bytes, and an import restarts the slot's tape at the record's current_sample), and the model weights.
  *
  * THE BLOB (version 2) carries, in addition, what a stream that is BOUND to a resampled rate holds (vad_pump_submit_resampled_packets):
  * its rate, its two counters, its fp32 pending outputs and its filter history.  vad_pump_export_streams_v2 writes it, for bound and

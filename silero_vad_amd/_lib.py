@@ -116,6 +116,11 @@ SYMBOLS = {
     "vad_pump_open": (c_int, [c_void_p, c_int]),
     "vad_pump_close": (c_int, [c_void_p, c_int]),
     "vad_pump_state": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vad_tape_window": (c_int, [c_int64, c_int64, c_int, c_int, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
+    "vad_pump_set_tape": (c_int, [c_void_p, c_int]),
+    "vad_pump_tape_window": (c_long, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "vad_pump_fetch_audio": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int]),
+    "vad_pump_tape_state": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "vad_pump_snapshot_bytes": (c_size_t, [c_int, c_long]),
     "vad_pump_export_streams": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_size_t]),
     "vad_pump_import_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_long]),

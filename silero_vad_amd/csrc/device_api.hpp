@@ -312,6 +312,21 @@ hipError_t launch_collect_segments(const void *pcm, int esz, long ld, int step, 
                                    long cap, const long *counts, int invert, const long *kept, const long *out_offset, void *out,
                                    hipStream_t s);
 
+// The pump's tape (kernel_tape.hip; the window rule and the ring's addressing are tape.hpp).  tape[streams][chunks][N] int16 and
+// clock[streams][2] int64 = {count, floor} are device memory, rows[streams][N] the batch rows of one step, flags[streams] its flag row or
+// nullptr; N is 256 or 512, every row 16-byte aligned.
+//   launch_tape_rows    stream b with flags == nullptr || flags[b]: rows[b] -> tape[b][count % chunks], count += 1
+//   launch_tape_gather  request i's `count` samples from sample `first` of stream `stream`'s clock to out + out_offset (elements); the
+//                       caller has confined every request to its stream's window (0 <= first, count <= max_count <= chunks * N);
+//                       nothing else is written
+struct TapeRequest {
+    int64_t stream, first, count, out_offset;
+};
+hipError_t launch_tape_rows(const int16_t *rows, const uint8_t *flags, int16_t *tape, int64_t *clock, int chunks, int streams, int N,
+                            hipStream_t s);
+hipError_t launch_tape_gather(const TapeRequest *req, long n_req, long max_count, const int16_t *tape, int chunks, int N, int16_t *out,
+                              hipStream_t s);
+
 // The threshold sweep (kernel_sweep.hip; the cell is sweeper.hpp): row i's n_chunks[i] probabilities at probs + (row_off ? row_off[i]
 // : i * ldp), its packed labels at labels + label_off[i]; tp / tn [n_rows][n_pairs], n_pos / n_valid [n_rows].  One wave per (row,
 // 64 pairs): n_rows * ceil(n_pairs / 64) blocks, which the caller keeps below 2^31.

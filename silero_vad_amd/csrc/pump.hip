@@ -100,6 +100,7 @@
 #include "../../include/silero_vad_hip.h"
 #include "device_api.hpp"
 #include "host_threads.hpp"
+#include "tape.hpp"
 
 struct vad_pump {
     vad_engine *eng = nullptr;                   // a clone of the caller's engine: the pump's calls never touch the caller's scratch
@@ -194,7 +195,16 @@ struct vad_pump {
     vad::SnapPart *d_snap_parts = nullptr;       // [parts] each part's state block and first slot
     uint8_t *d_snap = nullptr;                   // the packed records on the device: what the one copy of a call carries
     size_t snap_cap = 0;                         // ... its bytes
-    bool poisoned = false;                       // a tick failed half-way: the carried state is no longer what any caller expects
+    // the tape (vad_pump_set_tape; tape_chunks == 0: not enabled, none of this is allocated and no tick launches anything for it)
+    int tape_chunks = 0;                         // chunks of a stream's ring
+    int16_t *d_tape = nullptr;                   // [streams][tape_chunks][N] the chunks every stream was stepped on, chunk k in slot k % tape_chunks
+    int64_t *d_tape_clock = nullptr;             // [streams][2] {count, floor}: written by tape_rows_kernel, open and import, on the compute stream
+    std::vector<int64_t> tape_clock;             // [streams][2] what the last synchronising call read of it
+    vad::TapeRequest *h_tape_req = nullptr, *d_tape_req = nullptr;      // the requests of a fetch: page-locked, and on the device
+    size_t tape_req_cap = 0;                     // ... their number
+    int16_t *d_tape_out = nullptr, *h_tape_out = nullptr;               // a fetch into host memory: the packed samples on the device, and page-locked
+    size_t tape_out_cap = 0;                     // ... their samples
+    bool poisoned = false;                      // a tick failed half-way: the carried state is no longer what any caller expects
     std::string err;
 
     int32_t *slot_pos(int r) const { return reinterpret_cast<int32_t *>(h_ring + (size_t)r * slot_bytes + htab); }
@@ -389,6 +399,12 @@ void vad_pump_destroy(vad_pump *p) {
     if (p->d_snap) (void)hipFree(p->d_snap);
     if (p->d_snap_parts) (void)hipFree(p->d_snap_parts);
     if (p->h_snap_tab) (void)hipHostFree(p->h_snap_tab);
+    if (p->d_tape) (void)hipFree(p->d_tape);
+    if (p->d_tape_clock) (void)hipFree(p->d_tape_clock);
+    if (p->d_tape_req) (void)hipFree(p->d_tape_req);
+    if (p->h_tape_req) (void)hipHostFree(p->h_tape_req);
+    if (p->d_tape_out) (void)hipFree(p->d_tape_out);
+    if (p->h_tape_out) (void)hipHostFree(p->h_tape_out);
     if (p->h_ring) (void)hipHostFree(p->h_ring);
     if (p->h_prob) (void)hipHostFree(p->h_prob);
     for (hipStream_t cs : p->copy)
@@ -914,6 +930,9 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
                                             probs_j + a, masked ? flags_j + a : nullptr, p->compute);
             if (rc != VAD_OK) return broken(rc, std::string("vad_step_present: ") + vad_last_error(p->eng));
         }
+        // the tape: the rows this step read, of the streams it stepped (behind the last part: every h2d_done wait has been made)
+        if (p->tape_chunks)
+            TICK_TRY(vad::launch_tape_rows(rows_j, masked ? flags_j : nullptr, p->d_tape, p->d_tape_clock, p->tape_chunks, p->streams, p->N, p->compute));
     }
     TICK_TRY(hipEventRecord(p->batch_free[buf], p->compute));
     TICK_TRY(hipEventRecord(p->tick_done[r], p->compute));
@@ -1099,6 +1118,8 @@ int vad_pump_set_resample(vad_pump *p, const int *src_rates, int n_rates) {
     const std::string fn = "vad_pump_set_resample: ";
     if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
     if (!src_rates || n_rates < 1 || n_rates > VAD_PUMP_MAX_RATES) return pfail(p, VAD_ERR_ARG, fn + "1 ... VAD_PUMP_MAX_RATES source rates");
+    if (p->tape_chunks)                          // (a resampled tick steps an fp32 batch: an int16 tape of it would not be what the net saw)
+        return pfail(p, VAD_ERR_ARG, fn + "the pump has a tape (vad_pump_set_tape), and the tape does not hold the resampled route's fp32 chunks");
     if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, fn + "ticks in flight (retire them with vad_pump_poll first)");
     std::shared_ptr<const vad::ResampleHostTable> tabs[vad::kMaxPumpRates];
     long A = 0, hmax = 0;
@@ -1269,7 +1290,9 @@ int vad_pump_open(vad_pump *p, int stream) {
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + row * 128, 0, 128 * sizeof(float), p->compute));
     PUMP_TRY(p, hipMemsetAsync(p->d_state[k] + (n + row) * 128, 0, 128 * sizeof(float), p->compute));
     PUMP_TRY(p, hipMemsetAsync(p->d_ctx[p->flips & 1] + (size_t)stream * p->C, 0, (size_t)p->C * sizeof(float), p->compute));
-    p->drop_held(stream);                        // (the device carry needs nothing: the next packet tick's table says 0 samples pending)
+    if (p->tape_chunks)                          // ... and the tape's clock: the new stream's chunk 0 is the next one stepped here
+        PUMP_TRY(p, hipMemsetAsync(p->d_tape_clock + 2 * (size_t)stream, 0, 2 * sizeof(int64_t), p->compute));
+    p->drop_held(stream);                       // (the device carry needs nothing: the next packet tick's table says 0 samples pending)
     if (p->max_step) p->w_step[stream] = p->w_phase[stream] = 0;                // ... and the new stream's comb starts at its first sample
     if (p->n_rates) {                            // ... it is bound to no rate, and its filter history is zeros: "inputs before 0 are zero"
         PUMP_TRY(p, hipMemsetAsync(p->d_hist + (size_t)stream * p->r_hld, 0, (size_t)p->r_hld * sizeof(int16_t), p->compute));
@@ -1315,6 +1338,163 @@ int vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx) {
     if (h) PUMP_TRY(p, hipMemcpy(h, p->d_state[k] + row * 128, 128 * sizeof(float), hipMemcpyDeviceToHost));
     if (c) PUMP_TRY(p, hipMemcpy(c, p->d_state[k] + (n + row) * 128, 128 * sizeof(float), hipMemcpyDeviceToHost));
     if (ctx) PUMP_TRY(p, hipMemcpy(ctx, p->d_ctx[p->flips & 1] + (size_t)stream * p->C, (size_t)p->C * sizeof(float), hipMemcpyDeviceToHost));
+    return VAD_OK;
+}
+
+}  // extern "C"
+
+// The tape (include/silero_vad_hip.h "THE TAPE"; kernel_tape.hip; the window rule: tape.hpp)
+namespace {
+
+// every counter as of all the ticks submitted so far: the compute stream is drained first
+int tape_read_clock(vad_pump *p) {
+    PUMP_TRY(p, hipSetDevice(p->device));
+    PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    PUMP_TRY(p, hipMemcpy(p->tape_clock.data(), p->d_tape_clock, (size_t)p->streams * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return VAD_OK;
+}
+
+// room for n requests, and (host destination) for `samples` packed samples
+int tape_reserve(vad_pump *p, size_t n, size_t samples) {
+    if (n > p->tape_req_cap) {
+        if (p->d_tape_req) (void)hipFree(p->d_tape_req);
+        if (p->h_tape_req) (void)hipHostFree(p->h_tape_req);
+        p->d_tape_req = p->h_tape_req = nullptr, p->tape_req_cap = 0;
+        const size_t cap = std::max<size_t>(n, 256);
+        if (hipHostMalloc((void **)&p->h_tape_req, cap * sizeof(vad::TapeRequest), hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&p->d_tape_req, cap * sizeof(vad::TapeRequest)) != hipSuccess) {
+            if (p->h_tape_req) (void)hipHostFree(p->h_tape_req);
+            p->d_tape_req = p->h_tape_req = nullptr;
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, "vad_pump_fetch_audio: no memory for the request table");
+        }
+        p->tape_req_cap = cap;
+    }
+    if (samples > p->tape_out_cap) {
+        if (p->d_tape_out) (void)hipFree(p->d_tape_out);
+        if (p->h_tape_out) (void)hipHostFree(p->h_tape_out);
+        p->d_tape_out = p->h_tape_out = nullptr, p->tape_out_cap = 0;
+        if (hipMalloc((void **)&p->d_tape_out, samples * sizeof(int16_t)) != hipSuccess ||
+            hipHostMalloc((void **)&p->h_tape_out, samples * sizeof(int16_t), hipHostMallocDefault) != hipSuccess) {
+            if (p->d_tape_out) (void)hipFree(p->d_tape_out);
+            p->d_tape_out = p->h_tape_out = nullptr;
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, "vad_pump_fetch_audio: no memory to stage the samples");
+        }
+        p->tape_out_cap = samples;
+    }
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_tape_window(int64_t count, int64_t floor, int chunks, int N, int64_t start, int64_t end, int64_t *first, int64_t *n) {
+    // (count * N and floor * N must be int64 values: everything else about the rule is clamps)
+    if (chunks < 2 || N < 1 || count < 0 || count > INT64_MAX / N || floor < INT64_MIN / N || floor > INT64_MAX / N || start > end || !first || !n)
+        return VAD_ERR_ARG;
+    vad::tape_window(count, floor, chunks, N, start, end, first, n);
+    return VAD_OK;
+}
+
+int vad_pump_set_tape(vad_pump *p, int chunks) {
+    if (!p) return VAD_ERR_ARG;
+    const std::string fn = "vad_pump_set_tape: ";
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (chunks < 2) return pfail(p, VAD_ERR_ARG, fn + "a tape holds at least 2 chunks a stream");
+    if (p->tape_chunks) return pfail(p, VAD_ERR_ARG, fn + "the pump has its tape already");
+    if (p->ticks > 0) return pfail(p, VAD_ERR_ARG, fn + "only before the pump's first tick: the tape's clock is the count of every chunk stepped");
+    if (p->n_rates)                              // (a resampled tick steps an fp32 batch: an int16 tape of it would not be what the net saw)
+        return pfail(p, VAD_ERR_ARG, fn + "the pump takes resampled rows (vad_pump_set_resample), and the tape does not hold that route's fp32 chunks");
+    PUMP_TRY(p, hipSetDevice(p->device));
+    const size_t S = (size_t)p->streams;
+    int16_t *tape = nullptr;
+    int64_t *clock = nullptr;
+    const bool ok = hipMalloc((void **)&tape, S * (size_t)chunks * p->N * sizeof(int16_t)) == hipSuccess &&
+                    hipMalloc((void **)&clock, S * 2 * sizeof(int64_t)) == hipSuccess &&
+                    hipMemset(clock, 0, S * 2 * sizeof(int64_t)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        if (tape) (void)hipFree(tape);
+        if (clock) (void)hipFree(clock);
+        (void)hipGetLastError();
+        return pfail(p, VAD_ERR_ALLOC, fn + "no device memory for streams x chunks x N samples");
+    }
+    p->d_tape = tape, p->d_tape_clock = clock;
+    p->tape_clock.assign(S * 2, 0);
+    p->tape_chunks = chunks;
+    return VAD_OK;
+}
+
+int vad_pump_tape_state(vad_pump *p, int stream, int64_t *count, int64_t *floor) {
+    if (!p) return VAD_ERR_ARG;
+    if (!p->tape_chunks) return pfail(p, VAD_ERR_ARG, "vad_pump_tape_state: the pump has no tape (vad_pump_set_tape)");
+    if (stream < 0 || stream >= p->streams) return pfail(p, VAD_ERR_ARG, "vad_pump_tape_state: no such stream");
+    if (const int rc = tape_read_clock(p)) return rc;
+    if (count) *count = p->tape_clock[2 * (size_t)stream];
+    if (floor) *floor = p->tape_clock[2 * (size_t)stream + 1];
+    return VAD_OK;
+}
+
+long vad_pump_tape_window(vad_pump *p, const int32_t *stream, const int64_t *start, const int64_t *end, long n, int64_t *first, int64_t *count) {
+    if (!p) return -VAD_ERR_ARG;
+    const std::string fn = "vad_pump_tape_window: ";
+    if (!p->tape_chunks) return -pfail(p, VAD_ERR_ARG, fn + "the pump has no tape (vad_pump_set_tape)");
+    if (n < 0 || (n > 0 && (!stream || !start || !end || !first || !count))) return -pfail(p, VAD_ERR_ARG, fn + "bad request list");
+    for (long i = 0; i < n; ++i) {               // (before anything is written, and before the pump is made to wait)
+        if (stream[i] < 0 || stream[i] >= p->streams) return -pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": no such stream");
+        if (start[i] > end[i]) return -pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": start behind end");
+    }
+    if (const int rc = tape_read_clock(p)) return -rc;
+    long total = 0;
+    for (long i = 0; i < n; ++i) {
+        const int64_t *c = p->tape_clock.data() + 2 * (size_t)stream[i];
+        vad::tape_window(c[0], c[1], p->tape_chunks, p->N, start[i], end[i], first + i, count + i);
+        total += (long)count[i];
+    }
+    return total;
+}
+
+int vad_pump_fetch_audio(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
+                         int16_t *out, int out_on_device) {
+    if (!p) return VAD_ERR_ARG;
+    const std::string fn = "vad_pump_fetch_audio: ";
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (!p->tape_chunks) return pfail(p, VAD_ERR_ARG, fn + "the pump has no tape (vad_pump_set_tape)");
+    if (n < 0 || (n > 0 && (!stream || !first || !count || !out_offset))) return pfail(p, VAD_ERR_ARG, fn + "bad request list");
+    int64_t max_count = 0, total = 0;
+    for (long i = 0; i < n; ++i) {
+        if (stream[i] < 0 || stream[i] >= p->streams) return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": no such stream");
+        if (count[i] < 0 || out_offset[i] < 0) return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": a negative count or offset");
+        max_count = std::max(max_count, count[i]);
+    }
+    if (max_count == 0) return VAD_OK;           // (nothing to copy: no request has a sample)
+    if (!out) return pfail(p, VAD_ERR_ARG, fn + "no destination");
+    if (const int rc = tape_read_clock(p)) return rc;
+    // the same rule, against the counters as they are NOW: a tick submitted since vad_pump_tape_window may have taped over the range
+    for (long i = 0; i < n; ++i) {
+        if (count[i] == 0) continue;
+        const int64_t *c = p->tape_clock.data() + 2 * (size_t)stream[i];
+        const int64_t lo = vad::tape_held_lo(c[0], c[1], p->tape_chunks, p->N), hi = vad::tape_held_hi(c[0], p->N);
+        if (first[i] < lo || first[i] > hi || count[i] > hi - first[i])
+            return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": samples " + std::to_string(first[i]) + " ... of stream " +
+                                             std::to_string(stream[i]) + " are no longer held (the tape holds " + std::to_string(lo) + " ... " +
+                                             std::to_string(hi) + ")");
+        total += (count[i] + 7) / 8 * 8;
+    }
+    if (const int rc = tape_reserve(p, (size_t)n, out_on_device ? 0 : (size_t)total)) return rc;
+    int64_t at = 0;
+    for (long i = 0; i < n; ++i) {               // host destination: packed on the device, every request 16-byte aligned
+        p->h_tape_req[i] = vad::TapeRequest{stream[i], first[i], count[i], out_on_device ? out_offset[i] : at};
+        at += (count[i] + 7) / 8 * 8;
+    }
+    // read-only behind everything the compute stream has run: a failure leaves the pump as it was
+    PUMP_TRY(p, hipMemcpyAsync(p->d_tape_req, p->h_tape_req, (size_t)n * sizeof(vad::TapeRequest), hipMemcpyHostToDevice, p->compute));
+    PUMP_TRY(p, vad::launch_tape_gather(p->d_tape_req, n, (long)max_count, p->d_tape, p->tape_chunks, p->N, out_on_device ? out : p->d_tape_out, p->compute));
+    if (!out_on_device) PUMP_TRY(p, hipMemcpyAsync(p->h_tape_out, p->d_tape_out, (size_t)total * sizeof(int16_t), hipMemcpyDeviceToHost, p->compute));
+    PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    for (long i = 0; i < n && !out_on_device; ++i)       // exactly count[i] samples each: what lies between the requests is not touched
+        if (count[i] > 0) std::memcpy(out + out_offset[i], p->h_tape_out + p->h_tape_req[i].out_offset, (size_t)count[i] * sizeof(int16_t));
     return VAD_OK;
 }
 
@@ -1674,6 +1854,16 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
             p->unbind(b);
         }
         p->src_pos[b] = 0;
+    }
+    if (p->tape_chunks) {                        // the stream's clock continues and nothing before the import is held: count = floor = its chunk
+        const size_t bytes2 = (size_t)S * 2 * sizeof(int64_t);                 // (the pump is idle and synchronised: nothing else writes the counters)
+        hipError_t e = hipMemcpy(p->tape_clock.data(), p->d_tape_clock, bytes2, hipMemcpyDeviceToHost);
+        for (long k = 0; k < n; ++k) p->tape_clock[2 * (size_t)streams[k]] = p->tape_clock[2 * (size_t)streams[k] + 1] = p->current[streams[k]] / p->N;
+        if (e == hipSuccess) e = hipMemcpy(p->d_tape_clock, p->tape_clock.data(), bytes2, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            p->poisoned = true;
+            return pfail(p, VAD_ERR_HIP, fn + hipGetErrorString(e));
+        }
     }
     return VAD_OK;
 }

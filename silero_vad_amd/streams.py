@@ -3261,6 +3261,61 @@ def snapshot_info(blob) -> list:
     return out
 
 
+def tape_window(count: int, floor: int, chunks: int, n: int, start: int, end: int):
+    """(first, samples): the part of the sample range [start, end) that a tape of `chunks` chunks of n samples holds when the stream's
+    counters are (count, floor) -- held_lo = max(floor, count - chunks) * n, held_hi = count * n, first = min(max(start, held_lo),
+    held_hi), last = min(max(end, first), held_hi) (vad_tape_window: the rule `StreamPump.fetch_audio` applies; host only, no GPU).
+    Any int64 start <= end is legal; start > end raises."""
+    vals = [count, floor, chunks, n, start, end]
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError(f"tape_window takes integers, got {vals!r}")
+    if not all(-2 ** 63 <= int(v) < 2 ** 63 for v in vals) or not all(-2 ** 31 <= int(v) < 2 ** 31 for v in (chunks, n)):
+        raise ValueError(f"tape_window: a value out of its integer range in {vals!r}")
+    if start > end:
+        raise ValueError(f"tape_window: start {start} lies behind end {end}")
+    first, m = ctypes.c_int64(), ctypes.c_int64()
+    rc = lib().vad_tape_window(int(count), int(floor), int(chunks), int(n), int(start), int(end), ctypes.byref(first), ctypes.byref(m))
+    if rc:
+        raise ValueError(f"tape_window: chunks >= 2, n >= 1, count >= 0 and counters times n within int64, got {vals!r}")
+    return first.value, m.value
+
+
+class UtteranceCollector:
+    """The utterances behind a taped pump's events: `feed(events)` takes what `pump.poll()` returned, remembers each stream's `start`
+    and returns, for every `end`, (stream, start, end, first, audio) -- audio the int16 samples [first, end) of the stream as the net
+    heard them, first > start where the head of a long utterance had already left the tape.  All ENDs of one `feed` are fetched in
+    one `fetch_audio` call.  An END whose START was never fed comes back as (stream, None, end, None, None).  `forget(stream)` drops a
+    remembered START: call it with `pump.open_stream(stream)`, the slot's new stream starts a new clock."""
+
+    def __init__(self, pump):
+        if not getattr(pump, "tape_chunks", 0):
+            raise ValueError("UtteranceCollector needs a pump with a tape (StreamPump(..., tape_chunks=K))")
+        self.pump = pump
+        self._start = {}
+
+    def forget(self, stream: int):
+        self._start.pop(int(stream), None)
+
+    def feed(self, events) -> list:
+        done = []
+        for stream, ev in events or ():
+            if "start" in ev:
+                self._start[int(stream)] = int(ev["start"])
+            else:
+                done.append((int(stream), self._start.pop(int(stream), None), int(ev["end"])))
+        known = [d for d in done if d[1] is not None]
+        audios, first = ([], []) if not known else self.pump.fetch_audio([d[0] for d in known], [d[1] for d in known], [d[2] for d in known])
+        got = iter(zip(audios, first))
+        out = []
+        for stream, start, end in done:
+            if start is None:
+                out.append((stream, None, end, None, None))
+            else:
+                audio, f = next(got)
+                out.append((stream, start, end, int(f), audio))
+        return out
+
+
 class StreamPump:
     """BASELINE configs[4] through the native pump (include/silero_vad_hip.h "live streams: the pump", csrc/pump.hip): `streams`
     live streams on one GPU, host int16 chunks in, VADIterator events out, with no Python and no torch on the per-tick path
@@ -3298,11 +3353,22 @@ class StreamPump:
     pump of the same sample rate (another GPU, another process), and `snapshot_info(blob)` reads a blob without a pump; the streams go
     on bit for bit.  `export_streams(..., version=2)` also moves streams that are bound to a resampled rate.
 
+    The audio behind the events: with `tape_chunks=K` the pump keeps every stream's last K chunks on the device as the net heard them
+    (G.711 expanded, 32 / 48 kHz combed, silent rows as zeros), taped as a side effect of every step of every route but the resampled
+    one; the sample numbers of the events are tape positions, `fetch_audio(streams, starts, ends)` copies any still-held ranges out
+    (to numpy arrays, or with device=True into one packed tensor on the pump's GPU) and `UtteranceCollector(pump).feed(events)` hands
+    back the utterance behind every `end`.  A sample stays fetchable for K chunks of its stream (ticks in flight count):
+    K = longest utterance + pad + ring_slots x max_burst; the tape costs streams x K x N x 2 bytes.
+
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
     def __init__(self, engine, sampling_rate: int = 16000, streams: int = 8192, parts: int = 0, ring_slots: int = 0,
-                 threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1, source_rate=None):
+                 threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1, source_rate=None,
+                 tape_chunks: int = 0):
         _no_source_rate(source_rate, "StreamPump")
+        if isinstance(tape_chunks, (bool, np.bool_)) or not isinstance(tape_chunks, (int, np.integer)) or tape_chunks < 0 or tape_chunks == 1 \
+                or tape_chunks >= 2 ** 31:
+            raise ValueError(f"tape_chunks must be 0 (no tape) or 2 ... 2^31 - 1 chunks a stream, got {tape_chunks!r}")
         if sampling_rate not in (8000, 16000):
             raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
         if not isinstance(max_burst, (int, np.integer)) or not 1 <= max_burst <= 8:
@@ -3329,6 +3395,15 @@ class StreamPump:
                 self._L.vad_pump_destroy(h)
                 self._h = None
                 raise _lib.VadError(rc, msg)
+        self.tape_chunks = 0
+        self.device = getattr(engine, "device", 0)
+        if tape_chunks:                                          # (0: no tape, nothing is allocated or launched for it)
+            try:
+                self.set_tape(int(tape_chunks))
+            except Exception:
+                self._L.vad_pump_destroy(h)
+                self._h = None
+                raise
         self._events = (_lib.IterEvent * (self.streams * self.max_burst))()
         self._slots = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_slot(h, r), ctypes.POINTER(ctypes.c_int16)),
                                              shape=(self.streams, self.n)) for r in range(self.ring_slots)]
@@ -3756,6 +3831,86 @@ class StreamPump:
         h, c, x = np.empty(128, np.float32), np.empty(128, np.float32), np.empty(self.n // 8, np.float32)
         self._check(self._L.vad_pump_state(self._h, int(stream), h.ctypes.data, c.ctypes.data, x.ctypes.data))
         return h, c, x
+
+    def set_tape(self, chunks: int):
+        """Enable the tape (vad_pump_set_tape; what `StreamPump(..., tape_chunks=chunks)` calls): once, before the first tick, chunks
+        >= 2, not together with `set_resample`.  Allocates streams x chunks x N int16 samples on the device."""
+        self._check(self._L.vad_pump_set_tape(self._h, int(chunks)))
+        self.tape_chunks = int(chunks)
+
+    def tape_state(self, stream: int):
+        """(count, floor) of `stream`'s tape: the chunks stepped since its clock started (count * N is the iterator's current_sample)
+        and the first chunk the tape can hold (vad_pump_tape_state; synchronises; tests)."""
+        c, f = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vad_pump_tape_state(self._h, int(stream), ctypes.byref(c), ctypes.byref(f)))
+        return c.value, f.value
+
+    @staticmethod
+    def _int64_rows(x, name) -> np.ndarray:
+        a = np.asarray(x)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{name} must be a 1-D sequence of integers, got {a.dtype} of shape {a.shape}")
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    def tape_windows(self, streams, starts, ends):
+        """(first, count), two int64 arrays: the part of [starts[i], ends[i]) of streams[i]'s sample clock that the tape still holds,
+        as of every tick submitted so far (vad_pump_tape_window; synchronises).  first[i] > starts[i]: the head is no longer held."""
+        st, a, b = _int32_rows(streams, "streams"), self._int64_rows(starts, "starts"), self._int64_rows(ends, "ends")
+        if not len(st) == len(a) == len(b):
+            raise ValueError(f"streams, starts and ends must have one entry per request, got {len(st)}, {len(a)}, {len(b)}")
+        first, count = np.zeros(len(st), np.int64), np.zeros(len(st), np.int64)
+        n = len(st)
+        total = self._L.vad_pump_tape_window(self._h, *[x.ctypes.data if n else None for x in (st, a, b)], n,
+                                             first.ctypes.data if n else None, count.ctypes.data if n else None)
+        if total < 0:
+            raise _lib.VadError(-total, self._L.vad_pump_last_error(self._h).decode())
+        return first, count
+
+    def fetch_audio_into(self, streams, first, counts, out, out_offsets):
+        """counts[i] samples from sample first[i] of streams[i] to out[out_offsets[i] : ...] (vad_pump_fetch_audio): `out` is a flat
+        C-contiguous int16 numpy array, or a flat contiguous int16 torch tensor on the pump's GPU.  Exactly those samples are written.
+        Offsets that are multiples of 8 (of a 16-byte aligned `out`) take the gather kernel's 16-byte stores.  A range that is not
+        wholly inside its stream's window as it is NOW raises ("no longer held") and nothing is written."""
+        st, fi, ct, of = (_int32_rows(streams, "streams"), self._int64_rows(first, "first"), self._int64_rows(counts, "counts"),
+                          self._int64_rows(out_offsets, "out_offsets"))
+        if not len(st) == len(fi) == len(ct) == len(of):
+            raise ValueError(f"streams, first, counts and out_offsets must have one entry per request, got {len(st)}, {len(fi)}, {len(ct)}, {len(of)}")
+        on_device = isinstance(out, torch.Tensor)
+        if on_device:
+            if out.dtype != torch.int16 or out.dim() != 1 or not out.is_contiguous() or out.device != torch.device("cuda", self.device):
+                raise ValueError(f"out must be a flat contiguous int16 tensor on cuda:{self.device}")
+            size, ptr = out.numel(), out.data_ptr()
+        else:
+            if not isinstance(out, np.ndarray) or out.dtype != np.int16 or out.ndim != 1 or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("out must be a flat, writeable, C-contiguous int16 numpy array (or an int16 tensor on the pump's GPU)")
+            size, ptr = out.size, out.ctypes.data
+        if len(st) and (ct.min() < 0 or of.min() < 0 or int((of + ct).max()) > size):
+            raise ValueError("a request's samples do not fit into out")
+        n = len(st)
+        self._check(self._L.vad_pump_fetch_audio(self._h, *[x.ctypes.data if n else None for x in (st, fi, ct)], n, of.ctypes.data if n else None,
+                                                 ptr if size else None, 1 if on_device else 0))
+
+    def fetch_audio(self, streams, starts, ends, device: bool = False):
+        """The audio of [starts[i], ends[i]) of streams[i]'s sample clock -- the clock of the events -- as far as the tape still holds
+        it: -> (audios, first).  audios[i] is an int16 numpy array of the samples [first[i], first[i] + len(audios[i])); first[i] >
+        starts[i] means the head of the range was no longer held.  device=True: audios is (packed, offsets, counts) instead -- ONE int16
+        tensor on the pump's GPU, request i at packed[offsets[i] : offsets[i] + counts[i]] (every offset a multiple of 8 samples), for a
+        consumer on the same GPU; nothing crosses the link.  A stream may appear in any number of requests.  Raises without a tape, for
+        a stream out of range and for starts[i] > ends[i]."""
+        first, count = self.tape_windows(streams, starts, ends)
+        offsets = np.zeros(len(count), np.int64)
+        if len(count):
+            offsets[1:] = np.cumsum((count[:-1] + 7) // 8 * 8)
+        total = int(offsets[-1] + count[-1]) if len(count) else 0
+        if device:
+            with torch.cuda.device(self.device):
+                packed = torch.empty(total, dtype=torch.int16, device=torch.device("cuda", self.device))
+                torch.cuda.current_stream().synchronize()        # (the pump writes on its own stream: the allocation is settled first)
+            self.fetch_audio_into(streams, first, count, packed, offsets)
+            return (packed, offsets, count), first
+        packed = np.empty(total, np.int16)
+        self.fetch_audio_into(streams, first, count, packed, offsets)
+        return [packed[o:o + c] for o, c in zip(offsets.tolist(), count.tolist())], first
 
     def export_streams(self, streams=None, version: int = 1) -> np.ndarray:
         """Everything `streams` (distinct slots; None = every slot, ascending) carry, as one self-describing uint8 blob
