@@ -689,8 +689,8 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  *
  * vad_pump_set_tape: once, before the pump's first tick, chunks >= 2 (any value, not only powers of two).  Allocates
  * [streams][chunks][N] int16 and the counters, all zero.  VAD_ERR_ARG with nothing changed: after a tick was submitted, a second call,
- * chunks < 2, a pump with vad_pump_set_resample enabled -- and vad_pump_set_resample on a pump with a tape: that route steps an fp32
- * batch, an int16 tape of it would not be what the net saw.  VAD_ERR_ALLOC: no device memory; the pump stays usable without a tape.  A
+ * chunks < 2, a pump with vad_pump_set_resample enabled -- and vad_pump_set_resample on a pump with this tape: that route steps an fp32
+ * batch, an int16 tape of it would not be what the net saw (THE FP32 TAPE below holds it).  VAD_ERR_ALLOC: no device memory; the pump stays usable without a tape.  A
  * pump that never calls it allocates nothing and launches nothing for it.
  * SIZING.  streams x chunks x N x 2 bytes: 8192 streams x 512 chunks (16.4 s) = 4.3 GB.  A sample stays fetchable for `chunks` chunks of
  * ITS stream, counted from when it is stepped -- ticks in flight count: up to ring_slots x max_chunks chunks.  Size chunks as the
@@ -711,13 +711,38 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * inside its stream's window is VAD_ERR_ARG, "no longer held", and nothing is written (a tick submitted between the two calls taped
  * over it).  Also VAD_ERR_ARG: a pump without a tape, a stream out of range, a negative count or offset.  It touches none of the
  * pump's carried state and works with ticks in flight.
- * vad_pump_tape_state: test hook -> *count, *floor of one stream (either may be NULL).  Synchronises.                                  */
+ * vad_pump_tape_state: test hook -> *count, *floor of one stream (either may be NULL).  Synchronises.
+ *
+ * THE FP32 TAPE.  vad_pump_set_tape_f32 makes the tape's element what the net read: float32.  It allocates [streams][chunks][N] float and
+ * the same two counters a stream, by the rules of vad_pump_set_tape (once, before the first tick, chunks >= 2 of any value, VAD_ERR_ALLOC
+ * leaves the pump usable without a tape).  A pump holds at most ONE tape: either set call on a pump that has either tape is VAD_ERR_ARG
+ * ("already").  Unlike the int16 tape it goes together with vad_pump_set_resample, in either order -- a pump of 44.1 / 24 / 22.05 /
+ * 11.025 kHz clients is the one whose net-rate audio the host never holds.  What it tapes is every step of every route: a resampled tick
+ * tapes its rows of the fp32 batch bit for bit (the values vad_resample_rows_device gives for the stream's concatenated rows); a step
+ * over int16 rows (full, masked, compact, rows, packets, coded, burst sub-steps, wide) tapes (float)x * (1.0f / 32768.0f), the value the
+ * frontend computes from that sample, exact, in [-1, 1).  Bound and unbound streams of one pump share the one tape.  A second
+ * vad_pump_set_resample with other rates unbinds every stream, as ever, and leaves the tape and its clocks alone.  The clock, the window
+ * rule, vad_pump_open / close / import_streams, the exports (which do not carry it) and vad_tape_window / vad_pump_tape_window /
+ * vad_pump_tape_state are those of the int16 tape: none of them depends on the element.
+ * SIZING.  streams x chunks x N x 4 bytes: 8192 streams x 512 chunks = 8.6 GB.
+ * vad_pump_fetch_audio_f32: the contract of vad_pump_fetch_audio with "sample" meaning one float -- it synchronises, re-checks every
+ * range ("no longer held", nothing written), writes EXACTLY count[i] floats per request to out + out_offset[i] (in floats), stages a host
+ * destination through one D2H copy and lets the kernel write a device destination.  An exclusive sum of the counts, each rounded up to 4
+ * (or 8), keeps every start 16-byte aligned for the gather kernel's vector path; any other offset is honoured float by float.
+ * THE WRONG FETCH for the pump's tape -- vad_pump_fetch_audio on an fp32 tape, vad_pump_fetch_audio_f32 on an int16 tape -- is
+ * VAD_ERR_ARG with a message that names the right call; nothing is written and the pump stays usable.
+ * vad_pump_tape_format: 0 = no tape, 2 = the int16 tape, 4 = the fp32 tape (the element's size in bytes); -VAD_ERR_ARG for NULL.  Host
+ * only, no synchronisation.                                                                                                          */
 int  vad_tape_window(int64_t count, int64_t floor, int chunks, int N, int64_t start, int64_t end, int64_t *first, int64_t *n);
 int  vad_pump_set_tape(vad_pump *p, int chunks);
 long vad_pump_tape_window(vad_pump *p, const int32_t *stream, const int64_t *start, const int64_t *end, long n, int64_t *first, int64_t *count);
 int  vad_pump_fetch_audio(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
                           int16_t *out, int out_on_device);
 int  vad_pump_tape_state(vad_pump *p, int stream, int64_t *count, int64_t *floor);
+int  vad_pump_set_tape_f32(vad_pump *p, int chunks);
+int  vad_pump_fetch_audio_f32(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
+                              float *out, int out_on_device);
+int  vad_pump_tape_format(const vad_pump *p);
 
 /* SNAPSHOT AND RESTORE of live streams: everything a stream carries from one tick to the next leaves a pump as plain bytes and enters
  * any slot of any pump of the same sample rate -- another GPU, another process, another machine -- for a drain, a rebalancing of

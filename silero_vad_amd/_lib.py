@@ -121,6 +121,9 @@ SYMBOLS = {
     "vad_pump_tape_window": (c_long, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "vad_pump_fetch_audio": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int]),
     "vad_pump_tape_state": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "vad_pump_set_tape_f32": (c_int, [c_void_p, c_int]),
+    "vad_pump_fetch_audio_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int]),
+    "vad_pump_tape_format": (c_int, [c_void_p]),
     "vad_pump_snapshot_bytes": (c_size_t, [c_int, c_long]),
     "vad_pump_export_streams": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_size_t]),
     "vad_pump_import_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_long]),

@@ -326,6 +326,15 @@ hipError_t launch_tape_rows(const int16_t *rows, const uint8_t *flags, int16_t *
                             hipStream_t s);
 hipError_t launch_tape_gather(const TapeRequest *req, long n_req, long max_count, const int16_t *tape, int chunks, int N, int16_t *out,
                               hipStream_t s);
+// The fp32 tape (vad_pump_set_tape_f32): tape[streams][chunks][N] float, the same clock, the same requests ("sample" = one float).  Its
+// rows come from an int16 batch -- taped as load_pcm gives them, (float)x * (1.0f / 32768.0f), exact -- or, on a resampled tick, from
+// the fp32 batch, bit for bit.
+hipError_t launch_tape_rows(const int16_t *rows, const uint8_t *flags, float *tape, int64_t *clock, int chunks, int streams, int N,
+                            hipStream_t s);
+hipError_t launch_tape_rows(const float *rows, const uint8_t *flags, float *tape, int64_t *clock, int chunks, int streams, int N,
+                            hipStream_t s);
+hipError_t launch_tape_gather(const TapeRequest *req, long n_req, long max_count, const float *tape, int chunks, int N, float *out,
+                              hipStream_t s);
 
 // The threshold sweep (kernel_sweep.hip; the cell is sweeper.hpp): row i's n_chunks[i] probabilities at probs + (row_off ? row_off[i]
 // : i * ldp), its packed labels at labels + label_off[i]; tp / tn [n_rows][n_pairs], n_pos / n_valid [n_rows].  One wave per (row,

@@ -195,15 +195,17 @@ struct vad_pump {
     vad::SnapPart *d_snap_parts = nullptr;       // [parts] each part's state block and first slot
     uint8_t *d_snap = nullptr;                   // the packed records on the device: what the one copy of a call carries
     size_t snap_cap = 0;                         // ... its bytes
-    // the tape (vad_pump_set_tape; tape_chunks == 0: not enabled, none of this is allocated and no tick launches anything for it)
+    // the tape (vad_pump_set_tape / vad_pump_set_tape_f32; tape_chunks == 0: not enabled, none of this is allocated and no tick launches
+    // anything for it)
     int tape_chunks = 0;                         // chunks of a stream's ring
-    int16_t *d_tape = nullptr;                   // [streams][tape_chunks][N] the chunks every stream was stepped on, chunk k in slot k % tape_chunks
+    int tape_elem = 0;                           // bytes of its element: 2 (int16), 4 (float: what the net read, also on a resampled tick); 0: no tape
+    void *d_tape = nullptr;                      // [streams][tape_chunks][N] the chunks every stream was stepped on, chunk k in slot k % tape_chunks
     int64_t *d_tape_clock = nullptr;             // [streams][2] {count, floor}: written by tape_rows_kernel, open and import, on the compute stream
     std::vector<int64_t> tape_clock;             // [streams][2] what the last synchronising call read of it
     vad::TapeRequest *h_tape_req = nullptr, *d_tape_req = nullptr;      // the requests of a fetch: page-locked, and on the device
     size_t tape_req_cap = 0;                     // ... their number
-    int16_t *d_tape_out = nullptr, *h_tape_out = nullptr;               // a fetch into host memory: the packed samples on the device, and page-locked
-    size_t tape_out_cap = 0;                     // ... their samples
+    uint8_t *d_tape_out = nullptr, *h_tape_out = nullptr;               // a fetch into host memory: the packed samples on the device, and page-locked
+    size_t tape_out_cap = 0;                     // ... their bytes
     bool poisoned = false;                      // a tick failed half-way: the carried state is no longer what any caller expects
     std::string err;
 
@@ -931,8 +933,17 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
             if (rc != VAD_OK) return broken(rc, std::string("vad_step_present: ") + vad_last_error(p->eng));
         }
         // the tape: the rows this step read, of the streams it stepped (behind the last part: every h2d_done wait has been made)
-        if (p->tape_chunks)
-            TICK_TRY(vad::launch_tape_rows(rows_j, masked ? flags_j : nullptr, p->d_tape, p->d_tape_clock, p->tape_chunks, p->streams, p->N, p->compute));
+        // (a resampled tick: its rows of the one fp32 batch, which nothing overwrites before the next resampled tick's assembly, later
+        // on this stream)
+        if (p->tape_elem == 2)
+            TICK_TRY(vad::launch_tape_rows(rows_j, masked ? flags_j : nullptr, static_cast<int16_t *>(p->d_tape), p->d_tape_clock, p->tape_chunks,
+                                           p->streams, p->N, p->compute));
+        else if (p->tape_elem == 4 && pk && pk->res)
+            TICK_TRY(vad::launch_tape_rows(p->d_fbatch, masked ? flags_j : nullptr, static_cast<float *>(p->d_tape), p->d_tape_clock, p->tape_chunks,
+                                           p->streams, p->N, p->compute));
+        else if (p->tape_elem == 4)
+            TICK_TRY(vad::launch_tape_rows(rows_j, masked ? flags_j : nullptr, static_cast<float *>(p->d_tape), p->d_tape_clock, p->tape_chunks,
+                                           p->streams, p->N, p->compute));
     }
     TICK_TRY(hipEventRecord(p->batch_free[buf], p->compute));
     TICK_TRY(hipEventRecord(p->tick_done[r], p->compute));
@@ -1118,7 +1129,7 @@ int vad_pump_set_resample(vad_pump *p, const int *src_rates, int n_rates) {
     const std::string fn = "vad_pump_set_resample: ";
     if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
     if (!src_rates || n_rates < 1 || n_rates > VAD_PUMP_MAX_RATES) return pfail(p, VAD_ERR_ARG, fn + "1 ... VAD_PUMP_MAX_RATES source rates");
-    if (p->tape_chunks)                          // (a resampled tick steps an fp32 batch: an int16 tape of it would not be what the net saw)
+    if (p->tape_elem == 2)                       // (a resampled tick steps an fp32 batch: an int16 tape of it would not be what the net saw)
         return pfail(p, VAD_ERR_ARG, fn + "the pump has a tape (vad_pump_set_tape), and the tape does not hold the resampled route's fp32 chunks");
     if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, fn + "ticks in flight (retire them with vad_pump_poll first)");
     std::shared_ptr<const vad::ResampleHostTable> tabs[vad::kMaxPumpRates];
@@ -1354,8 +1365,8 @@ int tape_read_clock(vad_pump *p) {
     return VAD_OK;
 }
 
-// room for n requests, and (host destination) for `samples` packed samples
-int tape_reserve(vad_pump *p, size_t n, size_t samples) {
+// room for n requests, and (host destination) for `bytes` of packed samples
+int tape_reserve(vad_pump *p, size_t n, size_t bytes) {
     if (n > p->tape_req_cap) {
         if (p->d_tape_req) (void)hipFree(p->d_tape_req);
         if (p->h_tape_req) (void)hipHostFree(p->h_tape_req);
@@ -1370,19 +1381,97 @@ int tape_reserve(vad_pump *p, size_t n, size_t samples) {
         }
         p->tape_req_cap = cap;
     }
-    if (samples > p->tape_out_cap) {
+    if (bytes > p->tape_out_cap) {
         if (p->d_tape_out) (void)hipFree(p->d_tape_out);
         if (p->h_tape_out) (void)hipHostFree(p->h_tape_out);
         p->d_tape_out = p->h_tape_out = nullptr, p->tape_out_cap = 0;
-        if (hipMalloc((void **)&p->d_tape_out, samples * sizeof(int16_t)) != hipSuccess ||
-            hipHostMalloc((void **)&p->h_tape_out, samples * sizeof(int16_t), hipHostMallocDefault) != hipSuccess) {
+        if (hipMalloc((void **)&p->d_tape_out, bytes) != hipSuccess ||
+            hipHostMalloc((void **)&p->h_tape_out, bytes, hipHostMallocDefault) != hipSuccess) {
             if (p->d_tape_out) (void)hipFree(p->d_tape_out);
             p->d_tape_out = p->h_tape_out = nullptr;
             (void)hipGetLastError();
             return pfail(p, VAD_ERR_ALLOC, "vad_pump_fetch_audio: no memory to stage the samples");
         }
-        p->tape_out_cap = samples;
+        p->tape_out_cap = bytes;
     }
+    return VAD_OK;
+}
+
+// vad_pump_set_tape (elem = 2) and vad_pump_set_tape_f32 (elem = 4): one tape a pump, of either element
+int tape_set(vad_pump *p, int chunks, int elem, const std::string &fn) {
+    if (!p) return VAD_ERR_ARG;
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (chunks < 2) return pfail(p, VAD_ERR_ARG, fn + "a tape holds at least 2 chunks a stream");
+    if (p->tape_chunks) return pfail(p, VAD_ERR_ARG, fn + "the pump has its tape already");
+    if (p->ticks > 0) return pfail(p, VAD_ERR_ARG, fn + "only before the pump's first tick: the tape's clock is the count of every chunk stepped");
+    if (elem == 2 && p->n_rates)                 // (a resampled tick steps an fp32 batch: an int16 tape of it would not be what the net saw)
+        return pfail(p, VAD_ERR_ARG, fn + "the pump takes resampled rows (vad_pump_set_resample), and the tape does not hold that route's fp32 chunks");
+    PUMP_TRY(p, hipSetDevice(p->device));
+    const size_t S = (size_t)p->streams;
+    void *tape = nullptr;
+    int64_t *clock = nullptr;
+    const bool ok = hipMalloc(&tape, S * (size_t)chunks * p->N * (size_t)elem) == hipSuccess &&
+                    hipMalloc((void **)&clock, S * 2 * sizeof(int64_t)) == hipSuccess &&
+                    hipMemset(clock, 0, S * 2 * sizeof(int64_t)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        if (tape) (void)hipFree(tape);
+        if (clock) (void)hipFree(clock);
+        (void)hipGetLastError();
+        return pfail(p, VAD_ERR_ALLOC, fn + "no device memory for streams x chunks x N samples");
+    }
+    p->d_tape = tape, p->d_tape_clock = clock;
+    p->tape_clock.assign(S * 2, 0);
+    p->tape_chunks = chunks, p->tape_elem = elem;
+    return VAD_OK;
+}
+
+// vad_pump_fetch_audio (T = int16_t) and vad_pump_fetch_audio_f32 (T = float); offsets and counts are in elements of T
+template <typename T>
+int tape_fetch(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset, T *out,
+               int out_on_device, const std::string &fn) {
+    if (!p) return VAD_ERR_ARG;
+    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
+    if (!p->tape_chunks) return pfail(p, VAD_ERR_ARG, fn + "the pump has no tape (vad_pump_set_tape)");
+    if (p->tape_elem != (int)sizeof(T))
+        return pfail(p, VAD_ERR_ARG, fn + (p->tape_elem == 4 ? "the pump's tape is float32 (vad_pump_set_tape_f32): fetch it with vad_pump_fetch_audio_f32"
+                                                             : "the pump's tape is int16 (vad_pump_set_tape): fetch it with vad_pump_fetch_audio"));
+    if (n < 0 || (n > 0 && (!stream || !first || !count || !out_offset))) return pfail(p, VAD_ERR_ARG, fn + "bad request list");
+    int64_t max_count = 0, total = 0;
+    for (long i = 0; i < n; ++i) {
+        if (stream[i] < 0 || stream[i] >= p->streams) return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": no such stream");
+        if (count[i] < 0 || out_offset[i] < 0) return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": a negative count or offset");
+        max_count = std::max(max_count, count[i]);
+    }
+    if (max_count == 0) return VAD_OK;           // (nothing to copy: no request has a sample)
+    if (!out) return pfail(p, VAD_ERR_ARG, fn + "no destination");
+    if (const int rc = tape_read_clock(p)) return rc;
+    // the same rule, against the counters as they are NOW: a tick submitted since vad_pump_tape_window may have taped over the range
+    constexpr int64_t V = 16 / (int64_t)sizeof(T);     // elements of 16 bytes: every staged request starts on a multiple of it
+    for (long i = 0; i < n; ++i) {
+        if (count[i] == 0) continue;
+        const int64_t *c = p->tape_clock.data() + 2 * (size_t)stream[i];
+        const int64_t lo = vad::tape_held_lo(c[0], c[1], p->tape_chunks, p->N), hi = vad::tape_held_hi(c[0], p->N);
+        if (first[i] < lo || first[i] > hi || count[i] > hi - first[i])
+            return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": samples " + std::to_string(first[i]) + " ... of stream " +
+                                             std::to_string(stream[i]) + " are no longer held (the tape holds " + std::to_string(lo) + " ... " +
+                                             std::to_string(hi) + ")");
+        total += (count[i] + V - 1) / V * V;
+    }
+    if (const int rc = tape_reserve(p, (size_t)n, out_on_device ? 0 : (size_t)total * sizeof(T))) return rc;
+    int64_t at = 0;
+    for (long i = 0; i < n; ++i) {               // host destination: packed on the device, every request 16-byte aligned
+        p->h_tape_req[i] = vad::TapeRequest{stream[i], first[i], count[i], out_on_device ? out_offset[i] : at};
+        at += (count[i] + V - 1) / V * V;
+    }
+    // read-only behind everything the compute stream has run: a failure leaves the pump as it was
+    T *d_out = out_on_device ? out : reinterpret_cast<T *>(p->d_tape_out);
+    const T *h_out = reinterpret_cast<const T *>(p->h_tape_out);
+    PUMP_TRY(p, hipMemcpyAsync(p->d_tape_req, p->h_tape_req, (size_t)n * sizeof(vad::TapeRequest), hipMemcpyHostToDevice, p->compute));
+    PUMP_TRY(p, vad::launch_tape_gather(p->d_tape_req, n, (long)max_count, static_cast<const T *>(p->d_tape), p->tape_chunks, p->N, d_out, p->compute));
+    if (!out_on_device) PUMP_TRY(p, hipMemcpyAsync(p->h_tape_out, p->d_tape_out, (size_t)total * sizeof(T), hipMemcpyDeviceToHost, p->compute));
+    PUMP_TRY(p, hipStreamSynchronize(p->compute));
+    for (long i = 0; i < n && !out_on_device; ++i)       // exactly count[i] samples each: what lies between the requests is not touched
+        if (count[i] > 0) std::memcpy(out + out_offset[i], h_out + p->h_tape_req[i].out_offset, (size_t)count[i] * sizeof(T));
     return VAD_OK;
 }
 
@@ -1398,33 +1487,11 @@ int vad_tape_window(int64_t count, int64_t floor, int chunks, int N, int64_t sta
     return VAD_OK;
 }
 
-int vad_pump_set_tape(vad_pump *p, int chunks) {
-    if (!p) return VAD_ERR_ARG;
-    const std::string fn = "vad_pump_set_tape: ";
-    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
-    if (chunks < 2) return pfail(p, VAD_ERR_ARG, fn + "a tape holds at least 2 chunks a stream");
-    if (p->tape_chunks) return pfail(p, VAD_ERR_ARG, fn + "the pump has its tape already");
-    if (p->ticks > 0) return pfail(p, VAD_ERR_ARG, fn + "only before the pump's first tick: the tape's clock is the count of every chunk stepped");
-    if (p->n_rates)                              // (a resampled tick steps an fp32 batch: an int16 tape of it would not be what the net saw)
-        return pfail(p, VAD_ERR_ARG, fn + "the pump takes resampled rows (vad_pump_set_resample), and the tape does not hold that route's fp32 chunks");
-    PUMP_TRY(p, hipSetDevice(p->device));
-    const size_t S = (size_t)p->streams;
-    int16_t *tape = nullptr;
-    int64_t *clock = nullptr;
-    const bool ok = hipMalloc((void **)&tape, S * (size_t)chunks * p->N * sizeof(int16_t)) == hipSuccess &&
-                    hipMalloc((void **)&clock, S * 2 * sizeof(int64_t)) == hipSuccess &&
-                    hipMemset(clock, 0, S * 2 * sizeof(int64_t)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
-        if (tape) (void)hipFree(tape);
-        if (clock) (void)hipFree(clock);
-        (void)hipGetLastError();
-        return pfail(p, VAD_ERR_ALLOC, fn + "no device memory for streams x chunks x N samples");
-    }
-    p->d_tape = tape, p->d_tape_clock = clock;
-    p->tape_clock.assign(S * 2, 0);
-    p->tape_chunks = chunks;
-    return VAD_OK;
-}
+int vad_pump_set_tape(vad_pump *p, int chunks) { return tape_set(p, chunks, (int)sizeof(int16_t), "vad_pump_set_tape: "); }
+
+int vad_pump_set_tape_f32(vad_pump *p, int chunks) { return tape_set(p, chunks, (int)sizeof(float), "vad_pump_set_tape_f32: "); }
+
+int vad_pump_tape_format(const vad_pump *p) { return p ? p->tape_elem : -VAD_ERR_ARG; }
 
 int vad_pump_tape_state(vad_pump *p, int stream, int64_t *count, int64_t *floor) {
     if (!p) return VAD_ERR_ARG;
@@ -1457,45 +1524,12 @@ long vad_pump_tape_window(vad_pump *p, const int32_t *stream, const int64_t *sta
 
 int vad_pump_fetch_audio(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
                          int16_t *out, int out_on_device) {
-    if (!p) return VAD_ERR_ARG;
-    const std::string fn = "vad_pump_fetch_audio: ";
-    if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
-    if (!p->tape_chunks) return pfail(p, VAD_ERR_ARG, fn + "the pump has no tape (vad_pump_set_tape)");
-    if (n < 0 || (n > 0 && (!stream || !first || !count || !out_offset))) return pfail(p, VAD_ERR_ARG, fn + "bad request list");
-    int64_t max_count = 0, total = 0;
-    for (long i = 0; i < n; ++i) {
-        if (stream[i] < 0 || stream[i] >= p->streams) return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": no such stream");
-        if (count[i] < 0 || out_offset[i] < 0) return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": a negative count or offset");
-        max_count = std::max(max_count, count[i]);
-    }
-    if (max_count == 0) return VAD_OK;           // (nothing to copy: no request has a sample)
-    if (!out) return pfail(p, VAD_ERR_ARG, fn + "no destination");
-    if (const int rc = tape_read_clock(p)) return rc;
-    // the same rule, against the counters as they are NOW: a tick submitted since vad_pump_tape_window may have taped over the range
-    for (long i = 0; i < n; ++i) {
-        if (count[i] == 0) continue;
-        const int64_t *c = p->tape_clock.data() + 2 * (size_t)stream[i];
-        const int64_t lo = vad::tape_held_lo(c[0], c[1], p->tape_chunks, p->N), hi = vad::tape_held_hi(c[0], p->N);
-        if (first[i] < lo || first[i] > hi || count[i] > hi - first[i])
-            return pfail(p, VAD_ERR_ARG, fn + "request " + std::to_string(i) + ": samples " + std::to_string(first[i]) + " ... of stream " +
-                                             std::to_string(stream[i]) + " are no longer held (the tape holds " + std::to_string(lo) + " ... " +
-                                             std::to_string(hi) + ")");
-        total += (count[i] + 7) / 8 * 8;
-    }
-    if (const int rc = tape_reserve(p, (size_t)n, out_on_device ? 0 : (size_t)total)) return rc;
-    int64_t at = 0;
-    for (long i = 0; i < n; ++i) {               // host destination: packed on the device, every request 16-byte aligned
-        p->h_tape_req[i] = vad::TapeRequest{stream[i], first[i], count[i], out_on_device ? out_offset[i] : at};
-        at += (count[i] + 7) / 8 * 8;
-    }
-    // read-only behind everything the compute stream has run: a failure leaves the pump as it was
-    PUMP_TRY(p, hipMemcpyAsync(p->d_tape_req, p->h_tape_req, (size_t)n * sizeof(vad::TapeRequest), hipMemcpyHostToDevice, p->compute));
-    PUMP_TRY(p, vad::launch_tape_gather(p->d_tape_req, n, (long)max_count, p->d_tape, p->tape_chunks, p->N, out_on_device ? out : p->d_tape_out, p->compute));
-    if (!out_on_device) PUMP_TRY(p, hipMemcpyAsync(p->h_tape_out, p->d_tape_out, (size_t)total * sizeof(int16_t), hipMemcpyDeviceToHost, p->compute));
-    PUMP_TRY(p, hipStreamSynchronize(p->compute));
-    for (long i = 0; i < n && !out_on_device; ++i)       // exactly count[i] samples each: what lies between the requests is not touched
-        if (count[i] > 0) std::memcpy(out + out_offset[i], p->h_tape_out + p->h_tape_req[i].out_offset, (size_t)count[i] * sizeof(int16_t));
-    return VAD_OK;
+    return tape_fetch(p, stream, first, count, n, out_offset, out, out_on_device, "vad_pump_fetch_audio: ");
+}
+
+int vad_pump_fetch_audio_f32(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
+                             float *out, int out_on_device) {
+    return tape_fetch(p, stream, first, count, n, out_offset, out, out_on_device, "vad_pump_fetch_audio_f32: ");
 }
 
 }  // extern "C"

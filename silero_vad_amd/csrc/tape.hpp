@@ -1,7 +1,7 @@
 // tape.hpp -- which samples of a live stream the pump's tape still holds, written once for the host (pump.hip: vad_tape_window,
 // vad_pump_tape_window, vad_pump_fetch_audio) and for the device (kernel_tape.hip).
 //
-// The tape of a stream is a ring of `chunks` chunks of N int16 samples.  Two counters describe it: `count`, the chunks stepped since the
+// The tape of a stream is a ring of `chunks` chunks of N samples (int16, or float32: nothing here depends on the element).  Two counters describe it: `count`, the chunks stepped since the
 // stream's clock started (vad_pump_open, or the chunk an import continued at), and `floor`, the first chunk the tape can hold (0 after
 // an open; the chunk an import continued at).  Chunk k lies in ring slot k % chunks, so sample s of the stream's clock lies at element
 // s % (chunks * N) of its ring, and the tape holds the samples

@@ -3280,10 +3280,22 @@ def tape_window(count: int, floor: int, chunks: int, n: int, start: int, end: in
     return first.value, m.value
 
 
+def _tape_dtype(dtype) -> np.dtype:
+    """The tape's element, int16 or float32, from anything np.dtype() takes; anything else raises (before any native call)."""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        dt = None
+    if dt is None or dtype is None or dt not in (np.dtype(np.int16), np.dtype(np.float32)):
+        raise ValueError(f"tape_dtype must be int16 or float32, got {dtype!r}")
+    return dt
+
+
 class UtteranceCollector:
     """The utterances behind a taped pump's events: `feed(events)` takes what `pump.poll()` returned, remembers each stream's `start`
-    and returns, for every `end`, (stream, start, end, first, audio) -- audio the int16 samples [first, end) of the stream as the net
-    heard them, first > start where the head of a long utterance had already left the tape.  All ENDs of one `feed` are fetched in
+    and returns, for every `end`, (stream, start, end, first, audio) -- audio the samples [first, end) of the stream as the net heard
+    them, in the tape's dtype (int16, or float32 in [-1, 1) with `tape_dtype="float32"`, the only tape of the resampled route),
+    first > start where the head of a long utterance had already left the tape.  All ENDs of one `feed` are fetched in
     one `fetch_audio` call.  An END whose START was never fed comes back as (stream, None, end, None, None).  `forget(stream)` drops a
     remembered START: call it with `pump.open_stream(stream)`, the slot's new stream starts a new clock."""
 
@@ -3358,17 +3370,21 @@ class StreamPump:
     one; the sample numbers of the events are tape positions, `fetch_audio(streams, starts, ends)` copies any still-held ranges out
     (to numpy arrays, or with device=True into one packed tensor on the pump's GPU) and `UtteranceCollector(pump).feed(events)` hands
     back the utterance behind every `end`.  A sample stays fetchable for K chunks of its stream (ticks in flight count):
-    K = longest utterance + pad + ring_slots x max_burst; the tape costs streams x K x N x 2 bytes.
+    K = longest utterance + pad + ring_slots x max_burst; the tape costs streams x K x N x 2 bytes.  With `tape_dtype="float32"` the
+    tape holds what the net read, float32 in [-1, 1) (x / 32768 of an int16 sample, exact), at 4 bytes a sample: it also tapes the
+    resampled route, bit for bit `resample_device` of what the stream was fed, and goes together with `set_resample`; utterances come
+    out as float32, on the device if wanted, the form a model on the same GPU takes.  `tape_dtype` says which tape the pump has.
 
     `play(rows, ...)` runs the whole loop natively over memory-resident recordings (tests, benchmarks, file-fed servers)."""
 
     def __init__(self, engine, sampling_rate: int = 16000, streams: int = 8192, parts: int = 0, ring_slots: int = 0,
                  threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1, source_rate=None,
-                 tape_chunks: int = 0):
+                 tape_chunks: int = 0, tape_dtype="int16"):
         _no_source_rate(source_rate, "StreamPump")
         if isinstance(tape_chunks, (bool, np.bool_)) or not isinstance(tape_chunks, (int, np.integer)) or tape_chunks < 0 or tape_chunks == 1 \
                 or tape_chunks >= 2 ** 31:
             raise ValueError(f"tape_chunks must be 0 (no tape) or 2 ... 2^31 - 1 chunks a stream, got {tape_chunks!r}")
+        tape_dtype = _tape_dtype(tape_dtype)                     # (with tape_chunks == 0 it is only validated)
         if sampling_rate not in (8000, 16000):
             raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
         if not isinstance(max_burst, (int, np.integer)) or not 1 <= max_burst <= 8:
@@ -3396,10 +3412,11 @@ class StreamPump:
                 self._h = None
                 raise _lib.VadError(rc, msg)
         self.tape_chunks = 0
+        self.tape_dtype = None
         self.device = getattr(engine, "device", 0)
         if tape_chunks:                                          # (0: no tape, nothing is allocated or launched for it)
             try:
-                self.set_tape(int(tape_chunks))
+                self.set_tape(int(tape_chunks), tape_dtype)
             except Exception:
                 self._L.vad_pump_destroy(h)
                 self._h = None
@@ -3699,7 +3716,9 @@ class StreamPump:
         """Enable RESAMPLED packet ticks (vad_pump_set_resample): rows sampled at one of `rates` -- 1 ... 4 distinct source rates that
         `resample_geometry(rate, the pump's rate)` serves, e.g. (44100, 24000, 22050) -- on a pump with no tick in flight.  Allocates the
         resample slots ([streams * A] int16 each, A = the input samples of one chunk at the largest rate, rounded up to 8), their device
-        buffers, the fp32 batch and carry and every stream's filter history."""
+        buffers, the fp32 batch and carry and every stream's filter history.  Goes together with a float32 tape (`tape_dtype="float32"`),
+        in either order, and leaves that tape and its clocks alone; refused on a pump with the int16 tape, which cannot hold this route's
+        fp32 chunks."""
         rt = [r for r in rates]
         if not 1 <= len(rt) <= 4 or not all(isinstance(r, (int, np.integer)) and not isinstance(r, (bool, np.bool_)) and 0 < r < 2 ** 31 for r in rt):
             raise ValueError(f"rates must be 1 ... 4 (VAD_PUMP_MAX_RATES) positive integers, got {rates!r}")
@@ -3832,11 +3851,16 @@ class StreamPump:
         self._check(self._L.vad_pump_state(self._h, int(stream), h.ctypes.data, c.ctypes.data, x.ctypes.data))
         return h, c, x
 
-    def set_tape(self, chunks: int):
-        """Enable the tape (vad_pump_set_tape; what `StreamPump(..., tape_chunks=chunks)` calls): once, before the first tick, chunks
-        >= 2, not together with `set_resample`.  Allocates streams x chunks x N int16 samples on the device."""
-        self._check(self._L.vad_pump_set_tape(self._h, int(chunks)))
+    def set_tape(self, chunks: int, dtype="int16"):
+        """Enable the tape (vad_pump_set_tape / vad_pump_set_tape_f32; what `StreamPump(..., tape_chunks=chunks, tape_dtype=dtype)` calls):
+        once, before the first tick, chunks >= 2; a pump has one tape.  dtype "int16": streams x chunks x N int16 samples on the device,
+        not together with `set_resample`.  dtype "float32": 4 bytes a sample, every route taped as the net read it -- also the resampled
+        one, with `set_resample` before or after this call."""
+        dt = _tape_dtype(dtype)
+        call = self._L.vad_pump_set_tape_f32 if dt == np.float32 else self._L.vad_pump_set_tape
+        self._check(call(self._h, int(chunks)))
         self.tape_chunks = int(chunks)
+        self.tape_dtype = dt
 
     def tape_state(self, stream: int):
         """(count, floor) of `stream`'s tape: the chunks stepped since its clock started (count * N is the iterator's current_sample)
@@ -3867,48 +3891,53 @@ class StreamPump:
         return first, count
 
     def fetch_audio_into(self, streams, first, counts, out, out_offsets):
-        """counts[i] samples from sample first[i] of streams[i] to out[out_offsets[i] : ...] (vad_pump_fetch_audio): `out` is a flat
-        C-contiguous int16 numpy array, or a flat contiguous int16 torch tensor on the pump's GPU.  Exactly those samples are written.
-        Offsets that are multiples of 8 (of a 16-byte aligned `out`) take the gather kernel's 16-byte stores.  A range that is not
-        wholly inside its stream's window as it is NOW raises ("no longer held") and nothing is written."""
+        """counts[i] samples from sample first[i] of streams[i] to out[out_offsets[i] : ...] (vad_pump_fetch_audio, or vad_pump_fetch_audio_f32
+        on a float32 tape): `out` is a flat C-contiguous numpy array of the tape's dtype (`tape_dtype`: int16 or float32), or a flat
+        contiguous tensor of that dtype on the pump's GPU.  Exactly those samples are written.  Offsets that are multiples of 16 bytes
+        (8 int16 samples, 4 floats; of a 16-byte aligned `out`) take the gather kernel's 16-byte stores.  A range that is not wholly
+        inside its stream's window as it is NOW raises ("no longer held") and nothing is written."""
         st, fi, ct, of = (_int32_rows(streams, "streams"), self._int64_rows(first, "first"), self._int64_rows(counts, "counts"),
                           self._int64_rows(out_offsets, "out_offsets"))
         if not len(st) == len(fi) == len(ct) == len(of):
             raise ValueError(f"streams, first, counts and out_offsets must have one entry per request, got {len(st)}, {len(fi)}, {len(ct)}, {len(of)}")
+        f32 = self.tape_dtype == np.float32                      # (a pump without a tape: the int16 call refuses it)
+        name, np_dt, torch_dt = ("float32", np.float32, torch.float32) if f32 else ("int16", np.int16, torch.int16)
         on_device = isinstance(out, torch.Tensor)
         if on_device:
-            if out.dtype != torch.int16 or out.dim() != 1 or not out.is_contiguous() or out.device != torch.device("cuda", self.device):
-                raise ValueError(f"out must be a flat contiguous int16 tensor on cuda:{self.device}")
+            if out.dtype != torch_dt or out.dim() != 1 or not out.is_contiguous() or out.device != torch.device("cuda", self.device):
+                raise ValueError(f"out must be a flat contiguous {name} tensor on cuda:{self.device}")
             size, ptr = out.numel(), out.data_ptr()
         else:
-            if not isinstance(out, np.ndarray) or out.dtype != np.int16 or out.ndim != 1 or not out.flags.c_contiguous or not out.flags.writeable:
-                raise ValueError("out must be a flat, writeable, C-contiguous int16 numpy array (or an int16 tensor on the pump's GPU)")
+            if not isinstance(out, np.ndarray) or out.dtype != np_dt or out.ndim != 1 or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError(f"out must be a flat, writeable, C-contiguous {name} numpy array (or a {name} tensor on the pump's GPU)")
             size, ptr = out.size, out.ctypes.data
         if len(st) and (ct.min() < 0 or of.min() < 0 or int((of + ct).max()) > size):
             raise ValueError("a request's samples do not fit into out")
         n = len(st)
-        self._check(self._L.vad_pump_fetch_audio(self._h, *[x.ctypes.data if n else None for x in (st, fi, ct)], n, of.ctypes.data if n else None,
-                                                 ptr if size else None, 1 if on_device else 0))
+        fetch = self._L.vad_pump_fetch_audio_f32 if f32 else self._L.vad_pump_fetch_audio
+        self._check(fetch(self._h, *[x.ctypes.data if n else None for x in (st, fi, ct)], n, of.ctypes.data if n else None,
+                          ptr if size else None, 1 if on_device else 0))
 
     def fetch_audio(self, streams, starts, ends, device: bool = False):
         """The audio of [starts[i], ends[i]) of streams[i]'s sample clock -- the clock of the events -- as far as the tape still holds
-        it: -> (audios, first).  audios[i] is an int16 numpy array of the samples [first[i], first[i] + len(audios[i])); first[i] >
-        starts[i] means the head of the range was no longer held.  device=True: audios is (packed, offsets, counts) instead -- ONE int16
-        tensor on the pump's GPU, request i at packed[offsets[i] : offsets[i] + counts[i]] (every offset a multiple of 8 samples), for a
-        consumer on the same GPU; nothing crosses the link.  A stream may appear in any number of requests.  Raises without a tape, for
-        a stream out of range and for starts[i] > ends[i]."""
+        it: -> (audios, first).  audios[i] is a numpy array of the tape's dtype (int16, or float32 in [-1, 1)) of the samples [first[i],
+        first[i] + len(audios[i])); first[i] > starts[i] means the head of the range was no longer held.  device=True: audios is (packed,
+        offsets, counts) instead -- ONE tensor of that dtype on the pump's GPU, request i at packed[offsets[i] : offsets[i] + counts[i]]
+        (every offset a multiple of 8 samples), for a consumer on the same GPU; nothing crosses the link.  A stream may appear in any
+        number of requests.  Raises without a tape, for a stream out of range and for starts[i] > ends[i]."""
         first, count = self.tape_windows(streams, starts, ends)
         offsets = np.zeros(len(count), np.int64)
         if len(count):
             offsets[1:] = np.cumsum((count[:-1] + 7) // 8 * 8)
         total = int(offsets[-1] + count[-1]) if len(count) else 0
+        f32 = self.tape_dtype == np.float32
         if device:
             with torch.cuda.device(self.device):
-                packed = torch.empty(total, dtype=torch.int16, device=torch.device("cuda", self.device))
+                packed = torch.empty(total, dtype=torch.float32 if f32 else torch.int16, device=torch.device("cuda", self.device))
                 torch.cuda.current_stream().synchronize()        # (the pump writes on its own stream: the allocation is settled first)
             self.fetch_audio_into(streams, first, count, packed, offsets)
             return (packed, offsets, count), first
-        packed = np.empty(total, np.int16)
+        packed = np.empty(total, np.float32 if f32 else np.int16)
         self.fetch_audio_into(streams, first, count, packed, offsets)
         return [packed[o:o + c] for o, c in zip(offsets.tolist(), count.tolist())], first
 
