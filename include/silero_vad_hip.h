@@ -677,8 +677,10 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * counters in compute-stream order, behind the ticks in flight, exactly as it zeroes (h, c): so for every open stream count * N is
  * the iterator's current_sample at every tick boundary, and the sample numbers of the events ARE tape positions.  vad_pump_close
  * changes nothing (a closed stream that a full tick still steps is taped; the next open restarts its clock).  vad_pump_import_streams
- * into a pump with a tape sets count = floor = current_sample / N of the record: the clock continues, nothing before the import is held.
- * Snapshot blobs do not carry the tape: versions 1 and 2 are unchanged, and a pump with a tape exports the bytes one without it does.
+ * into a pump with a tape sets count = current_sample / N of the record: the clock continues; a version 1 or 2 record sets floor = count,
+ * nothing before the import is held, a version 3 record that carries a run of the source's tape sets floor = count - the chunks kept.
+ * Snapshot blobs of versions 1 and 2 do not carry the tape: they are unchanged, and a pump with a tape exports the bytes one without it
+ * does.  Blob version 3 (SNAPSHOT AND RESTORE below) carries, per stream, the newest whole chunks from a sample position the caller names.
  *
  * THE WINDOW.  With held_lo = max(floor, count - chunks) * N and held_hi = count * N the tape holds the samples [held_lo, held_hi) of
  * the stream's clock.  A request [start, end), start <= end, of ANY int64 values is confined to it:
@@ -686,6 +688,13 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * (csrc/tape.hpp, the one source of the rule).  first > start: the head of the range is no longer held (or lies before the clock).
  * vad_tape_window: the rule for given counters -> *first, *n.  Host only, re-entrant, no GPU.  VAD_ERR_ARG: start > end, chunks < 2,
  * N < 1, count < 0, or counters whose product with N is no int64.
+ * THE RUN a version 3 snapshot carries for a stream is whole chunks, from the chunk that holds sample `from` to the newest one, as far as
+ * the tape holds them: with held_lo = max(floor, count - chunks), in CHUNKS,
+ *     first_chunk = min(max(from / N, held_lo), count),  n_chunks = count - first_chunk
+ * where `from` is clamped into [held_lo * N, count * N] before it is divided: any int64 is legal (a negative value or one before the
+ * window gives everything held, one at or behind count * N gives nothing), and a position in the middle of a chunk rounds down to its
+ * chunk.  vad_tape_run: that rule for given counters -> *first_chunk, *n_chunks.  Host only, re-entrant, no GPU.  VAD_ERR_ARG: chunks < 2,
+ * N < 1, count < 0, floor < 0, or counters whose product with N is no int64.
  *
  * vad_pump_set_tape: once, before the pump's first tick, chunks >= 2 (any value, not only powers of two).  Allocates
  * [streams][chunks][N] int16 and the counters, all zero.  VAD_ERR_ARG with nothing changed: after a tick was submitted, a second call,
@@ -722,7 +731,7 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * over int16 rows (full, masked, compact, rows, packets, coded, burst sub-steps, wide) tapes (float)x * (1.0f / 32768.0f), the value the
  * frontend computes from that sample, exact, in [-1, 1).  Bound and unbound streams of one pump share the one tape.  A second
  * vad_pump_set_resample with other rates unbinds every stream, as ever, and leaves the tape and its clocks alone.  The clock, the window
- * rule, vad_pump_open / close / import_streams, the exports (which do not carry it) and vad_tape_window / vad_pump_tape_window /
+ * rule, vad_pump_open / close / import_streams, the exports (versions 1 and 2 do not carry it, version 3 carries its floats as they are) and vad_tape_window / vad_pump_tape_window /
  * vad_pump_tape_state are those of the int16 tape: none of them depends on the element.
  * SIZING.  streams x chunks x N x 4 bytes: 8192 streams x 512 chunks = 8.6 GB.
  * vad_pump_fetch_audio_f32: the contract of vad_pump_fetch_audio with "sample" meaning one float -- it synchronises, re-checks every
@@ -734,6 +743,7 @@ int  vad_pump_state(vad_pump *p, int stream, float *h, float *c, float *ctx);
  * vad_pump_tape_format: 0 = no tape, 2 = the int16 tape, 4 = the fp32 tape (the element's size in bytes); -VAD_ERR_ARG for NULL.  Host
  * only, no synchronisation.                                                                                                          */
 int  vad_tape_window(int64_t count, int64_t floor, int chunks, int N, int64_t start, int64_t end, int64_t *first, int64_t *n);
+int  vad_tape_run(int64_t count, int64_t floor, int chunks, int N, int64_t from, int64_t *first_chunk, int64_t *n_chunks);
 int  vad_pump_set_tape(vad_pump *p, int chunks);
 long vad_pump_tape_window(vad_pump *p, const int32_t *stream, const int64_t *start, const int64_t *end, long n, int64_t *first, int64_t *count);
 int  vad_pump_fetch_audio(vad_pump *p, const int32_t *stream, const int64_t *first, const int64_t *count, long n, const int64_t *out_offset,
@@ -774,8 +784,9 @@ int  vad_pump_tape_format(const vad_pump *p);
  * A record does not name the slot it came from.  Reserved bytes are written as zero and a reader refuses a record in which they are not;
  * samples behind `pending` are written as zero and ignored when read.  Two exports with no tick between them are byte for byte the same.
  * NOT carried: ticks in flight (there are none: see below), the position counter of the vad_pump_play* helpers (it restarts as after
- * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), the tape (THE TAPE above: a pump with a tape
- * writes the same bytes, and an import restarts the slot's tape at the record's current_sample), and the model weights.
+ * vad_pump_open), burst / wideband being enabled (properties of a pump, not of a stream), in versions 1 and 2 the tape (THE TAPE above: a
+ * pump with a tape writes the same bytes, and an import of such a record restarts the slot's tape at the record's current_sample;
+ * version 3 below carries it), and the model weights.
  *
  * THE BLOB (version 2) carries, in addition, what a stream that is BOUND to a resampled rate holds (vad_pump_submit_resampled_packets):
  * its rate, its two counters, its fp32 pending outputs and its filter history.  vad_pump_export_streams_v2 writes it, for bound and
@@ -805,11 +816,43 @@ int  vad_pump_tape_format(const vad_pump *p);
  *   vad_stream_info.pending == 0: a bound stream has no int16 samples pending (BINDING above)
  *   reserved bytes zero; carry[pending_out : N] all bits zero; history[H : 160] zero
  * and with src_rate == 0 every other byte of the tail is zero.  A version 1 layout that merely says version 2 is refused: header_bytes
- * and stride differ.                                                                                                                */
+ * and stride differ.
+ *
+ * THE BLOB (version 3) carries, in addition, a RUN of each stream's tape (THE TAPE above): the newest whole chunks of the audio the net
+ * heard, from a sample position the caller names per stream -- typically the START of the utterance the stream is in, so that the END
+ * event on the destination finds its audio there.  vad_pump_export_streams_v3 writes it; the other two exports write what they wrote.
+ *   header, VAD_SNAPSHOT_HEADER_BYTES_V3 = 128:
+ *      0  the 64 bytes of the version 1 header, with version = VAD_SNAPSHOT_VERSION_3, header_bytes = 128 and
+ *         stride = the version 2 stride + 32 = 3104 / 4768, a multiple of 16
+ *     64  int32   tape_elem      the element of the source's tape in bytes, vad_pump_tape_format: 0 (no tape), 2 (int16), 4 (float32)
+ *     68  int32   reserved       zero
+ *     72  int64   tape_bytes     the bytes of the tape section
+ *     80  uint8   reserved[48]   zero
+ *   then n_records records of `stride` bytes, each:
+ *      0  the version 2 record, unchanged, byte for byte (S2 = the version 2 stride, 3072 / 4736 bytes)
+ *     S2  vad_tape_info (32 bytes, below)
+ *   then the TAPE SECTION, tape_bytes bytes from byte 128 + n_records * stride on: the runs of the records in record order, without
+ *   gaps or padding.  Record i's run is n_chunks * N * tape_elem bytes at `offset` from the section's start: the chunks first_chunk ...
+ *   first_chunk + n_chunks - 1 of the stream's clock, oldest first, each N elements of tape_elem bytes as the tape held them.  The blob is
+ *   EXACTLY 128 + n_records * stride + tape_bytes bytes (a version 3 blob in a longer or a shorter buffer is refused).
+ * The writer carries a run only for a stream whose tape clock is its iterator clock, count * N == current_sample -- every open stream
+ * (THE CLOCK above); any other stream, every stream of a pump without a tape, and a stream whose run is empty has an ALL-ZERO
+ * vad_tape_info.  The fields, as the writer produces them and as every reader demands them:
+ *   tape_elem 0, 2 or 4; tape_bytes >= 0; with tape_elem == 0: tape_bytes == 0 and every vad_tape_info all zero
+ *   first_chunk >= 0; 0 <= n_chunks <= tape_bytes / (N * tape_elem) less the chunks of the earlier runs (checked before anything is
+ *   multiplied); reserved bytes zero
+ *   n_chunks == 0: first_chunk == 0 and offset == 0
+ *   n_chunks > 0:  offset == the bytes of all earlier runs, and (first_chunk + n_chunks) * N == current_sample of the record
+ *   the bytes of all runs == tape_bytes, and the buffer holds exactly header + records + tape_bytes
+ * The audio itself is payload, like h and c.  The version 2 part of every record is held to the version 2 rules.  A version 2 layout
+ * that merely says version 3 is refused: header_bytes and stride differ.  Two exports with no tick between them are byte for byte the
+ * same.                                                                                                                             */
 #define VAD_SNAPSHOT_VERSION 1
 #define VAD_SNAPSHOT_HEADER_BYTES 64
 #define VAD_SNAPSHOT_VERSION_2 2
 #define VAD_SNAPSHOT_HEADER_BYTES_V2 96
+#define VAD_SNAPSHOT_VERSION_3 3
+#define VAD_SNAPSHOT_HEADER_BYTES_V3 128
 #define VAD_SNAPSHOT_HISTORY 160
 typedef struct vad_stream_info {
     int64_t current_sample;      /* VADIterator.current_sample: samples stepped since vad_pump_open; >= 0                            */
@@ -828,10 +871,20 @@ typedef struct vad_resample_info {   /* the host's part of a version 2 record's 
     int64_t outputs_mod;         /* m: outputs emitted, less the same whole periods                                                  */
     uint8_t reserved[8];         /* zero                                                                                             */
 } vad_resample_info;
+typedef struct vad_tape_info {       /* behind a version 3 record's version 2 part: its run in the tape section; the rules are stated above */
+    int64_t first_chunk;         /* the run's first chunk, a chunk number of the stream's clock; 0 with an empty run                 */
+    int64_t n_chunks;            /* whole chunks of N elements; (first_chunk + n_chunks) * N == current_sample where > 0             */
+    int64_t offset;              /* of the run in the tape section, in bytes; 0 with an empty run                                    */
+    uint8_t reserved[8];         /* zero                                                                                             */
+} vad_tape_info;
 /* Bytes of a blob of n records at sample rate sr: 64 + n * stride.  0 for a bad sr or n < 0.  Host only.  _v2: 96 + n * the version 2
  * stride.                                                                                                                           */
 size_t vad_pump_snapshot_bytes(int sr, long n);
 size_t vad_pump_snapshot_bytes_v2(int sr, long n);
+/* Bytes of a version 3 blob of n records of a tape of tape_elem-byte elements whose runs have total_chunks chunks together: 128 + n *
+ * the version 3 stride + total_chunks * N * tape_elem.  0 for a bad sr, n < 0, tape_elem other than 0 / 2 / 4, total_chunks < 0 (or
+ * > 0 with tape_elem == 0) or a size that is no size_t.  Host only.                                                                  */
+size_t vad_snapshot_bytes_v3(int sr, long n, int tape_elem, int64_t total_chunks);
 /* EXPORT: the records of streams[0 ... n - 1] (distinct slots; NULL = every slot in ascending order, and n must be the pump's stream
  * count) into blob[0 : vad_pump_snapshot_bytes(sr, n)], ordinary host memory of `cap` bytes.  Read-only: the pump and the exported
  * streams go on exactly as if the call had not happened; the caller closes them when it wants to.  Synchronous: the blob is complete on
@@ -861,18 +914,45 @@ size_t vad_pump_snapshot_bytes_v2(int sr, long n);
  * rates) and the counters g, m, c on the host; the whole fp32 carry row and the whole history row, at the destination's own pitch, on the
  * device -- zeros behind c and behind H whatever the blob and the slot held before.  Refused in addition, with nothing queued and
  * nothing changed (VAD_ERR_ARG): a record whose src_rate is not among the destination's enabled rates (a pump without the route
- * included), and -- already by vad_snapshot_inspect -- any field outside the ranges stated with the layout.                          */
+ * included), and -- already by vad_snapshot_inspect -- any field outside the ranges stated with the layout.
+ * THE TAPE IN A SNAPSHOT.  vad_pump_export_streams_v3: the version 2 export with the same rules -- idle pump, read-only, synchronous, the
+ * same refusals, the records by the same gather kernel and copy -- into a version 3 blob.  tape_from[i] is the sample position of
+ * streams[i]'s clock from which its audio is wanted (any int64; NULL: everything each stream's tape holds); the run is THE RUN of
+ * (count, floor, tape_from[i]) as the counters are then, for a stream with count * N == current_sample, and empty for any other.  A
+ * second kernel on the compute stream packs the runs on the device, in record order, and ONE more copy brings them over.  On a pump
+ * without a tape tape_from is ignored and the blob has tape_elem = 0 and no tape section.  `cap` must hold what
+ * vad_pump_snapshot_plan_v3 says: that call synchronises the compute stream, reads the counters, applies the same rule to the same
+ * arguments and returns the bytes of the blob the export would write (0, with a message: a NULL pump, a bad slot list).  It changes
+ * nothing and works with ticks in flight, but only between an idle pump's plan and its export is the figure certain to be the same.
+ * The staging of the runs, device memory, is allocated by the first export that carries one and grows on demand; a pump that never
+ * makes these calls allocates nothing for them, and no tick does anything for them.
+ * vad_pump_import_streams takes version 3 as well.  Everything a version 2 record replaces, it replaces as before.  Into a pump whose
+ * tape has the blob's element, a record with n_chunks > 0 brings its audio along: kept = min(n_chunks, the destination's chunks), the
+ * newest `kept` chunks of the run land in ring slots c % chunks of the DESTINATION's ring (whatever the source's ring length was and
+ * whatever the slot's ring held), count = current_sample / N as ever and floor = count - kept -- so vad_pump_fetch_audio on the
+ * destination returns the stream's audio across the migration point.  A record with an empty run, and every record of versions 1 and
+ * 2, leaves count = floor.  A destination without a tape ignores the tape section; a blob with tape_elem == 0 enters a taped pump like a
+ * version 2 blob.  A blob whose tape_elem and the pump's are both non-zero and DIFFER (an int16 run for an fp32 tape, or the reverse) is
+ * refused with VAD_ERR_ARG, nothing queued and nothing changed: the import does not convert.  The tape bytes of the selected records
+ * cross the link in ONE copy, the span from the first selected run to the last, and one scatter kernel puts them in place.           */
 int  vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap);
 int  vad_pump_export_streams_v2(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap);
+size_t vad_pump_snapshot_plan_v3(vad_pump *p, const int32_t *streams, long n, const int64_t *tape_from);
+int  vad_pump_export_streams_v3(vad_pump *p, const int32_t *streams, long n, const int64_t *tape_from, void *blob, size_t cap);
 int  vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const int32_t *records, const int32_t *streams, long n);
-/* Readers of a blob of either version; host only, no pump and no device needed.  vad_snapshot_inspect: validate ALL of blob[0 : nbytes]
- * (header and every record's fields; version 2: also every byte that has to be zero) -> VAD_OK and *n_records, *sr (either may be
+/* Readers of a blob of any version; host only, no pump and no device needed.  vad_snapshot_inspect: validate ALL of blob[0 : nbytes]
+ * (header and every record's fields; versions 2 and 3: also every byte that has to be zero; version 3: every vad_tape_info, the sums and
+ * the buffer's exact size) -> VAD_OK and *n_records, *sr (either may be
  * NULL), or VAD_ERR_ARG.  vad_snapshot_stream: the version 1 part of record i of a valid blob -> *info, h[128], c[128], ctx[C],
  * pending[N] (any may be NULL); VAD_ERR_ARG for an invalid blob or i out of range.  vad_snapshot_resample: the tail of record i ->
- * *info, carry[N], history[VAD_SNAPSHOT_HISTORY] (any may be NULL); a version 1 blob has no tail: all three come back zero.          */
+ * *info, carry[N], history[VAD_SNAPSHOT_HISTORY] (any may be NULL); a version 1 blob has no tail: all three come back zero.
+ * vad_snapshot_tape: the run of record i -> *info and, with audio != NULL, its n_chunks * N * tape_elem bytes to audio[0 : cap]
+ * (VAD_ERR_ARG with nothing written if cap, in bytes, is smaller; the element is tape_elem at byte 64 of the header).  A blob of
+ * version 1 or 2 has no runs: *info comes back zero and nothing is written to audio.                                                 */
 int  vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr);
 int  vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info *info, float *h, float *c, float *ctx, int16_t *pending);
 int  vad_snapshot_resample(const void *blob, size_t nbytes, long i, vad_resample_info *info, float *carry, int16_t *history);
+int  vad_snapshot_tape(const void *blob, size_t nbytes, long i, vad_tape_info *info, void *audio, size_t cap);
 
 /* The whole loop in one native call -- for tests, benchmarks and file-fed servers: stream b plays rows[b * ld ...] circularly with
  * period `period` samples (a multiple of N): at tick t its chunk is rows[b * ld + (t * N) % period ...].  `fill_threads` SOURCE

@@ -61,6 +61,11 @@ class ResampleInfo(Structure):
                 ("reserved", ctypes.c_uint8 * 8)]
 
 
+class TapeInfo(Structure):
+    """vad_tape_info: behind a version 3 snapshot record's version 2 part, the stream's run in the blob's tape section."""
+    _fields_ = [("first_chunk", c_int64), ("n_chunks", c_int64), ("offset", c_int64), ("reserved", ctypes.c_uint8 * 8)]
+
+
 # every symbol include/silero_vad_hip.h declares: name -> (restype, argtypes)
 f32p, i16p = POINTER(c_float), POINTER(c_int16)
 SYMBOLS = {
@@ -117,6 +122,7 @@ SYMBOLS = {
     "vad_pump_close": (c_int, [c_void_p, c_int]),
     "vad_pump_state": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vad_tape_window": (c_int, [c_int64, c_int64, c_int, c_int, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
+    "vad_tape_run": (c_int, [c_int64, c_int64, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "vad_pump_set_tape": (c_int, [c_void_p, c_int]),
     "vad_pump_tape_window": (c_long, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "vad_pump_fetch_audio": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int]),
@@ -132,6 +138,10 @@ SYMBOLS = {
     "vad_pump_snapshot_bytes_v2": (c_size_t, [c_int, c_long]),
     "vad_pump_export_streams_v2": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_size_t]),
     "vad_snapshot_resample": (c_int, [c_void_p, c_size_t, c_long, POINTER(ResampleInfo), c_void_p, c_void_p]),
+    "vad_snapshot_bytes_v3": (c_size_t, [c_int, c_long, c_int, c_int64]),
+    "vad_pump_snapshot_plan_v3": (c_size_t, [c_void_p, c_void_p, c_long, c_void_p]),
+    "vad_pump_export_streams_v3": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_size_t]),
+    "vad_snapshot_tape": (c_int, [c_void_p, c_size_t, c_long, POINTER(TapeInfo), c_void_p, c_size_t]),
     "vad_pump_play": (c_long, [c_void_p, c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_void_p, c_long, POINTER(PumpStats)]),
     "vad_forward_audio": (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_long, c_void_p, c_void_p,
                                   c_void_p, c_long, c_void_p]),

@@ -173,10 +173,26 @@ hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart 
 // hist_ld a multiple of 8 (the pump's own pitch: the record's is always kSnapHistory); both null on a pump without the resampled route,
 // whose table may hold no bound entry.
 constexpr int kSnapHistory = 160;            // == kResampleMaxTaps: H = K - 1 of every served pair fits
+// extra_bytes (a multiple of 16; blob version 3: the 32 bytes of vad_tape_info, the host's): each record is that much longer -- gather2
+// writes the extra bytes as zeros, scatter2 skips them.
 hipError_t launch_snapshot_gather2(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, const float *fcarry,
-                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s);
+                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s, int extra_bytes = 0);
 hipError_t launch_snapshot_scatter2(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, float *fcarry, int16_t *hist,
-                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s);
+                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s, int extra_bytes = 0);
+// Blob version 3 (vad_pump_export_streams_v3): the RUNS of the pump's tape (kernel_tape.hip) that a snapshot carries.  runs[i] = {slot b,
+// n whole chunks, the first of them (a chunk number of the stream's clock, >= 0), where the run starts in `packed` (in chunks)}, all
+// range-checked by the host: n <= chunks, slot b inside the tape, [at, at + n) inside `packed`.  gather: packed[at + k] <- tape[b][(first
+// + k) % chunks]; scatter: the reverse, into the ring of a tape of `chunks` chunks (the destination's own).  elem: 2 (int16) or 4
+// (float); tape and packed are 16-byte aligned and N % 8 == 0, so every row is whole 16-byte vectors on both sides.  HBM to HBM.
+struct SnapRun {
+    int32_t slot, n;
+    int64_t first, at;
+    int64_t pad;
+};
+hipError_t launch_snapshot_tape_gather(const SnapRun *runs, long n_runs, long max_n, const void *tape, int chunks, int N, int elem, void *packed,
+                                       hipStream_t s);
+hipError_t launch_snapshot_tape_scatter(const SnapRun *runs, long n_runs, long max_n, void *tape, int chunks, int N, int elem, const void *packed,
+                                        hipStream_t s);
 
 // The comb of the reference's decimation x[::step] (src/silero_vad/utils_vad.py:39-42) over a stream that arrives in pieces: input sample g
 // of the stream is kept iff g % step == 0; `phase` = (samples that came before the piece) % step.  The one definition the pump's

@@ -24,9 +24,16 @@
 // carry row and the WHOLE history row -- zeros behind c and behind H whatever the record and the slot held -- at the destination's own
 // history pitch, which need not be the source's.  The history lies at the start of its row, oldest sample first, where
 // assemble_resampled_packets (kernel_present.hip) reads and writes it.
+//
+// Blob version 3 (vad_pump_export_streams_v3) carries, behind the records, a RUN of each stream's tape (kernel_tape.hip): whole chunks,
+// the newest ones, from a position the caller names (tape_run of tape.hpp).  Its record is the version 2 record followed by the 32 bytes
+// of vad_tape_info, the host's: gather2 / scatter2 take the count of such extra vectors, write them as zeros and skip them.  The runs
+// themselves are moved by snapshot_tape_gather_kernel / snapshot_tape_scatter_kernel below, between a stream's ring and a staging buffer
+// that holds the runs packed in record order -- the blob's tape section, which crosses the link in one copy.
 #include <hip/hip_runtime.h>
 
 #include "device_api.hpp"
+#include "tape.hpp"
 
 namespace vad {
 namespace {
@@ -113,7 +120,7 @@ __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_scatter_kernel(const
 __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_gather2_kernel(const int4 *__restrict__ table, long n, const SnapPart *__restrict__ parts,
                                                                            const f32x4 *__restrict__ ctx, const i16x8 *__restrict__ carry,
                                                                            const f32x4 *__restrict__ fcarry, const i16x8 *__restrict__ hist, int cv, int nv,
-                                                                           int fv, int hv, f32x4 *__restrict__ rec) {
+                                                                           int fv, int hv, int xv, f32x4 *__restrict__ rec) {
     const long i = (long)blockIdx.x * kSnapWaves + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (i >= n) return;
@@ -121,13 +128,14 @@ __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_gather2_kernel(const
     const SnapPart pt = parts[e.y];
     const size_t row = (size_t)(e.x - pt.lo);
     const f32x4 *h = reinterpret_cast<const f32x4 *>(pt.state + row * 128), *c = reinterpret_cast<const f32x4 *>(pt.state + ((size_t)pt.n + row) * 128);
-    const int v1 = kInfoVec + 2 * kStateVec + cv + nv, total = v1 + kTailInfoVec + fv + kTailHistVec;
+    const int v1 = kInfoVec + 2 * kStateVec + cv + nv, v2 = v1 + kTailInfoVec + fv + kTailHistVec, total = v2 + xv;
     const int live = t.z ? t.x : 0, H = t.z ? t.y : 0;         // (an unbound stream: fcarry / hist may be null, and are not read)
     f32x4 *out = rec + (size_t)e.w * total;
     for (int v = lane; v < total; v += 64) {
-        if (v >= v1) {                           // the tail: zeros for the host's block, the live carry, the live history
+        if (v >= v1) {                           // the tail: zeros for the host's block, the live carry, the live history; zeros for the xv vectors behind it
             const int w = v - v1 - kTailInfoVec;
-            if (w >= fv) reinterpret_cast<i16x8 *>(out)[v] = pending_vec(hist + (size_t)e.x * hv, w - fv, H);
+            if (v >= v2) out[v] = f32x4{};
+            else if (w >= fv) reinterpret_cast<i16x8 *>(out)[v] = pending_vec(hist + (size_t)e.x * hv, w - fv, H);
             else out[v] = w >= 0 ? live_vec(fcarry + (size_t)e.x * fv, w, live) : f32x4{};
             continue;
         }
@@ -147,7 +155,7 @@ __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_gather2_kernel(const
 // hv: the DESTINATION's history pitch in vectors.  A bound record writes carry vectors [0, fv) and history vectors [0, hv) of the slot.
 __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_scatter2_kernel(const int4 *__restrict__ table, long n, const SnapPart *__restrict__ parts,
                                                                             f32x4 *__restrict__ ctx, i16x8 *__restrict__ carry, f32x4 *__restrict__ fcarry,
-                                                                            i16x8 *__restrict__ hist, int cv, int nv, int fv, int hv,
+                                                                            i16x8 *__restrict__ hist, int cv, int nv, int fv, int hv, int xv,
                                                                             const f32x4 *__restrict__ rec) {
     const long i = (long)blockIdx.x * kSnapWaves + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -156,7 +164,7 @@ __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_scatter2_kernel(cons
     const SnapPart pt = parts[e.y];
     const size_t row = (size_t)(e.x - pt.lo);
     f32x4 *h = reinterpret_cast<f32x4 *>(pt.state + row * 128), *c = reinterpret_cast<f32x4 *>(pt.state + ((size_t)pt.n + row) * 128);
-    const int v1 = kInfoVec + 2 * kStateVec + cv + nv, stride = v1 + kTailInfoVec + fv + kTailHistVec;
+    const int v1 = kInfoVec + 2 * kStateVec + cv + nv, stride = v1 + kTailInfoVec + fv + kTailHistVec + xv;
     const f32x4 *in = rec + (size_t)e.w * stride;
     for (int v = kInfoVec + lane; v < v1; v += 64) {
         const int u = v - kInfoVec - 2 * kStateVec;
@@ -172,6 +180,69 @@ __global__ void __launch_bounds__(64 * kSnapWaves) snapshot_scatter2_kernel(cons
         if (w < fv) fcarry[(size_t)e.x * fv + w] = live_vec(in_carry, w, t.x);
         else hist[(size_t)e.x * hv + (w - fv)] = pending_vec(in_hist, w - fv, w - fv < kTailHistVec ? t.y : 0);
     }
+}
+
+// Version 3: the runs of the tape.  One item = (run r, group g): chunks [4 g, 4 g + 4) of the run, one wave; the items of a launch are
+// n_runs x groups (groups = the longest run's), dealt over a grid-stride loop, and a group behind its run's last chunk is left at once.
+// A row is rv = N * ELEM / 16 vectors (32 ... 128): lane l moves vectors l and, on the fp32 tape, l + 64 of each of the group's rows --
+// every one an aligned 16-byte load and an aligned 16-byte store, all of the item's loads in front of its first store.  The run's entry is
+// wave-uniform and read in place from the host's mapped table.  SCATTER: the same walk with the two sides exchanged.
+constexpr int kRunGroup = 4;
+using u32x4 = unsigned __attribute__((ext_vector_type(4)));
+
+template <int ELEM, bool SCATTER>
+__device__ __forceinline__ void move_runs(const SnapRun *__restrict__ runs, long n_runs, long groups, const u32x4 *__restrict__ from, int chunks, int rv,
+                                          u32x4 *__restrict__ to) {
+    constexpr int W = ELEM / 2;                  // vectors of a row a lane moves
+    const int lane = threadIdx.x & 63;
+    const long items = n_runs * groups;
+    for (long item = (long)blockIdx.x * kSnapWaves + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * kSnapWaves) {
+        const long r = item / groups, k0 = item % groups * kRunGroup;
+        const SnapRun q = runs[r];
+        if (k0 >= q.n) continue;
+        const unsigned s0 = (unsigned)tape_slot(q.first + k0, chunks);
+        size_t ring[kRunGroup], pack[kRunGroup];   // the rows' first vectors on the tape and in the packed runs
+        u32x4 x[kRunGroup][W];
+#pragma unroll
+        for (int j = 0; j < kRunGroup; ++j) {
+            ring[j] = ((size_t)q.slot * chunks + (s0 + j) % (unsigned)chunks) * rv;
+            pack[j] = (size_t)(q.at + k0 + j) * rv;
+        }
+#pragma unroll
+        for (int j = 0; j < kRunGroup; ++j)
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                if (k0 + j < q.n && lane + 64 * w < rv) x[j][w] = from[(SCATTER ? pack[j] : ring[j]) + lane + 64 * w];
+#pragma unroll
+        for (int j = 0; j < kRunGroup; ++j)
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                if (k0 + j < q.n && lane + 64 * w < rv) to[(SCATTER ? ring[j] : pack[j]) + lane + 64 * w] = x[j][w];
+    }
+}
+
+template <int ELEM>
+__global__ void __launch_bounds__(64 * kSnapWaves) snapshot_tape_gather_kernel(const SnapRun *__restrict__ runs, long n_runs, long groups,
+                                                                               const u32x4 *__restrict__ tape, int chunks, int rv, u32x4 *__restrict__ packed) {
+    move_runs<ELEM, false>(runs, n_runs, groups, tape, chunks, rv, packed);
+}
+
+template <int ELEM>
+__global__ void __launch_bounds__(64 * kSnapWaves) snapshot_tape_scatter_kernel(const SnapRun *__restrict__ runs, long n_runs, long groups,
+                                                                                u32x4 *__restrict__ tape, int chunks, int rv, const u32x4 *__restrict__ packed) {
+    move_runs<ELEM, true>(runs, n_runs, groups, packed, chunks, rv, tape);
+}
+
+// -> the launch's grid (0: nothing to do), or -1 for arguments no launch may have
+long snap_runs_grid(const SnapRun *runs, long n_runs, long max_n, const void *tape, int chunks, int N, int elem, const void *packed, long *groups) {
+    if (n_runs <= 0 || max_n <= 0) return 0;
+    if (!runs || !tape || !packed || (((size_t)tape | (size_t)packed) & 15) || (elem != 2 && elem != 4) || N < 8 || N % 8 || N * elem / 16 > 32 * elem ||
+        chunks < 1 || max_n > chunks)
+        return -1;
+    *groups = (max_n + kRunGroup - 1) / kRunGroup;
+    if (n_runs > 0x7fffffffL / *groups) return -1;
+    const long blocks = (n_runs * *groups + kSnapWaves - 1) / kSnapWaves;
+    return blocks < 8192 ? blocks : 8192;        // HBM to HBM: as wide as the chip, the rest by the loop
 }
 
 bool snap_args_ok(const int32_t *table, const SnapPart *parts, const void *ctx, const void *carry, int N, int C, const void *records) {
@@ -204,24 +275,52 @@ hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart 
 }
 
 hipError_t launch_snapshot_gather2(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, const float *fcarry,
-                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s) {
+                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s, int extra_bytes) {
     if (n <= 0) return hipSuccess;
-    if (!snap_args_ok(table, parts, ctx, carry, N, C, records) || !snap_tail_ok(fcarry, hist, hist_ld)) return hipErrorInvalidValue;
+    if (!snap_args_ok(table, parts, ctx, carry, N, C, records) || !snap_tail_ok(fcarry, hist, hist_ld) || extra_bytes < 0 || extra_bytes % 16) return hipErrorInvalidValue;
     hipLaunchKernelGGL(snapshot_gather2_kernel, dim3((unsigned)((n + kSnapWaves - 1) / kSnapWaves)), dim3(64 * kSnapWaves), 0, s,
                        reinterpret_cast<const int4 *>(table), n, parts, reinterpret_cast<const f32x4 *>(ctx), reinterpret_cast<const i16x8 *>(carry),
-                       reinterpret_cast<const f32x4 *>(fcarry), reinterpret_cast<const i16x8 *>(hist), C / 4, N / 8, N / 4, hist ? hist_ld / 8 : 0,
+                       reinterpret_cast<const f32x4 *>(fcarry), reinterpret_cast<const i16x8 *>(hist), C / 4, N / 8, N / 4, hist ? hist_ld / 8 : 0, extra_bytes / 16,
                        reinterpret_cast<f32x4 *>(records));
     return hipGetLastError();
 }
 
 hipError_t launch_snapshot_scatter2(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, float *fcarry, int16_t *hist,
-                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s) {
+                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s, int extra_bytes) {
     if (n <= 0) return hipSuccess;
-    if (!snap_args_ok(table, parts, ctx, carry, N, C, records) || !snap_tail_ok(fcarry, hist, hist_ld)) return hipErrorInvalidValue;
+    if (!snap_args_ok(table, parts, ctx, carry, N, C, records) || !snap_tail_ok(fcarry, hist, hist_ld) || extra_bytes < 0 || extra_bytes % 16) return hipErrorInvalidValue;
     hipLaunchKernelGGL(snapshot_scatter2_kernel, dim3((unsigned)((n + kSnapWaves - 1) / kSnapWaves)), dim3(64 * kSnapWaves), 0, s,
                        reinterpret_cast<const int4 *>(table), n, parts, reinterpret_cast<f32x4 *>(ctx), reinterpret_cast<i16x8 *>(carry),
-                       reinterpret_cast<f32x4 *>(fcarry), reinterpret_cast<i16x8 *>(hist), C / 4, N / 8, N / 4, hist ? hist_ld / 8 : 0,
+                       reinterpret_cast<f32x4 *>(fcarry), reinterpret_cast<i16x8 *>(hist), C / 4, N / 8, N / 4, hist ? hist_ld / 8 : 0, extra_bytes / 16,
                        reinterpret_cast<const f32x4 *>(records));
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_tape_gather(const SnapRun *runs, long n_runs, long max_n, const void *tape, int chunks, int N, int elem, void *packed,
+                                       hipStream_t s) {
+    long groups = 0;
+    const long grid = snap_runs_grid(runs, n_runs, max_n, tape, chunks, N, elem, packed, &groups);
+    if (grid <= 0) return grid ? hipErrorInvalidValue : hipSuccess;
+    const u32x4 *from = static_cast<const u32x4 *>(tape);
+    u32x4 *to = static_cast<u32x4 *>(packed);
+    if (elem == 2)
+        hipLaunchKernelGGL(snapshot_tape_gather_kernel<2>, dim3((unsigned)grid), dim3(64 * kSnapWaves), 0, s, runs, n_runs, groups, from, chunks, N * elem / 16, to);
+    else
+        hipLaunchKernelGGL(snapshot_tape_gather_kernel<4>, dim3((unsigned)grid), dim3(64 * kSnapWaves), 0, s, runs, n_runs, groups, from, chunks, N * elem / 16, to);
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_tape_scatter(const SnapRun *runs, long n_runs, long max_n, void *tape, int chunks, int N, int elem, const void *packed,
+                                        hipStream_t s) {
+    long groups = 0;
+    const long grid = snap_runs_grid(runs, n_runs, max_n, tape, chunks, N, elem, packed, &groups);
+    if (grid <= 0) return grid ? hipErrorInvalidValue : hipSuccess;
+    u32x4 *to = static_cast<u32x4 *>(tape);
+    const u32x4 *from = static_cast<const u32x4 *>(packed);
+    if (elem == 2)
+        hipLaunchKernelGGL(snapshot_tape_scatter_kernel<2>, dim3((unsigned)grid), dim3(64 * kSnapWaves), 0, s, runs, n_runs, groups, to, chunks, N * elem / 16, from);
+    else
+        hipLaunchKernelGGL(snapshot_tape_scatter_kernel<4>, dim3((unsigned)grid), dim3(64 * kSnapWaves), 0, s, runs, n_runs, groups, to, chunks, N * elem / 16, from);
     return hipGetLastError();
 }
 

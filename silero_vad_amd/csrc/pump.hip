@@ -195,6 +195,12 @@ struct vad_pump {
     vad::SnapPart *d_snap_parts = nullptr;       // [parts] each part's state block and first slot
     uint8_t *d_snap = nullptr;                   // the packed records on the device: what the one copy of a call carries
     size_t snap_cap = 0;                         // ... its bytes
+    // the tape in snapshots (vad_pump_export_streams_v3, and an import of a version 3 blob into a pump with a tape; allocated by the first
+    // such call that moves a run, none of it touched by a tick or by the version 1 / 2 calls)
+    vad::SnapRun *h_snap_runs = nullptr;         // [streams] the runs of a call: page-locked, mapped -- the kernels read it in place
+    vad::SnapRun *d_snap_runs = nullptr;         // device alias of h_snap_runs
+    uint8_t *d_snap_tape = nullptr;              // the packed runs on the device: what the one tape copy of a call carries
+    size_t snap_tape_cap = 0;                    // ... its bytes
     // the tape (vad_pump_set_tape / vad_pump_set_tape_f32; tape_chunks == 0: not enabled, none of this is allocated and no tick launches
     // anything for it)
     int tape_chunks = 0;                         // chunks of a stream's ring
@@ -401,6 +407,8 @@ void vad_pump_destroy(vad_pump *p) {
     if (p->d_snap) (void)hipFree(p->d_snap);
     if (p->d_snap_parts) (void)hipFree(p->d_snap_parts);
     if (p->h_snap_tab) (void)hipHostFree(p->h_snap_tab);
+    if (p->d_snap_tape) (void)hipFree(p->d_snap_tape);
+    if (p->h_snap_runs) (void)hipHostFree(p->h_snap_runs);
     if (p->d_tape) (void)hipFree(p->d_tape);
     if (p->d_tape_clock) (void)hipFree(p->d_tape_clock);
     if (p->d_tape_req) (void)hipFree(p->d_tape_req);
@@ -1487,6 +1495,12 @@ int vad_tape_window(int64_t count, int64_t floor, int chunks, int N, int64_t sta
     return VAD_OK;
 }
 
+int vad_tape_run(int64_t count, int64_t floor, int chunks, int N, int64_t from, int64_t *first_chunk, int64_t *n_chunks) {
+    if (chunks < 2 || N < 1 || count < 0 || count > INT64_MAX / N || floor < 0 || floor > INT64_MAX / N || !first_chunk || !n_chunks) return VAD_ERR_ARG;
+    vad::tape_run(count, floor, chunks, N, from, first_chunk, n_chunks);
+    return VAD_OK;
+}
+
 int vad_pump_set_tape(vad_pump *p, int chunks) { return tape_set(p, chunks, (int)sizeof(int16_t), "vad_pump_set_tape: "); }
 
 int vad_pump_set_tape_f32(vad_pump *p, int chunks) { return tape_set(p, chunks, (int)sizeof(float), "vad_pump_set_tape_f32: "); }
@@ -1557,6 +1571,13 @@ const char kSnapMagic[8] = {'S', 'V', 'A', 'D', 'S', 'N', 'A', 'P'};
 size_t snap_stride(int N, int C) { return sizeof(vad_stream_info) + (size_t)(2 * 128 + C) * sizeof(float) + (size_t)N * sizeof(int16_t); }
 // version 2: the version 1 record, then vad_resample_info, float carry[N], int16 history[VAD_SNAPSHOT_HISTORY]
 size_t snap_stride2(int N, int C) { return snap_stride(N, C) + sizeof(vad_resample_info) + (size_t)N * sizeof(float) + VAD_SNAPSHOT_HISTORY * sizeof(int16_t); }
+// version 3: the version 2 record, then vad_tape_info; the header goes on with {int32 tape_elem, int32 reserved, int64 tape_bytes} and zeros
+size_t snap_stride3(int N, int C) { return snap_stride2(N, C) + sizeof(vad_tape_info); }
+static_assert(sizeof(vad_tape_info) == 32 && sizeof(vad::SnapRun) == 32 && VAD_SNAPSHOT_HEADER_BYTES_V3 == sizeof(SnapHeader) + 64, "the version 3 layout is the documented one");
+struct SnapTape {                                // what a version 3 header says of the tape section (versions 1 and 2: no tape)
+    int32_t elem = 0;
+    int64_t bytes = 0;
+};
 
 bool any_byte_set(const uint8_t *at, size_t n) {
     uint8_t acc = 0;
@@ -1608,23 +1629,62 @@ const char *snap_info_fault(const vad_stream_info &f, int N) {
     return nullptr;
 }
 
+// The vad_tape_info of a version 3 record whose version 1 part is `f`.  *done: the chunks of the earlier runs; total: the chunks the tape
+// section holds, tape_bytes / (N * elem) (0 without a tape).  Every comparison comes before the arithmetic it makes safe.
+const char *snap_run_fault(const uint8_t *at, const vad_stream_info &f, int N, int elem, int64_t total, int64_t *done, vad_tape_info *out) {
+    vad_tape_info t;
+    std::memcpy(&t, at, sizeof(t));
+    for (const uint8_t z : t.reserved)
+        if (z) return "reserved bytes that are not zero";
+    if (t.first_chunk < 0 || t.n_chunks < 0) return "a run with a negative first_chunk or n_chunks";
+    if (t.n_chunks == 0) {
+        if (t.first_chunk != 0 || t.offset != 0) return "an empty run whose first_chunk or offset is not zero";
+    } else {
+        if (elem == 0) return "a run in a blob without a tape";
+        if (t.n_chunks > total - *done) return "runs longer than the tape section";
+        if (t.offset != *done * N * elem) return "a run that does not start where the run before it ends";       // (*done <= total: the product is below tape_bytes)
+        if (f.current_sample % N != 0 || t.first_chunk != f.current_sample / N - t.n_chunks) return "a run that does not end at the record's current_sample";
+        *done += t.n_chunks;
+    }
+    if (out) *out = t;
+    return nullptr;
+}
+
 // The whole blob, header and every record's fields (the blob may lie at any address: everything is read through memcpy).
-// -> nullptr and *hd, or what is wrong with it.
-const char *snap_check(const void *blob, size_t nbytes, SnapHeader *hd) {
+// -> nullptr, *hd and *tp (if asked for), or what is wrong with it.
+const char *snap_check(const void *blob, size_t nbytes, SnapHeader *hd, SnapTape *tp = nullptr) {
     if (!blob || nbytes < sizeof(SnapHeader)) return "shorter than a header";
     std::memcpy(hd, blob, sizeof(SnapHeader));
     if (std::memcmp(hd->magic, kSnapMagic, sizeof(kSnapMagic)) != 0) return "not a snapshot (magic)";
-    const bool v2 = hd->version == VAD_SNAPSHOT_VERSION_2;
-    if ((hd->version != VAD_SNAPSHOT_VERSION && !v2) || hd->header_bytes != (v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader)))
+    const bool v3 = hd->version == VAD_SNAPSHOT_VERSION_3, v2 = hd->version == VAD_SNAPSHOT_VERSION_2 || v3;
+    if ((hd->version != VAD_SNAPSHOT_VERSION && !v2) ||
+        hd->header_bytes != (v3 ? VAD_SNAPSHOT_HEADER_BYTES_V3 : v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader)))
         return "a version this library does not read";
     if (nbytes < hd->header_bytes) return "shorter than a header";
-    if (v2 && any_byte_set(static_cast<const uint8_t *>(blob) + sizeof(SnapHeader), VAD_SNAPSHOT_HEADER_BYTES_V2 - sizeof(SnapHeader)))
+    const uint8_t *bytes = static_cast<const uint8_t *>(blob);
+    SnapTape tape;
+    if (v3) {                                    // {int32 tape_elem, int32 reserved, int64 tape_bytes}, then zeros
+        int32_t word[2];
+        std::memcpy(word, bytes + sizeof(SnapHeader), sizeof(word));
+        std::memcpy(&tape.bytes, bytes + sizeof(SnapHeader) + sizeof(word), sizeof(tape.bytes));
+        tape.elem = word[0];
+        if (word[1] != 0 || any_byte_set(bytes + sizeof(SnapHeader) + 16, VAD_SNAPSHOT_HEADER_BYTES_V3 - sizeof(SnapHeader) - 16))
+            return "reserved bytes that are not zero";
+        if (tape.elem != 0 && tape.elem != 2 && tape.elem != 4) return "a tape_elem other than 0, 2 or 4";
+        if (tape.bytes < 0 || (tape.elem == 0 && tape.bytes != 0)) return "tape_bytes below zero, or not zero without a tape";
+    } else if (v2 && any_byte_set(bytes + sizeof(SnapHeader), VAD_SNAPSHOT_HEADER_BYTES_V2 - sizeof(SnapHeader))) {
         return "reserved bytes that are not zero";
+    }
     int N = 0, C = 0;
-    if (vad_geometry(hd->sr, &N, &C) != VAD_OK || hd->N != N || hd->C != C || hd->stride != (v2 ? snap_stride2(N, C) : snap_stride(N, C)))
+    if (vad_geometry(hd->sr, &N, &C) != VAD_OK || hd->N != N || hd->C != C ||
+        hd->stride != (v3 ? snap_stride3(N, C) : v2 ? snap_stride2(N, C) : snap_stride(N, C)))
         return "a sample rate / geometry that does not exist";
     if (hd->n_records < 0 || (uint64_t)hd->n_records > (nbytes - hd->header_bytes) / hd->stride) return "shorter than its header claims";
-    const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd->header_bytes;
+    // version 3: the buffer is exactly the header, the records and the tape section
+    if (v3 && (uint64_t)tape.bytes != nbytes - hd->header_bytes - (size_t)hd->n_records * hd->stride) return "not as long as its header claims";
+    const int64_t total = tape.elem ? tape.bytes / ((int64_t)N * tape.elem) : 0;
+    int64_t done = 0;
+    const uint8_t *rec = bytes + hd->header_bytes;
     SnapPair last;
     for (int64_t i = 0; i < hd->n_records; ++i) {
         vad_stream_info f;
@@ -1633,7 +1693,11 @@ const char *snap_check(const void *blob, size_t nbytes, SnapHeader *hd) {
         int H = 0;
         if (v2)
             if (const char *why = snap_tail_fault(rec + (size_t)i * hd->stride + snap_stride(N, C), f, hd->sr, N, &last, nullptr, &H)) return why;
+        if (v3)
+            if (const char *why = snap_run_fault(rec + (size_t)i * hd->stride + snap_stride2(N, C), f, N, tape.elem, total, &done, nullptr)) return why;
     }
+    if (v3 && tape.elem && done * N * tape.elem != tape.bytes) return "a tape section that is not the sum of its runs";
+    if (tp) *tp = tape;
     return nullptr;
 }
 
@@ -1675,16 +1739,36 @@ int snap_idle(vad_pump *p, const std::string &fn) {
     return VAD_OK;
 }
 
-// vad_pump_export_streams (v2 == false: blob version 1, the launch and the bytes it always had) and vad_pump_export_streams_v2
-int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap, bool v2) {
-    if (!p) return VAD_ERR_ARG;
-    const std::string fn = v2 ? "vad_pump_export_streams_v2: " : "vad_pump_export_streams: ";
-    if (const int rc = snap_idle(p, fn)) return rc;
+// the staging of a call's runs of the tape: the mapped table of runs (first call) and room for `bytes` of packed chunks on the device
+int snap_tape_reserve(vad_pump *p, size_t bytes) {
+    PUMP_TRY(p, hipSetDevice(p->device));
+    if (!p->h_snap_runs) {
+        void *dv = nullptr;
+        vad::SnapRun *tab = nullptr;
+        if (hipHostMalloc((void **)&tab, (size_t)p->streams * sizeof(vad::SnapRun), hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer(&dv, tab, 0) != hipSuccess || !dv) {
+            if (tab) (void)hipHostFree(tab);
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, "snapshot: no memory for the table of runs");
+        }
+        p->h_snap_runs = tab, p->d_snap_runs = static_cast<vad::SnapRun *>(dv);
+    }
+    if (bytes > p->snap_tape_cap) {
+        if (p->d_snap_tape) (void)hipFree(p->d_snap_tape);
+        p->d_snap_tape = nullptr, p->snap_tape_cap = 0;
+        if (hipMalloc((void **)&p->d_snap_tape, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, "snapshot: no device memory to stage the runs of the tape");
+        }
+        p->snap_tape_cap = bytes;
+    }
+    return VAD_OK;
+}
+
+// the slot list of an export: 0 = fine, 1 = a bad count, 2 = a slot out of range or listed twice
+int snap_slots_fault(vad_pump *p, const int32_t *streams, long n) {
     const long S = p->streams;
-    if (n < 0 || n > S || (!streams && n != S && n != 0) || !blob) return pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count) or no blob");
-    const size_t head = v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader), tail = snap_stride(p->N, p->C);       // tail: where a version 2 record's begins
-    const size_t stride = v2 ? snap_stride2(p->N, p->C) : tail, need = head + (size_t)n * stride;
-    if (cap < need) return pfail(p, VAD_ERR_ARG, fn + "the blob needs vad_pump_snapshot_bytes" + (v2 ? "_v2" : "") + "(sr, n) bytes");
+    if (n < 0 || n > S || (!streams && n != S && n != 0)) return 1;
     bool bad = false;
     long i = 0;
     for (; streams && i < n && !bad; ++i) {
@@ -1693,7 +1777,52 @@ int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t 
     }
     for (long k = 0; streams && k < i; ++k)      // (only valid slots were marked)
         if (streams[k] >= 0 && streams[k] < S) p->seen[streams[k]] = 0;
-    if (bad) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
+    return bad ? 2 : 0;
+}
+
+// The runs a version 3 export of these (checked) slots carries, as the counters are NOW (synchronises) -> run[k] = {first_chunk, n_chunks,
+// offset in chunks} and their chunks together.  A stream whose tape clock is not its iterator clock, and every stream of a pump
+// without a tape, carries none.
+struct SnapRunPlan {
+    int64_t first, n, at;
+};
+int snap_plan_runs(vad_pump *p, const int32_t *streams, long n, const int64_t *tape_from, std::vector<SnapRunPlan> *run, int64_t *total) {
+    run->assign((size_t)n, SnapRunPlan{0, 0, 0});
+    *total = 0;
+    if (!p->tape_chunks || n == 0) return VAD_OK;
+    if (const int rc = tape_read_clock(p)) return rc;
+    for (long k = 0; k < n; ++k) {
+        const int32_t b = streams ? streams[k] : (int32_t)k;
+        const int64_t count = p->tape_clock[2 * (size_t)b], floor = p->tape_clock[2 * (size_t)b + 1];
+        if (count < 0 || floor < 0 || count > INT64_MAX / p->N || count * p->N != p->current[b]) continue;
+        SnapRunPlan &q = (*run)[(size_t)k];
+        vad::tape_run(count, floor, p->tape_chunks, p->N, tape_from ? tape_from[k] : INT64_MIN, &q.first, &q.n);
+        if (q.n == 0) q.first = 0;               // (an empty run is all zeros in the blob)
+        else q.at = *total, *total += q.n;
+    }
+    return VAD_OK;
+}
+
+// vad_pump_export_streams (version 1: the launch and the bytes it always had), vad_pump_export_streams_v2 and vad_pump_export_streams_v3
+int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap, int version, const int64_t *tape_from = nullptr) {
+    if (!p) return VAD_ERR_ARG;
+    const bool v2 = version >= 2, v3 = version == 3;
+    const std::string fn = v3 ? "vad_pump_export_streams_v3: " : v2 ? "vad_pump_export_streams_v2: " : "vad_pump_export_streams: ";
+    if (const int rc = snap_idle(p, fn)) return rc;
+    const int slots = snap_slots_fault(p, streams, n);
+    if (slots == 1 || !blob) return pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count) or no blob");
+    if (slots) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
+    const size_t head = v3 ? VAD_SNAPSHOT_HEADER_BYTES_V3 : v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader), tail = snap_stride(p->N, p->C);       // tail: where a version 2 record's begins
+    const size_t stride = v3 ? snap_stride3(p->N, p->C) : v2 ? snap_stride2(p->N, p->C) : tail;
+    std::vector<SnapRunPlan> run;
+    int64_t run_chunks = 0;
+    if (v3)
+        if (const int rc = snap_plan_runs(p, streams, n, tape_from, &run, &run_chunks)) return rc;
+    const size_t row_bytes = (size_t)p->N * (size_t)p->tape_elem, tape_bytes = (size_t)run_chunks * row_bytes;       // (run_chunks <= streams x chunks: the tape itself is that large)
+    const size_t need = head + (size_t)n * stride + tape_bytes;
+    if (cap < need)
+        return pfail(p, VAD_ERR_ARG, fn + (v3 ? "the blob needs vad_pump_snapshot_plan_v3(p, streams, n, tape_from) bytes"
+                                              : std::string("the blob needs vad_pump_snapshot_bytes") + (v2 ? "_v2" : "") + "(sr, n) bytes"));
     for (long k = 0; !v2 && k < n && p->n_bound > 0; ++k)
         if (p->r_rate[streams ? streams[k] : k] >= 0)
             return pfail(p, VAD_ERR_ARG, fn + "stream " + std::to_string(streams ? streams[k] : k) + " is bound to a resampled rate: blob version 1 has no room for "
@@ -1701,6 +1830,8 @@ int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t 
     uint8_t *rec = static_cast<uint8_t *>(blob) + head;
     if (n > 0) {
         if (const int rc = snap_reserve(p, (size_t)n * stride)) return rc;
+        if (run_chunks > 0)
+            if (const int rc = snap_tape_reserve(p, tape_bytes)) return rc;
         for (long k = 0; k < n; ++k) {
             const int32_t b = streams ? streams[k] : (int32_t)k;
             int32_t *e = p->h_snap_tab + (v2 ? 8 : 4) * k;
@@ -1713,19 +1844,36 @@ int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t 
         // (read-only, behind everything the compute stream has run: a failure leaves the pump as it was)
         if (v2)
             PUMP_TRY(p, vad::launch_snapshot_gather2(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->d_fcarry, p->d_hist, p->r_hld,
-                                                     p->N, p->C, p->d_snap, p->compute));
+                                                     p->N, p->C, p->d_snap, p->compute, v3 ? (int)sizeof(vad_tape_info) : 0));
         else
             PUMP_TRY(p, vad::launch_snapshot_gather(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute));
         PUMP_TRY(p, hipMemcpyAsync(rec, p->d_snap, (size_t)n * stride, hipMemcpyDeviceToHost, p->compute));
+        if (run_chunks > 0) {                    // the runs: packed on the device in record order, ONE copy into the tape section
+            int64_t longest = 0;
+            for (long k = 0; k < n; ++k) {       // (n <= chunks by the run rule; [at, at + n) inside the staging by the sum)
+                const SnapRunPlan &q = run[(size_t)k];
+                p->h_snap_runs[k] = vad::SnapRun{streams ? streams[k] : (int32_t)k, (int32_t)q.n, q.first, q.at, 0};
+                longest = std::max(longest, q.n);
+            }
+            PUMP_TRY(p, vad::launch_snapshot_tape_gather(p->d_snap_runs, n, (long)longest, p->d_tape, p->tape_chunks, p->N, p->tape_elem, p->d_snap_tape,
+                                                         p->compute));
+            PUMP_TRY(p, hipMemcpyAsync(rec + (size_t)n * stride, p->d_snap_tape, tape_bytes, hipMemcpyDeviceToHost, p->compute));
+        }
         PUMP_TRY(p, hipStreamSynchronize(p->compute));
     }
     SnapHeader hd;
     std::memcpy(hd.magic, kSnapMagic, sizeof(kSnapMagic));
-    hd.version = v2 ? VAD_SNAPSHOT_VERSION_2 : VAD_SNAPSHOT_VERSION, hd.header_bytes = (uint32_t)head;
+    hd.version = (uint32_t)version, hd.header_bytes = (uint32_t)head;
     hd.sr = p->sr, hd.N = p->N, hd.C = p->C, hd.stride = (uint32_t)stride, hd.n_records = n;
     hd.threshold = p->threshold, hd.min_silence = p->min_silence, hd.pad = p->pad;
     std::memcpy(blob, &hd, sizeof(hd));
     std::memset(static_cast<uint8_t *>(blob) + sizeof(hd), 0, head - sizeof(hd));
+    if (v3) {
+        const int32_t elem = p->tape_elem;
+        const int64_t tb = (int64_t)tape_bytes;
+        std::memcpy(static_cast<uint8_t *>(blob) + sizeof(hd), &elem, sizeof(elem));
+        std::memcpy(static_cast<uint8_t *>(blob) + sizeof(hd) + 8, &tb, sizeof(tb));
+    }
     for (long k = 0; k < n; ++k) {               // the host's part of a record (the gather left it zero)
         const int32_t b = streams ? streams[k] : (int32_t)k;
         vad_stream_info f{};
@@ -1737,6 +1885,11 @@ int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t 
             vad_resample_info q{};
             q.src_rate = p->rates[p->r_rate[b]], q.pending_out = p->r_pend[b], q.inputs_mod = p->r_g[b], q.outputs_mod = p->r_m[b];
             std::memcpy(rec + (size_t)k * stride + tail, &q, sizeof(q));
+        }
+        if (v3 && run[(size_t)k].n > 0) {
+            vad_tape_info t{};
+            t.first_chunk = run[(size_t)k].first, t.n_chunks = run[(size_t)k].n, t.offset = run[(size_t)k].at * (int64_t)row_bytes;
+            std::memcpy(rec + (size_t)k * stride + snap_stride2(p->N, p->C), &t, sizeof(t));
         }
     }
     return VAD_OK;
@@ -1756,6 +1909,18 @@ size_t vad_pump_snapshot_bytes_v2(int sr, long n) {
     int N = 0, C = 0;
     if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
     return VAD_SNAPSHOT_HEADER_BYTES_V2 + (size_t)n * snap_stride2(N, C);
+}
+
+size_t vad_snapshot_bytes_v3(int sr, long n, int tape_elem, int64_t total_chunks) {
+    int N = 0, C = 0;
+    if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK || (tape_elem != 0 && tape_elem != 2 && tape_elem != 4) || total_chunks < 0 ||
+        (tape_elem == 0 && total_chunks != 0))
+        return 0;
+    const size_t stride = snap_stride3(N, C), row = (size_t)N * (size_t)tape_elem;
+    if ((size_t)n > (SIZE_MAX - VAD_SNAPSHOT_HEADER_BYTES_V3) / stride) return 0;
+    const size_t records = VAD_SNAPSHOT_HEADER_BYTES_V3 + (size_t)n * stride;
+    if (row && (uint64_t)total_chunks > (SIZE_MAX - records) / row) return 0;
+    return records + (size_t)total_chunks * row;
 }
 
 int vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr) {
@@ -1783,7 +1948,7 @@ int vad_snapshot_resample(const void *blob, size_t nbytes, long i, vad_resample_
     SnapHeader hd;
     if (snap_check(blob, nbytes, &hd) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
     const size_t cb = (size_t)hd.N * sizeof(float), hb = VAD_SNAPSHOT_HISTORY * sizeof(int16_t);
-    if (hd.version != VAD_SNAPSHOT_VERSION_2) {  // (a version 1 record has no tail: the stream is bound to no rate)
+    if (hd.version == VAD_SNAPSHOT_VERSION) {    // (a version 1 record has no tail: the stream is bound to no rate)
         if (info) std::memset(info, 0, sizeof(*info));
         if (carry) std::memset(carry, 0, cb);
         if (history) std::memset(history, 0, hb);
@@ -1796,22 +1961,64 @@ int vad_snapshot_resample(const void *blob, size_t nbytes, long i, vad_resample_
     return VAD_OK;
 }
 
-int vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) { return snap_export(p, streams, n, blob, cap, false); }
+int vad_snapshot_tape(const void *blob, size_t nbytes, long i, vad_tape_info *info, void *audio, size_t cap) {
+    SnapHeader hd;
+    SnapTape tape;
+    if (snap_check(blob, nbytes, &hd, &tape) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
+    vad_tape_info t{};                           // (versions 1 and 2: no runs)
+    if (hd.version == VAD_SNAPSHOT_VERSION_3)
+        std::memcpy(&t, static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)i * hd.stride + snap_stride2(hd.N, hd.C), sizeof(t));
+    const size_t bytes = (size_t)t.n_chunks * (size_t)hd.N * (size_t)tape.elem;     // (snap_check: inside the tape section)
+    if (audio && cap < bytes) return VAD_ERR_ARG;
+    if (info) *info = t;
+    if (audio && bytes)
+        std::memcpy(audio, static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)hd.n_records * hd.stride + (size_t)t.offset, bytes);
+    return VAD_OK;
+}
 
-int vad_pump_export_streams_v2(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) { return snap_export(p, streams, n, blob, cap, true); }
+int vad_pump_export_streams(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) { return snap_export(p, streams, n, blob, cap, 1); }
+
+int vad_pump_export_streams_v2(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap) { return snap_export(p, streams, n, blob, cap, 2); }
+
+size_t vad_pump_snapshot_plan_v3(vad_pump *p, const int32_t *streams, long n, const int64_t *tape_from) {
+    if (!p) return 0;
+    const std::string fn = "vad_pump_snapshot_plan_v3: ";
+    if (p->poisoned) return (void)pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")"), 0;
+    if (snap_slots_fault(p, streams, n)) return (void)pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count; distinct slots)"), 0;
+    std::vector<SnapRunPlan> run;
+    int64_t run_chunks = 0;
+    if (snap_plan_runs(p, streams, n, tape_from, &run, &run_chunks)) return 0;
+    return VAD_SNAPSHOT_HEADER_BYTES_V3 + (size_t)n * snap_stride3(p->N, p->C) + (size_t)run_chunks * (size_t)p->N * (size_t)p->tape_elem;
+}
+
+int vad_pump_export_streams_v3(vad_pump *p, const int32_t *streams, long n, const int64_t *tape_from, void *blob, size_t cap) {
+    return snap_export(p, streams, n, blob, cap, 3, tape_from);
+}
 
 int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const int32_t *records, const int32_t *streams, long n) {
     if (!p) return VAD_ERR_ARG;
     const std::string fn = "vad_pump_import_streams: ";
     if (const int rc = snap_idle(p, fn)) return rc;
     SnapHeader hd;
-    if (const char *why = snap_check(blob, nbytes, &hd)) return pfail(p, VAD_ERR_ARG, fn + "the blob is " + why);
+    SnapTape tape;
+    if (const char *why = snap_check(blob, nbytes, &hd, &tape)) return pfail(p, VAD_ERR_ARG, fn + "the blob is " + why);
     if (hd.sr != p->sr) return pfail(p, VAD_ERR_SAMPLE_RATE, fn + "the blob's sample rate is not the pump's");
+    if (tape.elem && p->tape_elem && tape.elem != p->tape_elem)
+        return pfail(p, VAD_ERR_ARG, fn + (tape.elem == 2 ? "the blob carries runs of an int16 tape and the pump's tape is float32"
+                                                          : "the blob carries runs of a float32 tape and the pump's tape is int16") +
+                                         ": an import does not convert");
     const long S = p->streams;
     if (n < 0 || n > S || (n > 0 && !streams)) return pfail(p, VAD_ERR_ARG, fn + "bad slot list");
     const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd.header_bytes;
     const size_t stride = hd.stride;
-    const bool v2 = hd.version == VAD_SNAPSHOT_VERSION_2;
+    const bool v2 = hd.version >= VAD_SNAPSHOT_VERSION_2;      // (version 3: the version 2 record goes first)
+    const bool taped = tape.elem != 0 && p->tape_elem == tape.elem;       // the runs of the blob's tape section enter this pump's tape
+    const size_t row_bytes = (size_t)p->N * (size_t)p->tape_elem;
+    auto run_of = [&](long r) {                  // (versions 1 and 2: no runs)
+        vad_tape_info t{};
+        if (taped) std::memcpy(&t, rec + (size_t)r * stride + snap_stride2(p->N, p->C), sizeof(t));
+        return t;
+    };
     auto info_of = [&](long r) {
         vad_stream_info f;
         std::memcpy(&f, rec + (size_t)r * stride, sizeof(f));
@@ -1830,6 +2037,7 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
     // everything is decided here, on the host, from values snap_check has range-checked: nothing is queued before the last check
     const char *why = nullptr;
     long i = 0, first = hd.n_records, last = -1;
+    int64_t run_lo = INT64_MAX, run_hi = 0, longest = 0;       // the span of the selected runs in the tape section, in bytes; the longest kept run
     for (; i < n && !why; ++i) {
         const long r = records ? records[i] : i;
         const int32_t b = streams[i];
@@ -1840,6 +2048,11 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         else {
             p->seen[b] = 1;
             first = std::min(first, r), last = std::max(last, r);
+            const vad_tape_info t = run_of(r);
+            if (t.n_chunks > 0) {
+                run_lo = std::min(run_lo, t.offset), run_hi = std::max(run_hi, t.offset + t.n_chunks * (int64_t)row_bytes);
+                longest = std::max(longest, std::min<int64_t>(t.n_chunks, p->tape_chunks));
+            }
         }
     }
     for (long k = 0; k < i; ++k)                 // (only valid slots were marked)
@@ -1848,6 +2061,13 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
     if (n == 0) return VAD_OK;
     const size_t bytes = (size_t)(last - first + 1) * stride;
     if (const int rc = snap_reserve(p, bytes)) return rc;
+    if (longest > 0)
+        if (const int rc = snap_tape_reserve(p, (size_t)(run_hi - run_lo))) return rc;
+    for (long k = 0; k < n && longest > 0; ++k) {                  // the newest `kept` chunks of each run, into this pump's own ring
+        const vad_tape_info t = run_of(records ? records[k] : k);
+        const int64_t kept = std::min<int64_t>(t.n_chunks, p->tape_chunks), skip = t.n_chunks - kept;
+        p->h_snap_runs[k] = vad::SnapRun{streams[k], (int32_t)kept, t.first_chunk + skip, kept ? (t.offset - run_lo) / (int64_t)row_bytes + skip : 0, 0};
+    }
     for (long k = 0; k < n; ++k) {
         const long r = records ? records[k] : k;
         int32_t *e = p->h_snap_tab + (v2 ? 8 : 4) * k;
@@ -1863,8 +2083,15 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         hipError_t e = hipMemcpyAsync(p->d_snap, rec + (size_t)first * stride, bytes, hipMemcpyHostToDevice, p->compute);
         if (e == hipSuccess)
             e = v2 ? vad::launch_snapshot_scatter2(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->d_fcarry, p->d_hist, p->r_hld, p->N,
-                                                   p->C, p->d_snap, p->compute)
+                                                   p->C, p->d_snap, p->compute, (int)(stride - snap_stride2(p->N, p->C)))
                    : vad::launch_snapshot_scatter(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute);
+        if (e == hipSuccess && longest > 0) {    // ONE more copy: the tape section from the first selected run to the last; the scatter behind it
+            e = hipMemcpyAsync(p->d_snap_tape, rec + (size_t)hd.n_records * stride + (size_t)run_lo, (size_t)(run_hi - run_lo), hipMemcpyHostToDevice,
+                               p->compute);
+            if (e == hipSuccess)
+                e = vad::launch_snapshot_tape_scatter(p->d_snap_runs, n, (long)longest, p->d_tape, p->tape_chunks, p->N, p->tape_elem, p->d_snap_tape,
+                                                      p->compute);
+        }
         return e == hipSuccess ? hipStreamSynchronize(p->compute) : e;
     }();
     if (rc != hipSuccess) {
@@ -1889,10 +2116,15 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         }
         p->src_pos[b] = 0;
     }
-    if (p->tape_chunks) {                        // the stream's clock continues and nothing before the import is held: count = floor = its chunk
+    if (p->tape_chunks) {                        // the stream's clock continues: count = its chunk; floor = count less the chunks of its run that were
+                                                 // kept (a version 3 record with a run), else count: nothing before the import is held
         const size_t bytes2 = (size_t)S * 2 * sizeof(int64_t);                 // (the pump is idle and synchronised: nothing else writes the counters)
         hipError_t e = hipMemcpy(p->tape_clock.data(), p->d_tape_clock, bytes2, hipMemcpyDeviceToHost);
-        for (long k = 0; k < n; ++k) p->tape_clock[2 * (size_t)streams[k]] = p->tape_clock[2 * (size_t)streams[k] + 1] = p->current[streams[k]] / p->N;
+        for (long k = 0; k < n; ++k) {
+            const int64_t count = p->current[streams[k]] / p->N;
+            p->tape_clock[2 * (size_t)streams[k]] = count;
+            p->tape_clock[2 * (size_t)streams[k] + 1] = count - std::min<int64_t>(run_of(records ? records[k] : k).n_chunks, p->tape_chunks);
+        }
         if (e == hipSuccess) e = hipMemcpy(p->d_tape_clock, p->tape_clock.data(), bytes2, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             p->poisoned = true;

@@ -1,5 +1,5 @@
 // tape.hpp -- which samples of a live stream the pump's tape still holds, written once for the host (pump.hip: vad_tape_window,
-// vad_pump_tape_window, vad_pump_fetch_audio) and for the device (kernel_tape.hip).
+// vad_pump_tape_window, vad_pump_fetch_audio; vad_tape_run and the version 3 snapshots) and for the device (kernel_tape.hip).
 //
 // The tape of a stream is a ring of `chunks` chunks of N samples (int16, or float32: nothing here depends on the element).  Two counters describe it: `count`, the chunks stepped since the
 // stream's clock started (vad_pump_open, or the chunk an import continued at), and `floor`, the first chunk the tape can hold (0 after
@@ -43,6 +43,16 @@ VAD_TAPE_HD inline void tape_window(int64_t count, int64_t floor, int64_t chunks
     const int64_t a = tape_first(start, lo, hi);
     *first = a;
     *n = tape_last(end, a, hi) - a;
+}
+
+// The RUN a snapshot carries (blob version 3): the whole chunks from the one that holds sample `from` to the newest one, as far as the
+// tape holds them (floor >= 0, so held_lo >= 0).  `from` is clamped into [held_lo, held_hi] BEFORE it is divided, so any int64 is safe;
+// a position in the middle of a chunk rounds down to its chunk.
+//     first_chunk = min(max(from / N, held_lo / N), count),  n_chunks = count - first_chunk
+VAD_TAPE_HD inline void tape_run(int64_t count, int64_t floor, int64_t chunks, int64_t N, int64_t from, int64_t *first_chunk, int64_t *n_chunks) {
+    const int64_t a = tape_first(from, tape_held_lo(count, floor, chunks, N), tape_held_hi(count, N));
+    *first_chunk = a / N;
+    *n_chunks = count - a / N;
 }
 
 // the ring slot chunk k of a stream is taped into (k >= 0)

@@ -3226,8 +3226,10 @@ def snapshot_info(blob) -> list:
     `h` [128], `c` [128], `ctx` [C] float32 and `pending_samples` [N] int16 (zeros behind `pending`).  A record of a version 2 blob
     (`export_streams(version=2)`) has a `resample` entry besides (what vad_snapshot_resample reads): a dict of `src_rate` (Hz; 0 = bound to no
     rate), `pending_out`, `inputs_mod`, `outputs_mod`, `carry` (the pending_out fp32 outputs that wait for their chunk) and `history`
-    (the last H int16 inputs at src_rate, oldest first).  A blob the library refuses -- bad magic or version, truncated, a field out of
-    range -- raises."""
+    (the last H int16 inputs at src_rate, oldest first).  A record of a version 3 blob (`export_streams_v3`) has that entry and a
+    `tape` entry (what vad_snapshot_tape reads): a dict of `first_chunk`, `n_chunks`, `offset` (of the run in the blob's tape section, in
+    bytes), `elem` (the tape's element in bytes: 0, 2 or 4) and `audio`, the run's n_chunks * N samples as int16 or float32 (empty int16
+    without a run).  A blob the library refuses -- bad magic or version, truncated, a field out of range -- raises."""
     a = _blob_bytes(blob)
     L = lib()
     n, sr = ctypes.c_long(), ctypes.c_int()
@@ -3250,15 +3252,59 @@ def snapshot_info(blob) -> list:
         d = {k: int(getattr(f, k)) for k in ("active", "triggered", "temp_end", "current_sample", "pending", "wide_step", "wide_phase")}
         d.update(h=rec[32:544].view("<f4").copy(), c=rec[544:1056].view("<f4").copy(), ctx=rec[1056:1056 + 4 * C].view("<f4").copy(),
                  pending_samples=rec[1056 + 4 * C:s1].view("<i2").copy())
-        if version == 2:
+        if version >= 2:
             q = _lib.ResampleInfo.from_buffer_copy(rec[s1:s1 + 32].tobytes())
             if q.src_rate not in H_of:
                 H_of[q.src_rate] = L.vad_resample_stream_history(q.src_rate, sr.value)
-            carry, hist = rec[s1 + 32:s1 + 32 + 4 * N].view("<f4"), rec[s1 + 32 + 4 * N:stride].view("<i2")
+            carry, hist = rec[s1 + 32:s1 + 32 + 4 * N].view("<f4"), rec[s1 + 32 + 4 * N:s1 + 32 + 4 * N + 320].view("<i2")
             d["resample"] = dict(src_rate=int(q.src_rate), pending_out=int(q.pending_out), inputs_mod=int(q.inputs_mod),
                                  outputs_mod=int(q.outputs_mod), carry=carry[:q.pending_out].copy(), history=hist[:H_of[q.src_rate]].copy())
+        if version == 3:
+            elem = int(a[64:68].view("<i4")[0])
+            t = _lib.TapeInfo.from_buffer_copy(rec[stride - 32:stride].tobytes())
+            at = head + n.value * stride + int(t.offset)
+            audio = a[at:at + int(t.n_chunks) * N * elem].view("<f4" if elem == 4 else "<i2").copy()
+            d["tape"] = dict(first_chunk=int(t.first_chunk), n_chunks=int(t.n_chunks), offset=int(t.offset), elem=elem, audio=audio)
         out.append(d)
     return out
+
+
+def snapshot_tape(blob, i: int) -> np.ndarray:
+    """The run of the tape that record i of a snapshot blob carries (vad_snapshot_tape; host only): its n_chunks * N samples, oldest first,
+    as int16 or float32 -- the element of the tape of the pump that wrote the blob.  Empty (int16) for a record without a run and for a
+    blob of version 1 or 2.  The samples are those [first_chunk * N, current_sample) of the stream's clock (`snapshot_info(blob)[i]["tape"]`
+    has the numbers).  An invalid blob or i out of range raises."""
+    a = _blob_bytes(blob)
+    L = lib()
+    t = _lib.TapeInfo()
+    rc = L.vad_snapshot_tape(a.ctypes.data if a.size else None, a.size, int(i), ctypes.byref(t), None, 0)
+    if rc:
+        raise _lib.VadError(rc, "vad_snapshot_tape: not a valid snapshot blob, or no such record")
+    elem = int(a[64:68].view("<i4")[0]) if t.n_chunks else 0       # (a run: the blob is version 3, and its header says the element)
+    N = int(a[20:24].view("<i4")[0])
+    out = np.empty(int(t.n_chunks) * N, np.float32 if elem == 4 else np.int16)
+    if out.size:
+        rc = L.vad_snapshot_tape(a.ctypes.data, a.size, int(i), None, out.ctypes.data, out.nbytes)
+        if rc:
+            raise _lib.VadError(rc, "vad_snapshot_tape")
+    return out
+
+
+def tape_run(count: int, floor: int, chunks: int, n: int, start: int):
+    """(first_chunk, n_chunks): the whole chunks a version 3 snapshot carries of a stream whose tape, `chunks` chunks of n samples, has the
+    counters (count, floor), when its audio is wanted from sample `start` on -- held_lo = max(floor, count - chunks), first_chunk =
+    min(max(start // n, held_lo), count) with `start` clamped into the held window first, n_chunks = count - first_chunk (vad_tape_run:
+    the rule `StreamPump.export_streams_v3(tape_from=...)` applies; host only, no GPU).  Any int64 `start` is legal."""
+    vals = [count, floor, chunks, n, start]
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError(f"tape_run takes integers, got {vals!r}")
+    if not all(-2 ** 63 <= int(v) < 2 ** 63 for v in vals) or not all(-2 ** 31 <= int(v) < 2 ** 31 for v in (chunks, n)):
+        raise ValueError(f"tape_run: a value out of its integer range in {vals!r}")
+    first, m = ctypes.c_int64(), ctypes.c_int64()
+    rc = lib().vad_tape_run(int(count), int(floor), int(chunks), int(n), int(start), ctypes.byref(first), ctypes.byref(m))
+    if rc:
+        raise ValueError(f"tape_run: chunks >= 2, n >= 1, count >= 0, floor >= 0 and counters times n within int64, got {vals!r}")
+    return first.value, m.value
 
 
 def tape_window(count: int, floor: int, chunks: int, n: int, start: int, end: int):
@@ -3297,7 +3343,10 @@ class UtteranceCollector:
     them, in the tape's dtype (int16, or float32 in [-1, 1) with `tape_dtype="float32"`, the only tape of the resampled route),
     first > start where the head of a long utterance had already left the tape.  All ENDs of one `feed` are fetched in
     one `fetch_audio` call.  An END whose START was never fed comes back as (stream, None, end, None, None).  `forget(stream)` drops a
-    remembered START: call it with `pump.open_stream(stream)`, the slot's new stream starts a new clock."""
+    remembered START: call it with `pump.open_stream(stream)`, the slot's new stream starts a new clock.
+    Streams that migrate in the middle of an utterance take their START along: `open_starts(streams)` -> {stream: start} of the streams
+    that are inside one, for `export_streams_v3(tape_from=...)` and for the destination's collector, which `adopt(stream, start)`
+    tells where the utterance of the stream in ITS slot began (`StreamPump.export_streams_v3` shows the whole move)."""
 
     def __init__(self, pump):
         if not getattr(pump, "tape_chunks", 0):
@@ -3307,6 +3356,19 @@ class UtteranceCollector:
 
     def forget(self, stream: int):
         self._start.pop(int(stream), None)
+
+    def open_starts(self, streams=None) -> dict:
+        """{stream: start} of the remembered STARTs -- the streams that are inside an utterance -- of `streams` (None: of every stream)."""
+        if streams is None:
+            return dict(self._start)
+        return {int(b): self._start[int(b)] for b in streams if int(b) in self._start}
+
+    def adopt(self, stream: int, start: int):
+        """Remember `start` as the START of the utterance the stream in slot `stream` is in, as if its event had been fed here: the stream
+        was imported in the middle of that utterance (its clock, and so the sample number, came along)."""
+        if isinstance(start, (bool, np.bool_)) or not isinstance(start, (int, np.integer)) or start < 0:
+            raise ValueError(f"start is a sample number of the stream's clock, got {start!r}")
+        self._start[int(stream)] = int(start)
 
     def feed(self, events) -> list:
         done = []
@@ -3363,7 +3425,8 @@ class StreamPump:
     Moving live streams (a drain, a rebalancing between per-GPU ranks, a restart): with no tick in flight `blob = pump.export_streams([3, 7])`
     packs everything those streams carry into one uint8 array, `other.import_streams(blob, [0, 5])` puts the records into slots of any
     pump of the same sample rate (another GPU, another process), and `snapshot_info(blob)` reads a blob without a pump; the streams go
-    on bit for bit.  `export_streams(..., version=2)` also moves streams that are bound to a resampled rate.
+    on bit for bit.  `export_streams(..., version=2)` also moves streams that are bound to a resampled rate, and
+    `export_streams_v3(..., tape_from=...)` also the taped audio of the utterances they are in (below).
 
     The audio behind the events: with `tape_chunks=K` the pump keeps every stream's last K chunks on the device as the net heard them
     (G.711 expanded, 32 / 48 kHz combed, silent rows as zeros), taped as a side effect of every step of every route but the resampled
@@ -3948,7 +4011,8 @@ class StreamPump:
         the pump and the streams go on as if nothing had happened.
         version=1 refuses a stream that is bound to a resampled rate; version=2 (vad_pump_export_streams_v2) writes the longer record
         that also carries the rate, the resampler's counters, the fp32 pending outputs and the filter history, for bound and unbound
-        streams alike.  `import_streams` takes both."""
+        streams alike.  `import_streams` takes both.  Blob version 3, which also carries the streams' taped audio, is written by
+        `export_streams_v3`."""
         if isinstance(version, (bool, np.bool_)) or not isinstance(version, (int, np.integer)) or version not in (1, 2):
             raise ValueError(f"version must be 1 or 2, got {version!r}")
         st = None if streams is None else _distinct_slots(streams, "streams")
@@ -3959,12 +4023,50 @@ class StreamPump:
         self._check(export(self._h, st.ctypes.data if st is not None and n else None, n, blob.ctypes.data, blob.size))
         return blob
 
+    def export_streams_v3(self, streams=None, tape_from=None) -> np.ndarray:
+        """`export_streams` in blob version 3 (vad_pump_snapshot_plan_v3 + vad_pump_export_streams_v3): the version 2 records and, behind
+        them, a run of each stream's tape -- the newest whole chunks from sample tape_from[i] of streams[i]'s clock on, as far as the tape
+        holds them (`tape_run`).  tape_from=None: everything held; a {stream: sample} dict: those streams from there, every other stream
+        nothing; on a pump without a tape: no audio.  The same rules: no tick in flight, read-only.  `import_streams` takes the blob, and
+        a pump whose tape has the same dtype keeps the audio.
+
+        Moving streams in the middle of their utterances, with the audio the END events will ask for:
+
+            col_a, col_b = UtteranceCollector(a), UtteranceCollector(b)
+            starts = col_a.open_starts(moving)                   # {stream: START sample} of the streams inside an utterance
+            blob = a.export_streams_v3(moving, tape_from=starts)
+            b.import_streams(blob, slots)
+            for s, d in zip(moving, slots):
+                if s in starts:
+                    col_b.adopt(d, starts[s])                    # the END on b then returns first == start
+                col_a.forget(s)
+        """
+        st = None if streams is None else _distinct_slots(streams, "streams")
+        n = self.streams if st is None else len(st)
+        slots = range(self.streams) if st is None else st.tolist()
+        if isinstance(tape_from, dict):                          # (behind every int64 sample of a clock: nothing)
+            tf = np.array([int(tape_from.get(b, 2 ** 63 - 1)) for b in slots], np.int64)
+        else:
+            tf = None if tape_from is None else self._int64_rows(tape_from, "tape_from")
+        if tf is not None and len(tf) != n:
+            raise ValueError(f"tape_from must have one sample position per exported stream, got {len(tf)} for {n}")
+        args = (self._h, st.ctypes.data if st is not None and n else None, n, tf.ctypes.data if tf is not None and n else None)
+        need = int(self._L.vad_pump_snapshot_plan_v3(*args))
+        if need == 0:
+            self._check(1)
+        blob = np.zeros(need, np.uint8)
+        self._check(self._L.vad_pump_export_streams_v3(*args, blob.ctypes.data, blob.size))
+        return blob
+
     def import_streams(self, blob, slots, records=None):
         """Record records[i] of `blob` (None = record i) replaces the whole carried state of slot slots[i] (vad_pump_import_streams); the
         stream continues bit for bit if this pump has the iterator parameters of the pump that wrote the blob.  Only with no tick in
         flight.  A blob of another sample rate, a malformed blob, a bad record index or slot, a 32 / 48 kHz stream for a pump without
         that wideband step, or (version 2) a stream bound to a rate that is none of this pump's `resample_rates` raises, and nothing
-        has changed.  A bound record binds its slot; every other record leaves its slot bound to no rate."""
+        has changed.  A bound record binds its slot; every other record leaves its slot bound to no rate.  The runs of a version 3
+        blob enter this pump's tape if it has one of the same dtype -- the newest `tape_chunks` chunks of each, `tape_state(slot)` is
+        then (count, count - kept) and `fetch_audio` reaches back across the move; without a tape here they are ignored; a tape of the
+        other dtype raises, and nothing has changed."""
         a = _blob_bytes(blob)
         sl = _distinct_slots(slots, "slots")
         rc = None if records is None else _int32_rows(records, "records")
