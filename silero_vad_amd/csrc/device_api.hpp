@@ -151,34 +151,34 @@ constexpr int kCombShift = kCodecShift + 4;
 constexpr int kMaxWideStep = 3;
 hipError_t launch_assemble_wide_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
                                         hipStream_t s);
-// Snapshot and restore of the pump's streams (vad_pump_export_streams / vad_pump_import_streams; kernel_snapshot.hip).  table[i] = {slot b,
-// its part k, pending c (0 ... N - 1), record r}, all range-checked by the host; parts[k] = part k's state block [2][n][128] and its
-// first slot.  gather: record r of `records` (the blob's record layout, 32 + 4 * (256 + C) + 2 * N bytes each) <- zeros for the info
-// block, h, c, ctx[b], carry[b][0:c] ++ zeros.  scatter: the reverse (the info block is the host's; the carry row gets the record's first
-// c samples ++ zeros).  `ctx` is the context buffer the pump's next tick reads.  HBM to HBM.
+// Snapshot and restore of the pump's streams (vad_pump_export_streams* / vad_pump_import_streams; kernel_snapshot.hip).
+// A RECORD of `records` (the blob's record layout) is the info block (32 bytes, the host's), h[128], c[128], ctx[C] (float) and int16
+// pending[N]: 32 + 4 * (256 + C) + 2 * N bytes.  With a `tail` (blob versions 2 and 3) it goes on with the 32 bytes of vad_resample_info
+// (the host's), float carry[N], int16 history[kSnapHistory] and tail->extra_bytes more of the host's (a multiple of 16; version 3: the 32
+// bytes of vad_tape_info).
+// The TABLE has one int4 per record, table[i] = {slot b, its part k, pending c (0 ... N - 1), record r}, and with a tail a second one
+// behind it, {fp32 pending c (0 ... N - 1), H (0 ... hist_ld and kSnapHistory), bound 0 / 1, 0}; all range-checked by the host.
+// parts[k] = part k's state block [2][n][128] and its first slot; `ctx` is the context buffer the pump's next tick reads.
+// gather: record r <- zeros for the host's bytes, h, c, ctx[b], carry[b][0:c] ++ zeros and, of a bound stream, fcarry[b][0:c] ++ zeros,
+// hist[b][0:H] ++ zeros (an unbound stream's tail: zeros).  scatter: the reverse -- the host's bytes are skipped, the carry row gets the
+// record's first c samples ++ zeros, a bound record writes fcarry[b][0:N] = its first c floats ++ zeros and hist[b][0:hist_ld] = its first
+// H samples ++ zeros, an unbound record leaves both rows alone.  fcarry: [streams][N] float, hist: [streams][hist_ld] int16, hist_ld a
+// multiple of 8 (the pump's own pitch: the record's is always kSnapHistory); both null on a pump without the resampled route, whose
+// table may hold no bound entry.  tail == nullptr (version 1): one table entry per record, neither buffer is known.  HBM to HBM.
 struct SnapPart {
     float *state;
     int32_t lo, n;
 };
-hipError_t launch_snapshot_gather(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, int N, int C,
-                                  uint8_t *records, hipStream_t s);
-hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, int N, int C,
-                                   const uint8_t *records, hipStream_t s);
-// Blob version 2 (vad_pump_export_streams_v2): the same records followed by the tail of a stream that is bound to a resampled rate --
-// 32 bytes of vad_resample_info (the host's), float carry[N], int16 history[kSnapHistory]; 32 + 4 * (256 + C) + 2 * N + 32 + 4 * N + 2 *
-// kSnapHistory bytes each.  The table has TWO int4 per record: the entry above and {fp32 pending c (0 ... N - 1), H (0 ... hist_ld and
-// kSnapHistory), bound 0 / 1, 0}.  gather2: a bound stream's tail <- zeros, fcarry[b][0:c] ++ zeros, hist[b][0:H] ++ zeros; an unbound
-// stream's tail <- zeros.  scatter2: a bound record writes fcarry[b][0:N] = the record's first c floats ++ zeros and hist[b][0:hist_ld] =
-// its first H samples ++ zeros; an unbound record leaves both rows alone.  fcarry: [streams][N] float, hist: [streams][hist_ld] int16,
-// hist_ld a multiple of 8 (the pump's own pitch: the record's is always kSnapHistory); both null on a pump without the resampled route,
-// whose table may hold no bound entry.
+struct SnapTail {
+    float *fcarry;
+    int16_t *hist;
+    int hist_ld, extra_bytes;
+};
 constexpr int kSnapHistory = 160;            // == kResampleMaxTaps: H = K - 1 of every served pair fits
-// extra_bytes (a multiple of 16; blob version 3: the 32 bytes of vad_tape_info, the host's): each record is that much longer -- gather2
-// writes the extra bytes as zeros, scatter2 skips them.
-hipError_t launch_snapshot_gather2(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, const float *fcarry,
-                                   const int16_t *hist, int hist_ld, int N, int C, uint8_t *records, hipStream_t s, int extra_bytes = 0);
-hipError_t launch_snapshot_scatter2(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, float *fcarry, int16_t *hist,
-                                    int hist_ld, int N, int C, const uint8_t *records, hipStream_t s, int extra_bytes = 0);
+hipError_t launch_snapshot_gather(const int32_t *table, long n, const SnapPart *parts, const float *ctx, const int16_t *carry, int N, int C,
+                                  uint8_t *records, hipStream_t s, const SnapTail *tail = nullptr);
+hipError_t launch_snapshot_scatter(const int32_t *table, long n, const SnapPart *parts, float *ctx, int16_t *carry, int N, int C,
+                                   const uint8_t *records, hipStream_t s, const SnapTail *tail = nullptr);
 // Blob version 3 (vad_pump_export_streams_v3): the RUNS of the pump's tape (kernel_tape.hip) that a snapshot carries.  runs[i] = {slot b,
 // n whole chunks, the first of them (a chunk number of the stream's clock, >= 0), where the run starts in `packed` (in chunks)}, all
 // range-checked by the host: n <= chunks, slot b inside the tape, [at, at + n) inside `packed`.  gather: packed[at + k] <- tape[b][(first
@@ -189,10 +189,8 @@ struct SnapRun {
     int64_t first, at;
     int64_t pad;
 };
-hipError_t launch_snapshot_tape_gather(const SnapRun *runs, long n_runs, long max_n, const void *tape, int chunks, int N, int elem, void *packed,
-                                       hipStream_t s);
-hipError_t launch_snapshot_tape_scatter(const SnapRun *runs, long n_runs, long max_n, void *tape, int chunks, int N, int elem, const void *packed,
-                                        hipStream_t s);
+hipError_t launch_snapshot_tape(bool scatter, const SnapRun *runs, long n_runs, long max_n, void *tape, int chunks, int N, int elem, void *packed,
+                                hipStream_t s);
 
 // The comb of the reference's decimation x[::step] (src/silero_vad/utils_vad.py:39-42) over a stream that arrives in pieces: input sample g
 // of the stream is kept iff g % step == 0; `phase` = (samples that came before the piece) % step.  The one definition the pump's

@@ -1568,15 +1568,50 @@ static_assert(sizeof(vad_resample_info) == 32 && VAD_SNAPSHOT_HEADER_BYTES_V2 % 
               "the version 2 tail is the documented one, and holds the history of every served pair");
 const char kSnapMagic[8] = {'S', 'V', 'A', 'D', 'S', 'N', 'A', 'P'};
 
-size_t snap_stride(int N, int C) { return sizeof(vad_stream_info) + (size_t)(2 * 128 + C) * sizeof(float) + (size_t)N * sizeof(int16_t); }
-// version 2: the version 1 record, then vad_resample_info, float carry[N], int16 history[VAD_SNAPSHOT_HISTORY]
-size_t snap_stride2(int N, int C) { return snap_stride(N, C) + sizeof(vad_resample_info) + (size_t)N * sizeof(float) + VAD_SNAPSHOT_HISTORY * sizeof(int16_t); }
-// version 3: the version 2 record, then vad_tape_info; the header goes on with {int32 tape_elem, int32 reserved, int64 tape_bytes} and zeros
-size_t snap_stride3(int N, int C) { return snap_stride2(N, C) + sizeof(vad_tape_info); }
-static_assert(sizeof(vad_tape_info) == 32 && sizeof(vad::SnapRun) == 32 && VAD_SNAPSHOT_HEADER_BYTES_V3 == sizeof(SnapHeader) + 64, "the version 3 layout is the documented one");
+// Where everything of a blob of `version` lies -- the one place that knows what a version adds.  A record is vad_stream_info, h, c, the
+// context and the pending samples; from version 2 on, behind them, the tail: vad_resample_info, float carry[N], int16
+// history[VAD_SNAPSHOT_HISTORY]; in version 3, behind that, vad_tape_info, and the header goes on with {int32 tape_elem, int32 reserved,
+// int64 tape_bytes} and zeros, the tape section follows the records.
+struct SnapLayout {
+    size_t header_bytes, stride;
+    size_t tail_at, run_at;                      // of vad_resample_info and of vad_tape_info in a record; 0: this version has none
+    int table_words;                             // of a record's entry in the kernels' work table (device_api.hpp)
+};
+constexpr SnapLayout snap_layout(int version, int N, int C) {
+    const size_t v1 = sizeof(vad_stream_info) + (size_t)(2 * 128 + C) * sizeof(float) + (size_t)N * sizeof(int16_t);
+    const size_t v2 = v1 + sizeof(vad_resample_info) + (size_t)N * sizeof(float) + VAD_SNAPSHOT_HISTORY * sizeof(int16_t);
+    return version == VAD_SNAPSHOT_VERSION_3   ? SnapLayout{VAD_SNAPSHOT_HEADER_BYTES_V3, v2 + sizeof(vad_tape_info), v1, v2, 8}
+           : version == VAD_SNAPSHOT_VERSION_2 ? SnapLayout{VAD_SNAPSHOT_HEADER_BYTES_V2, v2, v1, 0, 8}
+                                               : SnapLayout{VAD_SNAPSHOT_HEADER_BYTES, v1, 0, 0, 4};
+}
+static_assert(snap_layout(1, 512, 64).header_bytes == sizeof(SnapHeader) && snap_layout(1, 512, 64).stride == 2336 && snap_layout(1, 256, 32).stride == 1696,
+              "the version 1 layout is the documented one");
+static_assert(snap_layout(2, 512, 64).stride == 4736 && snap_layout(2, 512, 64).tail_at == snap_layout(1, 512, 64).stride && snap_layout(2, 256, 32).stride % 16 == 0,
+              "the version 2 layout is the documented one: the version 1 record goes first");
+static_assert(sizeof(vad_tape_info) == 32 && sizeof(vad::SnapRun) == 32 && snap_layout(3, 512, 64).header_bytes == sizeof(SnapHeader) + 64 &&
+                  snap_layout(3, 512, 64).run_at == snap_layout(2, 512, 64).stride && snap_layout(3, 512, 64).stride == snap_layout(2, 512, 64).stride + 32,
+              "the version 3 layout is the documented one: the version 2 record goes first");
 struct SnapTape {                                // what a version 3 header says of the tape section (versions 1 and 2: no tape)
     int32_t elem = 0;
     int64_t bytes = 0;
+};
+// A blob that snap_check has accepted (it may lie at any address: everything is read through memcpy).
+struct SnapBlob {
+    SnapHeader hd;
+    SnapLayout at;
+    SnapTape tape;
+    const uint8_t *rec = nullptr;                // record 0; the tape section lies behind record n_records - 1
+    const uint8_t *record(long r) const { return rec + (size_t)r * at.stride; }
+    const uint8_t *tape_section() const { return record((long)hd.n_records); }
+    template <class T>
+    T part(long r, size_t where, bool has) const {               // (a version without the part: zeros -- bound to no rate, no run)
+        T x{};
+        if (has) std::memcpy(&x, record(r) + where, sizeof(x));
+        return x;
+    }
+    vad_stream_info info(long r) const { return part<vad_stream_info>(r, 0, true); }
+    vad_resample_info tail(long r) const { return part<vad_resample_info>(r, at.tail_at, at.tail_at != 0); }
+    vad_tape_info run(long r) const { return part<vad_tape_info>(r, at.run_at, at.run_at != 0); }
 };
 
 bool any_byte_set(const uint8_t *at, size_t n) {
@@ -1585,19 +1620,18 @@ bool any_byte_set(const uint8_t *at, size_t n) {
     return acc != 0;
 }
 
-// The tail of a version 2 record whose version 1 part is `f` (all of it, like everything of a blob, is read through memcpy).  *last: the
-// pair looked up last, so that a blob of 8 192 records of a few rates takes the table's lock a few times.  *H: the pair's history.
+// The tail of a record whose info block is `f` (all of it, like everything of a blob, is read through memcpy).  *last: the pair looked
+// up last, so that a blob of 8 192 records of a few rates takes the table's lock a few times.
 struct SnapPair {
     int rate = 0;
     std::shared_ptr<const vad::ResampleHostTable> tab;
 };
-const char *snap_tail_fault(const uint8_t *tail, const vad_stream_info &f, int sr, int N, SnapPair *last, vad_resample_info *out, int *H) {
+const char *snap_tail_fault(const uint8_t *tail, const vad_stream_info &f, int sr, int N, SnapPair *last) {
     vad_resample_info q;
     std::memcpy(&q, tail, sizeof(q));
     for (const uint8_t z : q.reserved)
         if (z) return "reserved bytes that are not zero";
-    long c = 0;
-    *H = 0;
+    long c = 0, H = 0;                           // the live floats of the carry, the pair's history
     if (q.src_rate == 0) {
         if (q.pending_out || q.inputs_mod || q.outputs_mod) return "resample counters of a stream that is bound to no rate";
     } else {
@@ -1609,12 +1643,11 @@ const char *snap_tail_fault(const uint8_t *tail, const vad_stream_info &f, int s
         if (q.inputs_mod < 0 || q.inputs_mod >= t.end.back()) return "inputs_mod below 0, or so large that a whole period would be ready";
         if (vad::resample_stream_ready(t, q.inputs_mod) != q.outputs_mod) return "outputs_mod is not what a stream of inputs_mod inputs has emitted";
         if (f.pending != 0) return "a stream that is bound to a rate with int16 samples pending";
-        c = q.pending_out, *H = t.H;
+        c = q.pending_out, H = t.H;
     }
     const uint8_t *carry = tail + sizeof(q), *hist = carry + (size_t)N * sizeof(float);
     if (any_byte_set(carry + (size_t)c * sizeof(float), (size_t)(N - c) * sizeof(float))) return "a float behind pending_out that is not +0.0f";
-    if (any_byte_set(hist + (size_t)*H * sizeof(int16_t), (size_t)(VAD_SNAPSHOT_HISTORY - *H) * sizeof(int16_t))) return "a history sample behind H that is not zero";
-    if (out) *out = q;
+    if (any_byte_set(hist + (size_t)H * sizeof(int16_t), (size_t)(VAD_SNAPSHOT_HISTORY - H) * sizeof(int16_t))) return "a history sample behind H that is not zero";
     return nullptr;
 }
 
@@ -1629,9 +1662,9 @@ const char *snap_info_fault(const vad_stream_info &f, int N) {
     return nullptr;
 }
 
-// The vad_tape_info of a version 3 record whose version 1 part is `f`.  *done: the chunks of the earlier runs; total: the chunks the tape
+// The vad_tape_info of a record whose info block is `f`.  *done: the chunks of the earlier runs; total: the chunks the tape
 // section holds, tape_bytes / (N * elem) (0 without a tape).  Every comparison comes before the arithmetic it makes safe.
-const char *snap_run_fault(const uint8_t *at, const vad_stream_info &f, int N, int elem, int64_t total, int64_t *done, vad_tape_info *out) {
+const char *snap_run_fault(const uint8_t *at, const vad_stream_info &f, int N, int elem, int64_t total, int64_t *done) {
     vad_tape_info t;
     std::memcpy(&t, at, sizeof(t));
     for (const uint8_t z : t.reserved)
@@ -1646,122 +1679,128 @@ const char *snap_run_fault(const uint8_t *at, const vad_stream_info &f, int N, i
         if (f.current_sample % N != 0 || t.first_chunk != f.current_sample / N - t.n_chunks) return "a run that does not end at the record's current_sample";
         *done += t.n_chunks;
     }
-    if (out) *out = t;
     return nullptr;
 }
 
-// The whole blob, header and every record's fields (the blob may lie at any address: everything is read through memcpy).
-// -> nullptr, *hd and *tp (if asked for), or what is wrong with it.
-const char *snap_check(const void *blob, size_t nbytes, SnapHeader *hd, SnapTape *tp = nullptr) {
+// The whole blob, header and every record's fields.  -> nullptr and *b, the view of it, or what is wrong with it.
+const char *snap_check(const void *blob, size_t nbytes, SnapBlob *b) {
+    SnapHeader &hd = b->hd;
     if (!blob || nbytes < sizeof(SnapHeader)) return "shorter than a header";
-    std::memcpy(hd, blob, sizeof(SnapHeader));
-    if (std::memcmp(hd->magic, kSnapMagic, sizeof(kSnapMagic)) != 0) return "not a snapshot (magic)";
-    const bool v3 = hd->version == VAD_SNAPSHOT_VERSION_3, v2 = hd->version == VAD_SNAPSHOT_VERSION_2 || v3;
-    if ((hd->version != VAD_SNAPSHOT_VERSION && !v2) ||
-        hd->header_bytes != (v3 ? VAD_SNAPSHOT_HEADER_BYTES_V3 : v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader)))
+    std::memcpy(&hd, blob, sizeof(SnapHeader));
+    if (std::memcmp(hd.magic, kSnapMagic, sizeof(kSnapMagic)) != 0) return "not a snapshot (magic)";
+    if (hd.version < VAD_SNAPSHOT_VERSION || hd.version > VAD_SNAPSHOT_VERSION_3 || hd.header_bytes != snap_layout((int)hd.version, 0, 0).header_bytes)
         return "a version this library does not read";
-    if (nbytes < hd->header_bytes) return "shorter than a header";
+    if (nbytes < hd.header_bytes) return "shorter than a header";
     const uint8_t *bytes = static_cast<const uint8_t *>(blob);
-    SnapTape tape;
-    if (v3) {                                    // {int32 tape_elem, int32 reserved, int64 tape_bytes}, then zeros
+    const bool runs = snap_layout((int)hd.version, 0, 0).run_at != 0;
+    SnapTape &tape = b->tape = SnapTape{};
+    size_t zeros = sizeof(SnapHeader);           // the header is zeros from here on
+    if (runs) {                                  // {int32 tape_elem, int32 reserved, int64 tape_bytes}
         int32_t word[2];
-        std::memcpy(word, bytes + sizeof(SnapHeader), sizeof(word));
-        std::memcpy(&tape.bytes, bytes + sizeof(SnapHeader) + sizeof(word), sizeof(tape.bytes));
-        tape.elem = word[0];
-        if (word[1] != 0 || any_byte_set(bytes + sizeof(SnapHeader) + 16, VAD_SNAPSHOT_HEADER_BYTES_V3 - sizeof(SnapHeader) - 16))
-            return "reserved bytes that are not zero";
-        if (tape.elem != 0 && tape.elem != 2 && tape.elem != 4) return "a tape_elem other than 0, 2 or 4";
-        if (tape.bytes < 0 || (tape.elem == 0 && tape.bytes != 0)) return "tape_bytes below zero, or not zero without a tape";
-    } else if (v2 && any_byte_set(bytes + sizeof(SnapHeader), VAD_SNAPSHOT_HEADER_BYTES_V2 - sizeof(SnapHeader))) {
-        return "reserved bytes that are not zero";
+        std::memcpy(word, bytes + zeros, sizeof(word));
+        std::memcpy(&tape.bytes, bytes + zeros + sizeof(word), sizeof(tape.bytes));
+        tape.elem = word[0], zeros += 16;
+        if (word[1] != 0) return "reserved bytes that are not zero";
     }
+    if (any_byte_set(bytes + zeros, hd.header_bytes - zeros)) return "reserved bytes that are not zero";
+    if (tape.elem != 0 && tape.elem != 2 && tape.elem != 4) return "a tape_elem other than 0, 2 or 4";
+    if (tape.bytes < 0 || (tape.elem == 0 && tape.bytes != 0)) return "tape_bytes below zero, or not zero without a tape";
     int N = 0, C = 0;
-    if (vad_geometry(hd->sr, &N, &C) != VAD_OK || hd->N != N || hd->C != C ||
-        hd->stride != (v3 ? snap_stride3(N, C) : v2 ? snap_stride2(N, C) : snap_stride(N, C)))
+    if (vad_geometry(hd.sr, &N, &C) != VAD_OK || hd.N != N || hd.C != C || hd.stride != snap_layout((int)hd.version, N, C).stride)
         return "a sample rate / geometry that does not exist";
-    if (hd->n_records < 0 || (uint64_t)hd->n_records > (nbytes - hd->header_bytes) / hd->stride) return "shorter than its header claims";
-    // version 3: the buffer is exactly the header, the records and the tape section
-    if (v3 && (uint64_t)tape.bytes != nbytes - hd->header_bytes - (size_t)hd->n_records * hd->stride) return "not as long as its header claims";
+    b->at = snap_layout((int)hd.version, N, C);
+    b->rec = bytes + hd.header_bytes;
+    if (hd.n_records < 0 || (uint64_t)hd.n_records > (nbytes - hd.header_bytes) / hd.stride) return "shorter than its header claims";
+    // with a tape section the buffer is exactly the header, the records and that section
+    if (runs && (uint64_t)tape.bytes != nbytes - hd.header_bytes - (size_t)hd.n_records * hd.stride) return "not as long as its header claims";
     const int64_t total = tape.elem ? tape.bytes / ((int64_t)N * tape.elem) : 0;
     int64_t done = 0;
-    const uint8_t *rec = bytes + hd->header_bytes;
     SnapPair last;
-    for (int64_t i = 0; i < hd->n_records; ++i) {
-        vad_stream_info f;
-        std::memcpy(&f, rec + (size_t)i * hd->stride, sizeof(f));
+    for (int64_t i = 0; i < hd.n_records; ++i) {
+        const vad_stream_info f = b->info((long)i);
         if (const char *why = snap_info_fault(f, N)) return why;
-        int H = 0;
-        if (v2)
-            if (const char *why = snap_tail_fault(rec + (size_t)i * hd->stride + snap_stride(N, C), f, hd->sr, N, &last, nullptr, &H)) return why;
-        if (v3)
-            if (const char *why = snap_run_fault(rec + (size_t)i * hd->stride + snap_stride2(N, C), f, N, tape.elem, total, &done, nullptr)) return why;
+        if (b->at.tail_at)
+            if (const char *why = snap_tail_fault(b->record((long)i) + b->at.tail_at, f, hd.sr, N, &last)) return why;
+        if (b->at.run_at)
+            if (const char *why = snap_run_fault(b->record((long)i) + b->at.run_at, f, N, tape.elem, total, &done)) return why;
     }
-    if (v3 && tape.elem && done * N * tape.elem != tape.bytes) return "a tape section that is not the sum of its runs";
-    if (tp) *tp = tape;
+    if (tape.elem && done * N * tape.elem != tape.bytes) return "a tape section that is not the sum of its runs";
     return nullptr;
 }
 
 int part_of(const vad_pump *p, int b) { return (int)(std::upper_bound(p->hi.begin(), p->hi.end(), b) - p->hi.begin()); }
 
-// the work table and the part table (first call), and room for `bytes` of records on the device
-int snap_reserve(vad_pump *p, size_t bytes) {
+// One staging of a call: its table (first call: `entries` of T, page-locked and mapped, the kernels read it in place) and room for
+// `bytes` on the device.
+template <class T>
+int snap_stage(vad_pump *p, T **h_tab, T **d_tab, size_t entries, uint8_t **d_buf, size_t *cap, size_t bytes, const char *no_table, const char *no_room) {
     PUMP_TRY(p, hipSetDevice(p->device));
-    if (!p->h_snap_tab) {
+    if (!*h_tab) {
         void *dv = nullptr;
-        int32_t *tab = nullptr;
-        vad::SnapPart *dp = nullptr;
-        std::vector<vad::SnapPart> parts;
-        for (int k = 0; k < p->parts; ++k) parts.push_back(vad::SnapPart{p->d_state[k], p->lo[k], p->hi[k] - p->lo[k]});
-        const bool ok = hipHostMalloc((void **)&tab, (size_t)p->streams * 8 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess &&
-                        hipHostGetDevicePointer(&dv, tab, 0) == hipSuccess && dv &&
-                        hipMalloc((void **)&dp, parts.size() * sizeof(vad::SnapPart)) == hipSuccess &&
-                        hipMemcpy(dp, parts.data(), parts.size() * sizeof(vad::SnapPart), hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) {
-            if (dp) (void)hipFree(dp);
+        T *tab = nullptr;
+        if (hipHostMalloc((void **)&tab, entries * sizeof(T), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dv, tab, 0) != hipSuccess || !dv) {
             if (tab) (void)hipHostFree(tab);
-            return pfail(p, VAD_ERR_ALLOC, "snapshot: no memory for the work tables");
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, no_table);
         }
-        p->h_snap_tab = tab, p->d_snap_tab = static_cast<int32_t *>(dv), p->d_snap_parts = dp;
+        *h_tab = tab, *d_tab = static_cast<T *>(dv);
     }
-    if (bytes > p->snap_cap) {
-        if (p->d_snap) (void)hipFree(p->d_snap);
-        p->d_snap = nullptr, p->snap_cap = 0;
-        if (hipMalloc((void **)&p->d_snap, bytes) != hipSuccess) return pfail(p, VAD_ERR_ALLOC, "snapshot: no device memory for the records");
-        p->snap_cap = bytes;
+    if (bytes > *cap) {
+        if (*d_buf) (void)hipFree(*d_buf);
+        *d_buf = nullptr, *cap = 0;
+        if (hipMalloc((void **)d_buf, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, no_room);
+        }
+        *cap = bytes;
     }
     return VAD_OK;
+}
+
+// the records: the work table (8 words a stream: room for an entry with a tail), the packed records and the part table (first call)
+int snap_reserve(vad_pump *p, size_t bytes) {
+    if (const int rc = snap_stage(p, &p->h_snap_tab, &p->d_snap_tab, (size_t)p->streams * 8, &p->d_snap, &p->snap_cap, bytes,
+                                  "snapshot: no memory for the work tables", "snapshot: no device memory for the records"))
+        return rc;
+    if (!p->d_snap_parts) {
+        std::vector<vad::SnapPart> parts;
+        for (int k = 0; k < p->parts; ++k) parts.push_back(vad::SnapPart{p->d_state[k], p->lo[k], p->hi[k] - p->lo[k]});
+        vad::SnapPart *dp = nullptr;
+        if (hipMalloc((void **)&dp, parts.size() * sizeof(vad::SnapPart)) != hipSuccess ||
+            hipMemcpy(dp, parts.data(), parts.size() * sizeof(vad::SnapPart), hipMemcpyHostToDevice) != hipSuccess) {
+            if (dp) (void)hipFree(dp);
+            (void)hipGetLastError();
+            return pfail(p, VAD_ERR_ALLOC, "snapshot: no memory for the work tables");
+        }
+        p->d_snap_parts = dp;
+    }
+    return VAD_OK;
+}
+
+// the runs of the tape: the table of runs and the packed chunks
+int snap_tape_reserve(vad_pump *p, size_t bytes) {
+    return snap_stage(p, &p->h_snap_runs, &p->d_snap_runs, (size_t)p->streams, &p->d_snap_tape, &p->snap_tape_cap, bytes,
+                      "snapshot: no memory for the table of runs", "snapshot: no device memory to stage the runs of the tape");
+}
+
+// A record's entry of the work table: {slot, part, pending, record} and, in a layout with a tail, {c, H, bound, 0} behind it.
+void snap_entry(vad_pump *p, const SnapLayout &at, long k, int32_t slot, int32_t pending, int32_t record, int32_t c, int32_t H, bool bound) {
+    int32_t *e = p->h_snap_tab + at.table_words * k;
+    e[0] = slot, e[1] = part_of(p, slot), e[2] = pending, e[3] = record;
+    if (at.table_words == 8) e[4] = c, e[5] = H, e[6] = bound, e[7] = 0;
+}
+
+// the tail arguments of the record kernels (null: records without a tail)
+const vad::SnapTail *snap_tail_args(const vad_pump *p, const SnapLayout &at, vad::SnapTail *tl) {
+    if (!at.tail_at) return nullptr;
+    *tl = vad::SnapTail{p->d_fcarry, p->d_hist, p->r_hld, at.run_at ? (int)(at.stride - at.run_at) : 0};    // (what lies behind the tail is the host's)
+    return tl;
 }
 
 // both calls: not on a poisoned pump, not with a tick in flight
 int snap_idle(vad_pump *p, const std::string &fn) {
     if (p->poisoned) return pfail(p, VAD_ERR_HIP, "the pump failed half-way through an earlier tick; destroy it (" + p->err + ")");
     if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, fn + "ticks in flight (retire them with vad_pump_poll first)");
-    return VAD_OK;
-}
-
-// the staging of a call's runs of the tape: the mapped table of runs (first call) and room for `bytes` of packed chunks on the device
-int snap_tape_reserve(vad_pump *p, size_t bytes) {
-    PUMP_TRY(p, hipSetDevice(p->device));
-    if (!p->h_snap_runs) {
-        void *dv = nullptr;
-        vad::SnapRun *tab = nullptr;
-        if (hipHostMalloc((void **)&tab, (size_t)p->streams * sizeof(vad::SnapRun), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer(&dv, tab, 0) != hipSuccess || !dv) {
-            if (tab) (void)hipHostFree(tab);
-            (void)hipGetLastError();
-            return pfail(p, VAD_ERR_ALLOC, "snapshot: no memory for the table of runs");
-        }
-        p->h_snap_runs = tab, p->d_snap_runs = static_cast<vad::SnapRun *>(dv);
-    }
-    if (bytes > p->snap_tape_cap) {
-        if (p->d_snap_tape) (void)hipFree(p->d_snap_tape);
-        p->d_snap_tape = nullptr, p->snap_tape_cap = 0;
-        if (hipMalloc((void **)&p->d_snap_tape, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return pfail(p, VAD_ERR_ALLOC, "snapshot: no device memory to stage the runs of the tape");
-        }
-        p->snap_tape_cap = bytes;
-    }
     return VAD_OK;
 }
 
@@ -1803,50 +1842,43 @@ int snap_plan_runs(vad_pump *p, const int32_t *streams, long n, const int64_t *t
     return VAD_OK;
 }
 
-// vad_pump_export_streams (version 1: the launch and the bytes it always had), vad_pump_export_streams_v2 and vad_pump_export_streams_v3
+// vad_pump_export_streams, vad_pump_export_streams_v2 and vad_pump_export_streams_v3 (version = 1, 2, 3)
+const char *const kExportName[] = {"vad_pump_export_streams: ", "vad_pump_export_streams_v2: ", "vad_pump_export_streams_v3: "};
+const char *const kExportNeeds[] = {"vad_pump_snapshot_bytes(sr, n)", "vad_pump_snapshot_bytes_v2(sr, n)", "vad_pump_snapshot_plan_v3(p, streams, n, tape_from)"};
+
 int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t cap, int version, const int64_t *tape_from = nullptr) {
     if (!p) return VAD_ERR_ARG;
-    const bool v2 = version >= 2, v3 = version == 3;
-    const std::string fn = v3 ? "vad_pump_export_streams_v3: " : v2 ? "vad_pump_export_streams_v2: " : "vad_pump_export_streams: ";
+    const std::string fn = kExportName[version - 1];
     if (const int rc = snap_idle(p, fn)) return rc;
     const int slots = snap_slots_fault(p, streams, n);
     if (slots == 1 || !blob) return pfail(p, VAD_ERR_ARG, fn + "bad slot list (NULL = every slot: n is then the pump's stream count) or no blob");
     if (slots) return pfail(p, VAD_ERR_ARG, fn + "a slot out of range, or listed twice");
-    const size_t head = v3 ? VAD_SNAPSHOT_HEADER_BYTES_V3 : v2 ? VAD_SNAPSHOT_HEADER_BYTES_V2 : sizeof(SnapHeader), tail = snap_stride(p->N, p->C);       // tail: where a version 2 record's begins
-    const size_t stride = v3 ? snap_stride3(p->N, p->C) : v2 ? snap_stride2(p->N, p->C) : tail;
+    const SnapLayout at = snap_layout(version, p->N, p->C);
+    const size_t stride = at.stride;
     std::vector<SnapRunPlan> run;
     int64_t run_chunks = 0;
-    if (v3)
+    if (at.run_at)
         if (const int rc = snap_plan_runs(p, streams, n, tape_from, &run, &run_chunks)) return rc;
     const size_t row_bytes = (size_t)p->N * (size_t)p->tape_elem, tape_bytes = (size_t)run_chunks * row_bytes;       // (run_chunks <= streams x chunks: the tape itself is that large)
-    const size_t need = head + (size_t)n * stride + tape_bytes;
-    if (cap < need)
-        return pfail(p, VAD_ERR_ARG, fn + (v3 ? "the blob needs vad_pump_snapshot_plan_v3(p, streams, n, tape_from) bytes"
-                                              : std::string("the blob needs vad_pump_snapshot_bytes") + (v2 ? "_v2" : "") + "(sr, n) bytes"));
-    for (long k = 0; !v2 && k < n && p->n_bound > 0; ++k)
+    if (cap < at.header_bytes + (size_t)n * stride + tape_bytes) return pfail(p, VAD_ERR_ARG, fn + "the blob needs " + kExportNeeds[version - 1] + " bytes");
+    for (long k = 0; !at.tail_at && k < n && p->n_bound > 0; ++k)
         if (p->r_rate[streams ? streams[k] : k] >= 0)
             return pfail(p, VAD_ERR_ARG, fn + "stream " + std::to_string(streams ? streams[k] : k) + " is bound to a resampled rate: blob version 1 has no room for "
                                                   "its fp32 pending outputs and filter history (vad_pump_export_streams_v2 writes version 2)");
-    uint8_t *rec = static_cast<uint8_t *>(blob) + head;
+    uint8_t *rec = static_cast<uint8_t *>(blob) + at.header_bytes;
     if (n > 0) {
         if (const int rc = snap_reserve(p, (size_t)n * stride)) return rc;
         if (run_chunks > 0)
             if (const int rc = snap_tape_reserve(p, tape_bytes)) return rc;
         for (long k = 0; k < n; ++k) {
             const int32_t b = streams ? streams[k] : (int32_t)k;
-            int32_t *e = p->h_snap_tab + (v2 ? 8 : 4) * k;
-            e[0] = b, e[1] = part_of(p, b), e[2] = p->held[b], e[3] = (int32_t)k;
-            if (v2) {
-                const bool is_bound = p->bound(b);
-                e[4] = is_bound ? p->r_pend[b] : 0, e[5] = is_bound ? p->r_tab[p->r_rate[b]]->H : 0, e[6] = is_bound, e[7] = 0;
-            }
+            const bool is_bound = p->bound(b);
+            snap_entry(p, at, k, b, p->held[b], (int32_t)k, is_bound ? p->r_pend[b] : 0, is_bound ? p->r_tab[p->r_rate[b]]->H : 0, is_bound);
         }
         // (read-only, behind everything the compute stream has run: a failure leaves the pump as it was)
-        if (v2)
-            PUMP_TRY(p, vad::launch_snapshot_gather2(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->d_fcarry, p->d_hist, p->r_hld,
-                                                     p->N, p->C, p->d_snap, p->compute, v3 ? (int)sizeof(vad_tape_info) : 0));
-        else
-            PUMP_TRY(p, vad::launch_snapshot_gather(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute));
+        vad::SnapTail tl;
+        PUMP_TRY(p, vad::launch_snapshot_gather(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute,
+                                                snap_tail_args(p, at, &tl)));
         PUMP_TRY(p, hipMemcpyAsync(rec, p->d_snap, (size_t)n * stride, hipMemcpyDeviceToHost, p->compute));
         if (run_chunks > 0) {                    // the runs: packed on the device in record order, ONE copy into the tape section
             int64_t longest = 0;
@@ -1855,124 +1887,119 @@ int snap_export(vad_pump *p, const int32_t *streams, long n, void *blob, size_t 
                 p->h_snap_runs[k] = vad::SnapRun{streams ? streams[k] : (int32_t)k, (int32_t)q.n, q.first, q.at, 0};
                 longest = std::max(longest, q.n);
             }
-            PUMP_TRY(p, vad::launch_snapshot_tape_gather(p->d_snap_runs, n, (long)longest, p->d_tape, p->tape_chunks, p->N, p->tape_elem, p->d_snap_tape,
-                                                         p->compute));
+            PUMP_TRY(p, vad::launch_snapshot_tape(false, p->d_snap_runs, n, (long)longest, p->d_tape, p->tape_chunks, p->N, p->tape_elem, p->d_snap_tape, p->compute));
             PUMP_TRY(p, hipMemcpyAsync(rec + (size_t)n * stride, p->d_snap_tape, tape_bytes, hipMemcpyDeviceToHost, p->compute));
         }
         PUMP_TRY(p, hipStreamSynchronize(p->compute));
     }
     SnapHeader hd;
     std::memcpy(hd.magic, kSnapMagic, sizeof(kSnapMagic));
-    hd.version = (uint32_t)version, hd.header_bytes = (uint32_t)head;
+    hd.version = (uint32_t)version, hd.header_bytes = (uint32_t)at.header_bytes;
     hd.sr = p->sr, hd.N = p->N, hd.C = p->C, hd.stride = (uint32_t)stride, hd.n_records = n;
     hd.threshold = p->threshold, hd.min_silence = p->min_silence, hd.pad = p->pad;
     std::memcpy(blob, &hd, sizeof(hd));
-    std::memset(static_cast<uint8_t *>(blob) + sizeof(hd), 0, head - sizeof(hd));
-    if (v3) {
+    std::memset(static_cast<uint8_t *>(blob) + sizeof(hd), 0, at.header_bytes - sizeof(hd));
+    if (at.run_at) {
         const int32_t elem = p->tape_elem;
         const int64_t tb = (int64_t)tape_bytes;
         std::memcpy(static_cast<uint8_t *>(blob) + sizeof(hd), &elem, sizeof(elem));
         std::memcpy(static_cast<uint8_t *>(blob) + sizeof(hd) + 8, &tb, sizeof(tb));
     }
-    for (long k = 0; k < n; ++k) {               // the host's part of a record (the gather left it zero)
+    for (long k = 0; k < n; ++k) {               // the host's parts of a record (the gather left them zero)
         const int32_t b = streams ? streams[k] : (int32_t)k;
         vad_stream_info f{};
         f.current_sample = p->current[b], f.temp_end = p->temp_end[b], f.pending = p->held[b];
         f.active = p->active[b], f.triggered = p->triggered[b];
         if (p->max_step) f.wide_step = p->w_step[b], f.wide_phase = p->w_phase[b];
         std::memcpy(rec + (size_t)k * stride, &f, sizeof(f));
-        if (v2 && p->bound(b)) {
+        if (at.tail_at && p->bound(b)) {
             vad_resample_info q{};
             q.src_rate = p->rates[p->r_rate[b]], q.pending_out = p->r_pend[b], q.inputs_mod = p->r_g[b], q.outputs_mod = p->r_m[b];
-            std::memcpy(rec + (size_t)k * stride + tail, &q, sizeof(q));
+            std::memcpy(rec + (size_t)k * stride + at.tail_at, &q, sizeof(q));
         }
-        if (v3 && run[(size_t)k].n > 0) {
+        if (at.run_at && run[(size_t)k].n > 0) {
             vad_tape_info t{};
             t.first_chunk = run[(size_t)k].first, t.n_chunks = run[(size_t)k].n, t.offset = run[(size_t)k].at * (int64_t)row_bytes;
-            std::memcpy(rec + (size_t)k * stride + snap_stride2(p->N, p->C), &t, sizeof(t));
+            std::memcpy(rec + (size_t)k * stride + at.run_at, &t, sizeof(t));
         }
     }
     return VAD_OK;
+}
+
+// header + n records of `version`; 0 for arguments no blob has
+size_t snap_bytes(int version, int sr, long n) {
+    int N = 0, C = 0;
+    if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
+    const SnapLayout at = snap_layout(version, N, C);
+    return at.header_bytes + (size_t)n * at.stride;
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t vad_pump_snapshot_bytes(int sr, long n) {
-    int N = 0, C = 0;
-    if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
-    return sizeof(SnapHeader) + (size_t)n * snap_stride(N, C);
-}
+size_t vad_pump_snapshot_bytes(int sr, long n) { return snap_bytes(1, sr, n); }
 
-size_t vad_pump_snapshot_bytes_v2(int sr, long n) {
-    int N = 0, C = 0;
-    if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK) return 0;
-    return VAD_SNAPSHOT_HEADER_BYTES_V2 + (size_t)n * snap_stride2(N, C);
-}
+size_t vad_pump_snapshot_bytes_v2(int sr, long n) { return snap_bytes(2, sr, n); }
 
 size_t vad_snapshot_bytes_v3(int sr, long n, int tape_elem, int64_t total_chunks) {
     int N = 0, C = 0;
     if (n < 0 || vad_geometry(sr, &N, &C) != VAD_OK || (tape_elem != 0 && tape_elem != 2 && tape_elem != 4) || total_chunks < 0 ||
         (tape_elem == 0 && total_chunks != 0))
         return 0;
-    const size_t stride = snap_stride3(N, C), row = (size_t)N * (size_t)tape_elem;
-    if ((size_t)n > (SIZE_MAX - VAD_SNAPSHOT_HEADER_BYTES_V3) / stride) return 0;
-    const size_t records = VAD_SNAPSHOT_HEADER_BYTES_V3 + (size_t)n * stride;
+    const SnapLayout at = snap_layout(3, N, C);
+    const size_t row = (size_t)N * (size_t)tape_elem;
+    if ((size_t)n > (SIZE_MAX - at.header_bytes) / at.stride) return 0;
+    const size_t records = at.header_bytes + (size_t)n * at.stride;
     if (row && (uint64_t)total_chunks > (SIZE_MAX - records) / row) return 0;
     return records + (size_t)total_chunks * row;
 }
 
 int vad_snapshot_inspect(const void *blob, size_t nbytes, long *n_records, int *sr) {
-    SnapHeader hd;
-    if (snap_check(blob, nbytes, &hd)) return VAD_ERR_ARG;
-    if (n_records) *n_records = (long)hd.n_records;
-    if (sr) *sr = hd.sr;
+    SnapBlob b;
+    if (snap_check(blob, nbytes, &b)) return VAD_ERR_ARG;
+    if (n_records) *n_records = (long)b.hd.n_records;
+    if (sr) *sr = b.hd.sr;
     return VAD_OK;
 }
 
 int vad_snapshot_stream(const void *blob, size_t nbytes, long i, vad_stream_info *info, float *h, float *c, float *ctx, int16_t *pending) {
-    SnapHeader hd;
-    if (snap_check(blob, nbytes, &hd) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
-    const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)i * hd.stride;
-    const size_t st = 128 * sizeof(float), cx = (size_t)hd.C * sizeof(float);
-    if (info) std::memcpy(info, rec, sizeof(*info));
+    SnapBlob b;
+    if (snap_check(blob, nbytes, &b) || i < 0 || i >= b.hd.n_records) return VAD_ERR_ARG;
+    const uint8_t *rec = b.record(i);
+    const size_t st = 128 * sizeof(float), cx = (size_t)b.hd.C * sizeof(float);
+    if (info) *info = b.info(i);
     if (h) std::memcpy(h, rec + sizeof(vad_stream_info), st);
     if (c) std::memcpy(c, rec + sizeof(vad_stream_info) + st, st);
     if (ctx) std::memcpy(ctx, rec + sizeof(vad_stream_info) + 2 * st, cx);
-    if (pending) std::memcpy(pending, rec + sizeof(vad_stream_info) + 2 * st + cx, (size_t)hd.N * sizeof(int16_t));
+    if (pending) std::memcpy(pending, rec + sizeof(vad_stream_info) + 2 * st + cx, (size_t)b.hd.N * sizeof(int16_t));
     return VAD_OK;
 }
 
 int vad_snapshot_resample(const void *blob, size_t nbytes, long i, vad_resample_info *info, float *carry, int16_t *history) {
-    SnapHeader hd;
-    if (snap_check(blob, nbytes, &hd) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
-    const size_t cb = (size_t)hd.N * sizeof(float), hb = VAD_SNAPSHOT_HISTORY * sizeof(int16_t);
-    if (hd.version == VAD_SNAPSHOT_VERSION) {    // (a version 1 record has no tail: the stream is bound to no rate)
-        if (info) std::memset(info, 0, sizeof(*info));
+    SnapBlob b;
+    if (snap_check(blob, nbytes, &b) || i < 0 || i >= b.hd.n_records) return VAD_ERR_ARG;
+    const size_t cb = (size_t)b.hd.N * sizeof(float), hb = VAD_SNAPSHOT_HISTORY * sizeof(int16_t);
+    if (info) *info = b.tail(i);
+    if (!b.at.tail_at) {                         // (a record without a tail: the stream is bound to no rate)
         if (carry) std::memset(carry, 0, cb);
         if (history) std::memset(history, 0, hb);
         return VAD_OK;
     }
-    const uint8_t *tail = static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)i * hd.stride + snap_stride(hd.N, hd.C);
-    if (info) std::memcpy(info, tail, sizeof(*info));
-    if (carry) std::memcpy(carry, tail + sizeof(vad_resample_info), cb);
-    if (history) std::memcpy(history, tail + sizeof(vad_resample_info) + cb, hb);
+    const uint8_t *rows = b.record(i) + b.at.tail_at + sizeof(vad_resample_info);
+    if (carry) std::memcpy(carry, rows, cb);
+    if (history) std::memcpy(history, rows + cb, hb);
     return VAD_OK;
 }
 
 int vad_snapshot_tape(const void *blob, size_t nbytes, long i, vad_tape_info *info, void *audio, size_t cap) {
-    SnapHeader hd;
-    SnapTape tape;
-    if (snap_check(blob, nbytes, &hd, &tape) || i < 0 || i >= hd.n_records) return VAD_ERR_ARG;
-    vad_tape_info t{};                           // (versions 1 and 2: no runs)
-    if (hd.version == VAD_SNAPSHOT_VERSION_3)
-        std::memcpy(&t, static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)i * hd.stride + snap_stride2(hd.N, hd.C), sizeof(t));
-    const size_t bytes = (size_t)t.n_chunks * (size_t)hd.N * (size_t)tape.elem;     // (snap_check: inside the tape section)
+    SnapBlob b;
+    if (snap_check(blob, nbytes, &b) || i < 0 || i >= b.hd.n_records) return VAD_ERR_ARG;
+    const vad_tape_info t = b.run(i);
+    const size_t bytes = (size_t)t.n_chunks * (size_t)b.hd.N * (size_t)b.tape.elem;     // (snap_check: inside the tape section)
     if (audio && cap < bytes) return VAD_ERR_ARG;
     if (info) *info = t;
-    if (audio && bytes)
-        std::memcpy(audio, static_cast<const uint8_t *>(blob) + hd.header_bytes + (size_t)hd.n_records * hd.stride + (size_t)t.offset, bytes);
+    if (audio && bytes) std::memcpy(audio, b.tape_section() + (size_t)t.offset, bytes);
     return VAD_OK;
 }
 
@@ -1988,7 +2015,8 @@ size_t vad_pump_snapshot_plan_v3(vad_pump *p, const int32_t *streams, long n, co
     std::vector<SnapRunPlan> run;
     int64_t run_chunks = 0;
     if (snap_plan_runs(p, streams, n, tape_from, &run, &run_chunks)) return 0;
-    return VAD_SNAPSHOT_HEADER_BYTES_V3 + (size_t)n * snap_stride3(p->N, p->C) + (size_t)run_chunks * (size_t)p->N * (size_t)p->tape_elem;
+    const SnapLayout at = snap_layout(3, p->N, p->C);
+    return at.header_bytes + (size_t)n * at.stride + (size_t)run_chunks * (size_t)p->N * (size_t)p->tape_elem;
 }
 
 int vad_pump_export_streams_v3(vad_pump *p, const int32_t *streams, long n, const int64_t *tape_from, void *blob, size_t cap) {
@@ -1999,9 +2027,10 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
     if (!p) return VAD_ERR_ARG;
     const std::string fn = "vad_pump_import_streams: ";
     if (const int rc = snap_idle(p, fn)) return rc;
-    SnapHeader hd;
-    SnapTape tape;
-    if (const char *why = snap_check(blob, nbytes, &hd, &tape)) return pfail(p, VAD_ERR_ARG, fn + "the blob is " + why);
+    SnapBlob in;
+    if (const char *why = snap_check(blob, nbytes, &in)) return pfail(p, VAD_ERR_ARG, fn + "the blob is " + why);
+    const SnapHeader &hd = in.hd;
+    const SnapTape &tape = in.tape;
     if (hd.sr != p->sr) return pfail(p, VAD_ERR_SAMPLE_RATE, fn + "the blob's sample rate is not the pump's");
     if (tape.elem && p->tape_elem && tape.elem != p->tape_elem)
         return pfail(p, VAD_ERR_ARG, fn + (tape.elem == 2 ? "the blob carries runs of an int16 tape and the pump's tape is float32"
@@ -2009,26 +2038,10 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
                                          ": an import does not convert");
     const long S = p->streams;
     if (n < 0 || n > S || (n > 0 && !streams)) return pfail(p, VAD_ERR_ARG, fn + "bad slot list");
-    const uint8_t *rec = static_cast<const uint8_t *>(blob) + hd.header_bytes;
     const size_t stride = hd.stride;
-    const bool v2 = hd.version >= VAD_SNAPSHOT_VERSION_2;      // (version 3: the version 2 record goes first)
-    const bool taped = tape.elem != 0 && p->tape_elem == tape.elem;       // the runs of the blob's tape section enter this pump's tape
+    // the runs of the blob's tape section enter this pump's tape, the newest tape_chunks chunks of each: without a tape here none is kept
+    // (with one, its element is the blob's by now)
     const size_t row_bytes = (size_t)p->N * (size_t)p->tape_elem;
-    auto run_of = [&](long r) {                  // (versions 1 and 2: no runs)
-        vad_tape_info t{};
-        if (taped) std::memcpy(&t, rec + (size_t)r * stride + snap_stride2(p->N, p->C), sizeof(t));
-        return t;
-    };
-    auto info_of = [&](long r) {
-        vad_stream_info f;
-        std::memcpy(&f, rec + (size_t)r * stride, sizeof(f));
-        return f;
-    };
-    auto tail_of = [&](long r) {                 // (version 1: no tail, bound to no rate)
-        vad_resample_info q{};
-        if (v2) std::memcpy(&q, rec + (size_t)r * stride + snap_stride(p->N, p->C), sizeof(q));
-        return q;
-    };
     auto rate_index = [&](int src_rate) {        // among THIS pump's rates; -1: not enabled here
         for (int k = 0; k < p->n_rates; ++k)
             if (p->rates[k] == src_rate) return k;
@@ -2043,12 +2056,12 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         const int32_t b = streams[i];
         if (r < 0 || r >= hd.n_records) why = "a record index out of range";
         else if (b < 0 || b >= S || p->seen[b]) why = "a slot out of range, or listed twice";
-        else if (info_of(r).wide_step >= 2 && info_of(r).wide_step > p->max_step) why = "a record of a 32 / 48 kHz stream, and the pump's wideband max_step is smaller (vad_pump_set_wideband)";
-        else if (tail_of(r).src_rate && rate_index(tail_of(r).src_rate) < 0) why = "a record of a stream that is bound to a rate this pump has not enabled (vad_pump_set_resample)";
+        else if (in.info(r).wide_step >= 2 && in.info(r).wide_step > p->max_step) why = "a record of a 32 / 48 kHz stream, and the pump's wideband max_step is smaller (vad_pump_set_wideband)";
+        else if (in.tail(r).src_rate && rate_index(in.tail(r).src_rate) < 0) why = "a record of a stream that is bound to a rate this pump has not enabled (vad_pump_set_resample)";
         else {
             p->seen[b] = 1;
             first = std::min(first, r), last = std::max(last, r);
-            const vad_tape_info t = run_of(r);
+            const vad_tape_info t = in.run(r);
             if (t.n_chunks > 0) {
                 run_lo = std::min(run_lo, t.offset), run_hi = std::max(run_hi, t.offset + t.n_chunks * (int64_t)row_bytes);
                 longest = std::max(longest, std::min<int64_t>(t.n_chunks, p->tape_chunks));
@@ -2064,33 +2077,28 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
     if (longest > 0)
         if (const int rc = snap_tape_reserve(p, (size_t)(run_hi - run_lo))) return rc;
     for (long k = 0; k < n && longest > 0; ++k) {                  // the newest `kept` chunks of each run, into this pump's own ring
-        const vad_tape_info t = run_of(records ? records[k] : k);
+        const vad_tape_info t = in.run(records ? records[k] : k);
         const int64_t kept = std::min<int64_t>(t.n_chunks, p->tape_chunks), skip = t.n_chunks - kept;
         p->h_snap_runs[k] = vad::SnapRun{streams[k], (int32_t)kept, t.first_chunk + skip, kept ? (t.offset - run_lo) / (int64_t)row_bytes + skip : 0, 0};
     }
     for (long k = 0; k < n; ++k) {
         const long r = records ? records[k] : k;
-        int32_t *e = p->h_snap_tab + (v2 ? 8 : 4) * k;
-        e[0] = streams[k], e[1] = part_of(p, streams[k]), e[2] = info_of(r).pending, e[3] = (int32_t)(r - first);
-        if (v2) {                                // (snap_check has held c and the pair against their ranges; H <= this pump's pitch: the rate is enabled here)
-            const vad_resample_info q = tail_of(r);
-            e[4] = q.pending_out, e[5] = q.src_rate ? p->r_tab[rate_index(q.src_rate)]->H : 0, e[6] = q.src_rate != 0, e[7] = 0;
-        }
+        const vad_resample_info q = in.tail(r);    // (snap_check has held c and the pair against their ranges; H <= this pump's pitch: the rate is enabled here)
+        snap_entry(p, in.at, k, streams[k], in.info(r).pending, (int32_t)(r - first), q.pending_out, q.src_rate ? p->r_tab[rate_index(q.src_rate)]->H : 0,
+                   q.src_rate != 0);
     }
     // ONE copy: the records first ... last; the scatter behind it on the compute stream.  From the copy on a failure leaves slots
     // half-replaced: the pump says so from then on.
     const hipError_t rc = [&] {
-        hipError_t e = hipMemcpyAsync(p->d_snap, rec + (size_t)first * stride, bytes, hipMemcpyHostToDevice, p->compute);
+        vad::SnapTail tl;
+        hipError_t e = hipMemcpyAsync(p->d_snap, in.record(first), bytes, hipMemcpyHostToDevice, p->compute);
         if (e == hipSuccess)
-            e = v2 ? vad::launch_snapshot_scatter2(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->d_fcarry, p->d_hist, p->r_hld, p->N,
-                                                   p->C, p->d_snap, p->compute, (int)(stride - snap_stride2(p->N, p->C)))
-                   : vad::launch_snapshot_scatter(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute);
+            e = vad::launch_snapshot_scatter(p->d_snap_tab, n, p->d_snap_parts, p->d_ctx[p->flips & 1], p->d_carry, p->N, p->C, p->d_snap, p->compute,
+                                             snap_tail_args(p, in.at, &tl));
         if (e == hipSuccess && longest > 0) {    // ONE more copy: the tape section from the first selected run to the last; the scatter behind it
-            e = hipMemcpyAsync(p->d_snap_tape, rec + (size_t)hd.n_records * stride + (size_t)run_lo, (size_t)(run_hi - run_lo), hipMemcpyHostToDevice,
-                               p->compute);
+            e = hipMemcpyAsync(p->d_snap_tape, in.tape_section() + (size_t)run_lo, (size_t)(run_hi - run_lo), hipMemcpyHostToDevice, p->compute);
             if (e == hipSuccess)
-                e = vad::launch_snapshot_tape_scatter(p->d_snap_runs, n, (long)longest, p->d_tape, p->tape_chunks, p->N, p->tape_elem, p->d_snap_tape,
-                                                      p->compute);
+                e = vad::launch_snapshot_tape(true, p->d_snap_runs, n, (long)longest, p->d_tape, p->tape_chunks, p->N, p->tape_elem, p->d_snap_tape, p->compute);
         }
         return e == hipSuccess ? hipStreamSynchronize(p->compute) : e;
     }();
@@ -2099,13 +2107,13 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         return pfail(p, VAD_ERR_HIP, fn + hipGetErrorString(rc));
     }
     for (long k = 0; k < n; ++k) {               // the host's part of the slot
-        const vad_stream_info f = info_of(records ? records[k] : k);
+        const vad_stream_info f = in.info(records ? records[k] : k);
         const int32_t b = streams[k];
         p->active[b] = f.active, p->triggered[b] = f.triggered, p->temp_end[b] = f.temp_end, p->current[b] = f.current_sample;
         p->n_held += (f.pending > 0) - (p->held[b] > 0);
         p->held[b] = f.pending;
         if (p->max_step) p->w_step[b] = f.wide_step, p->w_phase[b] = f.wide_phase;
-        const vad_resample_info q = tail_of(records ? records[k] : k);
+        const vad_resample_info q = in.tail(records ? records[k] : k);
         if (q.src_rate) {                        // a bound record: the scatter wrote the slot's whole carry and history rows
             p->n_bound += p->r_rate[b] < 0;
             p->r_rate[b] = (int8_t)rate_index(q.src_rate);
@@ -2123,7 +2131,7 @@ int vad_pump_import_streams(vad_pump *p, const void *blob, size_t nbytes, const 
         for (long k = 0; k < n; ++k) {
             const int64_t count = p->current[streams[k]] / p->N;
             p->tape_clock[2 * (size_t)streams[k]] = count;
-            p->tape_clock[2 * (size_t)streams[k] + 1] = count - std::min<int64_t>(run_of(records ? records[k] : k).n_chunks, p->tape_chunks);
+            p->tape_clock[2 * (size_t)streams[k] + 1] = count - std::min<int64_t>(in.run(records ? records[k] : k).n_chunks, p->tape_chunks);
         }
         if (e == hipSuccess) e = hipMemcpy(p->d_tape_clock, p->tape_clock.data(), bytes2, hipMemcpyHostToDevice);
         if (e != hipSuccess) {

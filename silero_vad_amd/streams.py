@@ -3220,6 +3220,26 @@ def _distinct_slots(x, name) -> np.ndarray:
     return a
 
 
+_SNAPSHOT_HISTORY = 160                                    # VAD_SNAPSHOT_HISTORY: the int16 history of a record's tail
+_SnapshotLayout = collections.namedtuple("_SnapshotLayout", "version header_bytes sr N C stride n_records tape_elem tape_at "
+                                                             "info h c ctx pending resample carry history tape")
+
+
+def _snapshot_layout(a: np.ndarray) -> _SnapshotLayout:
+    """The header of a blob the library HAS validated (include/silero_vad_hip.h "SNAPSHOT AND RESTORE"; the layout is snap_layout's of
+    csrc/pump.hip), and the parts of a record as slices of its bytes: `resample`, `carry`, `history` (version 2 on) and `tape` (version 3)
+    are None in a blob without them.  tape_elem: the element of the tape section in bytes (0: none); tape_at: where it starts in the blob."""
+    version, head = (int(v) for v in a[8:16].view("<u4"))
+    sr, N, C = (int(v) for v in a[16:28].view("<i4"))
+    stride, n = int(a[28:32].view("<u4")[0]), int(a[32:40].view("<i8")[0])
+    cuts = np.cumsum([0, ctypes.sizeof(_lib.StreamInfo), 4 * 128, 4 * 128, 4 * C, 2 * N] +
+                     ([ctypes.sizeof(_lib.ResampleInfo), 4 * N, 2 * _SNAPSHOT_HISTORY] if version >= 2 else []) +
+                     ([ctypes.sizeof(_lib.TapeInfo)] if version >= 3 else [])).tolist()
+    parts = [slice(lo, hi) for lo, hi in zip(cuts[:-1], cuts[1:])]
+    return _SnapshotLayout(version, head, sr, N, C, stride, n, int(a[64:68].view("<i4")[0]) if version >= 3 else 0, head + n * stride,
+                           *(parts + [None] * (9 - len(parts))))
+
+
 def snapshot_info(blob) -> list:
     """The records of a snapshot blob (`StreamPump.export_streams`), host only (vad_snapshot_inspect validates it, once): per record a
     dict of the vad_stream_info fields (`active`, `triggered`, `temp_end`, `current_sample`, `pending`, `wide_step`, `wide_phase`) plus
@@ -3232,39 +3252,32 @@ def snapshot_info(blob) -> list:
     without a run).  A blob the library refuses -- bad magic or version, truncated, a field out of range -- raises."""
     a = _blob_bytes(blob)
     L = lib()
-    n, sr = ctypes.c_long(), ctypes.c_int()
-    rc = L.vad_snapshot_inspect(a.ctypes.data if a.size else None, a.size, ctypes.byref(n), ctypes.byref(sr))
+    rc = L.vad_snapshot_inspect(a.ctypes.data if a.size else None, a.size, None, None)
     if rc:
         raise _lib.VadError(rc, "vad_snapshot_inspect: not a valid snapshot blob")
     # The library has validated the WHOLE blob, once; the records are then read here from the documented layout.  (vad_snapshot_stream /
     # vad_snapshot_resample validate the whole blob again on every call, as a C caller that reads one record wants: a loop over them
     # would be quadratic in the blob, and a whole pump's version 2 blob is 39 MB.)
-    N = chunk_size(sr.value)
-    C = N // 8
-    version, head = (int(v) for v in a[8:16].view("<u4"))
-    stride = int(a[28:32].view("<u4")[0])
-    s1 = 32 + 4 * (256 + C) + 2 * N                                # the version 1 part of a record
+    at = _snapshot_layout(a)
     H_of = {0: 0}
     out = []
-    for i in range(n.value):
-        rec = a[head + i * stride:head + (i + 1) * stride]
-        f = _lib.StreamInfo.from_buffer_copy(rec[:32].tobytes())
+    for i in range(at.n_records):
+        rec = a[at.header_bytes + i * at.stride:at.header_bytes + (i + 1) * at.stride]
+        f = _lib.StreamInfo.from_buffer_copy(rec[at.info].tobytes())
         d = {k: int(getattr(f, k)) for k in ("active", "triggered", "temp_end", "current_sample", "pending", "wide_step", "wide_phase")}
-        d.update(h=rec[32:544].view("<f4").copy(), c=rec[544:1056].view("<f4").copy(), ctx=rec[1056:1056 + 4 * C].view("<f4").copy(),
-                 pending_samples=rec[1056 + 4 * C:s1].view("<i2").copy())
-        if version >= 2:
-            q = _lib.ResampleInfo.from_buffer_copy(rec[s1:s1 + 32].tobytes())
+        d.update(h=rec[at.h].view("<f4").copy(), c=rec[at.c].view("<f4").copy(), ctx=rec[at.ctx].view("<f4").copy(),
+                 pending_samples=rec[at.pending].view("<i2").copy())
+        if at.resample:
+            q = _lib.ResampleInfo.from_buffer_copy(rec[at.resample].tobytes())
             if q.src_rate not in H_of:
-                H_of[q.src_rate] = L.vad_resample_stream_history(q.src_rate, sr.value)
-            carry, hist = rec[s1 + 32:s1 + 32 + 4 * N].view("<f4"), rec[s1 + 32 + 4 * N:s1 + 32 + 4 * N + 320].view("<i2")
-            d["resample"] = dict(src_rate=int(q.src_rate), pending_out=int(q.pending_out), inputs_mod=int(q.inputs_mod),
-                                 outputs_mod=int(q.outputs_mod), carry=carry[:q.pending_out].copy(), history=hist[:H_of[q.src_rate]].copy())
-        if version == 3:
-            elem = int(a[64:68].view("<i4")[0])
-            t = _lib.TapeInfo.from_buffer_copy(rec[stride - 32:stride].tobytes())
-            at = head + n.value * stride + int(t.offset)
-            audio = a[at:at + int(t.n_chunks) * N * elem].view("<f4" if elem == 4 else "<i2").copy()
-            d["tape"] = dict(first_chunk=int(t.first_chunk), n_chunks=int(t.n_chunks), offset=int(t.offset), elem=elem, audio=audio)
+                H_of[q.src_rate] = L.vad_resample_stream_history(q.src_rate, at.sr)
+            d["resample"] = dict(src_rate=int(q.src_rate), pending_out=int(q.pending_out), inputs_mod=int(q.inputs_mod), outputs_mod=int(q.outputs_mod),
+                                 carry=rec[at.carry].view("<f4")[:q.pending_out].copy(), history=rec[at.history].view("<i2")[:H_of[q.src_rate]].copy())
+        if at.tape:
+            t = _lib.TapeInfo.from_buffer_copy(rec[at.tape].tobytes())
+            run = a[at.tape_at + int(t.offset):at.tape_at + int(t.offset) + int(t.n_chunks) * at.N * at.tape_elem]
+            d["tape"] = dict(first_chunk=int(t.first_chunk), n_chunks=int(t.n_chunks), offset=int(t.offset), elem=at.tape_elem,
+                             audio=run.view("<f4" if at.tape_elem == 4 else "<i2").copy())
         out.append(d)
     return out
 
@@ -3280,9 +3293,8 @@ def snapshot_tape(blob, i: int) -> np.ndarray:
     rc = L.vad_snapshot_tape(a.ctypes.data if a.size else None, a.size, int(i), ctypes.byref(t), None, 0)
     if rc:
         raise _lib.VadError(rc, "vad_snapshot_tape: not a valid snapshot blob, or no such record")
-    elem = int(a[64:68].view("<i4")[0]) if t.n_chunks else 0       # (a run: the blob is version 3, and its header says the element)
-    N = int(a[20:24].view("<i4")[0])
-    out = np.empty(int(t.n_chunks) * N, np.float32 if elem == 4 else np.int16)
+    at = _snapshot_layout(a)
+    out = np.empty(int(t.n_chunks) * at.N, np.float32 if t.n_chunks and at.tape_elem == 4 else np.int16)
     if out.size:
         rc = L.vad_snapshot_tape(a.ctypes.data, a.size, int(i), None, out.ctypes.data, out.nbytes)
         if rc:
@@ -4004,6 +4016,12 @@ class StreamPump:
         self.fetch_audio_into(streams, first, count, packed, offsets)
         return [packed[o:o + c] for o, c in zip(offsets.tolist(), count.tolist())], first
 
+    def _export_slots(self, streams):
+        """The slot list of an export -> (the distinct slots, int32, or None = every slot; their number; what the library takes for them)."""
+        st = None if streams is None else _distinct_slots(streams, "streams")
+        n = self.streams if st is None else len(st)
+        return st, n, st.ctypes.data if st is not None and n else None
+
     def export_streams(self, streams=None, version: int = 1) -> np.ndarray:
         """Everything `streams` (distinct slots; None = every slot, ascending) carry, as one self-describing uint8 blob
         (vad_pump_export_streams; layout: include/silero_vad_hip.h): (h, c), the context the next tick reads, the pending samples, the
@@ -4015,12 +4033,11 @@ class StreamPump:
         `export_streams_v3`."""
         if isinstance(version, (bool, np.bool_)) or not isinstance(version, (int, np.integer)) or version not in (1, 2):
             raise ValueError(f"version must be 1 or 2, got {version!r}")
-        st = None if streams is None else _distinct_slots(streams, "streams")
-        n = self.streams if st is None else len(st)
+        st, n, st_ptr = self._export_slots(streams)
         size, export = ((self._L.vad_pump_snapshot_bytes, self._L.vad_pump_export_streams) if version == 1 else
                         (self._L.vad_pump_snapshot_bytes_v2, self._L.vad_pump_export_streams_v2))
         blob = np.zeros(int(size(self.sr, n)), np.uint8)
-        self._check(export(self._h, st.ctypes.data if st is not None and n else None, n, blob.ctypes.data, blob.size))
+        self._check(export(self._h, st_ptr, n, blob.ctypes.data, blob.size))
         return blob
 
     def export_streams_v3(self, streams=None, tape_from=None) -> np.ndarray:
@@ -4041,8 +4058,7 @@ class StreamPump:
                     col_b.adopt(d, starts[s])                    # the END on b then returns first == start
                 col_a.forget(s)
         """
-        st = None if streams is None else _distinct_slots(streams, "streams")
-        n = self.streams if st is None else len(st)
+        st, n, st_ptr = self._export_slots(streams)
         slots = range(self.streams) if st is None else st.tolist()
         if isinstance(tape_from, dict):                          # (behind every int64 sample of a clock: nothing)
             tf = np.array([int(tape_from.get(b, 2 ** 63 - 1)) for b in slots], np.int64)
@@ -4050,7 +4066,7 @@ class StreamPump:
             tf = None if tape_from is None else self._int64_rows(tape_from, "tape_from")
         if tf is not None and len(tf) != n:
             raise ValueError(f"tape_from must have one sample position per exported stream, got {len(tf)} for {n}")
-        args = (self._h, st.ctypes.data if st is not None and n else None, n, tf.ctypes.data if tf is not None and n else None)
+        args = (self._h, st_ptr, n, tf.ctypes.data if tf is not None and n else None)
         need = int(self._L.vad_pump_snapshot_plan_v3(*args))
         if need == 0:
             self._check(1)

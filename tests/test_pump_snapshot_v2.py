@@ -1,4 +1,4 @@
-"""Blob version 2 of the pump's snapshots (vad_pump_export_streams_v2 / vad_pump_import_streams, kernel_snapshot.hip gather2 / scatter2):
+"""Blob version 2 of the pump's snapshots (vad_pump_export_streams_v2 / vad_pump_import_streams, kernel_snapshot.hip, the records with a tail):
 streams that are BOUND to a resampled rate leave a pump as bytes and enter another.  The yardstick is the UNINTERRUPTED pump, not an
 oracle: pump A runs every tick; pump B runs the first k ticks, exports version 2 and is closed; pump C imports -- into other slots, in
 the other part -- and runs the rest on the same packets.  C must equal A bit for bit in every later tick's probabilities and events and,
@@ -269,6 +269,64 @@ def _pair(rate, sr):
     return resample_geometry(rate, sr)[:2]
 
 
+# The edges of the kernels' record walk: 1, 4 and 5 records (a workgroup moves four, a wave each: one live wave, a full workgroup, a full
+# one and one live wave), slots of every part of a pump of 37 streams in three parts (16 + 16 + 5), and pending counts on both sides of the
+# edge of a 16-byte vector of the carry (8 samples).  A record is 146 or 106 vectors: a lane's last pass over it is ragged.
+EDGE_LISTS = ([33], [2, 17, 33, 36], [36, 1, 20, 33, 16])
+EDGE_PENDING = {33: 7, 17: 8, 36: 9, 2: 0, 1: 3, 20: 255, 16: 1}
+
+
+def edge_pump(model, golden, sr, **kw):
+    """-> the pump, every stream of EDGE_PENDING stepped on two chunks of speech and holding that many samples, and {stream: what it was fed}"""
+    from silero_vad_amd import StreamPump
+    n = chunk_of(sr)
+    pump = StreamPump(model.engine, sr, streams=37, parts=3, ring_slots=2, **kw)
+    assert pump.parts == 3
+    pcm = golden["16k" if sr == 16000 else "8k"]["pcm_i16"]
+    fed = {s: np.ascontiguousarray(np.roll(pcm, -(30 * n + 7919 * s))[:2 * n + c]) for s, c in EDGE_PENDING.items()}
+    for t in range(3):
+        pump.write_packets(t % 2, [(s, x[t * n:(t + 1) * n]) for s, x in fed.items() if len(x) > t * n])
+        pump.poll()
+    assert all(pump.pending(s) == c for s, c in EDGE_PENDING.items())
+    return pump, fed
+
+
+def edge_records_hold(pump, fed, slots, info):
+    """the records of `slots` say what the pump's own accessors say of those streams, and what they were fed"""
+    n = pump.n
+    assert len(info) == len(slots)
+    for s, rec in zip(slots, info):
+        c = EDGE_PENDING[s]
+        assert (rec["pending"], rec["current_sample"], rec["active"]) == (c, 2 * n, 1)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(pump.state(s), (rec["h"], rec["c"], rec["ctx"]))) and rec["h"].any() and rec["ctx"].any()
+        assert np.array_equal(rec["pending_samples"][:c], fed[s][2 * n:]) and not rec["pending_samples"][c:].any()
+
+
+def version_1_is_a_prefix_of_version_2_at_the_edges(model, golden, sr):
+    from silero_vad_amd import snapshot_info
+    n = chunk_of(sr)
+    s1 = 32 + 4 * (256 + n // 8) + 2 * n
+    s2 = s1 + 32 + 4 * n + 320
+    pump, fed = edge_pump(model, golden, sr)
+    twin, _ = edge_pump(model, golden, sr)
+    for slots in EDGE_LISTS:
+        v1, v2 = pump.export_streams(slots), pump.export_streams(slots, version=2)
+        assert len(v1) == 64 + len(slots) * s1 and len(v2) == 96 + len(slots) * s2
+        r1, r2 = v1[64:].reshape(-1, s1), v2[96:].reshape(-1, s2)
+        assert np.array_equal(r2[:, :s1], r1) and not r2[:, s1:].any()
+        edge_records_hold(pump, fed, slots, snapshot_info(v1))
+        edge_records_hold(pump, fed, slots, snapshot_info(v2))
+        # ... and enter other slots of another pump, in other parts, over what those held
+        dst = [(s + 16) % 37 for s in slots]
+        for blob in (v1, v2):
+            twin.import_streams(blob, dst)
+            assert all(twin.pending(d) == pump.pending(s) and all(a.tobytes() == b.tobytes() for a, b in zip(twin.state(d), pump.state(s)))
+                       for s, d in zip(slots, dst))
+            assert np.array_equal(twin.export_streams(dst, version=int(blob[8])), blob)
+    pump.close()
+    twin.close()
+
+
 def test_version_1_is_a_prefix_of_version_2(model, golden, speech):
     from silero_vad_amd import StreamPump, snapshot_info
     k = 6
@@ -298,6 +356,8 @@ def test_version_1_is_a_prefix_of_version_2(model, golden, speech):
     assert c.carried() == want[k - 1][2] and np.array_equal(c.pump.export_streams(version=2), whole)
     continue_on(c, plan, k, want)
     c.close()
+    for sr in (16000, 8000):
+        version_1_is_a_prefix_of_version_2_at_the_edges(model, golden, sr)
 
 
 def test_refusals_change_nothing(model, golden, speech):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from test_pump_resample_gpu import model, speech  # noqa: F401  (the module fixtures)
+from test_pump_snapshot_v2 import EDGE_LISTS, edge_pump, edge_records_hold
 
 pytestmark = pytest.mark.gpu
 
@@ -307,6 +308,24 @@ def test_a_pump_without_a_tape_writes_version_2_records_and_no_audio(model, gold
     assert all(c.pump.tape_state(s) == (3, 3) for s in DST) and c.carried() == b.carried()
     for p in (b, c):
         p.close()
+    # the edges of the record walk (test_pump_snapshot_v2.py): 1, 4 and 5 records of a pump of 37 streams in three parts
+    pump, fed = edge_pump(model, golden, sr)
+    twin, _ = edge_pump(model, golden, sr, tape_chunks=4)
+    for slots in EDGE_LISTS:
+        blob, v2 = pump.export_streams_v3(slots), pump.export_streams(slots, version=2)
+        assert len(blob) == HEADER3 + len(slots) * s3 and not blob[64:128].any()
+        r3, r2 = blob[HEADER3:].reshape(-1, s3), v2[96:].reshape(-1, s2)
+        assert np.array_equal(r3[:, :s2], r2) and not r3[:, s2:].any()
+        info = snapshot_info(blob)
+        edge_records_hold(pump, fed, slots, info)
+        assert all(g["tape"]["n_chunks"] == 0 and g["resample"]["src_rate"] == 0 for g in info)
+        dst = [(s + 16) % 37 for s in slots]
+        twin.import_streams(blob, dst)
+        assert all(twin.tape_state(d) == (2, 2) and twin.pending(d) == pump.pending(s) and
+                   all(x.tobytes() == y.tobytes() for x, y in zip(twin.state(d), pump.state(s))) for s, d in zip(slots, dst))
+        assert np.array_equal(twin.export_streams(dst, version=2), v2)
+    pump.close()
+    twin.close()
 
 
 @pytest.mark.parametrize("dtype", ["int16", "float32"])
