@@ -3011,6 +3011,52 @@ def _int32_rows(x, name) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _uint8_rows(x, name, what) -> np.ndarray:
+    a = np.asarray(x)
+    if a.ndim != 1 or (a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 255)):
+        raise ValueError(f"{name} must be a 1-D sequence of {what}, got {a.dtype} of shape {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _coded_sizes(ln, cd):
+    return ln * (2 if cd is None else np.where(cd == _PCM["s16"], 2, 1))
+
+
+# The pump's packet routes, one row each; `StreamPump._submit_route` is the one builder behind the five submit_* methods.
+#   entry    the C entry point: entry(pump, r, streams, offsets, lengths[, fourth column], n)
+#   offsets  the name of the offset argument: "offsets" counts samples, "byte_offsets" bytes
+#   align    what the default offsets round each row up to, in that unit
+#   col4     the fourth column's name (None: the route has none) and `rows4`, its check and conversion to uint8
+#   sizes    (lengths as int64, fourth column or None) -> each row's size in the offsets' unit
+#   per      the word of the count message: one entry per ...
+_Route = collections.namedtuple("_Route", "entry offsets align col4 rows4 sizes per")
+_ROUTES = {
+    "packets": _Route("vad_pump_submit_packets", "offsets", 8, None, None, lambda ln, _: ln, "packet"),
+    "coded": _Route("vad_pump_submit_coded_packets", "byte_offsets", 16, "codecs", _codec_rows, _coded_sizes, "packet"),
+    "burst": _Route("vad_pump_submit_burst", "byte_offsets", 16, "codecs", _codec_rows, _coded_sizes, "row"),
+    "wide": _Route("vad_pump_submit_wide_packets", "byte_offsets", 16, "steps",
+                   lambda x: _uint8_rows(x, "steps", "uint8 values"), lambda ln, _: ln * 2, "row"),
+    "resampled": _Route("vad_pump_submit_resampled_packets", "byte_offsets", 16, "rates",
+                        lambda x: _uint8_rows(x, "rates", "rate indices (uint8 values)"), lambda ln, _: ln * 2, "row"),
+}
+
+# What `StreamPump._pack` needs to know of a route that has a write_* method: the word its messages use for a row, the attribute that
+# caps a row's length (None: any length >= 1), and what a row tuple's third element is (None: (stream, x) only; "codec": it picks the
+# payload's dtype, int16 or uint8; "rate": one of resample_rates in Hz, refused in the first pass when it is not).
+_Packer = collections.namedtuple("_Packer", "noun cap third")
+_PACKERS = {
+    "packets": _Packer("packet", "n", None),
+    "coded": _Packer("packet", "n", "codec"),
+    "burst": _Packer("packet", None, "codec"),
+    "resampled": _Packer("row", "resample_row", "rate"),
+}
+
+
+def _pinned_view(ptr, ctype, shape) -> np.ndarray:
+    """A numpy view of page-locked memory the pump owns: `ptr` as an array of `ctype` elements of `shape`."""
+    return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=shape)
+
+
 def g711_expand(data, codec) -> np.ndarray:
     """ITU-T G.711 codes -> int16 linear PCM (vad_g711_expand: the values of audioop.ulaw2lin / alaw2lin(x, 2), from the definition the
     pump's device expansion uses).  codec "ulaw" / "alaw" takes uint8 codes, "s16" int16 samples (returned as a copy).  Same shape.
@@ -3497,16 +3543,13 @@ class StreamPump:
                 self._h = None
                 raise
         self._events = (_lib.IterEvent * (self.streams * self.max_burst))()
-        self._slots = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_slot(h, r), ctypes.POINTER(ctypes.c_int16)),
-                                             shape=(self.streams, self.n)) for r in range(self.ring_slots)]
-        self._probs = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_probs(h, r), ctypes.POINTER(ctypes.c_float)),
-                                             shape=(self.streams,)) for r in range(self.ring_slots)]
-        self._present = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_present(h, r), ctypes.POINTER(ctypes.c_uint8)),
-                                               shape=(self.streams,)) for r in range(self.ring_slots)]
+        ring = range(self.ring_slots)
+        self._slots = [_pinned_view(self._L.vad_pump_slot(h, r), ctypes.c_int16, (self.streams, self.n)) for r in ring]
+        self._probs = [_pinned_view(self._L.vad_pump_probs(h, r), ctypes.c_float, (self.streams,)) for r in ring]
+        self._present = [_pinned_view(self._L.vad_pump_present(h, r), ctypes.c_uint8, (self.streams,)) for r in ring]
         # sub-steps 1 ... max_burst - 1 of a burst tick: per ring slot [max_burst - 1, streams] (page-locked, one block per slot)
-        self._probs_more = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_burst_probs(h, r, 1), ctypes.POINTER(ctypes.c_float)),
-                                                  shape=(self.max_burst - 1, self.streams)) for r in range(self.ring_slots)] \
-            if self.max_burst > 1 else None
+        self._probs_more = [_pinned_view(self._L.vad_pump_burst_probs(h, r, 1), ctypes.c_float, (self.max_burst - 1, self.streams))
+                            for r in ring] if self.max_burst > 1 else None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -3567,53 +3610,86 @@ class StreamPump:
         offsets[i] == ROW_SILENT (-1): a SILENT row -- lengths[i] samples of digital silence, no bytes of the area, exempt from the
         alignment and fit checks, a row in every other respect; results are those of a row of int16 zeros.  Every other negative
         offset is refused.  With offsets=None every row has a payload."""
-        def table(x, name):
-            a = np.asarray(x)
-            if a.ndim != 1 or (a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < -2**31 or a.max() >= 2**31)):
-                raise ValueError(f"{name} must be a 1-D sequence of int32 values, got {a.dtype} of shape {a.shape}")
-            return np.ascontiguousarray(a, dtype=np.int32)
+        self._submit_route("packets", r, streams, lengths, offsets)
 
-        st, ln = table(streams, "streams"), table(lengths, "lengths")
-        off = None if offsets is None else table(offsets, "offsets")
-        if len(ln) != len(st) or (off is not None and len(off) != len(st)):
-            raise ValueError(f"streams, lengths and offsets must have one entry per packet, got {len(st)}, {len(ln)}, "
-                             f"{len(st) if off is None else len(off)}")
-        if off is None:
-            off = np.zeros(len(st), np.int32)
-            if len(st):
-                off[1:] = np.cumsum((ln[:-1].astype(np.int64) + 7) // 8 * 8)
+    def _submit_route(self, route, r, streams, lengths, offsets, col4=None):
+        """The row columns of a packet tick, for every route of `_ROUTES`: converted and checked, one entry per row, the default
+        offsets (the rows back to back, each rounded up to the route's alignment) filled in, and handed to the route's C entry."""
+        rt = _ROUTES[route]
+        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
+        off = None if offsets is None else _int32_rows(offsets, rt.offsets)
+        c4 = None if col4 is None else rt.rows4(col4)
         n = len(st)
-        self._check(self._L.vad_pump_submit_packets(self._h, int(r), *(x.ctypes.data if n else None for x in (st, off, ln)), n))
+        if len(ln) != n or (off is not None and len(off) != n) or (c4 is not None and len(c4) != n):
+            names = ["streams", "lengths"] + [rt.col4] * (rt.col4 is not None)
+            counts = [n, len(ln)] + [n if c4 is None else len(c4)] * (rt.col4 is not None) + [n if off is None else len(off)]
+            raise ValueError(f"{', '.join(names)} and {rt.offsets} must have one entry per {rt.per}, got {', '.join(map(str, counts))}")
+        if off is None:
+            off = np.zeros(n, np.int32)
+            if n:
+                sizes = rt.sizes(ln[:-1].astype(np.int64), None if c4 is None else c4[:-1])
+                off[1:] = np.cumsum((sizes + (rt.align - 1)) // rt.align * rt.align)
+        cols = (st, off, ln) if rt.col4 is None else (st, off, ln, c4)
+        ptrs = [x.ctypes.data if n and x is not None else None for x in cols]
+        self._check(getattr(self._L, rt.entry)(self._h, int(r), *ptrs, n))
+
+    def _pack(self, route, area, packets, default=None):
+        """The rows of a write_* method, for every route of `_PACKERS`: the payloads copied into `area` back to back, each rounded up to
+        16 bytes (8 samples of an int16 area), and the columns -> (streams, lengths, codecs or rate indices as uint8 or None, offsets
+        in the area's elements).  default: the third element of a row tuple that has none (None: the route's tuples are complete)."""
+        pk = _PACKERS[route]
+        cap = pk.cap and getattr(self, pk.cap)
+        packets = list(packets)
+
+        def rows():
+            for row in packets:
+                if pk.third is None:
+                    s, x = row
+                    yield s, x, None
+                elif default is None:
+                    s, x, t = row
+                    yield s, x, t
+                else:
+                    yield row if len(row) == 3 else (row[0], row[1], default)
+
+        too_long = f"a {pk.noun} holds 1 ... {cap} samples, got {{}} (submit a longer one over two ticks)"
+        for _, x, t in rows():                                   # (the rates and the silent rows first: nothing is written when one is bad)
+            if pk.third == "rate" and t not in self.resample_rates:
+                raise ValueError(f"rate {t!r} is none of the pump's resample_rates {self.resample_rates}")
+            n = _silent_len(x)
+            if n is not None and cap and n > cap:
+                raise ValueError(too_long.format(n))
+        align = 16 // area.itemsize
+        streams, lengths, thirds, offsets, at = [], [], [], [], 0
+        for s, x, t in rows():
+            c = _codec_id(t) if pk.third == "codec" else self.resample_rates.index(t) if pk.third == "rate" else None
+            streams.append(s)
+            thirds.append(c)
+            if _silent_len(x) is not None:
+                lengths.append(int(x))
+                offsets.append(ROW_SILENT)
+                continue
+            x = np.asarray(x)
+            want = np.uint8 if pk.third == "codec" and c != _PCM["s16"] else np.int16
+            if x.dtype != want or x.ndim != 1:
+                raise ValueError(f"a {t!r} packet must be a 1-D {np.dtype(want).name} array, got {x.dtype} of shape {x.shape}"
+                                 if pk.third == "codec" else f"a {pk.noun} must be a 1-D int16 array")
+            if len(x) < 1 or (cap and len(x) > cap):
+                raise ValueError(too_long.format(len(x)) if cap else "a packet holds at least 1 sample")
+            size = x.nbytes // area.itemsize
+            if at + size > len(area):
+                raise ValueError(f"the {pk.noun}s do not fit into the slot")
+            area[at:at + size] = x.view(area.dtype)
+            lengths.append(len(x))
+            offsets.append(at)
+            at += (size + align - 1) // align * align
+        return streams, lengths, None if pk.third is None else np.array(thirds, np.uint8), offsets
 
     def write_packets(self, r: int, packets):
         """Pack [(stream, int16 samples), ...] back to back (each rounded up to 8 samples) into `packet_area(r)` and submit the packet
         tick -- the convenience form for tests and small servers.  An int in place of the samples, `(stream, 160)`, is a silent row of
         that many samples (1 ... N): it takes no room in the area and advances no offset."""
-        area = self.packet_area(r)
-        packets = list(packets)
-        for _, x in packets:                                     # (the silent rows first: nothing is written when one is bad)
-            n = _silent_len(x)
-            if n is not None and n > self.n:
-                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {n} (submit a longer one over two ticks)")
-        streams, lengths, offsets, at = [], [], [], 0
-        for s, x in packets:
-            if _silent_len(x) is not None:
-                streams.append(s)
-                lengths.append(int(x))
-                offsets.append(ROW_SILENT)
-                continue
-            x = np.asarray(x)
-            if x.dtype != np.int16 or x.ndim != 1:
-                raise ValueError("a packet must be a 1-D int16 array")
-            if not 1 <= len(x) <= self.n:
-                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {len(x)} (submit a longer one over two ticks)")
-            if at + len(x) > len(area):
-                raise ValueError("the packets do not fit into the slot")
-            area[at:at + len(x)] = x
-            streams.append(s)
-            lengths.append(len(x))
-            offsets.append(at)
-            at += (len(x) + 7) // 8 * 8
+        streams, lengths, _, offsets = self._pack("packets", self.packet_area(r), packets)
         self.submit_packets(r, streams, lengths, offsets)
 
     def packet_bytes(self, r: int) -> np.ndarray:
@@ -3628,55 +3704,14 @@ class StreamPump:
         expanded by `g711_expand`.  A bad codec, stream, length or offset raises and queues nothing.
         byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] int16 zeros (see `submit_packets`); its codecs[i] is not looked
         at by the pump.  With byte_offsets=None every row has a payload."""
-        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
-        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
-        cd = None if codecs is None else _codec_rows(codecs)
-        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (cd is not None and len(cd) != len(st)):
-            raise ValueError(f"streams, lengths, codecs and byte_offsets must have one entry per packet, got {len(st)}, {len(ln)}, "
-                             f"{len(st) if cd is None else len(cd)}, {len(st) if off is None else len(off)}")
-        if off is None:
-            nbytes = ln.astype(np.int64) * (2 if cd is None else np.where(cd == _PCM["s16"], 2, 1))
-            off = np.zeros(len(st), np.int32)
-            if len(st):
-                off[1:] = np.cumsum((nbytes[:-1] + 15) // 16 * 16)
-        n = len(st)
-        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [cd.ctypes.data if n and cd is not None else None]
-        self._check(self._L.vad_pump_submit_coded_packets(self._h, int(r), *ptrs, n))
+        self._submit_route("coded", r, streams, lengths, byte_offsets, codecs)
 
     def write_coded_packets(self, r: int, packets):
         """Pack [(stream, samples, codec), ...] back to back (each rounded up to 16 bytes) into `packet_bytes(r)` and submit the tick:
         codec "s16" takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes (an RTP payload as it came off the wire).  An int
         in place of the samples, `(stream, 160, codec)`, is a silent row of that many samples (1 ... N), whatever the codec."""
-        area = self.packet_bytes(r)
-        packets = list(packets)
-        for _, x, _ in packets:                                  # (the silent rows first: nothing is written when one is bad)
-            n = _silent_len(x)
-            if n is not None and n > self.n:
-                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {n} (submit a longer one over two ticks)")
-        streams, lengths, codecs, offsets, at = [], [], [], [], 0
-        for s, x, codec in packets:
-            c = _codec_id(codec)
-            if _silent_len(x) is not None:
-                streams.append(s)
-                lengths.append(int(x))
-                codecs.append(c)
-                offsets.append(ROW_SILENT)
-                continue
-            x = np.asarray(x)
-            want = np.int16 if c == _PCM["s16"] else np.uint8
-            if x.dtype != want or x.ndim != 1:
-                raise ValueError(f"a {codec!r} packet must be a 1-D {np.dtype(want).name} array, got {x.dtype} of shape {x.shape}")
-            if not 1 <= len(x) <= self.n:
-                raise ValueError(f"a packet holds 1 ... {self.n} samples, got {len(x)} (submit a longer one over two ticks)")
-            if at + x.nbytes > len(area):
-                raise ValueError("the packets do not fit into the slot")
-            area[at:at + x.nbytes] = x.view(np.uint8)
-            streams.append(s)
-            lengths.append(len(x))
-            codecs.append(c)
-            offsets.append(at)
-            at += (x.nbytes + 15) // 16 * 16
-        self.submit_coded_packets(r, streams, lengths, np.array(codecs, np.uint8), offsets)
+        streams, lengths, codecs, offsets = self._pack("coded", self.packet_bytes(r), packets)
+        self.submit_coded_packets(r, streams, lengths, codecs, offsets)
 
     def submit_burst(self, r: int, streams, lengths, codecs=None, byte_offsets=None):
         """A BURST tick (vad_pump_submit_burst; needs `max_burst` > 1): rows as in `submit_coded_packets`, except that a stream may be
@@ -3686,55 +3721,15 @@ class StreamPump:
         than `streams`, a bad codec, stream, length or offset raises and queues nothing.
         byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] >= 1 int16 zeros (see `submit_packets`), longer than N if the
         gap was; it counts towards max_burst like any row.  With byte_offsets=None every row has a payload."""
-        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
-        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
-        cd = None if codecs is None else _codec_rows(codecs)
-        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (cd is not None and len(cd) != len(st)):
-            raise ValueError(f"streams, lengths, codecs and byte_offsets must have one entry per row, got {len(st)}, {len(ln)}, "
-                             f"{len(st) if cd is None else len(cd)}, {len(st) if off is None else len(off)}")
-        if off is None:
-            nbytes = ln.astype(np.int64) * (2 if cd is None else np.where(cd == _PCM["s16"], 2, 1))
-            off = np.zeros(len(st), np.int32)
-            if len(st):
-                off[1:] = np.cumsum((nbytes[:-1] + 15) // 16 * 16)
-        n = len(st)
-        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [cd.ctypes.data if n and cd is not None else None]
-        self._check(self._L.vad_pump_submit_burst(self._h, int(r), *ptrs, n))
+        self._submit_route("burst", r, streams, lengths, byte_offsets, codecs)
 
     def write_burst(self, r: int, packets):
         """Pack [(stream, samples) | (stream, samples, codec), ...] back to back in arrival order (each rounded up to 16 bytes) into
         `packet_bytes(r)` and submit the burst tick: packets of any length, streams repeated as often as they delivered.  codec "s16"
         (the default) takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes.  An int in place of the samples,
         `(stream, 3 * N + 5)`, is a silent row of that many samples."""
-        area = self.packet_bytes(r)
-        packets = list(packets)
-        for pk in packets:                                       # (the silent rows first: nothing is written when one is bad)
-            _silent_len(pk[1])
-        streams, lengths, codecs, offsets, at = [], [], [], [], 0
-        for pk in packets:
-            s, x, codec = pk if len(pk) == 3 else (pk[0], pk[1], "s16")
-            c = _codec_id(codec)
-            if _silent_len(x) is not None:
-                streams.append(s)
-                lengths.append(int(x))
-                codecs.append(c)
-                offsets.append(ROW_SILENT)
-                continue
-            x = np.asarray(x)
-            want = np.int16 if c == _PCM["s16"] else np.uint8
-            if x.dtype != want or x.ndim != 1:
-                raise ValueError(f"a {codec!r} packet must be a 1-D {np.dtype(want).name} array, got {x.dtype} of shape {x.shape}")
-            if len(x) < 1:
-                raise ValueError("a packet holds at least 1 sample")
-            if at + x.nbytes > len(area):
-                raise ValueError("the packets do not fit into the slot")
-            area[at:at + x.nbytes] = x.view(np.uint8)
-            streams.append(s)
-            lengths.append(len(x))
-            codecs.append(c)
-            offsets.append(at)
-            at += (x.nbytes + 15) // 16 * 16
-        self.submit_burst(r, streams, lengths, np.array(codecs, np.uint8), offsets)
+        streams, lengths, codecs, offsets = self._pack("burst", self.packet_bytes(r), packets, default="s16")
+        self.submit_burst(r, streams, lengths, codecs, offsets)
 
     def set_wideband(self, max_step: int):
         """Enable WIDE packet ticks (vad_pump_set_wideband): rows sampled at up to max_step x 16 kHz -- 2 (32 kHz) or 3 (48 kHz) -- on a
@@ -3742,8 +3737,7 @@ class StreamPump:
         self._check(self._L.vad_pump_set_wideband(self._h, int(max_step)))
         self.max_step = int(max_step)
         nbytes = self.streams * self.n * self.max_step * 2
-        self._wide = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_wide_slot(self._h, r), ctypes.POINTER(ctypes.c_uint8)),
-                                            shape=(nbytes,)) for r in range(self.ring_slots)]
+        self._wide = [_pinned_view(self._L.vad_pump_wide_slot(self._h, r), ctypes.c_uint8, (nbytes,)) for r in range(self.ring_slots)]
 
     def wide_slot(self, r: int) -> np.ndarray:
         """Wide slot r's sample area as one flat uint8 array of streams * N * max_step * 2 bytes (page-locked): where a wide tick's rows
@@ -3761,24 +3755,7 @@ class StreamPump:
         offset raises and queues nothing.
         byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] input samples of silence at steps[i] (see `submit_packets`): the
         phase advances by lengths[i], the stream gains the zeros the comb keeps.  With byte_offsets=None every row has a payload."""
-        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
-        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
-        sp = None
-        if steps is not None:
-            sp = np.asarray(steps)
-            if sp.ndim != 1 or (sp.size and (not np.issubdtype(sp.dtype, np.integer) or sp.min() < 0 or sp.max() > 255)):
-                raise ValueError(f"steps must be a 1-D sequence of uint8 values, got {sp.dtype} of shape {sp.shape}")
-            sp = np.ascontiguousarray(sp, dtype=np.uint8)
-        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (sp is not None and len(sp) != len(st)):
-            raise ValueError(f"streams, lengths, steps and byte_offsets must have one entry per row, got {len(st)}, {len(ln)}, "
-                             f"{len(st) if sp is None else len(sp)}, {len(st) if off is None else len(off)}")
-        if off is None:
-            off = np.zeros(len(st), np.int32)
-            if len(st):
-                off[1:] = np.cumsum((ln[:-1].astype(np.int64) * 2 + 15) // 16 * 16)
-        n = len(st)
-        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [sp.ctypes.data if n and sp is not None else None]
-        self._check(self._L.vad_pump_submit_wide_packets(self._h, int(r), *ptrs, n))
+        self._submit_route("wide", r, streams, lengths, byte_offsets, steps)
 
     def wide_phase(self, stream: int) -> int:
         """The comb phase of `stream`: the input samples it has delivered since its comb started, modulo its step (0 ... step - 1)."""
@@ -3803,8 +3780,7 @@ class StreamPump:
         self.resample_row = max(-(-self.n * resample_geometry(r, self.sr)[0] // resample_geometry(r, self.sr)[1]) for r in rt)
         self.resample_row = (self.resample_row + 7) // 8 * 8
         nbytes = self.streams * self.resample_row * 2
-        self._res = [np.ctypeslib.as_array(ctypes.cast(self._L.vad_pump_resample_slot(self._h, r), ctypes.POINTER(ctypes.c_uint8)),
-                                           shape=(nbytes,)) for r in range(self.ring_slots)]
+        self._res = [_pinned_view(self._L.vad_pump_resample_slot(self._h, r), ctypes.c_uint8, (nbytes,)) for r in range(self.ring_slots)]
 
     def resample_slot(self, r: int) -> np.ndarray:
         """Resample slot r's sample area as one flat uint8 array of streams * resample_row * 2 bytes (page-locked): where a resampled
@@ -3824,58 +3800,14 @@ class StreamPump:
         or a row that would complete two chunks raises and queues nothing.
         byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] input samples of silence (see `submit_packets`): zeros enter the
         filter.  With byte_offsets=None every row has a payload."""
-        st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
-        off = None if byte_offsets is None else _int32_rows(byte_offsets, "byte_offsets")
-        rt = None
-        if rates is not None:
-            rt = np.asarray(rates)
-            if rt.ndim != 1 or (rt.size and (not np.issubdtype(rt.dtype, np.integer) or rt.min() < 0 or rt.max() > 255)):
-                raise ValueError(f"rates must be a 1-D sequence of rate indices (uint8 values), got {rt.dtype} of shape {rt.shape}")
-            rt = np.ascontiguousarray(rt, dtype=np.uint8)
-        if len(ln) != len(st) or (off is not None and len(off) != len(st)) or (rt is not None and len(rt) != len(st)):
-            raise ValueError(f"streams, lengths, rates and byte_offsets must have one entry per row, got {len(st)}, {len(ln)}, "
-                             f"{len(st) if rt is None else len(rt)}, {len(st) if off is None else len(off)}")
-        if off is None:
-            off = np.zeros(len(st), np.int32)
-            if len(st):
-                off[1:] = np.cumsum((ln[:-1].astype(np.int64) * 2 + 15) // 16 * 16)
-        n = len(st)
-        ptrs = [x.ctypes.data if n else None for x in (st, off, ln)] + [rt.ctypes.data if n and rt is not None else None]
-        self._check(self._L.vad_pump_submit_resampled_packets(self._h, int(r), *ptrs, n))
+        self._submit_route("resampled", r, streams, lengths, byte_offsets, rates)
 
     def write_resampled_packets(self, r: int, packets):
         """Pack [(stream, int16 samples, rate) | (stream, int16 samples), ...] back to back (each rounded up to 16 bytes) into
         `resample_slot(r)` and submit the resampled tick, mirroring `write_packets`: `rate` is one of `resample_rates` in Hz (left out:
         resample_rates[0]).  An int in place of the samples, `(stream, 441, 44100)`, is a silent row of that many input samples."""
-        area = self.resample_slot(r)
-        packets = [pk if len(pk) == 3 else (pk[0], pk[1], self.resample_rates[0]) for pk in packets]
-        for _, x, rate in packets:                               # (the rates and the silent rows first: nothing is written when one is bad)
-            if rate not in self.resample_rates:
-                raise ValueError(f"rate {rate!r} is none of the pump's resample_rates {self.resample_rates}")
-            n = _silent_len(x)
-            if n is not None and n > self.resample_row:
-                raise ValueError(f"a row holds 1 ... {self.resample_row} samples, got {n} (submit a longer one over two ticks)")
-        streams, lengths, rates, offsets, at = [], [], [], [], 0
-        for s, x, rate in packets:
-            rates.append(self.resample_rates.index(rate))
-            if _silent_len(x) is not None:
-                streams.append(s)
-                lengths.append(int(x))
-                offsets.append(ROW_SILENT)
-                continue
-            x = np.asarray(x)
-            if x.dtype != np.int16 or x.ndim != 1:
-                raise ValueError("a row must be a 1-D int16 array")
-            if not 1 <= len(x) <= self.resample_row:
-                raise ValueError(f"a row holds 1 ... {self.resample_row} samples, got {len(x)} (submit a longer one over two ticks)")
-            if at + x.nbytes > len(area):
-                raise ValueError("the rows do not fit into the slot")
-            area[at:at + x.nbytes] = x.view(np.uint8)
-            streams.append(s)
-            lengths.append(len(x))
-            offsets.append(at)
-            at += (x.nbytes + 15) // 16 * 16
-        self.submit_resampled_packets(r, streams, lengths, np.array(rates, np.uint8), offsets)
+        streams, lengths, rates, offsets = self._pack("resampled", self.resample_slot(r), packets, default=self.resample_rates[0])
+        self.submit_resampled_packets(r, streams, lengths, rates, offsets)
 
     def resample_state(self, stream: int):
         """(rate the stream is bound to in Hz or 0, its input samples received less O * (outputs emitted // N), its fp32 outputs pending)
