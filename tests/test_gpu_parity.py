@@ -1962,10 +1962,11 @@ class _F64Net:
     four ReLU(conv k = 3), LSTM cell, head -- JIT!/vad/utils/pytorch_stft.py:17-34, JIT!/vad/utils/model_utils.py:19-25,
     JIT!/torch/nn/modules/rnn.py:69, JIT!/torch/nn/modules/container/___torch_mangle_7.py:10-19."""
 
-    def __init__(self, sr, device):
+    def __init__(self, sr, device, container=None):
+        """container: the bytes of the weight container to evaluate (default: the published one)"""
         from oracle.weights import read_container
         from silero_vad_amd import _lib
-        w = read_container(_lib.WEIGHTS_PATH.read_bytes())
+        w = read_container(_lib.WEIGHTS_PATH.read_bytes() if container is None else bytes(container))
         pre = "_model" if sr == 16000 else "_model_8k"
         t = lambda k: torch.from_numpy(w[pre + "." + k].astype(np.float64)).to(device)
         self.basis = t("stft.forward_basis_buffer").squeeze(1)                 # [2K, F]
@@ -2017,15 +2018,16 @@ class _F64Net:
         return probs, torch.stack([h, c])
 
 
-def state_vs_float64(model, rows, sr, got_state, oracle_state, state=None, ctx=None, label="", record=None, factor=1.5, floor=TOL):
+def state_vs_float64(model, rows, sr, got_state, oracle_state, state=None, ctx=None, label="", record=None, factor=1.5, floor=TOL, container=None):
     """Which of the two fp32 evaluations is further from float64?  For the carried (h, c) of `rows` (whole chunks): the engine's and the
     oracle's error against a float64 evaluation of the network (_F64Net), in the state_err metric.  The engine passes if it is inside
     the 1e-4 contract against float64, or no further from float64 than 1.5 x the oracle is (two fp32 summation orders of an
     ill-conditioned entry: neither is "the" answer; what must not happen is that the engine is the worse one by a margin).
-    Returns (engine_err, oracle_err) and appends the figures and the worst entry to `record`."""
+    Returns (engine_err, oracle_err) and appends the figures and the worst entry to `record`.  container: the weights both were run
+    on, where they are not the published ones."""
     n = chunk_of(sr)
     x = torch.as_tensor(rows)[:, :(rows.shape[1] // n) * n].contiguous().to(model.device)
-    _, s64 = _F64Net(sr, model.device).audio_forward(x, state=state, ctx=ctx)
+    _, s64 = _F64Net(sr, model.device, container).audio_forward(x, state=state, ctx=ctx)
     s64 = s64.cpu().numpy()
     den = np.maximum(1.0, np.abs(s64))
     e_eng, e_orc = np.abs(got_state - s64) / den, np.abs(oracle_state - s64) / den

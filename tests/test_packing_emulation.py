@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import decoder_variants as dv
 import emu_wave as E
 from conftest import SRS, state_err
 
@@ -103,8 +104,14 @@ def test_mfma_emulation_is_transpose_detecting():
             assert abs(acc[r, lane] - D[4 * (lane >> 4) + r, lane & 15]) < 1e-5
 
 
-@pytest.mark.parametrize("tag", ["16k", "8k"])
-def test_bf16x9_recurrent_image_is_exact(built, tag):
+# the two bf16 x 9 images on the published container (ids 16k / 8k) and on every container of tests/decoder_variants.py: a three-piece
+# split that is exact only for weights the published tensors happen to hold would pass on the published container alone
+CONTAINERS = [pytest.param(tag, "published", id=tag) for tag in ("16k", "8k")] + \
+             [pytest.param(tag, name, id=f"{tag}-{name}") for name in dv.VARIANTS for tag in ("16k", "8k")]
+
+
+@pytest.mark.parametrize("tag,container", CONTAINERS)
+def test_bf16x9_recurrent_image_is_exact(built, tag, container):
     """The three-piece bf16 image of W_hh (option rec=bf16x9, csrc/kernel_rec_b9.hip): the pieces of every weight add up to
     the fp32 weight EXACTLY, each piece is a bf16 (low 16 bits of its fp32 pattern are zero), and slot (g, e) of K32 step u
     of wave w, gate q, row i holds W_hh[128 q + 16 w + i][32 u + 8 g + e]."""
@@ -112,7 +119,7 @@ def test_bf16x9_recurrent_image_is_exact(built, tag):
     from silero_vad_amd import _lib
     sr = SRS[tag]
     L = _lib.lib()
-    blob = _lib.WEIGHTS_PATH.read_bytes()
+    blob = dv.variant_blob(container)
     h = ctypes.c_void_p()
     assert L.vad_create_host_only(blob, len(blob), ctypes.byref(h)) == 0
     n = L.vad_debug_packed_floats(h, sr, 7)
@@ -129,8 +136,8 @@ def test_bf16x9_recurrent_image_is_exact(built, tag):
     assert np.all(np.abs(pieces[:, 2]) <= np.abs(pieces[:, 0]) * 2.0 ** -16 + 1e-45)
 
 
-@pytest.mark.parametrize("tag", ["16k", "8k"])
-def test_bf16x9_frontend_image_is_the_f43_program_exactly(packed, built, tag):
+@pytest.mark.parametrize("tag,container", CONTAINERS)
+def test_bf16x9_frontend_image_is_the_f43_program_exactly(packed, built, tag, container):
     """The three-piece bf16 image of the frontend (option front_mma=bf16x9, csrc/kernel_front_b9.hip) is the F(4,3) program
     unit for unit: the pieces of every weight add up to the fp32 weight EXACTLY, and slot (g, e) of K32 step kp of a unit
     holds what the fp32 unit holds for k-step 8 kp + e at k = g (same rows) -- so the wave program the emulator validates
@@ -139,14 +146,15 @@ def test_bf16x9_frontend_image_is_the_f43_program_exactly(packed, built, tag):
     sr = SRS[tag]
     Q = 32 if sr == 16000 else 16
     L = _lib.lib()
-    blob = _lib.WEIGHTS_PATH.read_bytes()
+    blob = dv.variant_blob(container)
     h = ctypes.c_void_p()
     assert L.vad_create_host_only(blob, len(blob), ctypes.byref(h)) == 0
     n = L.vad_debug_packed_floats(h, sr, 8)
     raw = np.empty(n, np.float32)
     assert L.vad_debug_packed_copy(h, sr, 8, raw.ctypes.data_as(_lib.f32p), n) == 0
     L.vad_destroy(h)
-    f32 = packed[sr, 6].reshape(-1, 8, 2, 64, 4)                            # [unit][fp32 step][rb][lane][ks]
+    fp32_image = packed[sr, 6] if container == "published" else dv.packed_images(container)[sr, 6]
+    f32 = fp32_image.reshape(-1, 8, 2, 64, 4)                               # [unit][fp32 step][rb][lane][ks]
     NU = f32.shape[0]
     img = raw.view(np.uint16).reshape(NU, 4, 3, 2, 64, 8)                   # [unit][step][piece][rb][lane][e]
     pieces = (img.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
