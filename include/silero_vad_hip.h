@@ -63,7 +63,7 @@ void vad_destroy(vad_engine *e);
  * (tests/test_concurrency.py).  What the engine does not arrange: a hipGraph capture is a process-wide state of the runtime --
  * while one thread captures (global capture mode), allocating calls of other threads (vad_create / vad_clone / vad_pump_create, a
  * scratch growth) fail; capture while the other threads make no such call.
- * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed, vad_g711_expand, vad_deinterleave and vad_decimate are re-entrant (no shared state);
+ * Host-only entry points across threads: vad_segment_probs, vad_iterator_feed, vad_g711_expand, vad_adpcm_expand, vad_deinterleave and vad_decimate are re-entrant (no shared state);
  * vad_stage_rows and vad_segment_probs_batch serialise themselves on the process-wide helper pool (tests/test_host_concurrency.py). */
 int  vad_clone(const vad_engine *e, vad_engine **out);
 const char *vad_strerror(int status);
@@ -491,7 +491,20 @@ int  vad_pump_submit_packets(vad_pump *p, int r, const int32_t *stream_of_row, c
                              long n_rows);
 /* Sample formats of a packet row: 16-bit linear PCM, ITU-T G.711 mu-law (PCMU) or A-law (PCMA), 1 byte per sample (SIP trunks,
  * telephony media streams: 8 kHz).                                                                                              */
-enum { VAD_PCM_S16 = 0, VAD_PCM_ULAW = 1, VAD_PCM_ALAW = 2 };
+enum { VAD_PCM_S16 = 0, VAD_PCM_ULAW = 1, VAD_PCM_ALAW = 2, VAD_PCM_DVI4 = 3 };
+/* VAD_PCM_DVI4 (vad_pump_submit_coded_packets and vad_pump_submit_burst only): RFC 3551 section 4.5.1, 4-bit IMA ADPCM, RTP payload
+ * types 5 (8 kHz) and 6 (16 kHz).  A row is the RTP payload as it came off the wire: bytes 0-1 `predict` (int16, big-endian: the
+ * decoder's predictor before the first sample), byte 2 `index` (the step index before the first sample; a value above 88 is used as
+ * 88), byte 3 reserved (ignored), then the 4-bit codes, two a byte, the first sample in the high nibble.  len_of_row[i] stays the
+ * row's length in SAMPLES and must be even; the row takes 4 + len / 2 bytes -- 84 bytes for 20 ms at 8 kHz against 160 of G.711 and
+ * 320 of int16.  Every packet carries its own decoder state, so the pump keeps nothing per stream for this format; the device decodes
+ * the row (the values of vad_adpcm_expand) on its way into the stream's chunk, and the carry, the tape and a snapshot hold expanded
+ * int16 as for every other format.  Results are bit for bit those of the same route fed vad_adpcm_expand of each payload as an S16
+ * row.  The corpus routes (vad_upload_rows_coded, _channels), vad_g711_expand and vad_deinterleave go on refusing it.
+ * A pump takes DVI4 rows once vad_pump_set_adpcm(p, 1) has enabled them (only while no tick is in flight: VAD_ERR_ARG otherwise;
+ * vad_pump_set_adpcm(p, 0) switches them off again; nothing is allocated either way).  A pump on which it was never called refuses
+ * codec 3 as a bad codec, as it always did, and runs every route through the code it always ran.                                  */
+int  vad_pump_set_adpcm(vad_pump *p, int on);
 /* A packet tick whose rows may be G.711: row i of slot r's sample area (seen as streams * N * 2 BYTES) holds len_of_row[i] samples
  * (1 ... N) of stream stream_of_row[i] in format codec_of_row[i] (VAD_PCM_*; NULL = every row VAD_PCM_S16), starting at BYTE offset
  * byte_off_of_row[i], a multiple of 16; the row takes len bytes (G.711) or 2 * len bytes (S16).  The device expands G.711 to int16
@@ -502,7 +515,10 @@ enum { VAD_PCM_S16 = 0, VAD_PCM_ULAW = 1, VAD_PCM_ALAW = 2 };
  * runs past the slot.  Pending samples, open / close and the chunk routes' refusal behave as for vad_pump_submit_packets.
  * A row with byte_off_of_row[i] == VAD_ROW_SILENT is a silent row of 1 ... N samples (see vad_pump_submit_packets): int16 zeros,
  * also in a G.711 tick (A-law has no code for 0).  Its codec_of_row entry is not looked at -- any byte value is accepted -- and it
- * does not make the tick a G.711 tick.                                                                                            */
+ * does not make the tick a G.711 tick.
+ * A VAD_PCM_DVI4 row (above; on a pump with vad_pump_set_adpcm) has an even length of 2 ... N samples and takes 4 + len / 2 bytes at its offset: an odd length, a row
+ * whose 4 + len / 2 bytes run past the slot and a codec above VAD_PCM_DVI4 are VAD_ERR_ARG like the rest.  A tick with such a row
+ * takes a kernel of its own; every other tick runs the code it ran before.                                                         */
 int  vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row,
                                    const int32_t *len_of_row, const uint8_t *codec_of_row, long n_rows);
 /* BURST ticks -- a 60 ms Opus frame is longer than a chunk, a jitter buffer that waited out a stall releases several packets of one
@@ -531,7 +547,9 @@ int  vad_pump_submit_coded_packets(vad_pump *p, int r, const int32_t *stream_of_
  * vad_pump_pending, vad_pump_open / _close and the chunk routes' refusal behave as for packet ticks.
  * A row with byte_off_of_row[i] == VAD_ROW_SILENT is a silent row (see vad_pump_submit_packets) of any length >= 1, longer than N
  * included (after a stall the whole gap may arrive as one row), subject to the max_chunks rule like any row; its codec_of_row entry
- * is not looked at.                                                                                                               */
+ * is not looked at.
+ * A VAD_PCM_DVI4 row of a burst (on a pump with vad_pump_set_adpcm) has any even length >= 2 and takes 4 + len / 2 bytes; a row longer than N is decoded in pieces of N
+ * samples, the decoder's state carried from piece to piece on the device.                                                          */
 #define VAD_PUMP_MAX_BURST 8
 int  vad_pump_set_burst(vad_pump *p, int max_chunks);
 int  vad_pump_submit_burst(vad_pump *p, int r, const int32_t *stream_of_row, const int32_t *byte_off_of_row, const int32_t *len_of_row,
@@ -645,6 +663,11 @@ long vad_decimate(int step, int phase, const int16_t *in, long n, int16_t *out);
  * G.711 expansion, the values of Python's audioop.ulaw2lin / alaw2lin(x, 2), from the same definition the device uses.  VAD_OK, or
  * VAD_ERR_ARG for a bad codec, n < 0 or a NULL buffer with n > 0.                                                               */
 int  vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out);
+/* A DVI4 payload (VAD_PCM_DVI4: 4 header bytes, then 4-bit codes) of nbytes bytes at `payload` -> out[0 .. 2 * (nbytes - 4)) int16 on
+ * the host, from the same single-code step the device uses: the values of Python's audioop.adpcm2lin(payload[4:], 2, (predict,
+ * min(index, 88))).  Returns the samples written; nbytes == 4 (a header alone) gives 0 and looks at neither pointer.  -VAD_ERR_ARG for
+ * nbytes < 4 or a NULL pointer with nbytes > 4.  Host only, re-entrant.                                                              */
+long vad_adpcm_expand(const uint8_t *payload, long nbytes, int16_t *out);
 /* Samples of `stream` submitted in packets and not yet stepped (0 ... N - 1; host bookkeeping, no synchronisation); < 0: bad argument. */
 long vad_pump_pending(const vad_pump *p, int stream);
 /* Retire the OLDEST submitted tick: wait for it (block != 0) or return VAD_PUMP_BUSY, run the iterator logic of every open

@@ -7,7 +7,7 @@ from .engine import Engine, HipSileroVAD, load_silero_vad  # noqa: F401
 from .timestamps import (VADIterator, collect_chunks, drop_chunks, get_speech_timestamps,  # noqa: F401
                          read_audio, read_wav_raw, save_audio, segment_probs)
 from .streams import (BatchVADIterator, PackedRecordings, RaggedPlan, RefillPlan, StreamPool, StreamPump, UtteranceCollector, tape_window, tape_run, snapshot_tape, refill_probs, refill_reserve, refill_segments_stream, refill_speech_segments, ragged_buckets, ragged_probs, ragged_reserve,  # noqa: F401
-                      ragged_speech_segments, ragged_speech_audio, collect_chunks_device, segment_probs_batch, segment_probs_batch_device, g711_expand, decimate, resample, resample_device, resample_geometry, resample_table, resample_stream, resample_stream_ready, resample_stream_history, snapshot_info, ROW_SILENT, deinterleave, channel_rows,
+                      ragged_speech_segments, ragged_speech_audio, collect_chunks_device, segment_probs_batch, segment_probs_batch_device, g711_expand, adpcm_expand, decimate, resample, resample_device, resample_geometry, resample_table, resample_stream, resample_stream_ready, resample_stream_history, snapshot_info, ROW_SILENT, deinterleave, channel_rows,
                       ThresholdCounts, ThresholdPairs, LABEL_IGNORE, threshold_pairs, chunk_labels, threshold_counts, threshold_counts_device, ragged_threshold_counts, search_thresholds,
                       ValidationScores, SCORE_KEY_NONE, chunk_scores, chunk_scores_device, ragged_validation, validate)
 from .tuning import (DecoderTrainer, decoder_grad, decoder_grad_host, decoder_grad_workspace_bytes, decoder_state_dict, replace_decoder, tune,  # noqa: F401

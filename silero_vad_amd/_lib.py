@@ -101,6 +101,8 @@ SYMBOLS = {
     "vad_pump_pending": (c_long, [c_void_p, c_int]),
     "vad_pump_submit_coded_packets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
     "vad_g711_expand": (c_int, [c_int, c_void_p, c_long, c_void_p]),
+    "vad_adpcm_expand": (c_long, [c_void_p, c_long, c_void_p]),
+    "vad_pump_set_adpcm": (c_int, [c_void_p, c_int]),
     "vad_pump_set_burst": (c_int, [c_void_p, c_int]),
     "vad_pump_submit_burst": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
     "vad_pump_burst_steps": (c_int, [c_void_p, c_int]),

@@ -131,14 +131,20 @@ hipError_t launch_assemble_packets(const int32_t *table, long n_rows, const int1
 constexpr int kCodecShift = 16;
 hipError_t launch_assemble_coded_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
                                          hipStream_t s);
+// The same for a tick with at least one DVI4 row (codec VAD_PCM_DVI4: a 4-byte header {predict, index}, then len / 2 bytes of 4-bit
+// codes, len even): that row is decoded (adpcm.hpp: two wave scans, the values of vad_adpcm_expand) on its way into the carry / the
+// batch row; S16 and G.711 rows of the tick move as in launch_assemble_coded_packets.  Only ticks with a DVI4 row take this kernel.
+hipError_t launch_assemble_adpcm_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
+                                         hipStream_t s);
 // A burst tick of the pump (vad_pump_submit_burst): a stream may have several rows and a row may be longer than N.  The table's rows are
 // GROUPED BY STREAM, a stream's rows in arrival order: table[i] = {stream b, BYTE offset into `pkt` (a multiple of 16), len | codec <<
 // kCodecShift, w}, w = pending c | k << kCodecShift on the first row of a stream (k = (c + the stream's lengths) / N chunks complete,
 // k <= max_chunks) and < 0 on its other rows.  The work unit is the stream: carry[b][0:c] ++ row ++ row ... is cut into chunks of N;
 // chunk 0 -> row b of `batch`, chunk j >= 1 -> row b of more[j - 1] (`more` = [max_chunks - 1][streams][N]), the remainder -> carry[b]
-// (in place).  N <= 512, a multiple of 16.
+// (in place).  N <= 512, a multiple of 16.  adpcm: the tick has a DVI4 row (decoded in pieces of N samples, the decoder's state carried
+// from piece to piece) and takes the kernel's ADPCM form; without one it takes the form it always took.
 hipError_t launch_assemble_burst(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int16_t *more,
-                                 int max_chunks, int streams, int N, hipStream_t s);
+                                 int max_chunks, int streams, int N, bool adpcm, hipStream_t s);
 // The flag rows of a burst tick's sub-steps 1 ... steps - 1: the tick's flag row holds k[b] (0 for a stream that completes no chunk),
 // flags[(j - 1) * ld + b] = k[b] > j.
 hipError_t launch_burst_flags(const uint8_t *k_of_stream, uint8_t *flags, long ld, int steps, int streams, hipStream_t s);

@@ -44,6 +44,7 @@
 // dereferenced.  The zeros are spliced at the unaligned pending length like samples.
 #include <hip/hip_runtime.h>
 
+#include "adpcm.hpp"
 #include "device_api.hpp"
 
 namespace vad {
@@ -143,6 +144,108 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_coded_packe
     if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
 }
 
+// DVI4 (VAD_PCM_DVI4, adpcm.hpp): a row is {predict, index, reserved} and then 4-bit IMA ADPCM codes, and decoding them is a recurrence
+// -- (pred, idx) runs from sample to sample.  Both updates are saturating adds, and saturating adds compose (adpcm_then), so a wave
+// decodes up to 512 samples with two inclusive scans over that monoid instead of one lane walking the row:
+//   lane l holds dword 1 + l of the row = the codes of samples 8 l ... 8 l + 7 (first sample in the high nibble of the first byte);
+//   scan 1 over (IDX[d], 0, 88): the lane folds its 8 codes, six __shfl_up rounds scan the folds across the lanes, the fold of the lanes
+//     in front applied to the header's index is the lane's first index, and the lane walks its 8 codes from there: 8 steps (the 89-entry
+//     table sits in LDS, the lanes index it divergently) and with them 8 signed changes +-v;
+//   scan 2 over (+-v, -32768, 32767): the same fold / scan / re-apply from the header's predictor gives the 8 samples.
+// Codes behind the row's last sample (a zero register, or the bytes up to the row's 16-byte end) sit behind every sample that is
+// stored: an inclusive scan never carries them forward.  Integer arithmetic only, no atomics; the scans need the whole wave, and the
+// row's codec is uniform across it.
+__device__ inline AdpcmSat wave_scan_before(AdpcmSat f, int lane) {
+    // -> the composition of the lanes in FRONT of this one (lane 0: the identity)
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const AdpcmSat g{__shfl_up(f.a, s, 64), __shfl_up(f.lo, s, 64), __shfl_up(f.hi, s, 64)};
+        if (lane >= s) f = adpcm_then(g, f);
+    }
+    const AdpcmSat g{__shfl_up(f.a, 1, 64), __shfl_up(f.lo, 1, 64), __shfl_up(f.hi, 1, 64)};
+    return lane ? g : adpcm_identity();
+}
+
+// One piece of a DVI4 row: w = the lane's 8 codes, (pred, idx) = the decoder's state in front of the piece's first sample (uniform).
+// out[j] <- sample 8 lane + j of the piece; (pred, idx) <- the state behind the lane's last code.
+__device__ inline void adpcm_decode_wave(unsigned w, int lane, const short *steps, int &pred, int &idx, int (&out)[8]) {
+    unsigned d[8];
+    AdpcmSat f = adpcm_identity();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        d[j] = (w >> (8 * (j >> 1) + (j & 1 ? 0 : 4))) & 15u;
+        f = adpcm_then(f, AdpcmSat{adpcm_index_add(d[j]), 0, kAdpcmMaxIndex});
+    }
+    idx = adpcm_apply(wave_scan_before(f, lane), idx);
+    f = adpcm_identity();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        out[j] = adpcm_delta(steps[idx], d[j]);
+        idx = adpcm_clamp(idx + adpcm_index_add(d[j]), 0, kAdpcmMaxIndex);
+        f = adpcm_then(f, AdpcmSat{out[j], -32768, 32767});
+    }
+    pred = adpcm_apply(wave_scan_before(f, lane), pred);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = pred = adpcm_clamp(pred + out[j], -32768, 32767);
+}
+
+// the header dword of a DVI4 row as the little-endian load delivers it -> (predict: big-endian on the wire, index: above 88 used as 88)
+__device__ inline void adpcm_header(unsigned h, int &pred, int &idx) {
+    pred = adpcm_header_predict(h, h >> 8);
+    idx = adpcm_header_index(h >> 16);
+}
+
+// assemble_coded_packets for a tick with at least one DVI4 row: the same table, the same LDS splice, the same 16-byte carry and batch
+// stores; S16 and G.711 rows move as there.  A DVI4 row's lane loads ONE dword of codes (8 samples: 64 lanes cover N = 512) and every
+// lane the header dword; the decoded samples go into the LDS row at c + 8 lane + j.
+__global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_adpcm_packets_kernel(const int4 *__restrict__ table, long n_rows,
+                                                                                           const uint8_t *__restrict__ pkt, int16_t *carry,
+                                                                                           i16x8 *__restrict__ batch, int N) {
+    __shared__ __attribute__((aligned(16))) short joined[kPacketRowsPerBlock][2 * 512];      // carry[0:c] ++ packet, < 2N samples
+    __shared__ short steps[kAdpcmSteps];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * kPacketRowsPerBlock + w;
+    const bool live = i < n_rows;                // (no early return: the barriers are the workgroup's)
+    const int4 e = live ? table[i] : make_int4(0, 0, 0, 0);
+    const int b = e.x, off = e.y, len = e.z & ((1 << kCodecShift) - 1), codec = e.z >> kCodecShift, c = e.w, at = lane * 8;
+    short *row = joined[w];
+    i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
+    const bool dvi4 = codec == VAD_PCM_DVI4;
+    const int from = codec == VAD_PCM_S16 || dvi4 ? at : lane * 16;         // the lane's first sample of the packet
+    u32x4 v = {};
+    unsigned head = 0;
+    if (dvi4) {                                  // (never a silent row: those are S16; dword 1 + lane ends inside the row's 16-byte end)
+        const unsigned *src = reinterpret_cast<const unsigned *>(pkt + off);
+        head = src[0];
+        if (from < len) v[0] = __builtin_nontemporal_load(src + 1 + lane);
+    } else if (off >= 0 && from < len)
+        v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(pkt + off) + lane);     // (a silent row: S16 zeros)
+    if (threadIdx.x < kAdpcmSteps) steps[threadIdx.x] = (short)adpcm_step_of(threadIdx.x);
+    if (at < c) *reinterpret_cast<i16x8 *>(row + at) = crow[lane];
+    __syncthreads();
+    // the packet behind the pending samples, at the unaligned offset c
+    if (dvi4) {
+        int pred, idx, out[8];
+        adpcm_header(head, pred, idx);
+        adpcm_decode_wave(v[0], lane, steps, pred, idx, out);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (from + j < len) row[c + from + j] = (short)out[j];
+    } else if (codec == VAD_PCM_S16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (from + j < len) row[c + from + j] = (short)(v[j >> 1] >> (16 * (j & 1)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (from + j < len) row[c + from + j] = g711_to_s16(codec, (uint8_t)(v[j >> 2] >> (8 * (j & 3))));
+    }
+    __syncthreads();
+    const int base = c + len >= N ? N : 0, rest = c + len - base;     // base N: a chunk is complete, the rest is the new carry
+    if (base && at < N) batch[(size_t)b * (N / 8) + lane] = *reinterpret_cast<const i16x8 *>(row + at);
+    if (at < rest) crow[lane] = *reinterpret_cast<const i16x8 *>(row + base + at);
+}
+
 // assemble_packets for a wide tick (vad_pump_submit_wide_packets): int16 rows sampled at step x 16 kHz, of which the comb k0, k0 + step,
 // ... is kept (device_api.hpp comb_first / comb_kept; step and k0 ride in the high bits of len, uniform across the wave).  Lane l owns
 // the input samples [8 step l, 8 step (l + 1)) of its row: `step` consecutive 16-byte loads.  The span starts on a multiple of step, so
@@ -198,10 +301,16 @@ __global__ void __launch_bounds__(64 * kPacketRowsPerBlock) assemble_wide_packet
 // what has arrived since, always < 2N samples: a row goes in in pieces of at most N samples (16-byte loads: 8 samples of int16 or 16
 // G.711 codes a lane, expanded in registers, written at the unaligned fill), and whenever N samples are there they leave as one chunk
 // (16-byte stores) and the rest moves to the front.  What is left at the end (< N) is the new carry, stored in place.
+//
+// ADPCM (a tick with at least one DVI4 row; the instantiation without it is the kernel as it always was): a DVI4 row goes in in the same
+// pieces of at most N samples, a dword of 8 codes a lane, decoded by adpcm_decode_wave.  The decoder's state in front of the row's
+// first piece is the header's; behind a whole piece it is the state behind sample N - 1, lane N / 8 - 1's, broadcast to the wave.
+template <bool ADPCM>
 __global__ void __launch_bounds__(64) assemble_burst_kernel(const int4 *__restrict__ table, long n_rows, const uint8_t *__restrict__ pkt,
                                                             int16_t *carry, i16x8 *__restrict__ batch, i16x8 *__restrict__ more,
                                                             int max_chunks, long streams, int N) {
     __shared__ __attribute__((aligned(16))) short joined[2 * 512];
+    __shared__ short steps[ADPCM ? kAdpcmSteps : 1];
     const int lane = threadIdx.x, at = lane * 8;
     const long i0 = blockIdx.x;
     const int4 first = table[i0];
@@ -210,6 +319,10 @@ __global__ void __launch_bounds__(64) assemble_burst_kernel(const int4 *__restri
     i16x8 *crow = reinterpret_cast<i16x8 *>(carry + (size_t)b * N);
     int fill = first.w & ((1 << kCodecShift) - 1), chunk = 0;
     if (at < fill) *reinterpret_cast<i16x8 *>(joined + at) = crow[lane];
+    if constexpr (ADPCM) {
+        steps[lane] = (short)adpcm_step_of(lane);
+        if (lane + 64 < kAdpcmSteps) steps[lane + 64] = (short)adpcm_step_of(lane + 64);
+    }
     __syncthreads();
     for (long i = i0; i < n_rows; ++i) {
         const int4 e = i == i0 ? first : table[i];
@@ -218,12 +331,26 @@ __global__ void __launch_bounds__(64) assemble_burst_kernel(const int4 *__restri
         const int per = codec == VAD_PCM_S16 ? 8 : 16;                         // samples in a lane's 16 bytes
         const bool quiet = e.y < 0;                                             // a silent row: its pieces are zeros, pkt is not touched
         const u32x4 *src = reinterpret_cast<const u32x4 *>(pkt + e.y);                     // (... nor is this)
+        const bool dvi4 = ADPCM && codec == VAD_PCM_DVI4;                       // (never a silent row: those are S16)
+        int pred = 0, idx = 0;                                                  // a DVI4 row: the decoder's state in front of the piece
+        if (dvi4) adpcm_header(*reinterpret_cast<const unsigned *>(src), pred, idx);
         for (int s0 = 0; s0 < len; s0 += N) {                                   // a piece: samples [s0, s0 + n) of the row
-            const int n = min(N, len - s0), from = lane * per;
+            const int n = min(N, len - s0), from = dvi4 ? at : lane * per;
             u32x4 v = {};
-            if (!quiet && from < n) v = __builtin_nontemporal_load(src + s0 / per + lane);
+            if (dvi4) {                                                         // (dword 1 + s0 / 8 + lane ends inside the row's 16-byte end)
+                if (from < n) v[0] = __builtin_nontemporal_load(reinterpret_cast<const unsigned *>(src) + 1 + s0 / 8 + lane);
+            } else if (!quiet && from < n)
+                v = __builtin_nontemporal_load(src + s0 / per + lane);
             short *dst = joined + fill + from;
-            if (codec == VAD_PCM_S16) {
+            if (dvi4) {
+                int out[8];
+                adpcm_decode_wave(v[0], lane, steps, pred, idx, out);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (from + j < n) dst[j] = (short)out[j];
+                pred = __shfl(pred, N / 8 - 1, 64);                             // (of use behind a whole piece only)
+                idx = __shfl(idx, N / 8 - 1, 64);
+            } else if (codec == VAD_PCM_S16) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     if (from + j < n) dst[j] = (short)(v[j >> 1] >> (16 * (j & 1)));
@@ -329,12 +456,13 @@ __global__ void __launch_bounds__(256) burst_flags_kernel(const uint8_t *__restr
 }  // namespace
 
 hipError_t launch_assemble_burst(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int16_t *more,
-                                 int max_chunks, int streams, int N, hipStream_t s) {
+                                 int max_chunks, int streams, int N, bool adpcm, hipStream_t s) {
     if (n_rows <= 0) return hipSuccess;
     if (!table || !pkt || !carry || !batch || (max_chunks > 1 && !more) || max_chunks < 1 || streams <= 0 || N <= 0 || N > 512 || N % 16)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(assemble_burst_kernel, dim3((unsigned)n_rows), dim3(64), 0, s, reinterpret_cast<const int4 *>(table), n_rows, pkt, carry,
-                       reinterpret_cast<i16x8 *>(batch), reinterpret_cast<i16x8 *>(more), max_chunks, (long)streams, N);
+    hipLaunchKernelGGL(adpcm ? assemble_burst_kernel<true> : assemble_burst_kernel<false>, dim3((unsigned)n_rows), dim3(64), 0, s,
+                       reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch),
+                       reinterpret_cast<i16x8 *>(more), max_chunks, (long)streams, N);
     return hipGetLastError();
 }
 
@@ -361,6 +489,16 @@ hipError_t launch_assemble_coded_packets(const int32_t *table, long n_rows, cons
     if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
     const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
     hipLaunchKernelGGL(assemble_coded_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
+                       reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_adpcm_packets(const int32_t *table, long n_rows, const uint8_t *pkt, int16_t *carry, int16_t *batch, int N,
+                                         hipStream_t s) {
+    if (n_rows <= 0) return hipSuccess;
+    if (!table || !pkt || !carry || !batch || N <= 0 || N > 512 || N % 8) return hipErrorInvalidValue;
+    const long blocks = (n_rows + kPacketRowsPerBlock - 1) / kPacketRowsPerBlock;
+    hipLaunchKernelGGL(assemble_adpcm_packets_kernel, dim3((unsigned)blocks), dim3(64 * kPacketRowsPerBlock), 0, s,
                        reinterpret_cast<const int4 *>(table), n_rows, pkt, carry, reinterpret_cast<i16x8 *>(batch), N);
     return hipGetLastError();
 }

@@ -46,7 +46,11 @@
 // the tail as the new carry) in place of expand_rows; everything behind it is the masked tick, bit for bit.  The chunk routes refuse a
 // stream with pending samples; while no stream has any, they run exactly as before.  vad_pump_submit_coded_packets: the same tick with
 // rows that may be G.711 mu-law / A-law (1 byte a sample, byte offsets); a tick with such a row takes assemble_coded_packets, which
-// expands them to int16 on the device, and the carry holds int16 whatever the packets were.
+// expands them to int16 on the device, and the carry holds int16 whatever the packets were.  A row may also be DVI4 (VAD_PCM_DVI4:
+// a 4-byte header with the decoder's state, then 4-bit IMA ADPCM codes -- 4 + len / 2 bytes); a tick with such a row takes
+// assemble_adpcm_packets, which decodes it by two wave scans (adpcm.hpp), and a burst tick with one the ADPCM form of assemble_burst.
+// The pump takes such rows once vad_pump_set_adpcm has said so; until then codec 3 is the bad codec it always was.
+// Every packet carries its own state: nothing is kept per stream, and the carry, the tape and a snapshot see int16 as before.
 //
 // BURST ticks (vad_pump_set_burst + vad_pump_submit_burst): a stream may have several rows in a tick and a row may be longer than N (a 60 ms
 // Opus frame; what a jitter buffer releases after a stall), so a stream may complete k <= max_chunks chunks.  The host groups the rows by
@@ -98,6 +102,7 @@
 #include <vector>
 
 #include "../../include/silero_vad_hip.h"
+#include "adpcm.hpp"
 #include "device_api.hpp"
 #include "host_threads.hpp"
 #include "tape.hpp"
@@ -149,6 +154,7 @@ struct vad_pump {
     std::vector<uint8_t> seen;                   // [streams] scratch of the packet-row validation (all zero between calls)
     // burst ticks (vad_pump_set_burst; max_burst == 0: not enabled, none of this is allocated)
     int max_burst = 0;                           // chunks a stream may complete in one tick
+    bool adpcm = false;                          // vad_pump_set_adpcm: the coded packet and burst routes take VAD_PCM_DVI4 rows
     int16_t *d_more = nullptr;                   // [max_burst - 1][streams][N] the batch rows of sub-steps 1 ... (compute stream only)
     uint8_t *d_more_flags = nullptr;             // [max_burst - 1][hdr]        their flag rows
     float *h_prob_more = nullptr;                // [R][max_burst - 1][streams] page-locked, mapped: their probabilities
@@ -560,27 +566,33 @@ struct Packets {
     bool res = false;                            // vad_pump_submit_resampled_packets: int16 rows of the RESAMPLE slot, at rates[rate of row]
     const uint8_t *rate = nullptr;               // ... the rate index per row, or null (every row at rate 0)
 };
+const char *const kCodecWhy[2] = {" is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW (VAD_PCM_DVI4 rows are not enabled on this pump: vad_pump_set_adpcm)",
+                                   " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW / VAD_PCM_DVI4"};
+const char *const kOddWhy = "a DVI4 row of an odd length (its codes come two a byte)";
+// the bytes a payload row of `len` samples takes in the slot: 2 a sample, 1 a sample (G.711), or a 4-byte header and 2 samples a byte
+inline long row_bytes(int codec, long len) { return codec == VAD_PCM_S16 ? 2 * len : codec == VAD_PCM_DVI4 ? 4 + len / 2 : len; }
 const char *const kBoundWhy = "a stream that is bound to a resampled rate (vad_pump_submit_resampled_packets) until vad_pump_open / vad_pump_close";
 
 // Validate a packet tick's rows and write its row table (ending where slot r's flags start) and its flags (the streams that complete
 // a chunk).  -> the bytes of the slot's sample area the copy has to carry, or < 0 (VAD_ERR_ARG, p->err says why; nothing queued).
-// *g711: a row is mu-law or A-law -- the table then holds byte offsets and each row's codec in the high bits of its length, for
-// assemble_coded_packets; otherwise it holds sample offsets, for assemble_packets, whichever entry point was called.
+// *g711: a row is not int16 -- the table then holds byte offsets and each row's codec in the high bits of its length, for
+// assemble_coded_packets; otherwise it holds sample offsets, for assemble_packets, whichever entry point was called.  *adpcm: one of
+// those rows is DVI4 (an even length, 4 + len / 2 bytes) -- the same table, for assemble_adpcm_packets.
 // A SILENT row (offset VAD_ROW_SILENT: len samples of digital silence, no bytes in the slot) keeps the marker in the table's offset
 // column, is S16 whatever codec_of_row says (its entry is not looked at, it does not make the tick a G.711 tick), passes neither the
 // alignment nor the fits-the-area check and does not count towards the bytes the copy carries; everything else applies to it.
-long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g711) {
+long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g711, bool *adpcm) {
     const long S = p->streams, N = p->N;
     const char *fn = pk.coded ? "vad_pump_submit_coded_packets: " : "vad_pump_submit_packets: ";
     if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
         return pfail(p, VAD_ERR_ARG, std::string(fn) + "bad row list"), -1;
-    *g711 = false;
+    *g711 = *adpcm = false;
     for (long i = 0; pk.codec && i < n_rows; ++i) {
         if (pk.off[i] == VAD_ROW_SILENT) continue;
-        if (pk.codec[i] > VAD_PCM_ALAW)
-            return pfail(p, VAD_ERR_ARG, std::string(fn) + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) +
-                                             " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW"), -1;
+        if (pk.codec[i] > (p->adpcm ? VAD_PCM_DVI4 : VAD_PCM_ALAW))
+            return pfail(p, VAD_ERR_ARG, std::string(fn) + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) + kCodecWhy[p->adpcm]), -1;
         *g711 |= pk.codec[i] != VAD_PCM_S16;
+        *adpcm |= pk.codec[i] == VAD_PCM_DVI4;
     }
     uint8_t *fl = p->slot_present(r);
     int32_t *tab = reinterpret_cast<int32_t *>(fl) - 4 * n_rows;
@@ -591,10 +603,11 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
         const int32_t b = pk.stream[i], off = pk.off[i], len = pk.len[i];
         const bool silent = off == VAD_ROW_SILENT;
         const int codec = pk.codec && !silent ? pk.codec[i] : VAD_PCM_S16;
-        const long at = pk.coded ? off : 2L * off, bytes = codec == VAD_PCM_S16 ? 2L * len : len;      // the row, in bytes
+        const long at = pk.coded ? off : 2L * off, bytes = row_bytes(codec, len);      // the row, in bytes
         if (b < 0 || b >= S || p->seen[b]) why = "a stream out of range, or listed twice in one tick";
         else if (p->bound(b)) why = kBoundWhy;
         else if (len < 1 || len > N) why = "a packet length out of 1 ... N (a longer packet goes in over two ticks)";
+        else if (codec == VAD_PCM_DVI4 && len % 2) why = kOddWhy;
         else if (!silent && (at < 0 || at % 16 || at + bytes > S * N * 2))
             why = pk.coded ? "a packet byte offset that is not a multiple of 16, or a row that runs past the slot"
                            : "a packet offset that is not a multiple of 8 samples, or runs past the slot";
@@ -621,27 +634,33 @@ long build_packets(vad_pump *p, int r, const Packets &pk, long n_rows, bool *g71
 // holds k, the chunks it completes (0 ... max_burst).  *steps = max(1, largest k).  The pending counts are NOT touched: p->b_new holds
 // them for the caller to apply once the tick is queued.  A SILENT row (offset VAD_ROW_SILENT) is a row of any length >= 1 like another:
 // S16 in the table whatever its codec entry says, no offset checks, no bytes of the copy.
-long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps) {
+long build_burst(vad_pump *p, int r, const Packets &pk, long n_rows, int *steps, bool *adpcm) {
     const long S = p->streams, N = p->N, M = p->max_burst;
     const std::string fn = "vad_pump_submit_burst: ";
     if (M < 1) return pfail(p, VAD_ERR_ARG, fn + "bursts are not enabled on this pump (vad_pump_set_burst)"), -1;
     if (n_rows < 0 || n_rows > S || (n_rows > 0 && (!pk.stream || !pk.off || !pk.len)))
         return pfail(p, VAD_ERR_ARG, fn + "bad row list (a tick holds at most `streams` rows)"), -1;
-    for (long i = 0; pk.codec && i < n_rows; ++i)
-        if (pk.off[i] != VAD_ROW_SILENT && pk.codec[i] > VAD_PCM_ALAW)
-            return pfail(p, VAD_ERR_ARG, fn + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) +
-                                             " is none of VAD_PCM_S16 / VAD_PCM_ULAW / VAD_PCM_ALAW"), -1;
+    *adpcm = false;
+    for (long i = 0; pk.codec && i < n_rows; ++i) {
+        if (pk.off[i] == VAD_ROW_SILENT) continue;
+        if (pk.codec[i] > (p->adpcm ? VAD_PCM_DVI4 : VAD_PCM_ALAW))
+            return pfail(p, VAD_ERR_ARG, fn + "row " + std::to_string(i) + ": codec " + std::to_string(pk.codec[i]) + kCodecWhy[p->adpcm]), -1;
+        *adpcm |= pk.codec[i] == VAD_PCM_DVI4;
+    }
     p->b_touched.clear();
     p->b_new.clear();
     long end = 0;
     const char *why = nullptr;
     for (long i = 0; i < n_rows && !why; ++i) {
         const int32_t b = pk.stream[i];
-        const long at = pk.off[i], len = pk.len[i], bytes = (pk.codec ? pk.codec[i] : VAD_PCM_S16) == VAD_PCM_S16 ? 2 * len : len;
+        const long at = pk.off[i], len = pk.len[i];
         const bool silent = at == VAD_ROW_SILENT;
+        const int codec = pk.codec && !silent ? pk.codec[i] : VAD_PCM_S16;
+        const long bytes = row_bytes(codec, len);
         if (b < 0 || b >= S) why = "a stream out of range";
         else if (p->bound(b)) why = kBoundWhy;
         else if (len < 1) why = "a row length below 1";
+        else if (codec == VAD_PCM_DVI4 && len % 2) why = kOddWhy;
         else if (!silent && (at < 0 || at % 16 || at + bytes > S * N * 2)) why = "a row byte offset that is not a multiple of 16, or a row that runs past the slot";
         else {
             if (p->b_cnt[b]++ == 0) p->b_touched.push_back(b);
@@ -799,13 +818,13 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
     const int buf = (int)(p->ticks % p->nb), pp = (int)(p->ticks & 1), cp = (int)(p->flips & 1);
     const size_t S = (size_t)p->streams, N = (size_t)p->N, C = (size_t)p->C;
     long pk_bytes = 0;                           // a packet tick: the bytes of the slot's sample area its copy carries
-    bool g711 = false;                           // ... and it has a mu-law / A-law row
+    bool g711 = false, adpcm = false;            // ... and it has a row that is not int16, a DVI4 row
     int steps = 1;                               // a burst tick: the masked steps it runs
     if (pk) {
         if ((pk_bytes = pk->res     ? build_resampled(p, r, *pk, n_rows)
                         : pk->wide  ? build_wide(p, r, *pk, n_rows)
-                        : pk->burst ? build_burst(p, r, *pk, n_rows, &steps)
-                                    : build_packets(p, r, *pk, n_rows, &g711)) < 0)
+                        : pk->burst ? build_burst(p, r, *pk, n_rows, &steps, &adpcm)
+                                    : build_packets(p, r, *pk, n_rows, &g711, &adpcm)) < 0)
             return VAD_ERR_ARG;
         present = pk->res ? p->res_present(r) : pk->wide ? p->wide_present(r) : p->slot_present(r);      // (a wide / resampled tick's flags: copied to the slot's own row for vad_pump_poll)
     } else if (rows != nullptr || n_rows != 0) {
@@ -899,9 +918,11 @@ int submit_tick(vad_pump *p, int r, const uint8_t *present, bool compact, const 
             TICK_TRY(vad::launch_assemble_wide_packets(table, n_rows, d_fl + p->hdr, p->d_carry, batch, p->N, p->compute));
         } else if (pk->burst) {                  // (chunk 0 of every stream into `batch`, chunks 1 ... into d_more; flags_j = k > j)
             TICK_TRY(vad::launch_assemble_burst(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->d_more, p->max_burst, p->streams, p->N,
-                                                p->compute));
+                                                adpcm, p->compute));
             TICK_TRY(vad::launch_burst_flags(d_present, p->d_more_flags, (long)p->hdr, steps, p->streams, p->compute));
-        } else if (g711)                         // (G.711 rows are expanded on the way; an all-int16 tick takes the int16 kernel)
+        } else if (adpcm)                        // (a DVI4 row is decoded on the way, by two wave scans; only such ticks take this kernel)
+            TICK_TRY(vad::launch_assemble_adpcm_packets(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->N, p->compute));
+        else if (g711)                           // (G.711 rows are expanded on the way; an all-int16 tick takes the int16 kernel)
             TICK_TRY(vad::launch_assemble_coded_packets(table, n_rows, cbuf + p->hpos + p->hdr, p->d_carry, batch, p->N, p->compute));
         else
             TICK_TRY(vad::launch_assemble_packets(table, n_rows, reinterpret_cast<const int16_t *>(cbuf + p->hpos + p->hdr), p->d_carry, batch,
@@ -1023,6 +1044,14 @@ int vad_pump_submit_burst(vad_pump *p, int r, const int32_t *stream_of_row, cons
     Packets pk{stream_of_row, byte_off_of_row, len_of_row, true, codec_of_row};
     pk.burst = true;
     return submit_tick(p, r, nullptr, true, nullptr, n_rows, &pk);
+}
+
+int vad_pump_set_adpcm(vad_pump *p, int on) {
+    if (!p) return VAD_ERR_ARG;
+    if (on != 0 && on != 1) return pfail(p, VAD_ERR_ARG, "vad_pump_set_adpcm: on is 0 or 1");
+    if (!p->inflight.empty()) return pfail(p, VAD_ERR_ARG, "vad_pump_set_adpcm: ticks in flight (retire them with vad_pump_poll first)");
+    p->adpcm = on != 0;
+    return VAD_OK;
 }
 
 int vad_pump_set_burst(vad_pump *p, int max_chunks) {
@@ -1235,6 +1264,11 @@ int vad_g711_expand(int codec, const uint8_t *in, long n, int16_t *out) {
     }
     for (long i = 0; i < n; ++i) out[i] = vad::g711_to_s16(codec, in[i]);
     return VAD_OK;
+}
+
+long vad_adpcm_expand(const uint8_t *payload, long nbytes, int16_t *out) {
+    const long n = vad::adpcm_expand_serial(payload, nbytes, out);
+    return n < 0 ? -VAD_ERR_ARG : n;
 }
 
 long vad_deinterleave(int codec, int channels, int channel, const void *in, long frames, int16_t *out) {

@@ -2962,27 +2962,32 @@ class BatchVADIterator:
         return [(ev[i].slot, {"end" if ev[i].kind else "start": ev[i].sample}) for i in range(m)]
 
 
-# sample formats of a packet row (include/silero_vad_hip.h VAD_PCM_*): int16, G.711 mu-law (PCMU), G.711 A-law (PCMA)
-_PCM = {"s16": 0, "ulaw": 1, "alaw": 2}
+# sample formats of a packet row (include/silero_vad_hip.h VAD_PCM_*): int16, G.711 mu-law (PCMU), G.711 A-law (PCMA), DVI4 (RFC 3551
+# 4-bit IMA ADPCM: a 4-byte header, then two samples a byte -- the pump's coded packet and burst routes only)
+_PCM = {"s16": 0, "ulaw": 1, "alaw": 2, "dvi4": 3}
+_DVI4_HEADER = 4                                        # bytes in front of a DVI4 payload's codes
 
 
-def _codec_id(codec) -> int:
+def _codec_id(codec, dvi4: bool = False) -> int:
+    """A codec's name or number -> its number.  dvi4: "dvi4" / 3 is one of them -- on the packet routes of a pump with `adpcm=True`;
+    everywhere else (the corpus routes, g711_expand, deinterleave, a pump without it) the codecs are the three they always were."""
+    known = _PCM if dvi4 else {k: v for k, v in _PCM.items() if k != "dvi4"}
     if isinstance(codec, str):
-        if codec not in _PCM:
-            raise ValueError(f"codec must be one of {sorted(_PCM)}, got {codec!r}")
-        return _PCM[codec]
-    if not isinstance(codec, (int, np.integer)) or int(codec) not in _PCM.values():
-        raise ValueError(f"codec must be one of {sorted(_PCM)} or {sorted(_PCM.values())}, got {codec!r}")
+        if codec not in known:
+            raise ValueError(f"codec must be one of {sorted(known)}, got {codec!r}")
+        return known[codec]
+    if not isinstance(codec, (int, np.integer)) or int(codec) not in known.values():
+        raise ValueError(f"codec must be one of {sorted(known)} or {sorted(known.values())}, got {codec!r}")
     return int(codec)
 
 
-def _codec_rows(codecs) -> np.ndarray:
+def _codec_rows(codecs, dvi4: bool = False) -> np.ndarray:
     """Per-row codecs as uint8: names are mapped here, numbers go to the pump as they are (it refuses a bad one)."""
     a = np.asarray(codecs)
     if a.ndim != 1:
         raise ValueError(f"codecs must be a 1-D sequence, got shape {a.shape}")
     if a.dtype.kind in "US":
-        return np.array([_codec_id(str(c)) for c in a], np.uint8)
+        return np.array([_codec_id(str(c), dvi4) for c in a], np.uint8)
     if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 255):
         raise ValueError(f"codecs must be names or uint8 values, got {a.dtype}")
     return np.ascontiguousarray(a, dtype=np.uint8)
@@ -3019,7 +3024,10 @@ def _uint8_rows(x, name, what) -> np.ndarray:
 
 
 def _coded_sizes(ln, cd):
-    return ln * (2 if cd is None else np.where(cd == _PCM["s16"], 2, 1))
+    """Each row's bytes: 2 a sample (int16), 1 a sample (G.711), or a DVI4 payload's 4 + len / 2."""
+    if cd is None:
+        return ln * 2
+    return np.where(cd == _PCM["dvi4"], _DVI4_HEADER + ln // 2, ln * np.where(cd == _PCM["s16"], 2, 1))
 
 
 # The pump's packet routes, one row each; `StreamPump._submit_route` is the one builder behind the five submit_* methods.
@@ -3070,6 +3078,23 @@ def g711_expand(data, codec) -> np.ndarray:
     rc = lib().vad_g711_expand(c, x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None)
     if rc:
         raise _lib.VadError(rc, "vad_g711_expand")
+    return out
+
+
+def adpcm_expand(payload) -> np.ndarray:
+    """A DVI4 payload (RFC 3551 section 4.5.1, RTP payload types 5 / 6: uint8, the 4 header bytes {predict, index, reserved} included)
+    -> its 2 * (len - 4) int16 samples (vad_adpcm_expand: the values of audioop.adpcm2lin(payload[4:], 2, (predict, min(index, 88))),
+    from the single-code step the pump's device decoder uses).  A DVI4 stream for `StreamPump.write_packets`: `adpcm_expand(payload)`;
+    `write_coded_packets(r, [(stream, payload, "dvi4")])` has the device do it.  There is no encoder in this package."""
+    x = np.ascontiguousarray(payload)
+    if x.dtype != np.uint8 or x.ndim != 1:
+        raise ValueError(f"a DVI4 payload must be a 1-D uint8 array, got {x.dtype} of shape {x.shape}")
+    if len(x) < _DVI4_HEADER:
+        raise ValueError(f"a DVI4 payload holds at least its {_DVI4_HEADER} header bytes, got {len(x)}")
+    out = np.empty(2 * (len(x) - _DVI4_HEADER), np.int16)
+    n = lib().vad_adpcm_expand(x.ctypes.data, len(x), out.ctypes.data if out.size else None)
+    if n < 0:
+        raise _lib.VadError(int(-n), "vad_adpcm_expand")
     return out
 
 
@@ -3465,7 +3490,8 @@ class StreamPump:
     comfort-noise period) is a SILENT row: `(stream, 160)` in a `write_*` list, or `ROW_SILENT` as the row's offset -- that many zero
     samples of the stream, no bytes written or sent; a stream listed in no row is absent (late) and stands still instead.  G.711 (PCMU / PCMA) packets go in as they came off
     the wire, 1 byte a sample: `pump.write_coded_packets(r, [(stream, packet, "ulaw" | "alaw" | "s16"), ...])` (or `packet_bytes(r)` +
-    `submit_coded_packets(...)`); the device expands them.  With `max_burst=M` (2 ... 8) a tick may be a BURST:
+    `submit_coded_packets(...)`); the device expands them.  With `adpcm=True` the same two routes and bursts also take DVI4 payloads
+    (RFC 3551 4-bit IMA ADPCM, header included: `(stream, payload, "dvi4")`), decoded on the device.  With `max_burst=M` (2 ... 8) a tick may be a BURST:
     `pump.write_burst(r, [(stream, packet[, codec]), ...])` takes any number of packets of one stream and packets longer than a chunk (a
     60 ms Opus frame, what a jitter buffer releases after a stall); a stream that completes k <= M chunks is stepped k times inside the
     tick, `burst_steps(r)` / `burst_probs(r)` give the sub-steps, and `poll` returns their events one sub-step after the other.
@@ -3500,7 +3526,7 @@ class StreamPump:
 
     def __init__(self, engine, sampling_rate: int = 16000, streams: int = 8192, parts: int = 0, ring_slots: int = 0,
                  threshold: float = 0.5, min_silence_duration_ms: int = 100, speech_pad_ms: int = 30, max_burst: int = 1, source_rate=None,
-                 tape_chunks: int = 0, tape_dtype="int16"):
+                 tape_chunks: int = 0, tape_dtype="int16", adpcm: bool = False):
         _no_source_rate(source_rate, "StreamPump")
         if isinstance(tape_chunks, (bool, np.bool_)) or not isinstance(tape_chunks, (int, np.integer)) or tape_chunks < 0 or tape_chunks == 1 \
                 or tape_chunks >= 2 ** 31:
@@ -3532,6 +3558,14 @@ class StreamPump:
                 self._L.vad_pump_destroy(h)
                 self._h = None
                 raise _lib.VadError(rc, msg)
+        self.adpcm = False
+        if adpcm:                                                # (off: codec 3 stays the bad codec it was)
+            try:
+                self.set_adpcm(True)
+            except Exception:
+                self._L.vad_pump_destroy(h)
+                self._h = None
+                raise
         self.tape_chunks = 0
         self.tape_dtype = None
         self.device = getattr(engine, "device", 0)
@@ -3618,7 +3652,7 @@ class StreamPump:
         rt = _ROUTES[route]
         st, ln = _int32_rows(streams, "streams"), _int32_rows(lengths, "lengths")
         off = None if offsets is None else _int32_rows(offsets, rt.offsets)
-        c4 = None if col4 is None else rt.rows4(col4)
+        c4 = None if col4 is None else _codec_rows(col4, getattr(self, "adpcm", False)) if rt.rows4 is _codec_rows else rt.rows4(col4)
         n = len(st)
         if len(ln) != n or (off is not None and len(off) != n) or (c4 is not None and len(c4) != n):
             names = ["streams", "lengths"] + [rt.col4] * (rt.col4 is not None)
@@ -3662,7 +3696,7 @@ class StreamPump:
         align = 16 // area.itemsize
         streams, lengths, thirds, offsets, at = [], [], [], [], 0
         for s, x, t in rows():
-            c = _codec_id(t) if pk.third == "codec" else self.resample_rates.index(t) if pk.third == "rate" else None
+            c = _codec_id(t, getattr(self, "adpcm", False)) if pk.third == "codec" else self.resample_rates.index(t) if pk.third == "rate" else None
             streams.append(s)
             thirds.append(c)
             if _silent_len(x) is not None:
@@ -3674,13 +3708,18 @@ class StreamPump:
             if x.dtype != want or x.ndim != 1:
                 raise ValueError(f"a {t!r} packet must be a 1-D {np.dtype(want).name} array, got {x.dtype} of shape {x.shape}"
                                  if pk.third == "codec" else f"a {pk.noun} must be a 1-D int16 array")
-            if len(x) < 1 or (cap and len(x) > cap):
-                raise ValueError(too_long.format(len(x)) if cap else "a packet holds at least 1 sample")
+            n = len(x)                                           # the row's samples
+            if pk.third == "codec" and c == _PCM["dvi4"]:        # (the payload's header is no sample; two samples a byte behind it)
+                if n <= _DVI4_HEADER:
+                    raise ValueError(f"a 'dvi4' packet is its {_DVI4_HEADER} header bytes and at least 1 byte of codes, got {n} bytes")
+                n = 2 * (n - _DVI4_HEADER)
+            if n < 1 or (cap and n > cap):
+                raise ValueError(too_long.format(n) if cap else "a packet holds at least 1 sample")
             size = x.nbytes // area.itemsize
             if at + size > len(area):
                 raise ValueError(f"the {pk.noun}s do not fit into the slot")
             area[at:at + size] = x.view(area.dtype)
-            lengths.append(len(x))
+            lengths.append(n)
             offsets.append(at)
             at += (size + align - 1) // align * align
         return streams, lengths, None if pk.third is None else np.array(thirds, np.uint8), offsets
@@ -3703,13 +3742,18 @@ class StreamPump:
         rounded up to 16 bytes).  The device expands G.711 to int16: the same results, bit for bit, as `submit_packets` with the rows
         expanded by `g711_expand`.  A bad codec, stream, length or offset raises and queues nothing.
         byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] int16 zeros (see `submit_packets`); its codecs[i] is not looked
-        at by the pump.  With byte_offsets=None every row has a payload."""
+        at by the pump.  With byte_offsets=None every row has a payload.
+        codecs[i] == "dvi4" (RFC 3551 4-bit IMA ADPCM; on a pump with `adpcm=True` / `set_adpcm()`): the row is the RTP payload, header included -- 4 + lengths[i] / 2 bytes for
+        an even lengths[i] of 2 ... N SAMPLES; the device decodes it, with the results of the row `adpcm_expand`ed.  An odd length
+        raises."""
         self._submit_route("coded", r, streams, lengths, byte_offsets, codecs)
 
     def write_coded_packets(self, r: int, packets):
         """Pack [(stream, samples, codec), ...] back to back (each rounded up to 16 bytes) into `packet_bytes(r)` and submit the tick:
         codec "s16" takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes (an RTP payload as it came off the wire).  An int
-        in place of the samples, `(stream, 160, codec)`, is a silent row of that many samples (1 ... N), whatever the codec."""
+        in place of the samples, `(stream, 160, codec)`, is a silent row of that many samples (1 ... N), whatever the codec.
+        codec "dvi4" (on a pump with `adpcm=True`) takes a uint8 array too: the whole payload, its 4 header bytes included (5 bytes at least); the row's length is
+        derived from it, 2 * (size - 4) samples."""
         streams, lengths, codecs, offsets = self._pack("coded", self.packet_bytes(r), packets)
         self.submit_coded_packets(r, streams, lengths, codecs, offsets)
 
@@ -3720,14 +3764,15 @@ class StreamPump:
         those of the same audio fed chunk by chunk, bit for bit.  A stream that would complete more than max_burst chunks, more rows
         than `streams`, a bad codec, stream, length or offset raises and queues nothing.
         byte_offsets[i] == ROW_SILENT (-1): a SILENT row of lengths[i] >= 1 int16 zeros (see `submit_packets`), longer than N if the
-        gap was; it counts towards max_burst like any row.  With byte_offsets=None every row has a payload."""
+        gap was; it counts towards max_burst like any row.  With byte_offsets=None every row has a payload.
+        A "dvi4" row: any even length >= 2, 4 + lengths[i] / 2 bytes (see `submit_coded_packets`)."""
         self._submit_route("burst", r, streams, lengths, byte_offsets, codecs)
 
     def write_burst(self, r: int, packets):
         """Pack [(stream, samples) | (stream, samples, codec), ...] back to back in arrival order (each rounded up to 16 bytes) into
         `packet_bytes(r)` and submit the burst tick: packets of any length, streams repeated as often as they delivered.  codec "s16"
-        (the default) takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes.  An int in place of the samples,
-        `(stream, 3 * N + 5)`, is a silent row of that many samples."""
+        (the default) takes an int16 array, "ulaw" / "alaw" a uint8 array of G.711 codes, "dvi4" a uint8 DVI4 payload with its header
+        (`write_coded_packets`).  An int in place of the samples, `(stream, 3 * N + 5)`, is a silent row of that many samples."""
         streams, lengths, codecs, offsets = self._pack("burst", self.packet_bytes(r), packets, default="s16")
         self.submit_burst(r, streams, lengths, codecs, offsets)
 
@@ -3857,6 +3902,13 @@ class StreamPump:
         h, c, x = np.empty(128, np.float32), np.empty(128, np.float32), np.empty(self.n // 8, np.float32)
         self._check(self._L.vad_pump_state(self._h, int(stream), h.ctypes.data, c.ctypes.data, x.ctypes.data))
         return h, c, x
+
+    def set_adpcm(self, on: bool = True):
+        """Enable (or switch off) DVI4 rows, codec "dvi4", on `submit_coded_packets` / `write_coded_packets` / `submit_burst` /
+        `write_burst` (vad_pump_set_adpcm; what `StreamPump(..., adpcm=True)` calls): only with no tick in flight; nothing is allocated.
+        Without it the pump and its packers know "s16", "ulaw" and "alaw" and refuse codec 3, as they always did."""
+        self._check(self._L.vad_pump_set_adpcm(self._h, 1 if on else 0))
+        self.adpcm = bool(on)
 
     def set_tape(self, chunks: int, dtype="int16"):
         """Enable the tape (vad_pump_set_tape / vad_pump_set_tape_f32; what `StreamPump(..., tape_chunks=chunks, tape_dtype=dtype)` calls):

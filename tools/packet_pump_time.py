@@ -9,7 +9,9 @@ reaches, and the time per second of audio of every route (equal audio throughput
 
 sr: 16000 (default) or 8000.  codecs: a comma-separated list of packet formats, timed alternately with the chunk route -- "s16" (the
 default: int16 packets through vad_pump_submit_packets), "ulaw" / "alaw" (G.711 packets, 1 byte a sample, through
-vad_pump_submit_coded_packets; the device expands them).  The telephony case: `python tools/packet_pump_time.py 2000 3 8000 s16,ulaw,alaw`.
+vad_pump_submit_coded_packets; the device expands them), "dvi4" (RFC 3551 4-bit IMA ADPCM payloads, a 4-byte header and 2 samples a
+byte, through the same entry; the device decodes them).  The telephony case: `python tools/packet_pump_time.py 2000 3 8000 s16,ulaw,alaw,dvi4`.
+For the routes without gaps the tool asserts what a tick's one copy carries: rows x (16 + the row's bytes rounded up to 16) + streams.
 
 burst_share d (e.g. `0.1 3`): burst mode -- adds the route "burst" (vad_pump_submit_burst on a pump with max_burst = 8).  That share of
 the streams is withheld for d ticks at a time (in d + 1 phases, so every tick sees the same load) and then delivers its d + 1 packets
@@ -29,7 +31,7 @@ zeros instead, each where its packet would lie: what a caller without silent row
 with).  Both give the same chunks to the step kernels.  "link_bytes_per_tick" is what the tick's one copy carries either way, and
 "tick_ms_p50" the median time from a tick's submission to its retirement, two ticks in flight.
 
-assemble_packets_kernel's / assemble_coded_packets_kernel's / assemble_burst_kernel's / assemble_wide_packets_kernel's own time: run it under
+assemble_packets_kernel's / assemble_coded_packets_kernel's / assemble_adpcm_packets_kernel's / assemble_burst_kernel's / assemble_wide_packets_kernel's own time: run it under
 `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/packet_pump_time.py ...` (in a run of its own) and read the
 kernels' lines of the stats file."""
 import json
@@ -55,6 +57,37 @@ def g711_encode(pcm, law):
     return codes[order[j]]
 
 
+def dvi4_encode(pcm):
+    """int16 [rows, P] (P even) -> DVI4 payloads uint8 [rows, 4 + P / 2]: a plain IMA encoder over all rows at once, each row's header
+    {predict = its first sample, index = 30}."""
+    import numpy as np
+    step_of = np.array([7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118,
+                        130, 143, 157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060,
+                        1166, 1282, 1411, 1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484,
+                        7132, 7845, 8630, 9493, 10442, 11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767])
+    index_add = np.array([-1, -1, -1, -1, 2, 4, 6, 8])
+    x = pcm.astype(np.int64)
+    rows, P = x.shape
+    pred, idx = x[:, 0].copy(), np.full(rows, 30)
+    out = np.zeros((rows, 4 + P // 2), np.uint8)
+    out[:, 0], out[:, 1], out[:, 2] = (pred >> 8) & 0xFF, pred & 0xFF, idx
+    for j in range(P):
+        step = step_of[idx]
+        diff = x[:, j] - pred
+        d = np.where(diff < 0, 8, 0)
+        diff = np.abs(diff)
+        v = step >> 3
+        for bit, sh in ((4, 0), (2, 1), (1, 2)):
+            on = diff >= step >> sh
+            d |= np.where(on, bit, 0)
+            diff -= np.where(on, step >> sh, 0)
+            v = v + np.where(on, step >> sh, 0)
+        pred = np.clip(np.where(d & 8, pred - v, pred + v), -32768, 32767)
+        idx = np.clip(idx + index_add[d & 7], 0, 88)
+        out[:, 4 + j // 2] |= (d << (0 if j & 1 else 4)).astype(np.uint8)
+    return out
+
+
 def main():
     import numpy as np
     import torch
@@ -76,8 +109,10 @@ def main():
     codecs = sys.argv[4].split(",") if len(sys.argv) > 4 else ["s16"]
     share = float(sys.argv[5]) if len(sys.argv) > 6 else 0.0
     d = int(sys.argv[6]) if len(sys.argv) > 6 else 0
-    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw"} or not 0.0 <= share <= 1.0 or not 0 <= d <= 11 or (wide and sr != 16000):
-        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw] [burst_share d (0 ... 11)] [--wide (16000 only)]")
+    if silent and "dvi4" in codecs:
+        raise SystemExit("--silent times the s16 / ulaw / alaw routes")
+    if sr not in (8000, 16000) or not set(codecs) <= {"s16", "ulaw", "alaw", "dvi4"} or not 0.0 <= share <= 1.0 or not 0 <= d <= 11 or (wide and sr != 16000):
+        raise SystemExit("usage: packet_pump_time.py [ticks] [reps] [8000|16000] [s16,ulaw,alaw,dvi4] [burst_share d (0 ... 11)] [--wide (16000 only)]")
     S, R = 8192, 4
     N, P = (512 if sr == 16000 else 256), sr // 50                     # a chunk, a 20 ms packet (samples)
     dev = torch.device("cuda", 0)
@@ -90,7 +125,9 @@ def main():
     n_gap = int(S * silent)                                             # rows 0 ... n_gap - 1 of the arrival order are in a gap
     packed = n_gap > 0 and not zeros                                    # silent rows: the payload rows move up, back to back
     # route -> packet format (None: the chunk route)
-    names = {"s16": "packets", "ulaw": "packets_ulaw", "alaw": "packets_alaw"}
+    names = {"s16": "packets", "ulaw": "packets_ulaw", "alaw": "packets_alaw", "dvi4": "packets_dvi4"}
+    row_bytes = {"s16": 2 * P, "ulaw": P, "alaw": P, "dvi4": 4 + P // 2}     # a row in the slot: 320 / 160 / 84 bytes for 20 ms at 8 kHz
+    pitch = {c: (b + 15) // 16 * 16 for c, b in row_bytes.items()}           # ... and where the next one starts
     fmt = {names[c]: c for c in codecs}
     fmt["chunks"] = None
     if share > 0:
@@ -108,17 +145,20 @@ def main():
         elif c is None:                                                 # position table + flags + the chunks
             routes[name] = {"bytes": page(4 * S) + page(S) + S * N * 2, "ms_audio": 1000.0 * N / sr}
         else:                                                           # row table (16 bytes a row) + flags + the packets
-            row = P * (2 if c == "s16" else 1)
+            row = row_bytes[c]
             carried = S - n_gap if packed and "_on_" not in name else S
             if zeros and c != "s16":                                    # (the rows of zeros are int16 among 1-byte rows: see below)
                 carried = n_gap * 2 + (S - n_gap)
             routes[name] = {"bytes": 16 * S + page(S) + carried * ((row + 15) // 16 * 16), "ms_audio": 1000.0 * P / sr}
+            if not n_gap:                                               # what the tick's one copy carries: table + rows, and the flags
+                assert routes[name]["bytes"] == S * (16 + pitch[c]) + S, (name, routes[name]["bytes"])
     pumps = {}
+    dvi4_payloads = dvi4_encode(rows[order, :P]) if "dvi4" in codecs else None
     for name, c in fmt.items():
         if name == "packets_on_wide_pump":                              # (the same pump object: its ordinary slots)
             pump = pumps["wide"]
         else:
-            pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R, max_burst=8 if "burst" in name else 1)
+            pump = StreamPump(eng, sr, streams=S, parts=1, ring_slots=R, max_burst=8 if "burst" in name else 1, adpcm=c == "dvi4")
         if c == "wide":
             pump.set_wideband(3)
         for r in range(R):
@@ -130,6 +170,8 @@ def main():
                 pump.slot(r)[:] = rows[order]
             elif c == "s16":
                 pump.packet_area(r)[:S * P].reshape(S, P)[:] = rows[order, :P]
+            elif c == "dvi4":
+                pump.packet_bytes(r)[:S * pitch[c]].reshape(S, pitch[c])[:, :row_bytes[c]] = dvi4_payloads
             else:
                 pump.packet_bytes(r)[:S * P].reshape(S, P)[:] = g711_encode(rows[order, :P], c)
         pumps[name] = pump
@@ -158,7 +200,8 @@ def main():
                     area[:n_gap * 2 * P] = 0
             gap_offsets[c], gap_codecs[c] = off, cd
     wide_lengths, wide_offsets = np.full(S, 3 * P, np.int32), (np.arange(S) * P * 6).astype(np.int32)
-    codec_rows = {"ulaw": np.full(S, 1, np.uint8), "alaw": np.full(S, 2, np.uint8)}
+    codec_rows = {"ulaw": np.full(S, 1, np.uint8), "alaw": np.full(S, 2, np.uint8), "dvi4": np.full(S, 3, np.uint8)}
+    dvi4_offsets = (np.arange(S) * pitch["dvi4"]).astype(np.int32)      # 96 bytes a row at 8 kHz, 176 at 16 kHz
 
     # burst mode: the first `share` of the arrival order stalls, in d + 1 phases; phase f delivers (d + 1) packets as ONE row at ticks
     # t = f (mod d + 1), the rest of the group is silent, everybody else delivers a packet (rows back to back: S * P samples a tick)
@@ -194,7 +237,7 @@ def main():
             elif c == "s16":
                 pump.submit_packets(t % R, order, lengths, offsets)
             else:
-                pump.submit_coded_packets(t % R, order, lengths, codec_rows[c], offsets)
+                pump.submit_coded_packets(t % R, order, lengths, codec_rows[c], dvi4_offsets if c == "dvi4" else offsets)
             inflight += 1
             if inflight >= 2:
                 pump.poll()
